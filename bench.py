@@ -9,11 +9,20 @@ One "step" = one pass of the hot path over one batch of synthetic frame pairs pe
 encoder -> 512-d feature. After the K steps the timed region also holds the sequence tail: ONE RCCL
 all-gather of the features and the ordered LSTM/MLP scan + rel2abs that turns them into the 6-DoF
 trajectory (every rank ends up with all N*K*B poses). The uint8 frames are resident in HBM before timing starts
-(`value`); a second timed pass ingests them from pinned host memory instead (`h2d_inclusive`, never the headline).
-Secondary legs in the same JSON line (none of them is `value`): `config3` = BASELINE configs[2] as a benchmark — ONE
-synthetic 4,541-frame uint8 sequence in pinned host memory, sharded over the N ranks, through
-OdometryPipeline.run_sequence (ingest, flow, head, one all-gather, replicated scan, rel2abs): 4540 / max-over-ranks wall;
-`f16_fast` = the opt-in plain-f16 mode with its measured flow error against the split-f16 output of the same clip.
+(`value`). A plain run does only that: set-up, warm-up, the K timed steps + tail, and the result line.
+
+--full adds everything else, in the same JSON line (none of it is `value`): a second timed pass that ingests the frames from
+pinned host memory (`h2d_inclusive`); `config3` = BASELINE configs[2] as a benchmark — ONE synthetic 4,541-frame uint8
+sequence in pinned host memory, sharded over the N ranks, through OdometryPipeline.run_sequence (ingest, flow, head, one
+all-gather, replicated scan, rel2abs): 4540 / max-over-ranks wall; `f16_fast` = the opt-in plain-f16 mode with its measured
+flow error against the split-f16 output of the same clip; `f32_exact`; `per_frame`; the per-stage profile with the per-kernel
+roofline table (`roofline`, `kernels`, `stages_ms_per_forward`, `lookup`); the CPU baseline. The --no-* switches turn single
+legs of --full off.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed path computed as DIR/<name>.npy (float32 / float64):
+`features` [B,512] and `flow_up` [B,2,376,1232] of the last step, and the tail's `rot`, `tr` [N*K*B,3] and `poses`
+[N*K*B+1,4,4]; an array larger than its share of 56 MB (DUMP_BYTES; flow_up always) is written as a fixed, seeded sample of
+its elements. The inputs are seeded: two builds run with the same arguments can be compared output for output.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md §Measurement for every field).
 """
@@ -222,6 +231,23 @@ def cpu_baseline(gsd, hsd, frames, budget_s=12.0, budget_1t_s=16.0):
     return allc, one
 
 
+DUMP_BYTES = {"features": 8 << 20, "flow_up": 24 << 20, "rot": 4 << 20, "tr": 4 << 20, "poses": 16 << 20}   # 56 MB at most
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs`: every array as <out_dir>/<name>.npy, float64 stays float64, everything else float32. An array larger
+    than its DUMP_BYTES share is written as a fixed, seeded sample of its flattened elements (sorted indices, the same for
+    every run with the same arguments)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        n = DUMP_BYTES[name] // a.itemsize
+        if a.size > n:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 MFMA_PER_PRODUCT = {"split_f16": 3, "f16": 1, "f32": 1}   # MFMAs the engine executes per algorithmic product
 MFMA_PER_PRODUCT_NOW = [3]                                 # ... of the precision this run's headline uses (set in main)
 DTYPE_LABEL = {"split_f16": "f32 via 3xf16 split MFMA (fp32 accumulate)",
@@ -276,6 +302,11 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="dry run of the launch plumbing only: every rank joins a gloo group, the ranks all-gather their "
                          "(rank, local rank, threads), rank 0 prints one JSON line; no GPU call is made")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs, the per-kernel profile / roofline table and the CPU baseline "
+                         "(a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the timed path's last step (and the tail's poses) as DIR/<name>.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -306,6 +337,7 @@ def main():
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
     B, K, Wm = args.batch, args.steps, args.warmup
+    full = args.full
     MFMA_PER_PRODUCT_NOW[0] = MFMA_PER_PRODUCT[args.precision]
 
     gsd = syn.to_torch(syn.make_gma_state(seed=1))
@@ -331,8 +363,9 @@ def main():
 
     calls = [0] * S
     active = [pipes]   # the pipelines step() drives (the f16 leg swaps in its own)
+    last = {}          # flow of the last timed step and the tail's poses (--dump-outputs)
 
-    def step(i, feats, slot=None, host=False):
+    def step(i, feats, slot=None, host=False, keep=False):
         pipes = active[0]
         p = i % S
         j = calls[p]
@@ -344,8 +377,10 @@ def main():
                 frames = ingests[p](seq_host[key:key + B + 1])
             else:      # uint8 frames resident in HBM: the reference's per-frame resize to 376x1232, fused with the conversion
                 frames = resize_frames(seq_dev[key:key + B + 1])
-            f, _ = pipes[p].features_clip(frames, continued=(j > 0))   # B consecutive pairs of the sequence
+            f, flow = pipes[p].features_clip(frames, continued=(j > 0))   # B consecutive pairs of the sequence
             feats[slot * B:(slot + 1) * B] = f
+            if keep:
+                last["flow_up"] = flow
 
     def join():
         for st_ in streams:
@@ -388,7 +423,7 @@ def main():
         ev[0].record()
         try:
             for i in range(K):
-                step(i, feats, host=host)
+                step(i, feats, host=host, keep=(i == K - 1))
                 ev[i + 1].record(streams[i % S])
             join()
             torch.cuda.current_stream().synchronize()
@@ -403,6 +438,7 @@ def main():
             allf = feats[:K * B]
         rot, tr = pipe.scan(allf)
         poses = transforms.rel2abs(rot.cpu().numpy(), tr.cpu().numpy())
+        last.update(rot=rot, tr=tr, poses=poses)
         torch.cuda.synchronize()
         if dist_on:
             dist.barrier()
@@ -417,13 +453,16 @@ def main():
         return float(tmax.item()), step_ms, tail_ms
 
     dt, step_ms, tail_ms = timed(host=False)
-    h2d = None if args.no_h2d_leg else timed(host=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"features": feats[(K - 1) * B:K * B], "flow_up": last["flow_up"], "rot": last["rot"],
+                                         "tr": last["tr"], "poses": last["poses"]})
+    h2d = None if not full or args.no_h2d_leg else timed(host=True)
 
     # ---- config3: ONE long sequence sharded over the ranks (evaluate_odometry.py:60-75: the LSTM state is never reset
     # inside a sequence), uint8 frames in pinned host memory, through the product's sequence driver; both streams of every
     # GPU walk their own contiguous sub-shard (lanes). Timed host-clock, barrier + synchronize on both sides, max over ranks.
     c3 = None
-    if not args.no_config3:
+    if full and not args.no_config3:
         T3 = max(2, args.config3_frames)
         cyc = CyclicSequence(seq_host, period, T3)
         lanes = pipes[1:]
@@ -459,7 +498,7 @@ def main():
 
     # ---- f16 fast mode as a secondary leg: same steps, same frames, precision="f16" handles (never the headline)
     f16 = None
-    if not args.no_f16_leg and args.precision == "split_f16":
+    if full and not args.no_f16_leg and args.precision == "split_f16":
         fast = [OdometryPipeline(gsd, hsd, device=dev, max_batch=B, iters=ITERS, precision="f16") for _ in range(S)]
         frames0 = resize_frames(seq_dev[:B + 1])
         _, up_ref = pipe.features_clip(frames0)
@@ -475,7 +514,7 @@ def main():
     # activations leave the split-f16 range — every GEMM on v_mfma_f32_32x32x2_f32, the reference's data flow (row-major
     # pyramid, separate lookup, logits + softmax). Same clip and frames, a quarter of the steps (never the headline).
     f32 = None
-    if not args.no_f32_leg and args.precision == "split_f16":
+    if full and not args.no_f32_leg and args.precision == "split_f16":
         exact = [OdometryPipeline(gsd, hsd, device=dev, max_batch=B, iters=ITERS, precision="f32") for _ in range(S)]
         frames0 = resize_frames(seq_dev[:B + 1])
         _, up_ref = pipe.features_clip(frames0)
@@ -492,7 +531,7 @@ def main():
     # neural_slam.py:192-227 = pipeline.VisualOdometry): host uint8 frame -> H2D -> resize -> flow (one pair, the low-latency form) ->
     # head (one LSTM step) -> pose on the host, synchronous; rank 0 only, never the headline
     per_frame = None
-    if not args.no_per_frame_leg and rank == 0 and args.precision == "split_f16":
+    if full and not args.no_per_frame_leg and rank == 0 and args.precision == "split_f16":
         from atdn_vslam_amd.pipeline import VisualOdometry
         vo = VisualOdometry(gsd, hsd, device=dev, iters=ITERS)
         nf = 24
@@ -509,24 +548,6 @@ def main():
 
     if rank == 0:
         total_pairs = world * K * B
-        # per-stage device time of the same forward in this run, eager with HIP events on the launch stream
-        reps = 3
-        # in the call form the timed loop uses: a CONTINUED clip (B feature-network passes, not the 2B of pair mode)
-        st = pipe.flow_net.profile(H, W, B, iters=ITERS, reps=reps, mode="continued")
-        rows = kernel_table(st, B)
-        # HBM-side bytes per launch from the committed PMC passes (NOT this run: `traffic_source` names the file) on every row
-        # whose kernel the profile holds, and their ratio to the row's algorithmic bytes — the lookup and the level-0
-        # correlation are the two kernels that move more than they must
-        for r in rows:
-            # (the correlation kernel runs once per pyramid level: level 0 is its largest launch)
-            tb, src = pmc_traffic(r["rocprof_name_contains"], B, largest=(r["stage"] == "corr"))
-            if tb is not None:
-                r["traffic"], r["traffic_source"] = tb, src
-                ab = r.get("algorithmic_bytes_per_launch", r["algorithmic_per_launch"] if r["bound"] == "hbm" else None)
-                if ab:
-                    r["traffic_ratio"] = tb / ab
-        top = rows[0]
-        traffic, traffic_src = pmc_traffic(top["rocprof_name_contains"], B)
         fwd_ms = float(np.median(step_ms))
         mfma_x = MFMA_PER_PRODUCT[args.precision]
         out = {
@@ -538,40 +559,59 @@ def main():
                                    "12 GRU iters + CLVO head -> 6-DoF trajectory (BASELINE configs[1])",
                        "pairs_per_step_per_gpu": B, "streams_per_gpu": S, "gru_iters": ITERS, "parallelism": "pairs sharded x%d, one "
                        "all-gather of 512-d features, replicated LSTM scan" % world},
-            # the dominant kernel = the top row of `kernels` (same-run HIP-event time per forward). For an hbm-bound kernel
-            # achieved = algorithmic bytes / launch time; for an mfma-bound one algorithmic FLOP / launch time (the split-f16
-            # engine executes 3 f16 MFMAs per algorithmic product: mfma_executed_*). `traffic` is NOT measured in this run:
-            # it is the PMC figure (2 x FETCH_SIZE + WRITE_SIZE per launch) of the committed profile named in traffic_source.
-            "roofline": {"bound": top["bound"], "kernel": top["kernel"], "rocprof_name_contains": top["rocprof_name_contains"],
-                         "achieved": top["achieved"], "peak": top["peak"], "unit": top["unit"], "frac": top["frac"],
-                         "traffic": traffic, "traffic_source": traffic_src, "launch_ms": top["us_per_launch"] / 1e3,
-                         "algorithmic_per_launch": top["algorithmic_per_launch"],
-                         "algorithmic_unit": top["algorithmic_unit"],
-                         # share of the eager stage sum of one continued-clip forward (one stream, events between launches)
-                         # and of the timed step (two streams overlapping: completion-to-completion interval)
-                         "share_of_forward": top["ms_per_forward"] / sum(st.values()),
-                         "share_of_timed_step": top["ms_per_forward"] / fwd_ms},
-            "kernels": rows[:5] + [r for r in rows[5:] if r["stage"] in ("lookup", "corr")],
-            "stages_mode": "continued clip (B feature-network passes per B pairs): the call form the timed loop uses",
             "forward": {"ms_per_batch_median": fwd_ms,
                         "tflops_algorithmic_0.951_per_pair": FLOP_PER_PAIR * B / (fwd_ms * 1e-3) / 1e12,
                         "tflops_executed_work": FLOP_PER_PAIR_EXECUTED * B / (fwd_ms * 1e-3) / 1e12,
                         "mfma_executed_tflops": mfma_x * FLOP_PER_PAIR_EXECUTED * B / (fwd_ms * 1e-3) / 1e12,
                         "frac_of_f16_mfma_peak_algorithmic": FLOP_PER_PAIR * B / (fwd_ms * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS,
                         "frac_of_f32_mfma_peak": FLOP_PER_PAIR * B / (fwd_ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS},
-            "lookup": {"ms_per_launch": st["lookup"] / ITERS, "achieved_GBps": LOOKUP_BYTES * B / (st["lookup"] / ITERS * 1e-3) / 1e9,
-                       "peak_GBps": PEAK_HBM_GBS},
-            "stages_ms_per_forward": {k: round(v, 4) for k, v in st.items()},
             # inside the timed region, after the K steps: grows with N (every rank scans all N*K*B features in order)
             "sequence_tail_ms": round(tail_ms, 3),
         }
-        out["stages_ms_per_forward"]["attention_total"] = round(st["attention"] + st["attn_logits"], 4)
-        for k in ("mfma_executed_tflops", "mfma_executed_frac", "stored_bytes_per_launch", "frac_stored_bytes"):
-            if k in top:
-                out["roofline"][k] = top[k]
-        if traffic is not None and top["bound"] == "hbm":
-            # PMC bytes (committed profile) over this run's launch time: the fraction of the HBM peak in REAL bytes
-            out["roofline"]["frac_real_bytes"] = traffic / (top["us_per_launch"] * 1e-6) / 1e9 / PEAK_HBM_GBS
+        if full:
+            # per-stage device time of the same forward in this run, eager with HIP events on the launch stream
+            reps = 3
+            # in the call form the timed loop uses: a CONTINUED clip (B feature-network passes, not the 2B of pair mode)
+            st = pipe.flow_net.profile(H, W, B, iters=ITERS, reps=reps, mode="continued")
+            rows = kernel_table(st, B)
+            # HBM-side bytes per launch from the committed PMC passes (NOT this run: `traffic_source` names the file) on every row
+            # whose kernel the profile holds, and their ratio to the row's algorithmic bytes — the lookup and the level-0
+            # correlation are the two kernels that move more than they must
+            for r in rows:
+                # (the correlation kernel runs once per pyramid level: level 0 is its largest launch)
+                tb, src = pmc_traffic(r["rocprof_name_contains"], B, largest=(r["stage"] == "corr"))
+                if tb is not None:
+                    r["traffic"], r["traffic_source"] = tb, src
+                    ab = r.get("algorithmic_bytes_per_launch", r["algorithmic_per_launch"] if r["bound"] == "hbm" else None)
+                    if ab:
+                        r["traffic_ratio"] = tb / ab
+            top = rows[0]
+            traffic, traffic_src = pmc_traffic(top["rocprof_name_contains"], B)
+            # the dominant kernel = the top row of `kernels` (same-run HIP-event time per forward). For an hbm-bound kernel
+            # achieved = algorithmic bytes / launch time; for an mfma-bound one algorithmic FLOP / launch time (the split-f16
+            # engine executes 3 f16 MFMAs per algorithmic product: mfma_executed_*). `traffic` is NOT measured in this run:
+            # it is the PMC figure (2 x FETCH_SIZE + WRITE_SIZE per launch) of the committed profile named in traffic_source.
+            out["roofline"] = {"bound": top["bound"], "kernel": top["kernel"], "rocprof_name_contains": top["rocprof_name_contains"],
+                               "achieved": top["achieved"], "peak": top["peak"], "unit": top["unit"], "frac": top["frac"],
+                               "traffic": traffic, "traffic_source": traffic_src, "launch_ms": top["us_per_launch"] / 1e3,
+                               "algorithmic_per_launch": top["algorithmic_per_launch"],
+                               "algorithmic_unit": top["algorithmic_unit"],
+                               # share of the eager stage sum of one continued-clip forward (one stream, events between launches)
+                               # and of the timed step (two streams overlapping: completion-to-completion interval)
+                               "share_of_forward": top["ms_per_forward"] / sum(st.values()),
+                               "share_of_timed_step": top["ms_per_forward"] / fwd_ms}
+            out["kernels"] = rows[:5] + [r for r in rows[5:] if r["stage"] in ("lookup", "corr")]
+            out["stages_mode"] = "continued clip (B feature-network passes per B pairs): the call form the timed loop uses"
+            out["lookup"] = {"ms_per_launch": st["lookup"] / ITERS,
+                             "achieved_GBps": LOOKUP_BYTES * B / (st["lookup"] / ITERS * 1e-3) / 1e9, "peak_GBps": PEAK_HBM_GBS}
+            out["stages_ms_per_forward"] = {k: round(v, 4) for k, v in st.items()}
+            out["stages_ms_per_forward"]["attention_total"] = round(st["attention"] + st["attn_logits"], 4)
+            for k in ("mfma_executed_tflops", "mfma_executed_frac", "stored_bytes_per_launch", "frac_stored_bytes"):
+                if k in top:
+                    out["roofline"][k] = top[k]
+            if traffic is not None and top["bound"] == "hbm":
+                # PMC bytes (committed profile) over this run's launch time: the fraction of the HBM peak in REAL bytes
+                out["roofline"]["frac_real_bytes"] = traffic / (top["us_per_launch"] * 1e-6) / 1e9 / PEAK_HBM_GBS
         if c3 is not None:
             out["config3"] = {"workload": "ONE synthetic KITTI-00-shaped sequence of %d uint8 frames (pinned host memory) sharded over %d "
                                           "rank(s), OdometryPipeline.run_sequence: ingest + flow + head, one all-gather, replicated "
@@ -604,11 +644,12 @@ def main():
             out["h2d_inclusive"] = {"value": total_pairs / h2d[0], "unit": "frame-pairs/s", "ms_per_step": h2d[0] * 1e3 / K,
                                     "ratio_to_value": (total_pairs / h2d[0]) / (total_pairs / dt),
                                     "host_bytes_per_step": (B + 1) * 3 * H_KITTI * W_KITTI}
-        if not args.no_cpu_baseline and world == 1:   # the CPU leg is timed at N = 1 only (rank 0)
+        if full and not args.no_cpu_baseline and world == 1:   # the CPU leg is timed at N = 1 only (rank 0)
             out["cpu_baseline"], out["cpu_baseline_1thread"] = cpu_baseline(gsd, hsd, resize_frames(seq_dev[:6]))
         else:
             out["cpu_baseline"] = None
-            out["cpu_baseline_reason"] = ("--no-cpu-baseline" if world == 1 else "the CPU leg is timed at N = 1 only (rank 0 "
+            out["cpu_baseline_reason"] = ("not measured without --full" if not full else "--no-cpu-baseline" if world == 1 else
+                                          "the CPU leg is timed at N = 1 only (rank 0 "
                                           "would hold the other %d ranks in the closing barrier and share its cores with them); "
                                           "the N = 1 line of the same build carries it" % (world - 1))
         print(json.dumps(out))

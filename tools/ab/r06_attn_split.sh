@@ -4,7 +4,7 @@
 out=gpurun_out/r06/ab_attn_split.txt
 mkdir -p gpurun_out/r06
 : > $out
-LEGS="--no-cpu-baseline --no-config3 --no-f16-leg --no-f32-leg --no-per-frame-leg --no-h2d-leg"
+LEGS="--full --no-cpu-baseline --no-config3 --no-f16-leg --no-f32-leg --no-per-frame-leg --no-h2d-leg"
 for rep in 1 2; do
   for n in 1 8 4 2; do
     ATDN_LOW_LATENCY=1 ATDN_ATTN_FORCE_SPLIT=$n python3 bench.py --steps 12 --warmup 4 $LEGS > /tmp/ab.json 2>/dev/null

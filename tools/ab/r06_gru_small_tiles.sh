@@ -4,7 +4,7 @@
 out=gpurun_out/r06/ab_gru_small_tiles2.txt
 mkdir -p gpurun_out/r06
 : > $out
-LEGS="--no-cpu-baseline --no-config3 --no-f16-leg --no-f32-leg --no-per-frame-leg --no-h2d-leg"
+LEGS="--full --no-cpu-baseline --no-config3 --no-f16-leg --no-f32-leg --no-per-frame-leg --no-h2d-leg"
 for rep in 1 2; do
   for f in 0 2; do
     ATDN_CONV_SMALL_TILES=$f python3 bench.py --steps 12 --warmup 4 $LEGS > /tmp/ab.json 2>/dev/null

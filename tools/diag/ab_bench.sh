@@ -1,6 +1,6 @@
 # A/B of two library builds in one job: bash tools/diag/ab_bench.sh <old.so>   (new = the in-tree library)
 export TMPDIR=/tmp
-LEGS="--no-cpu-baseline --no-config3 --no-f16-leg --no-h2d-leg"
+LEGS="--full --no-cpu-baseline --no-config3 --no-f16-leg --no-h2d-leg"
 for r in 1 2; do
   python3 bench.py --steps 10 --warmup 2 $LEGS > gpurun_out/ab_new_$r.json 2> gpurun_out/ab_new_$r.err
   ATDN_LIB_PATH=$1 python3 bench.py --steps 10 --warmup 2 $LEGS > gpurun_out/ab_old_$r.json 2> gpurun_out/ab_old_$r.err
