@@ -1,11 +1,12 @@
 """CPU ORACLE (test infrastructure, not product code) — CLVO pose head `ATDNVO`.
 
-Functional fp32 restatement on stock torch CPU ops of
+Functional restatement on stock torch CPU ops of
 `ATDNVO.forward` (atdn_vslam/odometry/network.py:122-146), its blocks
 (`Conv.forward` layers/conv.py:36-37 = BN(Mish(conv)); `ResidualConv.forward`
 layers/conv.py:83-90; `Linear.forward` layers/linear.py:35-42) and the flow
 normalisation (utils/normalizations.py:8-10).  The LSTM state is explicit
-(h1, c1, h2, c2) instead of hidden module attributes.
+(h1, c1, h2, c2) instead of hidden module attributes.  Every function computes in the dtype of the state dict and
+inputs it is given: fp32 as the reference, fp64 as a high-precision yardstick.
 
 Parity pin: tests/golden/clvo.npz (outputs of the imported reference).
 """
@@ -50,8 +51,8 @@ def clvo_encode(sd, flows):
     return _lin_mish(x, sd, "encoder_CNN.8")
 
 
-def zero_state(batch=1):
-    return [torch.zeros(batch, 512) for _ in range(4)]
+def zero_state(batch=1, dtype=torch.float32):
+    return [torch.zeros(batch, 512, dtype=dtype) for _ in range(4)]
 
 
 def _lstm_cell(x, h, c, sd, p):

@@ -78,20 +78,20 @@ def clvo_loss(pred_rot, pred_tr, true_rot, true_tr, alpha=1.0, w=3):
     if alpha == 1.0:
         return l_rel.mean()
     from . import pose_ref
-    com = []
+    com, dt = [], pred_rot.dtype
     with torch.no_grad():
         for b in range(pred_rot.shape[0]):
-            pm = [torch.from_numpy(pose_ref.transform(pred_rot[b, i].numpy(), pred_tr[b, i].numpy())).float()
+            pm = [torch.from_numpy(pose_ref.transform(pred_rot[b, i].numpy(), pred_tr[b, i].numpy())).to(dt)
                   for i in range(pred_rot.shape[1])]
-            tm = [torch.from_numpy(pose_ref.transform(true_rot[b, i].numpy(), true_tr[b, i].numpy())).float()
+            tm = [torch.from_numpy(pose_ref.transform(true_rot[b, i].numpy(), true_tr[b, i].numpy())).to(dt)
                   for i in range(pred_rot.shape[1])]
             tot = 0.0
             for j in range(len(pm) - w + 1):
                 a, c = pm[j], tm[j]
                 for i in range(j + 1, j + w):
                     a, c = a @ pm[i], c @ tm[i]
-                pr_, tr2 = torch.from_numpy(pose_ref.matrix2euler(a[:3, :3].numpy())).float(), \
-                    torch.from_numpy(pose_ref.matrix2euler(c[:3, :3].numpy())).float()
+                pr_, tr2 = torch.from_numpy(pose_ref.matrix2euler(a[:3, :3].numpy())).to(dt), \
+                    torch.from_numpy(pose_ref.matrix2euler(c[:3, :3].numpy())).to(dt)
                 tot = tot + transform_loss(pr_, a[:3, 3], tr2, c[:3, 3])
             com.append(tot)
     return (alpha * l_rel + (1 - alpha) * torch.stack(com)).mean()
@@ -111,10 +111,12 @@ def adamw_step(p, g, m, v, t, lr, wd, eps, b1=0.9, b2=0.999):
     p.addcdiv_(m, denom, value=-lr / (1 - b1 ** t))
 
 
-def split_state(sd):
-    """state_dict -> (trainable parameters with requires_grad, BatchNorm running statistics)."""
+def split_state(sd, dtype=None):
+    """state_dict -> (trainable parameters with requires_grad, BatchNorm running statistics), cast to `dtype` if given."""
     P, S = {}, {}
     for k, v in sd.items():
+        if dtype is not None and v.is_floating_point():
+            v = v.to(dtype)
         if k.endswith("running_mean") or k.endswith("running_var"):
             S[k] = v.clone()
         elif k.endswith("num_batches_tracked"):
@@ -125,16 +127,19 @@ def split_state(sd):
 
 
 def train_iteration(P, S, flows, true_rot, true_tr, alpha=1.0, w=3):
-    """flows [B,T,2,H,W]; returns (loss, pred_rot [B,T,3], pred_tr [B,T,3]) with gradients left in P[k].grad."""
+    """flows [B,T,2,H,W]; returns (loss, pred_rot [B,T,3], pred_tr [B,T,3]) with gradients left in P[k].grad.
+    Runs in the dtype of the parameters P (fp32 as the reference, or fp64 as a high-precision yardstick): flows, the
+    LSTM state and the targets follow it; S must hold running statistics of that dtype too."""
     B, T = flows.shape[:2]
-    state = [torch.zeros(B, 512) for _ in range(4)]
+    dt = next(iter(P.values())).dtype
+    state = [torch.zeros(B, 512, dtype=dt) for _ in range(4)]
     rots, trs = [], []
     for j in range(T):
-        r, t, state = forward_train(P, S, flows[:, j].float(), state)
+        r, t, state = forward_train(P, S, flows[:, j].to(dt), state)
         rots.append(r)
         trs.append(t)
     pred_rot, pred_tr = torch.stack(rots, dim=1), torch.stack(trs, dim=1)
-    loss = clvo_loss(pred_rot, pred_tr, true_rot, true_tr, alpha, w)
+    loss = clvo_loss(pred_rot, pred_tr, true_rot.to(dt), true_tr.to(dt), alpha, w)
     for p in P.values():
         p.grad = None
     loss.backward()

@@ -42,3 +42,37 @@ def test_training_iteration_oracle_matches_reference(golden_dir):
         for k, s in S.items():
             if "stat%d/" % it + k in g.files:
                 np.testing.assert_allclose(s.double().numpy(), g["stat%d/" % it + k], rtol=2e-5, atol=1e-6, err_msg=k)
+
+
+def test_fp64_oracle_agrees_with_fp32_at_a_kitti_04_geometry():
+    """The oracle is dtype-generic: run in fp64 it is the yardstick the GPU trainer is measured against at the other
+    KITTI geometries (tests/test_gpu_train_geometry.py). At 370x1226 (sequences 04-10, odd at three of five levels),
+    B = 2, T = 2, the fp32 and fp64 oracles agree on loss, predictions, every element of every gradient and every
+    running statistic to fp32 rounding (worst gradient max|g32 - g64| / max|g64| was 1.2e-4, encoder_CNN.1.conv.bias)."""
+    torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
+    B, T, H, W = 2, 2, 370, 1226
+    sd = syn.to_torch(syn.make_clvo_state(seed=3))
+    flows = torch.from_numpy(syn.make_flow(B * T, H, W, seed=90)).view(B, T, 2, H, W)
+    r = np.random.RandomState(91)
+    true_rot = torch.from_numpy(r.normal(0, 0.01, (B, T, 3)).astype(np.float32))
+    true_tr = torch.from_numpy(r.normal(0, 0.5, (B, T, 3)).astype(np.float32))
+    out = {}
+    for dt in (torch.float32, torch.float64):
+        P, S = tr.split_state(sd, dt)
+        loss, pr, pt = tr.train_iteration(P, S, flows, true_rot, true_tr)
+        assert loss.dtype == dt and pr.dtype == dt and all(s.dtype == dt for s in S.values())
+        out[dt] = (loss, pr, pt, {k: p.grad for k, p in P.items()}, S)
+    (l32, r32, t32, g32, s32), (l64, r64, t64, g64, s64) = out[torch.float32], out[torch.float64]
+    assert abs(float(l32) - float(l64)) <= 1e-5 * abs(float(l64)), (float(l32), float(l64))
+    for a, b in ((r32, r64), (t32, t64)):
+        assert float((a.double() - b).abs().max()) <= 1e-5 * float(b.abs().max())
+    assert sorted(k for k, g in g64.items() if g is None) == ["polar_norm.bias", "polar_norm.weight"]
+    for k, g in g64.items():
+        if g is None:
+            assert g32[k] is None, k
+            continue
+        assert g32[k].dtype == torch.float32 and g.dtype == torch.float64, k
+        err, scale = float((g32[k].double() - g).abs().max()), float(g.abs().max())
+        assert scale > 0 and err <= 5e-4 * scale, (k, err / scale)
+    for k, s in s64.items():
+        assert float((s32[k].double() - s).abs().max()) <= 1e-5 * float(s.abs().max()) + 1e-9, k
