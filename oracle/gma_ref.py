@@ -1,9 +1,12 @@
 """CPU ORACLE (test infrastructure, not product code) — GMA optical-flow forward.
 
-Functional fp32 restatement, on stock torch CPU ops, of the op sequence the
+Functional restatement, on stock torch CPU ops, of the op sequence the
 reference executes in `RAFTGMA.forward(..., test_mode=True)`
 (whl:GMA/core/network.py:72-129).  Weights come in as a flat {key: tensor}
-dict in the reference's state-dict layout.  Only `tests/`,
+dict in the reference's state-dict layout.  It computes in the dtype of the
+weights and frames it is given: fp32 ones give the reference's fp32 result,
+fp64 ones a result that never rounds through fp32 (the yardstick of
+tests/test_gpu_flow_geometry.py).  Only `tests/`,
 `__graft_entry__.smoke()` and `bench.py`'s cpu_baseline leg may import this
 package; the product path never does.
 
@@ -69,7 +72,7 @@ def corr_lookup(pyr, coords, radius=4):
     """corr.py:32-53 + utils.py:59-73.  coords [B,2,H,W] (x,y) → [B,L*(2r+1)^2,H,W]."""
     b, _, h, w = coords.shape
     c = coords.permute(0, 2, 3, 1).reshape(b * h * w, 1, 1, 2)
-    d = torch.linspace(-radius, radius, 2 * radius + 1)
+    d = torch.linspace(-radius, radius, 2 * radius + 1, dtype=coords.dtype)
     # reference quirk: meshgrid(dy, dx) stacked then added to (x, y) → first window
     # axis steps x, second steps y
     delta = torch.stack(torch.meshgrid(d, d, indexing="ij"), dim=-1).view(1, 2 * radius + 1, 2 * radius + 1, 2)
@@ -81,7 +84,7 @@ def corr_lookup(pyr, coords, radius=4):
         gy = 2 * pos[..., 1:2] / (hh - 1) - 1
         s = F.grid_sample(corr, torch.cat([gx, gy], dim=-1), align_corners=True)
         out.append(s.view(b, h, w, -1))
-    return torch.cat(out, dim=-1).permute(0, 3, 1, 2).contiguous().float()
+    return torch.cat(out, dim=-1).permute(0, 3, 1, 2).contiguous()
 
 
 def attention(inp, sd):
@@ -145,10 +148,10 @@ def convex_upsample(flow, mask):
     return torch.sum(m * uf, dim=2).permute(0, 1, 4, 2, 5, 3).reshape(n, 2, 8 * h, 8 * w)
 
 
-def coords_grid(b, h, w):
+def coords_grid(b, h, w, dtype=torch.float32):
     """utils.py:76-79: channel 0 = x, channel 1 = y."""
     ys, xs = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
-    return torch.stack([xs, ys], 0).float()[None].repeat(b, 1, 1, 1)
+    return torch.stack([xs, ys], 0).to(dtype)[None].repeat(b, 1, 1, 1)
 
 
 def strip_prefix(sd):
@@ -165,7 +168,7 @@ def gma_forward(sd, image1, image2, iters=12, flow_init=None, taps=None, predict
     im1 = (2 * (image1 / 255.0) - 1.0).contiguous()
     im2 = (2 * (image2 / 255.0) - 1.0).contiguous()
     bsz = im1.shape[0]
-    fmaps = encoder(torch.cat([im1, im2], 0), sd, "fnet.", "instance").float()
+    fmaps = encoder(torch.cat([im1, im2], 0), sd, "fnet.", "instance")
     fmap1, fmap2 = fmaps[:bsz], fmaps[bsz:]
     pyr = corr_pyramid(fmap1, fmap2)
     cnet = encoder(im1, sd, "cnet.", "batch")
@@ -174,8 +177,8 @@ def gma_forward(sd, image1, image2, iters=12, flow_init=None, taps=None, predict
     inp = torch.relu(inp)
     attn = attention(inp, sd)
     h8, w8 = im1.shape[2] // 8, im1.shape[3] // 8
-    coords0 = coords_grid(bsz, h8, w8)
-    coords1 = coords_grid(bsz, h8, w8)
+    coords0 = coords_grid(bsz, h8, w8, fmaps.dtype)
+    coords1 = coords_grid(bsz, h8, w8, fmaps.dtype)
     if flow_init is not None:
         coords1 = coords1 + flow_init
     if taps is not None:
