@@ -226,6 +226,27 @@ int atdn_ingest_frames_u8(atdn_ingest* h, const uint8_t* host_frames, int n_fram
 void atdn_ingest_destroy(atdn_ingest* h);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Flow bank  —  replaces the reference's fp16 flow files and FlowKittiDataset3 (flowbank.py)
+ *   files:   dataset/flows2/<seq>/%06d.pt, fp16 [1,2,376,1232+] (read at odometry/datasets.py:176-189)
+ *   samples: FlowKittiDataset3.__getitem__ (odometry/datasets.py:196-226), batched by the DataLoader of
+ *            train_odometry.py:78-85
+ * fp16 buffers are raw device pointers to IEEE binary16 values (torch.float16 data_ptr()).
+ * ------------------------------------------------------------------------------------------------- */
+
+/* `flow_up[..., x0:x0+W].half()` into a bank slot: the fp16 flow file the reference stores, written on the device.
+ *   flow_up [B,2,H,Wsrc] fp32 -> dst [B,2,H,W] fp16 (16-byte aligned; W % 8 == 0; 0 <= x0, x0 + W <= Wsrc).
+ * Round to nearest even; a NaN stays a NaN and values beyond +-65504 become +-inf, as tensor.half() does. */
+int atdn_flow_pack_f16(const float* flow_up, int B, int H, int Wsrc, int x0, int W, uint16_t* dst, void* stream);
+
+/* One training batch out of the bank, the reverse-flow augmentation folded in (odometry/datasets.py:220-224):
+ *   out[b,t] = reverse[b] ? -bank[start[b]+T-1-t] : bank[start[b]+t]
+ * bank [n_flows,2,H,W] fp16 -> out [B,T,2,H,W] fp32 (what atdn_clvo_trainer_forward_backward reads). `start` and `reverse`
+ * are HOST arrays of B ints; every start must satisfy 0 <= start[b] <= n_flows - T, or the call fails before launching
+ * anything. H * W % 4 == 0; bank and out 16-byte aligned. Bit-identical to the torch expression (exact decode and negation). */
+int atdn_flow_gather_clips(const uint16_t* bank, int n_flows, int H, int W, const int* start, const int* reverse, int B, int T,
+                           float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Individual kernels, exported for unit parity tests and roofline micro-benchmarks
  * ------------------------------------------------------------------------------------------------- */
 
