@@ -1,0 +1,292 @@
+"""The relocalisation map of NeuralSLAM kept in HBM: keyframe images, their MappingVAE embeddings and a one-launch search.
+
+The reference keeps a Python list of `Frame`s (slam_framework/frame.py): an image file per keyframe, a pose and a latent
+embedding, and answers a relocalisation query with a loop of `torch.norm(kf.embedding - mu, p=2)` over that list, an
+`argmin`, a `torch.load` of the winner's image and a batch-1 odometry step (slam_framework/neural_slam.py:355-399). Here:
+
+* the image bank is one uint8 device buffer [capacity,3,H,W]; `images(indices)` is `atdn_map_gather_images_u8`, the fp32
+  batch the encoder and the flow network read;
+* the embedding bank is one fp32 device buffer [capacity, D], D = h * w * 128, a row being exactly what `atdn_vae_encode`
+  writes for one image (CHANNELS-LAST: element (y * w + x) * 128 + c of a row is `MappingVAE(image)[0][0, c, y, x]`), so
+  `embed` lets the encoder write straight into the rows of a batch of keyframes. The L2 norm does not care about element
+  order, as long as the queries are in the same one;
+* `search` is `atdn_map_search`: every distance of every query in one pass over the bank, and the top_k nearest keyframes
+  per query;
+* `relocalize` answers a batch of queries: one encoder call, one search, one image gather, the flow network and the pose
+  head at batch Q.
+
+Poses live on the host ([K,4,4] float32), as in the reference.
+"""
+import ctypes as C
+import glob
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, transforms
+
+MAX_TOP_K = 16
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def embedding_hw(hw):
+    """Size of the MappingVAE embedding map of an H x W image: six stride-2 blocks (3x3, padding 1), 376x1232 -> 6x20."""
+    h, w = int(hw[0]), int(hw[1])
+    for _ in range(6):
+        h, w = (h + 1) // 2, (w + 1) // 2
+    return h, w
+
+
+def _homogeneous(poses):
+    p = torch.as_tensor(poses, dtype=torch.float32)
+    if p.dim() == 2 and p.shape[1] == 12:
+        p = p.view(-1, 3, 4)
+    if p.dim() == 3 and tuple(p.shape[1:]) == (3, 4):
+        last = torch.tensor([0.0, 0.0, 0.0, 1.0]).view(1, 1, 4).repeat(len(p), 1, 1)
+        p = torch.cat([p, last], dim=1)
+    if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4):
+        raise ValueError("poses must be [K,12], [K,3,4] or [K,4,4], got %s" % (tuple(p.shape),))
+    return p
+
+
+def gather_images(bank, indices):
+    """bank [K,3,H,W] uint8 (device) -> fp32 [n,3,H,W] with out[j] = bank[indices[j]].float() (atdn_map_gather_images_u8; the
+    indices are a host array, each checked against [0, K) before anything is launched)."""
+    K = int(bank.shape[0])
+    if isinstance(indices, torch.Tensor):
+        indices = indices.detach().cpu().numpy()
+    ix = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+    if ix.size == 0:
+        raise RuntimeError("gather_images: no index")
+    if ix.min() < -2 ** 31 or ix.max() >= 2 ** 31:
+        raise RuntimeError("gather_images: index outside the int range")
+    ix = ix.astype(np.int32)
+    if bank.dtype != torch.uint8 or not bank.is_contiguous():
+        raise RuntimeError("gather_images: the bank must be a contiguous uint8 tensor")
+    shape = (ix.size,) + tuple(bank.shape[1:])
+    out = torch.empty(shape, dtype=torch.float32, device=bank.device)
+    plane = int(np.prod(bank.shape[1:]))
+    with torch.cuda.device(bank.device):
+        _lib.check(_lib.lib().atdn_map_gather_images_u8(_ptr(bank), K, plane, ix.ctypes.data_as(C.c_void_p), int(ix.size),
+                                                        _ptr(out), _stream()))
+    return out
+
+
+def search_bank(bank, queries, top_k=1):
+    """bank [K,D], queries [Q,D] fp32 on one device -> (distances [Q,K] fp32, indices [Q,top_k] int32), device tensors
+    (atdn_map_search)."""
+    K, D = int(bank.shape[0]), int(bank.shape[1])
+    if queries.dim() != 2 or int(queries.shape[1]) != D:
+        raise RuntimeError("search: queries must be [Q,%d], got %s" % (D, tuple(queries.shape)))
+    if queries.device != bank.device:
+        raise RuntimeError("search: queries on %s but the map is on %s" % (queries.device, bank.device))
+    q = queries.float().contiguous()
+    Q = int(q.shape[0])
+    dist = torch.empty((Q, K), dtype=torch.float32, device=bank.device)
+    idx = torch.empty((Q, int(top_k)), dtype=torch.int32, device=bank.device)
+    with torch.cuda.device(bank.device):
+        _lib.check(_lib.lib().atdn_map_search(_ptr(bank), K, D, _ptr(q), Q, int(top_k), _ptr(dist), _ptr(idx), _stream()))
+    return dist, idx
+
+
+class KeyframeMap:
+    """Keyframe images (uint8), embeddings (fp32, channels-last rows) and poses of one map; the first two in device memory."""
+
+    def __init__(self, device, hw=(376, 1232), capacity=256):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("KeyframeMap lives in device memory: there is no CPU fallback")
+        self.hw = (int(hw[0]), int(hw[1]))
+        if (3 * self.hw[0] * self.hw[1]) % 16 != 0:
+            raise ValueError("3 * H * W must be a multiple of 16 (16-byte image rows in the bank), got %dx%d" % self.hw)
+        self.capacity = int(capacity)
+        if self.capacity < 1:
+            raise ValueError("KeyframeMap needs room for at least one keyframe")
+        self.embedding_hw = embedding_hw(self.hw)
+        self.D = self.embedding_hw[0] * self.embedding_hw[1] * 128
+        self.image_bank = torch.empty((self.capacity, 3) + self.hw, dtype=torch.uint8, device=self.device)
+        self.embedding_bank = None          # [capacity, D] fp32, allocated by the first embed()
+        self._poses = torch.zeros((self.capacity, 4, 4), dtype=torch.float32)
+        self.n = 0
+        self.n_embedded = 0
+        self._embed_fp = None               # (module, its parameter fingerprint) of the rows embedded so far
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def poses(self):
+        """[K,4,4] float32, host."""
+        return self._poses[:self.n]
+
+    # ------------------------------------------------------------------ filling
+    def _grow(self):
+        cap = self.capacity * 2
+        images = torch.empty((cap, 3) + self.hw, dtype=torch.uint8, device=self.device)
+        images[:self.n].copy_(self.image_bank[:self.n])
+        self.image_bank = images
+        if self.embedding_bank is not None:
+            emb = torch.empty((cap, self.D), dtype=torch.float32, device=self.device)
+            emb[:self.n_embedded].copy_(self.embedding_bank[:self.n_embedded])
+            self.embedding_bank = emb
+        poses = torch.zeros((cap, 4, 4), dtype=torch.float32)
+        poses[:self.n] = self._poses[:self.n]
+        self._poses = poses
+        self.capacity = cap
+
+    def append(self, image, pose):
+        """Store one keyframe: image [3,H,W] (or [1,3,H,W]) uint8, or float with values 0..255 (`.byte()` of it is stored:
+        what the reference writes to rgb/%06d.pth), on any device; pose [4,4]. The copy into the bank runs on the device.
+        A full map doubles its capacity (new buffers, device-to-device copies). Returns the keyframe's index."""
+        im = image[0] if image.dim() == 4 and image.shape[0] == 1 else image
+        if tuple(im.shape) != (3,) + self.hw:
+            raise ValueError("keyframe image must be [3,%d,%d], got %s" % (self.hw + (tuple(image.shape),)))
+        pose = torch.as_tensor(pose, dtype=torch.float32).cpu()
+        if tuple(pose.shape) != (4, 4):
+            raise ValueError("keyframe pose must be [4,4], got %s" % (tuple(pose.shape),))
+        if self.n == self.capacity:
+            self._grow()
+        im = im.to(self.device)
+        self.image_bank[self.n].copy_(im if im.dtype == torch.uint8 else im.byte())
+        self._poses[self.n] = pose
+        self.n += 1
+        return self.n - 1
+
+    @classmethod
+    def from_directory(cls, keyframes_path, device, mapping_net=None):
+        """The map of a keyframe directory as the reference and slam.NeuralSLAM write it: `rgb/*.pth` (sorted; uint8
+        [3,H,W]) and `poses.pth` ([K,12]). Every file is read once; the directory is validated (poses.pth present, as many
+        poses as frames, all frames of the first one's size) before anything touches the device.
+        With `mapping_net` the keyframes are embedded too."""
+        poses_file = os.path.join(keyframes_path, "poses.pth")
+        if not os.path.exists(poses_file):
+            raise FileNotFoundError("%s is missing: not a keyframe directory (end_odometry() writes it)" % poses_file)
+        files = sorted(glob.glob(os.path.join(keyframes_path, "rgb", "*.pth")))
+        if not files:
+            raise ValueError("%s holds no keyframe (rgb/*.pth)" % keyframes_path)
+        poses = _homogeneous(torch.load(poses_file, map_location="cpu"))
+        if len(poses) != len(files):
+            raise ValueError("%s: %d poses in poses.pth but %d frames under rgb/" % (keyframes_path, len(poses), len(files)))
+        frames, hw = [], None
+        for f in files:
+            im = torch.load(f, map_location="cpu")
+            if im.dim() == 4 and im.shape[0] == 1:
+                im = im[0]
+            if hw is None:
+                if im.dim() != 3 or im.shape[0] != 3:
+                    raise ValueError("%s: expected a [3,H,W] frame, got %s" % (f, tuple(im.shape)))
+                hw = (int(im.shape[1]), int(im.shape[2]))
+            if tuple(im.shape) != (3,) + hw:
+                raise ValueError("%s: frame of size %s in a map of %dx%d frames" % (f, tuple(im.shape), hw[0], hw[1]))
+            frames.append(im if im.dtype == torch.uint8 else im.byte())
+        m = cls(device, hw=hw, capacity=len(files))
+        for im, pose in zip(frames, poses):
+            m.append(im, pose)
+        if mapping_net is not None:
+            m.embed(mapping_net)
+        return m
+
+    @torch.no_grad()
+    def embed(self, mapping_net, batch=16):
+        """Embed the keyframes that are not embedded yet, `batch` at a time: one image gather and one `atdn_vae_encode`
+        whose output is the bank row of the first of them (no copy, no permute). Everything is embedded again when
+        `mapping_net` is another module or its weights changed since the last call (the modules' `_fingerprint()`)."""
+        fp = (id(mapping_net), mapping_net._fingerprint())
+        if self._embed_fp != fp:
+            self.n_embedded = 0
+        if self.embedding_bank is None:
+            self.embedding_bank = torch.empty((self.capacity, self.D), dtype=torch.float32, device=self.device)
+        batch = max(1, int(batch))
+        with torch.cuda.device(self.device):
+            while self.n_embedded < self.n:
+                first, b = self.n_embedded, min(batch, self.n - self.n_embedded)
+                images = gather_images(self.image_bank[:self.n], np.arange(first, first + b))
+                mapping_net.encode_rows(images, out=self.embedding_bank[first:first + b])
+                self.n_embedded = first + b
+        self._embed_fp = (id(mapping_net), mapping_net._fingerprint())   # (a handle built above does not touch the weights)
+        return self
+
+    # ------------------------------------------------------------------ reading
+    def embedding(self, k):
+        """Keyframe k's embedding as `Frame.embedding` holds it: [1,128,h,w], a (permuted) VIEW of the bank row."""
+        if not 0 <= k < self.n_embedded:
+            raise IndexError("keyframe %d is not embedded (%d of %d are)" % (k, self.n_embedded, self.n))
+        h, w = self.embedding_hw
+        return self.embedding_bank[k].view(1, h, w, 128).permute(0, 3, 1, 2)
+
+    def images(self, indices):
+        """fp32 [n,3,H,W]: `image_bank[indices].float()`, any order, repeats allowed."""
+        if self.n == 0:
+            raise RuntimeError("the map holds no keyframe")
+        return gather_images(self.image_bank[:self.n], indices)
+
+    def rows(self, mu):
+        """Queries in the bank's row order: `mu` as MappingVAE returns it, [Q,128,h,w], is permuted to channels-last
+        (`mu.permute(0, 2, 3, 1)`, then flattened); a [Q,D] tensor is taken as channels-last already (what
+        `MappingVAE.encode_rows` returns)."""
+        if mu.dim() == 4:
+            h, w = self.embedding_hw
+            if tuple(mu.shape[1:]) != (128, h, w):
+                raise RuntimeError("expected mu [Q,128,%d,%d], got %s" % (h, w, tuple(mu.shape)))
+            return mu.permute(0, 2, 3, 1).contiguous().view(mu.shape[0], self.D)
+        if mu.dim() != 2 or mu.shape[1] != self.D:
+            raise RuntimeError("expected mu [Q,128,%d,%d] or channels-last rows [Q,%d], got %s"
+                               % (self.embedding_hw + (self.D, tuple(mu.shape))))
+        return mu
+
+    def search(self, queries_mu, top_k=1):
+        """(distances [Q,K] fp32, indices [Q,top_k] int32), device tensors: distances[q, k] = torch.norm(embedding(k) - mu[q]),
+        indices[q] = the top_k nearest keyframes, ascending, equal distances by the lower index (indices[q, 0] is the
+        reference's argmin). `queries_mu`: see `rows`. 1 <= top_k <= min(K, 16)."""
+        if self.n == 0 or self.n_embedded < self.n:
+            raise RuntimeError("search: %d of %d keyframes are embedded (call embed(mapping_net) first)" % (self.n_embedded, self.n))
+        if not 1 <= int(top_k) <= min(self.n, MAX_TOP_K):
+            raise ValueError("top_k must be in [1, min(K, %d)] (K = %d), got %d" % (MAX_TOP_K, self.n, top_k))
+        return search_bank(self.embedding_bank[:self.n], self.rows(queries_mu), top_k)
+
+    @torch.no_grad()
+    def relocalize(self, images, flow_net, odometry_net, mapping_net, top_k=1, refine=True):
+        """Answer Q relocalisation queries at once (neural_slam.py:355-399 for a batch). images [Q,3,H,W] (or [3,H,W]),
+        values 0..255. Returns host tensors `distances` [Q,K], `indices` [Q,top_k] (int64), `initial` [Q,4,4] (the pose of
+        the nearest keyframe) and `refined` [Q,4,4] (= initial @ the odometry step from that keyframe's image to the query;
+        = initial when `refine` is False): one encoder call, one search, one image gather, the flow network on the Q
+        (keyframe, query) pairs in chunks of its `max_batch` (at most 16), the pose head's encoder per chunk and ONE
+        recurrent step with Q independent sequences.
+
+        Pose-head state: every query is evaluated from the reset (zero) LSTM state, and the state `odometry_net` carries
+        between its own calls is neither read nor changed. The reference's single-query call starts from whatever state
+        earlier calls left behind (neural_slam.py:396); a batch has no such order. `NeuralSLAM.__call__` keeps the
+        reference's semantics."""
+        q = images.to(self.device)
+        if q.dim() == 3:
+            q = q.unsqueeze(0)
+        if q.dim() != 4 or tuple(q.shape[1:]) != (3,) + self.hw:
+            raise RuntimeError("expected queries [Q,3,%d,%d], got %s" % (self.hw + (tuple(images.shape),)))
+        q = q.float().contiguous()
+        Q = int(q.shape[0])
+        with torch.cuda.device(self.device):
+            mu, _ = mapping_net.encode_rows(q)
+            dist, idx = self.search(mu, top_k)
+            indices = idx.cpu().long()
+            best = indices[:, 0]
+            initial = self.poses[best].clone()
+            if not refine:
+                return dist.cpu(), indices, initial, initial.clone()
+            keyframes = self.images(best)
+            chunk = max(1, min(int(getattr(flow_net, "max_batch", 1)), 16))
+            feats = []
+            for a in range(0, Q, chunk):
+                _, flow = flow_net(keyframes[a:a + chunk], q[a:a + chunk], iters=12, test_mode=True)
+                feats.append(odometry_net.encode(flow))
+            rot, tr, _ = odometry_net.scan(torch.cat(feats, dim=0)[None], state=None, hw=self.hw)
+            rot, tr = rot[0].cpu(), tr[0].cpu()
+        refined = torch.stack([initial[i] @ transforms.transform(rot[i], tr[i]) for i in range(Q)], dim=0)
+        return dist.cpu(), indices, initial, refined

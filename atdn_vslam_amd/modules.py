@@ -514,6 +514,28 @@ class MappingVAE(_NativeModule):
         return ent[0]
 
     @torch.no_grad()
+    def encode_rows(self, images, out=None):
+        """`atdn_vae_encode` as it is: images [B,3,H,W] -> mu [B, h*w*128] CHANNELS-LAST (element (y*w + x)*128 + c of a row is
+        `forward(image)[0][b, c, y, x]`), written into `out` when given — a contiguous fp32 [B, h*w*128] tensor on the images'
+        device, e.g. B consecutive rows of the keyframe map's embedding bank: no copy, no permute. Returns (rows, (h, w))."""
+        self._require_input(images, "MappingVAE.encode_rows")
+        if images.dim() != 4 or images.shape[1] != 3:
+            raise RuntimeError("expected images [B,3,H,W], got %s" % (tuple(images.shape),))
+        B, _, H, W = images.shape
+        with torch.cuda.device(images.device):
+            im = images.float().contiguous()
+            h = self._handle(H, W, B)
+            oh, ow = C.c_int(), C.c_int()
+            _lib.check(_lib.lib().atdn_vae_embedding_shape(h, C.byref(oh), C.byref(ow)))
+            D = oh.value * ow.value * 128
+            if out is None:
+                out = torch.empty((B, D), dtype=torch.float32, device=images.device)
+            if tuple(out.shape) != (B, D) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != images.device:
+                raise RuntimeError("encode_rows: out must be contiguous fp32 [%d,%d] on %s" % (B, D, images.device))
+            _lib.check(_lib.lib().atdn_vae_encode(h, _ptr(im), B, _ptr(out), _stream()))
+        return out, (oh.value, ow.value)
+
+    @torch.no_grad()
     def forward(self, image):
         self._require_input(image, "MappingVAE.forward")
         if image.dim() == 3:

@@ -71,12 +71,16 @@ class NeuralSLAM:
     odometry_weights / flow_weights / mapping_weights: checkpoint path or state dict. `flow_weights` defaults to the
     path the reference's `GMA_Parameters` names. `map_options`: keyword arguments for `mapping.create_map` when
     `end_odometry()` has to train the map itself.
+    `resident_map=True` keeps the keyframe map in device memory (keyframe_map.KeyframeMap): keyframe images and embeddings
+    sit in HBM banks, a relocalisation query searches them in one launch and takes the keyframe image from the bank instead
+    of its file, and `relocalize_batch` answers several queries per call. Files on disk and return values are the same; with
+    the default (False) nothing changes.
     """
 
     FLOW_CHECKPOINT = "atdn_vslam/checkpoints/gma-kitti.pth"  # utils/gma_parameters.py
 
     def __init__(self, args, odometry_weights=None, start_mode=None, flow_weights=None, mapping_weights=None,
-                 precision=None, map_options=None):
+                 precision=None, map_options=None, resident_map=False):
         self._args = args
         self._map_options = dict(map_options or {})   # keyword arguments of mapping.create_map (e.g. num_epochs)
         self._base = args.keyframes_path
@@ -95,6 +99,10 @@ class NeuralSLAM:
         self._keyframes = []
         self._policy = KeyframePolicy()
         self._current_pose = torch.eye(4, dtype=torch.float32)
+        self._precision = precision
+        self._resident = bool(resident_map)
+        self._map = None            # keyframe_map.KeyframeMap when resident_map=True
+        self._batch_flow_net = None  # relocalize_batch's flow handle (batch > 1), created on first use
 
         if start_mode == "mapping":
             self._load_keyframes(embed=False)
@@ -115,6 +123,9 @@ class NeuralSLAM:
                 if os.path.exists(stale_path):
                     os.remove(stale_path)
             self._mode = "idle"
+            if self._resident:
+                from .keyframe_map import KeyframeMap
+                self._map = KeyframeMap(self._device, hw=SLAM_SIZE)
 
     # ------------------------------------------------------------------ state machine
     def start_odometry(self):
@@ -142,15 +153,13 @@ class NeuralSLAM:
                 create_map(self._base, device=self._device, **self._map_options)
                 mapping_weights = default
             self._set_mapping_net(mapping_weights)
-            for kf in self._keyframes:
-                kf.embedding = self._embed(torch.load(kf.rgb_file_name))
+            self._embed_keyframes()
             self._mode = "relocalization"
         elif len(self._keyframes) == 0:
             print("There is no explored enviromnent yet!")
         elif self._mode == "mapping" and mapping_weights is not None:
             self._set_mapping_net(mapping_weights)
-            for kf in self._keyframes:
-                kf.embedding = self._embed(torch.load(kf.rgb_file_name))
+            self._embed_keyframes()
             self._mode = "relocalization"
         else:
             print("Current state is not odometry")
@@ -172,13 +181,13 @@ class NeuralSLAM:
                 self._current_pose = transforms.accumulate(self._current_pose, rot, tr)  # float32 pose @ pred_mat
                 if self._policy(pred_mat):
                     name = os.path.join(self._base, "rgb", "%06d.pth" % len(self._keyframes))
-                    torch.save(im2.to("cpu").byte(), name)
+                    self._store_keyframe(im2, name)
                     self._keyframes.append(Frame(name, self._current_pose))
                 self._image_buffer = im2
             else:
                 self._image_buffer = self._padder.pad(im)[0]
                 name = os.path.join(self._base, "rgb", "000000.pth")
-                torch.save(im.to("cpu").byte(), name)
+                self._store_keyframe(im, name)
                 self._keyframes.append(Frame(name, self._current_pose))
             return self._current_pose
         if self._mode == "relocalization":
@@ -198,6 +207,7 @@ class NeuralSLAM:
         self._odometry_net = self._odometry_net.to(device)
         if self._mapping_net is not None:
             self._mapping_net = self._mapping_net.to(device)
+        self._batch_flow_net = None   # (a resident keyframe map stays where it was built: its search names both devices)
 
     def get_keyframe(self, index):
         return self._keyframes[index]
@@ -220,20 +230,80 @@ class NeuralSLAM:
             rgb = rgb.unsqueeze(0)
         return self._mapping_net(rgb)[0]
 
+    def _store_keyframe(self, im, name):
+        """Write the keyframe's uint8 image file (neural_slam.py:213,224); with the resident map the same bytes also go into
+        the image bank, converted and copied on the device."""
+        if self._map is None:
+            torch.save(im.to("cpu").byte(), name)
+            return
+        u8 = im.byte()
+        self._map.append(u8, self._current_pose)
+        torch.save(u8.to("cpu"), name)
+
+    def _embed_keyframes(self):
+        if self._map is None:
+            for kf in self._keyframes:
+                kf.embedding = self._embed(torch.load(kf.rgb_file_name))
+            return
+        self._map.embed(self._mapping_net, batch=16)
+        for i, kf in enumerate(self._keyframes):
+            kf.embedding = self._map.embedding(i)
+
     def _load_keyframes(self, embed):
+        if self._resident:
+            from .keyframe_map import KeyframeMap
+            self._map = KeyframeMap.from_directory(self._base, self._device)
+            files = sorted(glob.glob(os.path.join(self._base, "rgb", "*.pth")))
+            self._keyframes = [Frame(f, self._map.poses[i].clone()) for i, f in enumerate(files)]
+            if embed:
+                self._embed_keyframes()
+            return
         poses = _homogeneous(torch.load(os.path.join(self._base, "poses.pth")))
         files = sorted(glob.glob(os.path.join(self._base, "rgb", "*")))
         for i, f in enumerate(files):
             code = self._embed(torch.load(f)) if embed else None
             self._keyframes.append(Frame(f, poses[i], code))
 
+    def _flow_for_batches(self):
+        if self._batch_flow_net is None:
+            net = RAFTGMA(max_batch=16, precision=self._precision, saturation_check_every=1)
+            net.load_state_dict(self._flow_net.state_dict())
+            self._batch_flow_net = net.to(self._device).eval()
+        return self._batch_flow_net
+
+    @torch.no_grad()
+    def relocalize_batch(self, images, top_k=1, refine=True):
+        """Several relocalisation queries per call (resident map only): `KeyframeMap.relocalize` with this object's
+        networks. images [Q,3,376,1232] (or a list of [3,376,1232] frames). Returns host tensors `distances` [Q,K],
+        `indices` [Q,top_k] (nearest first), `initial` [Q,4,4], `refined` [Q,4,4]. Every query is refined from the reset
+        (zero) state of the pose head, and the state the head carries between `slam(image)` calls is neither read nor
+        changed. The flow network runs on a second handle with the same weights (batches of at most 16), created on the
+        first call."""
+        if getattr(self, "_map", None) is None:
+            raise RuntimeError("relocalize_batch needs the keyframe map in device memory: construct "
+                               "NeuralSLAM(..., resident_map=True)")
+        if self._mode != "relocalization":
+            raise Exception("SLAM called in invalid state!")
+        if isinstance(images, (list, tuple)):
+            images = torch.stack([torch.as_tensor(im) for im in images], dim=0)
+        return self._map.relocalize(images, self._flow_for_batches(), self._odometry_net, self._mapping_net, top_k=top_k,
+                                    refine=refine)
+
     def _relocalize(self, image):
         mu = self._mapping_net(image)[0]
-        distances = torch.stack([torch.norm(kf.embedding - mu, p=2) for kf in self._keyframes], dim=0)
-        closest = self._keyframes[int(torch.argmin(distances))]
+        if self._map is None:
+            distances = torch.stack([torch.norm(kf.embedding - mu, p=2) for kf in self._keyframes], dim=0)
+            closest = self._keyframes[int(torch.argmin(distances))]
+            im1 = torch.load(closest.rgb_file_name).unsqueeze(0).to(self._device).float()
+        else:
+            # resident map: every distance and the nearest keyframe in one launch, its image from the bank
+            distances, nearest = self._map.search(mu, top_k=1)
+            distances = distances[0]
+            closest = self._keyframes[int(nearest[0, 0])]
+            im1 = self._map.images([int(nearest[0, 0])])
         initial_pose = closest.pose
-        # refinement: odometry between the stored keyframe image and the query (neural_slam.py:386-399)
-        im1 = torch.load(closest.rgb_file_name).unsqueeze(0).to(self._device).float()
+        # refinement: odometry between the stored keyframe image and the query (neural_slam.py:386-399); batch 1 on the
+        # low-latency flow handle and the stateful head in both cases: the reference's semantics, carried state included
         _, flow = self._flow_net(im1, image, iters=12, test_mode=True)
         pred_rot, pred_tr = self._odometry_net(flow)
         pose_diff = transforms.transform(pred_rot.squeeze().cpu(), pred_tr.squeeze().cpu())

@@ -247,6 +247,30 @@ int atdn_flow_gather_clips(const uint16_t* bank, int n_flows, int H, int W, cons
                            float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Keyframe map  —  replaces the keyframe list of NeuralSLAM's relocalisation (keyframe_map.py)
+ *   embeddings: Frame.embedding, one MappingVAE call per keyframe (slam_framework/neural_slam.py:88-103,158-164)
+ *   search:     the per-keyframe torch.norm loop, torch.stack and argmin (neural_slam.py:374-383)
+ *   images:     torch.load(rgb_file).to(device).float() of the chosen keyframe (neural_slam.py:386-390)
+ * ------------------------------------------------------------------------------------------------- */
+
+/* dist[q][k] = torch.norm(bank[k] - queries[q], p=2) (neural_slam.py:379) for every keyframe and query in one launch, then
+ * idx[q][0..topk) = the topk nearest keyframes of query q, ascending, equal distances by the lower index (idx[q][0] is
+ * torch.argmin of the reference's list, neural_slam.py:382).
+ *   bank [K][D] fp32 (a row is what atdn_vae_encode writes for one image: D = out_h * out_w * 128), queries [Q][D],
+ *   dist [Q][K] fp32, idx [Q][topk] int32; all DEVICE. D % 4 == 0, bank and queries 16-byte aligned, K >= 1, any Q >= 1
+ *   (16 queries share one pass over the bank), 1 <= topk <= min(K, 16); anything else fails before a launch.
+ * The difference is formed first and squared (no |a|^2 + |b|^2 - 2ab expansion): a row equal to the query gives exactly 0.
+ * The summation order is fixed (keyframe_map.hip), so dist[q][k] depends on row k and query q alone: the same bits whatever
+ * Q, K, the row's slot or the other queries are. Relative error of a distance <= 2.3e-6 for D <= 16384. */
+int atdn_map_search(const float* bank, int K, int D, const float* queries, int Q, int topk, float* dist, int* idx, void* stream);
+
+/* out[j] = float(bank[index_host[j]]): uint8 keyframe images of the image bank as the fp32 batch the VAE encoder and the
+ * flow network read. bank [K][plane_bytes] uint8 (plane_bytes = 3 * H * W, a multiple of 16; DEVICE, 16-byte aligned),
+ * out [n][plane_bytes] fp32 (DEVICE, 16-byte aligned). `index_host` is a HOST array of n ints, each checked against
+ * [0, K) before anything is launched; repeated and unordered indices are fine. Exact. */
+int atdn_map_gather_images_u8(const uint8_t* bank, int K, long plane_bytes, const int* index_host, int n, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Individual kernels, exported for unit parity tests and roofline micro-benchmarks
  * ------------------------------------------------------------------------------------------------- */
 
