@@ -26,6 +26,11 @@ SIGNATURES = {
     "atdn_gma_debug_read": (C.c_long, [_vp, C.c_char_p, _vp, C.c_long, _vp]),
     "atdn_gma_profile": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _f32p, _vp]),
     "atdn_gma_profile_mode": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _vp]),
+    "atdn_gma_set_range_probe": (C.c_int, [_vp, C.c_int]),
+    "atdn_gma_range_rows": (C.c_long, [_vp]),
+    "atdn_gma_range_row": (C.c_int, [_vp, C.c_long, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _f32p, _i64p, _i64p]),
+    "atdn_range_probe": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _f32p, _i64p, _i64p, _vp]),
+    "atdn_range_probe_launch": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
     "atdn_gma_workspace_bytes": (C.c_size_t, [_vp]),
     "atdn_gma_destroy": (None, [_vp]),
     "atdn_clvo_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int]),

@@ -2,6 +2,7 @@
 #include "../../include/atdn_hip.h"
 
 #include <cmath>
+#include <cstring>
 
 #include "clvo.h"
 #include "gma.h"
@@ -150,6 +151,57 @@ int atdn_gma_profile_mode(atdn_gma* h, int B, int iters, int reps, int mode, flo
   ATDN_CHECK(h && ms_out, "null argument");
   ATDN_CHECK(mode >= 0 && mode <= 2, "mode must be 0 (pair), 1 (sequence) or 2 (continued sequence)");
   h->net.profile(B, iters, reps, ms_out, (hipStream_t)stream, mode);
+  ATDN_API_END
+}
+int atdn_gma_set_range_probe(atdn_gma* h, int on) {
+  ATDN_API_BEGIN
+  ATDN_CHECK(h, "null handle");
+  h->net.set_probe(on != 0);
+  ATDN_API_END
+}
+long atdn_gma_range_rows(atdn_gma* h) {
+  if (!h) { set_last_error("null handle"); return -1; }
+  return (long)h->net.probe_rows().size();
+}
+int atdn_gma_range_row(atdn_gma* h, long index, char* name, int name_capacity, int* iteration, int* limited, float* max_abs,
+                       int64_t* over, int64_t* nonfinite) {
+  ATDN_API_BEGIN
+  ATDN_CHECK(h && name && iteration && limited && max_abs && over && nonfinite, "null argument");
+  const auto& rows = h->net.probe_rows();
+  ATDN_CHECK(index >= 0 && index < (long)rows.size(), "row index out of range");
+  const GmaNet::ProbeRow& r = rows[(size_t)index];
+  ATDN_CHECK(name_capacity > (int)r.name.size(), "name buffer too small");
+  memcpy(name, r.name.c_str(), r.name.size() + 1);
+  *iteration = r.iter; *limited = r.limited ? 1 : 0; *max_abs = r.max_abs;
+  *over = (int64_t)r.over; *nonfinite = (int64_t)r.nonfinite;
+  ATDN_API_END
+}
+int atdn_range_probe_launch(const float* x, int64_t rows, int64_t cols, int64_t ld, void* slot, void* stream) {
+  ATDN_API_BEGIN
+  launch_range_probe(x, (long)rows, (long)cols, (long)ld, static_cast<RangeSlot*>(slot), (hipStream_t)stream);
+  ATDN_API_END
+}
+int atdn_range_probe(const float* x, int64_t rows, int64_t cols, int64_t ld, float* max_abs, int64_t* over, int64_t* nonfinite,
+                     void* stream) {
+  ATDN_API_BEGIN
+  ATDN_CHECK(x && max_abs && over && nonfinite, "null argument");
+  hipStream_t st = (hipStream_t)stream;
+  RangeSlot* slot = nullptr;
+  RangeSlot host{};
+  ATDN_HIP(hipMalloc(&slot, sizeof(RangeSlot)));
+  try {
+    ATDN_HIP(hipMemsetAsync(slot, 0, sizeof(RangeSlot), st));
+    launch_range_probe(x, (long)rows, (long)cols, (long)ld, slot, st);
+    ATDN_HIP(hipMemcpyAsync(&host, slot, sizeof(RangeSlot), hipMemcpyDeviceToHost, st));
+    ATDN_HIP(hipStreamSynchronize(st));
+  } catch (...) {
+    (void)hipFree(slot);
+    throw;
+  }
+  (void)hipFree(slot);
+  memcpy(max_abs, &host.max_bits, sizeof(float));
+  *over = (int64_t)host.over;
+  *nonfinite = (int64_t)host.nonfinite;
   ATDN_API_END
 }
 size_t atdn_gma_workspace_bytes(atdn_gma* h) { return h ? h->net.workspace_bytes() : 0; }

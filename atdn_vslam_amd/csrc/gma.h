@@ -7,6 +7,7 @@
 #include "attention.h"
 #include "conv_dispatch.h"
 #include "kernels.h"
+#include "range_probe.h"
 #include "weights.h"
 
 namespace atdn {
@@ -90,7 +91,24 @@ class GmaNet {
   BrickPyramid brick_pyramid() const;
   DeviceBuf rowmax_, rinv_;
 
+  // Range probe (exact-fp32 handles only; DESIGN.md "Range report"). While it is on, forward() and forward_predictions() launch
+  // eagerly and run launch_range_probe (range_probe.h) on the valid part of every tensor the path has just written: one row per
+  // tensor written outside the loop, one per iteration for those written inside it, in execution order. `limited`: the default
+  // (split-f16) path keeps this tensor, or values that are this tensor's one to one, in the range-limited sf format (sf.h).
+  // Off (the default) the handle launches exactly what it launched before the probe existed.
+  struct ProbeRow { std::string name; int iter; bool limited; float max_abs; long long over, nonfinite; };
+  static constexpr int kProbeMaxRows = 1536;   // < 100 rows outside the loop + 19 per iteration x 64 iterations at the most
+  void set_probe(bool on);
+  const std::vector<ProbeRow>& probe_rows() const { return probe_rows_; }
+
  private:
+  bool probe_ = false;
+  int probe_it_ = -1;                 // iteration the rows being recorded belong to (-1: outside the loop)
+  RangeSlot* probe_slots_ = nullptr;  // [kProbeMaxRows] device slots, zeroed on the stream at the start of a probed forward
+  std::vector<ProbeRow> probe_rows_;
+  void probe_begin(hipStream_t st);
+  void probe_end(hipStream_t st);     // one copy of the slot table back, then the stream is synchronised
+  void probe(const std::string& name, bool limited, const float* p, long rows, long cols, long ld, hipStream_t st);
   void run_body(int B, int iters, hipStream_t st);  // everything between input prep and upsampling
   void run_encoder(const EncoderWeights& E, bool instance, int nimg, hipStream_t st, float** out_buf, int* outH,
                    int* outW);

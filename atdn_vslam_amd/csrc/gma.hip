@@ -110,6 +110,7 @@ void GmaNet::mark(int stage, hipStream_t st) {
 void GmaNet::profile(int B, int iters, int reps, float* ms, hipStream_t st, int mode) {
   ATDN_CHECK(ready_ && B >= 1 && B <= maxB && reps >= 1, "bad profile request");
   ATDN_CHECK(mode == 0 || precision >= 1, "sequence modes are built for the split-f16 pipeline");
+  ATDN_CHECK(!probe_, "switch the range probe off before profiling: its launches would be timed with the stages");
   for (int i = 0; i < ST_COUNT; ++i) ms[i] = 0.f;
   seq_ = mode;   // 0 pair, 1 sequence, 2 continued sequence (fmap_ slot 0 is read as it stands: timing only)
   last_frame_ = 0;   // fmap_ is overwritten: a continued sequence call must not read it
@@ -174,7 +175,43 @@ GmaNet::~GmaNet() {
                       &fbrick_[0], &fbrick_[1], &fbrick_[2], &fbrick_[3], &fplain_[0], &fplain_[1], &fplain_[2], &coords_used_, &fhG_,
                       &attn_part_, &enc2_[0], &enc2_[1], &enc2_[2], &enc2_[3]};
   for (auto* b : all) b->release();
+  if (probe_slots_) (void)hipFree(probe_slots_);
   arena_.release();
+}
+
+// ---------------------------------------------------------------- range probe (gma.h)
+void GmaNet::set_probe(bool on) {
+  ATDN_CHECK(!on || precision == 0,
+             "the range probe needs an exact-fp32 handle (ATDN_PRECISION_F32): only that path writes every intermediate tensor "
+             "as plain fp32 and never clamps; the split-f16 / f16 paths store range-limited values and fuse some tensors away");
+  probe_ = on;
+}
+
+void GmaNet::probe_begin(hipStream_t st) {
+  if (!probe_slots_) ATDN_HIP(hipMalloc(&probe_slots_, kProbeMaxRows * sizeof(RangeSlot)));
+  ATDN_HIP(hipMemsetAsync(probe_slots_, 0, kProbeMaxRows * sizeof(RangeSlot), st));
+  probe_rows_.clear();
+  probe_it_ = -1;
+}
+
+void GmaNet::probe(const std::string& name, bool limited, const float* p, long rows, long cols, long ld, hipStream_t st) {
+  ATDN_CHECK((int)probe_rows_.size() < kProbeMaxRows, "range probe: slot table full");
+  launch_range_probe(p, rows, cols, ld, probe_slots_ + probe_rows_.size(), st);
+  probe_rows_.push_back({name, probe_it_, limited, 0.f, 0, 0});
+}
+
+void GmaNet::probe_end(hipStream_t st) {
+  std::vector<RangeSlot> host(probe_rows_.size());
+  if (!host.empty())
+    ATDN_HIP(hipMemcpyAsync(host.data(), probe_slots_, host.size() * sizeof(RangeSlot), hipMemcpyDeviceToHost, st));
+  ATDN_HIP(hipStreamSynchronize(st));
+  for (size_t i = 0; i < host.size(); ++i) {
+    ProbeRow& r = probe_rows_[i];
+    static_assert(sizeof(float) == sizeof(unsigned int), "fp32");
+    memcpy(&r.max_abs, &host[i].max_bits, sizeof(float));
+    r.over = (long long)host[i].over;
+    r.nonfinite = (long long)host[i].nonfinite;
+  }
 }
 
 void GmaNet::finalize() {
@@ -340,15 +377,25 @@ void GmaNet::run_encoder(const EncoderWeights& E, bool instance, int nimg, hipSt
   };
   using TapT = std::integral_constant<int, MODE_TAP>;
   using RowT = std::integral_constant<int, MODE_ROW>;
+  // range probe (gma.h): the tensor just written, [nimg * pixels][channels] without pitch padding, under the reference's module
+  // path; bi < 0: the stem. `.raw`: convolution + bias in front of InstanceNorm (fp32 on the default path too: not limited).
+  auto pr = [&](int bi, const char* leaf, bool limited, const float* p, long pixels, int ch) {
+    if (!probe_) return;
+    std::string name = instance ? "fnet." : "cnet.";
+    if (bi >= 0) name += "layer" + std::to_string(bi / 2 + 1) + "." + std::to_string(bi % 2);
+    probe(name + leaf, limited, p, (long)nimg * pixels, ch, ch, st);
+  };
 
   // stem: conv 7x7/2 + norm + relu
   if (instance) {
     stats_conv(RowT{}, E.stem, img4_.p, 4, H, W, 2, 3, P, 0);
+    pr(-1, "conv1.raw", false, P, (long)h * w, 64);
     launch_in_apply(P, mean_[0].p, rstd_[0].p, nullptr, nullptr, nullptr, nimg, (long)h * w, 64, st);
   } else {
     ConvShape s = conv_shape(E.stem, img4_.p, 4, (long)H * W * 4, nimg, H, W, 2, 3, 3);
     conv_dispatch<MODE_ROW>(s, EpiBias<ACT_RELU>{E.stem.b, P, (long)h * w * 64, 64, 1.f}, st);
   }
+  pr(-1, "conv1.out", true, P, (long)h * w, 64);
   int c = 64;
   for (int bi = 0; bi < 6; ++bi) {
     const auto& Bk = E.blk[bi];
@@ -358,10 +405,14 @@ void GmaNet::run_encoder(const EncoderWeights& E, bool instance, int nimg, hipSt
     const long ohw = (long)oh * ow;
     if (instance) {
       stats_conv(TapT{}, Bk.c1, P, c, h, w, stride, 1, Q, 0);
+      pr(bi, ".conv1.raw", false, Q, ohw, co);
       launch_in_apply(Q, mean_[0].p, rstd_[0].p, nullptr, nullptr, nullptr, nimg, ohw, co, st);
+      pr(bi, ".conv1.out", true, Q, ohw, co);
       stats_conv(TapT{}, Bk.c2, Q, co, oh, ow, 1, 1, R, 0);
+      pr(bi, ".conv2.raw", false, R, ohw, co);
       if (Bk.has_ds) {
         stats_conv(TapT{}, Bk.ds, P, c, h, w, 2, 0, Q, 1);
+        pr(bi, ".downsample.raw", false, Q, ohw, co);
         launch_in_apply(R, mean_[0].p, rstd_[0].p, Q, mean_[1].p, rstd_[1].p, nimg, ohw, co, st);
       } else {
         launch_in_apply(R, mean_[0].p, rstd_[0].p, P, nullptr, nullptr, nimg, ohw, co, st);
@@ -370,10 +421,12 @@ void GmaNet::run_encoder(const EncoderWeights& E, bool instance, int nimg, hipSt
     } else {
       ConvShape s1 = conv_shape(Bk.c1, P, c, (long)h * w * c, nimg, h, w, stride, 1, 1);
       conv_dispatch<MODE_TAP>(s1, EpiBias<ACT_RELU>{Bk.c1.b, Q, ohw * co, co, 1.f}, st);
+      pr(bi, ".conv1.out", true, Q, ohw, co);
       ConvShape s2 = conv_shape(Bk.c2, Q, co, ohw * co, nimg, oh, ow, 1, 1, 1);
       if (Bk.has_ds) {
         ConvShape sd = conv_shape(Bk.ds, P, c, (long)h * w * c, nimg, h, w, 2, 0, 0);
         conv_dispatch<MODE_TAP>(sd, EpiBias<ACT_NONE>{Bk.ds.b, R, ohw * co, co, 1.f}, st);
+        pr(bi, ".downsample.out", true, R, ohw, co);
         // P (the block input) is dead once the downsample conv has read it: reuse it for the output
         conv_dispatch<MODE_TAP>(s2, EpiBiasReluAddRelu{Bk.c2.b, R, ohw * co, co, P, ohw * co, co}, st);
       } else {
@@ -381,6 +434,7 @@ void GmaNet::run_encoder(const EncoderWeights& E, bool instance, int nimg, hipSt
         std::swap(P, R);
       }
     }
+    pr(bi, "", true, P, ohw, co);   // the block's output
     h = oh; w = ow; c = co;
   }
   *out_buf = P; *outH = h; *outW = w;
@@ -393,31 +447,43 @@ void GmaNet::iteration(int B, hipStream_t st) {
   for (int l = 0; l < 4; ++l) { pl.base[l] = pyr_[l].p; pl.H[l] = pyrH_[l]; pl.W[l] = pyrW_[l]; }
   launch_lookup(pl, coords1_.p, n8, corrfeat_.p, CORR_LD, st);
   mark(ST_LOOKUP, st);
+  // range probe (gma.h): the valid channels of what the launch above has just written; a no-op unless the probe is on
+  auto pr = [&](const char* name, bool limited, const float* p, long rows, long cols, long ld) {
+    if (probe_) probe(name, limited, p, rows, cols, ld, st);
+  };
+  pr("corr_lookup", true, corrfeat_.p, n8, 324, CORR_LD);
 
   // -- motion encoder (update.py:76-84); torch.cat is realised by writing channel slices
   ConvShape s = conv_shape(convc1_, corrfeat_.p, CORR_LD, (long)N * CORR_LD, B, H8, W8, 1, 0, 0);
   conv_dispatch<MODE_TAP>(s, EpiBias<ACT_RELU>{convc1_.b, cor1_.p, (long)N * 256, 256, 1.f}, st);
   mark(ST_CONVC1, st);
+  pr("encoder.convc1", true, cor1_.p, n8, 256, 256);
   s = conv_shape(convc2_, cor1_.p, 256, (long)N * 256, B, H8, W8, 1, 1, 1);
   conv_dispatch<MODE_TAP>(s, EpiBias<ACT_RELU>{convc2_.b, corflo_.p, (long)N * 256, 256, 1.f}, st);
+  pr("encoder.convc2", true, corflo_.p, n8, convc2_.N, 256);
   s = conv_shape(convf1_, flow4_.p, 4, (long)N * 4, B, H8, W8, 1, 3, 3);
   conv_dispatch<MODE_ROW>(s, EpiBias<ACT_RELU>{convf1_.b, flo1_.p, (long)N * 128, 128, 1.f}, st);
+  pr("encoder.convf1", true, flo1_.p, n8, 128, 128);
   s = conv_shape(convf2_, flo1_.p, 128, (long)N * 128, B, H8, W8, 1, 1, 1);
   conv_dispatch<MODE_TAP>(s, EpiBias<ACT_RELU>{convf2_.b, corflo_.p + 192, (long)N * 256, 256, 1.f}, st);
+  pr("encoder.convf2", true, corflo_.p + 192, n8, convf2_.N, 256);
   s = conv_shape(convm_, corflo_.p, 256, (long)N * 256, B, H8, W8, 1, 1, 1);
   float* mf = x_.p + 128;  // motion_features: 126 conv channels + 2 flow channels (written by the flow update)
   conv_dispatch<MODE_TAP>(s, EpiBias<ACT_RELU>{convm_.b, mf, (long)N * XLD, XLD, 1.f}, st);
   mark(ST_MOTION, st);
+  pr("encoder.conv", true, mf, n8, convm_.N, XLD);
 
   // -- global motion aggregation (gma.py:102-115): v^T, then attn @ v with the residual fused
   s = conv_shape(to_v_, mf, XLD, (long)N * XLD, B, H8, W8, 1, 0, 0);
   conv_dispatch<MODE_TAP>(s, EpiStoreT{vT_.p, (long)128 * ldN, ldN}, st);
   mark(ST_AGG_VT, st);
+  pr("aggregator.to_v", true, vT_.p, (long)B * 128, N, ldN);   // stored transposed: [pair][channel][pixel]
   ConvShape a;
   a.src0 = attn_.p; a.ld0 = ldN; a.sb0 = (long)N * ldN; a.C0 = ldN; a.H = 1; a.W = N;
   a.w = vT_.p; a.wb = (long)128 * ldN; a.ldw = ldN; a.N = 128; a.nimg = B;
   conv_dispatch<MODE_TAP>(a, EpiAggregate{gamma_, mf, (long)N * XLD, XLD, x_.p + 256, (long)N * XLD, XLD}, st);
   mark(ST_AGG, st);
+  pr("aggregator.out", true, x_.p + 256, n8, 128, XLD);
 
   // -- separable ConvGRU (update.py:48-63): horizontal (1x5) then vertical (5x1)
   for (int p = 0; p < 2; ++p) {
@@ -428,18 +494,24 @@ void GmaNet::iteration(int B, hipStream_t st) {
     g.C0 = 128; g.src1 = x_.p; g.ld1 = XLD; g.sb1 = (long)N * XLD; g.C1 = XLD;
     conv_dispatch<MODE_TAP>(g, EpiGruZR{gru_zr_[p].b, hin, z_.p, rh_.p, (long)N * 128}, st);
     mark(p ? ST_GRU_ZR_V : ST_GRU_ZR, st);
+    pr(p ? "gru.z2" : "gru.z1", false, z_.p, n8, 128, 128);   // (z stays fp32 on the default path: epilogues_sf.h, SfGruZR)
+    pr(p ? "gru.rh2" : "gru.rh1", true, rh_.p, n8, 128, 128);
     g.src0 = rh_.p; g.w = gru_q_[p].w; g.ldw = gru_q_[p].ldw; g.N = gru_q_[p].N;
     conv_dispatch<MODE_TAP>(g, EpiGruQ{gru_q_[p].b, hin, z_.p, hout, (long)N * 128}, st);
     mark(p ? ST_GRU_Q_V : ST_GRU_Q, st);
+    pr(p ? "gru.h2" : "gru.h1", true, hout, n8, 128, 128);
   }
   // two passes: the state is back in h_[0]
 
   // -- flow head (update.py:7-15) and coordinate update (network.py:116)
   s = conv_shape(fh1_, h_[0].p, 128, (long)N * 128, B, H8, W8, 1, 1, 1);
   conv_dispatch<MODE_TAP>(s, EpiBias<ACT_RELU>{fh1_.b, fh_.p, (long)N * 256, 256, 1.f}, st);
+  pr("flow_head.conv1", true, fh_.p, n8, 256, 256);
   s = conv_shape(fh2_, fh_.p, 256, (long)N * 256, B, H8, W8, 1, 1, 1);
   conv_dispatch<MODE_TAP>(s, EpiFlowDelta{fh2_.b, coords1_.p, flow4_.p, x_.p + 254, XLD, (long)N * XLD, W8, (long)N}, st);
   mark(ST_FLOWHEAD, st);
+  pr("flow", true, flow4_.p, n8, 2, 4);         // coords1 - coords0; the same two values go into x[:, 254:256]
+  pr("coords1", false, coords1_.p, n8, 2, 2);
 }
 
 void GmaNet::run_body(int B, int iters, hipStream_t st) {
@@ -450,6 +522,12 @@ void GmaNet::run_body(int B, int iters, hipStream_t st) {
   ConvShape s = conv_shape(fnet_.head, f, 128, (long)N * 128, 2 * B, H8, W8, 1, 0, 0);
   conv_dispatch<MODE_TAP>(s, EpiBias<ACT_NONE>{fnet_.head.b, fmap_.p, (long)N * 256, 256, 1.f}, st);
   mark(ST_FNET, st);
+  // range probe (gma.h): a no-op unless the probe is on. Only what this forward wrote: the pairs 0..B-1 of buffers sized for
+  // max_batch, the N valid columns of rows with pitch ldN.
+  auto pr = [&](const char* name, bool limited, const float* p, long rows, long cols, long ld) {
+    if (probe_) probe(name, limited, p, rows, cols, ld, st);
+  };
+  pr("fnet.conv2", true, fmap_.p, 2L * B * N, 256, 256);
 
   // ---- all-pairs correlation (corr.py:55-63) and its 4-level pyramid (corr.py:28-30)
   ConvShape c;
@@ -457,7 +535,12 @@ void GmaNet::run_body(int B, int iters, hipStream_t st) {
   c.w = fmap_.p + (long)B * N * 256; c.wb = (long)N * 256; c.ldw = 256; c.N = N; c.nimg = B;
   conv_dispatch<MODE_TAP>(c, EpiScale{1.0f / sqrtf(256.0f), pyr_[0].p, (long)N * N, N}, st);
   mark(ST_CORR, st);
-  for (int l = 1; l < 4; ++l) launch_avgpool(pyr_[l - 1].p, pyrH_[l - 1], pyrW_[l - 1], pyr_[l].p, (long)B * N, st);
+  // (the default path's bricked pyramid is plain fp32 too, corr_bricks.hip: the volume is not limited, its SAMPLES are)
+  pr("corr.0", false, pyr_[0].p, (long)B * N, N, N);
+  for (int l = 1; l < 4; ++l) {
+    launch_avgpool(pyr_[l - 1].p, pyrH_[l - 1], pyrW_[l - 1], pyr_[l].p, (long)B * N, st);
+    if (probe_) probe("corr." + std::to_string(l), false, pyr_[l].p, (long)B * N, (long)pyrH_[l] * pyrW_[l], (long)pyrH_[l] * pyrW_[l], st);
+  }
   mark(ST_POOL, st);
 
   // ---- context network on im1 (network.py:94-97): tanh -> hidden state, relu -> x[:, 0:128]
@@ -465,25 +548,35 @@ void GmaNet::run_body(int B, int iters, hipStream_t st) {
   s = conv_shape(cnet_.head, f, 128, (long)N * 128, B, H8, W8, 1, 0, 0);
   conv_dispatch<MODE_TAP>(s, EpiContextSplit{cnet_.head.b, h_[0].p, (long)N * 128, x_.p, (long)N * XLD, XLD}, st);
   mark(ST_CNET, st);
+  pr("net0", true, h_[0].p, (long)B * N, 128, 128);
+  pr("inp", true, x_.p, (long)B * N, 128, XLD);
 
   // ---- attention (gma.py:54-76): q,k projection, q·k^T, row softmax
   s = conv_shape(to_qk_, x_.p, XLD, (long)N * XLD, B, H8, W8, 1, 0, 0);
   conv_dispatch<MODE_TAP>(s, EpiQK{1.0f / sqrtf(128.0f), 128, qk_.p, (long)N * 256, 256}, st);
+  pr("att.qk", true, qk_.p, (long)B * N, 256, 256);
   ConvShape q;
   q.src0 = qk_.p; q.ld0 = 256; q.sb0 = (long)N * 256; q.C0 = 128; q.H = 1; q.W = N;
   q.w = qk_.p + 128; q.wb = (long)N * 256; q.ldw = 256; q.N = N; q.nimg = B;
   conv_dispatch<MODE_TAP>(q, EpiScale{1.0f, attn_.p, (long)N * ldN, ldN}, st);
   mark(ST_ATTN_LOGITS, st);
+  // (the default path never has the logits in memory, attention.hip: not limited; of the attention matrix it stores
+  // exp(s - max) <= 1 in its own operand format and the row sums in fp32, not the normalised rows probed here)
+  pr("att.logits", false, attn_.p, (long)B * N, N, ldN);
   launch_softmax_rows(attn_.p, (long)B * N, N, ldN, st);
   mark(ST_ATTN, st);
+  pr("att.attn", false, attn_.p, (long)B * N, N, ldN);
 
   for (int it = 0; it < iters; ++it) {
+    probe_it_ = it;
     iteration(B, st);
     if (preds_out_) {   // forward_predictions: every iteration's flow through its own mask (network.py:118-124)
       mask_head(B, st);
       launch_upsample(mask_.p, flow4_.p, B, H8, W8, nullptr, preds_out_ + it * preds_stride_, st);
+      pr("flow_up", false, preds_out_ + it * preds_stride_, 1, preds_stride_, preds_stride_);
     }
   }
+  probe_it_ = -1;
   // ---- mask head, once (update.py:120-123,138): only the last iteration's mask reaches the output
   if (!preds_out_) mask_head(B, st);
   mark(ST_MASK, st);
@@ -492,8 +585,10 @@ void GmaNet::run_body(int B, int iters, hipStream_t st) {
 void GmaNet::mask_head(int B, hipStream_t st) {
   ConvShape s = conv_shape(mask0_, h_[0].p, 128, (long)N * 128, B, H8, W8, 1, 1, 1);
   conv_dispatch<MODE_TAP>(s, EpiBias<ACT_RELU>{mask0_.b, fh_.p, (long)N * 256, 256, 1.f}, st);
+  if (probe_) probe("mask.0", true, fh_.p, (long)B * N, 256, 256, st);
   s = conv_shape(mask2_, fh_.p, 256, (long)N * 256, B, H8, W8, 1, 0, 0);
   conv_dispatch<MODE_TAP>(s, EpiBias<ACT_NONE>{mask2_.b, mask_.p, (long)N * 576, 576, 0.25f}, st);
+  if (probe_) probe("mask", false, mask_.p, (long)B * N, 576, 576, st);   // (fp32 on the default path too: mask_head_sf)
 }
 
 // =============================================================== split-f16 pipeline (precision == 1)
@@ -822,7 +917,7 @@ void GmaNet::forward_sequence(const float* frames, int B, int iters, const float
 
 void GmaNet::launch_body(int B, int iters, hipStream_t st) {
   last_B_ = B;
-  if (use_graph_) {
+  if (use_graph_ && !probe_) {   // (a probed forward is launched kernel by kernel: the probe rows are recorded as it goes)
     auto key = std::make_pair(B, iters * 4 + seq_);
     if (!graphs_.count(key)) capture(B, iters);
     ATDN_HIP(hipGraphLaunch(graphs_[key], st));
@@ -839,11 +934,21 @@ void GmaNet::forward(const float* im1, const float* im2, int B, int iters, const
   ATDN_CHECK(im1 && im2 && flow_low && flow_up, "null tensor");
   seq_ = 0;
   last_frame_ = 0;   // pair mode overwrites fmap_: a later continued sequence call fails loudly instead of reading it
+  if (probe_) probe_begin(st);
   launch_prep_images(im1, im2, B, H, W, img4_.p, st, B);
   if (precision >= 1) launch_init_coords_sf(flow_init, B, H8, W8, coords1_.p, flow4_.p, x_.p, XLD, 254, st);
   else launch_init_coords(flow_init, B, H8, W8, coords1_.p, flow4_.p, x_.p + 254, XLD, st);
+  if (probe_) {   // (probe_ implies the exact-fp32 path)
+    probe("image", true, img4_.p, 2L * B * H * W, 3, 4, st);    // 2 (x / 255) - 1; the stems split it on load (stem_sf.hip)
+    probe("flow_init", true, flow4_.p, (long)B * N, 2, 4, st);
+  }
   launch_body(B, iters, st);
   launch_upsample(mask_.p, flow4_.p, B, H8, W8, flow_low, flow_up, st);
+  if (probe_) {
+    probe("flow_low", false, flow_low, 1, 2L * B * N, 2L * B * N, st);
+    probe("flow_up", false, flow_up, 1, 2L * B * H * W, 2L * B * H * W, st);
+    probe_end(st);
+  }
 }
 
 void GmaNet::forward_predictions(const float* im1, const float* im2, int B, int iters, const float* flow_init, float* preds,
@@ -855,15 +960,21 @@ void GmaNet::forward_predictions(const float* im1, const float* im2, int B, int 
   seq_ = 0;
   last_frame_ = 0;
   last_B_ = B;
+  if (probe_) probe_begin(st);
   launch_prep_images(im1, im2, B, H, W, img4_.p, st, B);
   if (precision >= 1) launch_init_coords_sf(flow_init, B, H8, W8, coords1_.p, flow4_.p, x_.p, XLD, 254, st);
   else launch_init_coords(flow_init, B, H8, W8, coords1_.p, flow4_.p, x_.p + 254, XLD, st);
+  if (probe_) {
+    probe("image", true, img4_.p, 2L * B * H * W, 3, 4, st);
+    probe("flow_init", true, flow4_.p, (long)B * N, 2, 4, st);
+  }
   struct Guard {   // the body reads the destination from the handle: never leave it set behind an exception
     GmaNet* n; ~Guard() { n->preds_out_ = nullptr; n->preds_stride_ = 0; }
   } guard{this};
   preds_out_ = preds;
   preds_stride_ = (long)B * 2 * H * W;
   if (precision >= 1) { FastGuard fg(precision == 2); run_body_sf(B, iters, st); } else run_body(B, iters, st);
+  if (probe_) probe_end(st);
 }
 
 BrickPyramid GmaNet::brick_pyramid() const {

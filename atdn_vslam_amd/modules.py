@@ -368,6 +368,94 @@ class RAFTGMA(_NativeModule):
             self._stream_tail = (cur, cur._version, ent[0].value)   # (holds `cur`: its storage cannot be handed to another tensor)
         return low, up
 
+    def _read_counter(self, handle, who):
+        """Reads (and resets) the device's saturation counter through `handle` and publishes a non-zero count in the per-device
+        ledger exactly as check_saturation does; returns the count. Nothing is raised and no module's bookkeeping is touched."""
+        out = torch.empty(1, dtype=torch.float32)
+        n = _lib.lib().atdn_gma_debug_read(handle, b"sf_clamped", C.c_void_p(out.data_ptr()), 1, _stream())
+        if n < 0:
+            _lib.check(1)
+        fresh = int(out[0])
+        if fresh:
+            led = _SAT_LEDGER.setdefault(self._device().index, {"events": 0, "count": 0, "reader": None})
+            led["events"] += 1
+            led["count"] += fresh
+            led["reader"] = who
+        return fresh
+
+    @torch.no_grad()
+    def range_report(self, image1, image2, iters=12, flow_init=None, check_default=True):
+        """How far this checkpoint's activations are from the limit of the split-f16 format on these frames — BEFORE anything
+        clamps (range_report.RangeReport; `python -m atdn_vslam_amd.range_report` is the command-line form). Works on a module of
+        any precision and leaves it alone: the frames go through PRIVATE handles — an exact-fp32 one (max_batch = B) with the
+        library's range probe on, which reduces every tensor that path writes to (max |x|, values beyond 65504, non-finite
+        values) on the device, and, with `check_default`, a split-f16 one whose clamp count on the same frames is read — loaded
+        with the module's current weights and destroyed before the call returns. `precision`, the module's own handles,
+        `fell_back`, `saturation_checks`, a forward_consecutive chain in progress and the bits of every later forward are
+        unchanged. The saturation counter is one per device: what it held before the private run belongs to earlier forwards and
+        is published in the ledger for the modules that own them; what the private run adds is published too (never swallowed)
+        and answered for by this module through the report — nothing is raised from here."""
+        import time
+        from .range_report import RangeReport
+        self._require_input(image1, "RAFTGMA.range_report")
+        if image1.shape != image2.shape or image1.dim() != 4 or image1.shape[1] != 3:
+            raise RuntimeError("expected two [B,3,H,W] frames, got %s and %s" % (tuple(image1.shape), tuple(image2.shape)))
+        B, _, H, W = image1.shape
+        L = _lib.lib()
+        t0 = time.perf_counter()
+        with torch.cuda.device(image1.device):
+            im1 = image1.float().contiguous()
+            im2 = image2.float().contiguous()
+            fi = None
+            if flow_init is not None:
+                fi = flow_init.to(image1.device).float().contiguous()
+                if tuple(fi.shape) != (B, 2, H // 8, W // 8):
+                    raise RuntimeError("flow_init must be [B,2,H/8,W/8]")
+            state = self.state_dict()
+
+            def run(precision, probe):
+                """One forward on a private handle; returns (flow_up, rows or None, clamp count or None)."""
+                h = C.c_void_p()
+                _lib.check(L.atdn_gma_create(C.byref(h), H, W, B, self.PRECISIONS[precision]))
+                try:
+                    _lib.load_state(L.atdn_gma_load, h, state)
+                    _lib.check(L.atdn_gma_finalize(h))
+                    who = "RAFTGMA.range_report handle %#x (%s, %dx%d)" % (h.value or 0, precision, H, W)
+                    if probe:
+                        _lib.check(L.atdn_gma_set_range_probe(h, 1))
+                    else:
+                        self._read_counter(h, who)   # clamps of earlier forwards on this device: theirs, not this run's
+                    low = torch.empty((B, 2, H // 8, W // 8), dtype=torch.float32, device=image1.device)
+                    up = torch.empty((B, 2, H, W), dtype=torch.float32, device=image1.device)
+                    _lib.check(L.atdn_gma_forward(h, _ptr(im1), _ptr(im2), B, int(iters), _ptr(fi), _ptr(low), _ptr(up), _stream()))
+                    if not probe:
+                        return up, None, self._read_counter(h, who)
+                    n = L.atdn_gma_range_rows(h)
+                    if n < 0:
+                        _lib.check(1)
+                    rows = []
+                    name = C.create_string_buffer(128)
+                    it, lim, mx = C.c_int(), C.c_int(), C.c_float()
+                    over, nonf = C.c_int64(), C.c_int64()
+                    for i in range(n):
+                        _lib.check(L.atdn_gma_range_row(h, i, name, len(name), C.byref(it), C.byref(lim), C.byref(mx),
+                                                        C.byref(over), C.byref(nonf)))
+                        rows.append((name.value.decode(), it.value, bool(lim.value), mx.value, over.value, nonf.value))
+                    return up, rows, None
+                finally:
+                    torch.cuda.current_stream().synchronize()
+                    L.atdn_gma_destroy(h)
+
+            up32, rows, _ = run("f32", True)
+            clamped = diff = None
+            if check_default:
+                up_sf, _, clamped = run("split_f16", False)
+                d = (up_sf - up32).abs()
+                diff = float(d[torch.isfinite(d)].max()) if bool(torch.isfinite(d).any()) else float("nan")
+                if self.precision != "f32":   # (an f32 module's `_sat_seen` follows the ledger by itself, check_saturation)
+                    self._sat_seen += clamped
+        return RangeReport(rows, clamped, diff, time.perf_counter() - t0, pairs=B)
+
     def debug_read(self, name, shape, H, W):
         """Copy an internal activation of the (H, W) handle to a CPU tensor (parity tests)."""
         out = torch.empty(shape, dtype=torch.float32)

@@ -111,6 +111,35 @@ int atdn_gma_profile(atdn_gma* h, int B, int iters, int reps, float* ms_out, voi
  * a continued clip of a long sequence, the form bench.py times). Split-f16 / f16 handles only for modes 1 and 2. */
 int atdn_gma_profile_mode(atdn_gma* h, int B, int iters, int reps, int mode, float* ms_out, void* stream);
 
+/* Range report (how far a checkpoint's activations are from the 65504 limit of the split-f16 format, BEFORE it clamps).
+ * atdn_gma_set_range_probe switches the probe of an ATDN_PRECISION_F32 handle on / off (`on` = 1 / 0; any other precision is
+ * an error that says why: only the exact-fp32 path writes every intermediate tensor as plain fp32 and never clamps). While it
+ * is on, atdn_gma_forward (and atdn_gma_forward_predictions) launch kernel by kernel instead of replaying a graph, and after
+ * every producing launch a reduction kernel takes (max |x|, finite values with |x| > 65504, non-finite values) of the valid part
+ * of the tensor just written; the call returns after the stream has been synchronised and the table read back. Switched off
+ * again (the default) the handle launches exactly what it did before, and gives the same bits.
+ *   atdn_gma_range_rows   number of rows of the last probed forward (0 before one), -1 on error
+ *   atdn_gma_range_row    row `index` in execution order: `name` (the reference's module path, e.g. "fnet.layer2.0.conv1.raw",
+ *                         "corr.0", "gru.h2"; NUL-terminated into a HOST buffer of name_capacity bytes, 64 suffice),
+ *                         `iteration` (0-based refinement iteration, -1 for tensors written outside the loop: one row per tensor
+ *                         there, one row per tensor and iteration inside it), `limited` (1: the default split-f16 path keeps
+ *                         this tensor, or values that are this tensor's one to one, in the range-limited format; 0: it holds it
+ *                         in plain fp32 or never has it in memory — "att.logits", "corr.0".."corr.3"), `max_abs` (largest finite
+ *                         magnitude), `over` (finite values with |x| > 65504; 65504 itself is not counted), `nonfinite` (infinities
+ *                         and NaNs; they do not enter max_abs). All outputs are HOST pointers. */
+int atdn_gma_set_range_probe(atdn_gma* h, int on);
+long atdn_gma_range_rows(atdn_gma* h);
+int atdn_gma_range_row(atdn_gma* h, long index, char* name, int name_capacity, int* iteration, int* limited, float* max_abs,
+                       int64_t* over, int64_t* nonfinite);
+/* The reduction kernel on a caller's DEVICE tensor: `rows` rows of `cols` fp32 values, row pitch `ld` floats (ld >= cols unless
+ * rows <= 1), starting at any 4-byte boundary; 64-bit element indexing. A pure read.
+ *   atdn_range_probe         allocates and zeroes a slot, launches, synchronises `stream`, writes the three results (HOST pointers)
+ *   atdn_range_probe_launch  the launch alone, adding into `slot`: 24 bytes of DEVICE memory { uint32 max_bits; uint32 unused;
+ *                            uint64 over; uint64 nonfinite } that the caller zeroed (maximum and sums accumulate over launches) */
+int atdn_range_probe(const float* x, int64_t rows, int64_t cols, int64_t ld, float* max_abs, int64_t* over, int64_t* nonfinite,
+                     void* stream);
+int atdn_range_probe_launch(const float* x, int64_t rows, int64_t cols, int64_t ld, void* slot, void* stream);
+
 size_t atdn_gma_workspace_bytes(atdn_gma* h);
 void atdn_gma_destroy(atdn_gma* h);
 
