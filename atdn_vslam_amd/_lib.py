@@ -51,6 +51,9 @@ SIGNATURES = {
     "atdn_clvo_trainer_forward_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32p, _vp]),
     "atdn_clvo_trainer_gradients": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_long)]),
     "atdn_clvo_trainer_adamw_step": (C.c_int, [_vp, C.c_float, C.c_float, C.c_float, C.c_int, _vp]),
+    "atdn_clvo_trainer_set_loss": (C.c_int, [_vp, C.c_float, C.c_int, C.c_int]),
+    "atdn_clvo_trainer_loss_terms": (C.c_int, [_vp, _f32p]),
+    "atdn_clvo_loss": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _f32p, _vp, _vp, _vp]),
     "atdn_clvo_trainer_read": (C.c_long, [_vp, C.c_char_p, C.c_int, _vp, C.c_long, _vp]),
     "atdn_clvo_trainer_destroy": (None, [_vp]),
     "atdn_pose_transform_f32": (C.c_int, [_vp, _vp, _vp]),

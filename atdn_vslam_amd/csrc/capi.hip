@@ -310,6 +310,37 @@ int atdn_clvo_trainer_adamw_step(atdn_clvo_trainer* h, float lr, float weight_de
   h->net.adamw_step(lr, weight_decay, eps, step, (hipStream_t)stream);
   ATDN_API_END
 }
+int atdn_clvo_trainer_set_loss(atdn_clvo_trainer* h, float alpha, int w, int mode) {
+  ATDN_API_BEGIN
+  ATDN_CHECK(h, "null handle");
+  h->net.set_loss(alpha, w, mode);
+  ATDN_API_END
+}
+int atdn_clvo_trainer_loss_terms(atdn_clvo_trainer* h, float* terms3_host) {
+  ATDN_API_BEGIN
+  ATDN_CHECK(h && terms3_host, "null argument");
+  const float* t = h->net.loss_terms();
+  ATDN_CHECK(t, "loss_terms: no iteration with alpha != 1 has run since set_loss");
+  std::memcpy(terms3_host, t, 3 * sizeof(float));
+  ATDN_API_END
+}
+int atdn_clvo_loss(const float* pred_rot, const float* pred_tr, const float* true_rot, const float* true_tr, int B, int T, float alpha,
+                   int w, int mode, float* loss3_host, float* d_rot, float* d_tr, void* stream) {
+  ATDN_API_BEGIN
+  ATDN_CHECK(pred_rot && pred_tr && true_rot && true_tr && loss3_host && d_rot && d_tr, "null argument");
+  ATDN_CHECK(mode == 0 || mode == 1, "atdn_clvo_loss: mode is 0 (reference) or 1 (gradient)");
+  ATDN_CHECK(B >= 1 && T >= 1 && w >= 1 && w <= T, "atdn_clvo_loss: the composite window needs 1 <= w <= sequence length");
+  hipStream_t st = (hipStream_t)stream;
+  DeviceBuf loss3;
+  loss3.alloc(4);
+  try {
+    launch_clvo_loss_composite(pred_rot, pred_tr, true_rot, true_tr, B, T, alpha, w, mode == 1, false, loss3.p, d_rot, d_tr, st);
+    ATDN_HIP(hipMemcpyAsync(loss3_host, loss3.p, 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    ATDN_HIP(hipStreamSynchronize(st));
+  } catch (...) { loss3.release(); throw; }
+  loss3.release();
+  ATDN_API_END
+}
 long atdn_clvo_trainer_read(atdn_clvo_trainer* h, const char* key, int kind, float* host, long capacity, void* stream) {
   try {
     ATDN_CHECK(h && key && host, "null argument");

@@ -1,6 +1,6 @@
 // One CLVO training iteration on the device (train_odometry.py:21-49 per batch):
-// ATDNVO in train mode over the T frames of B clips, CLVO_Loss (alpha = 1), back-propagation through time and
-// through the convolutional encoder, AdamW. Gradients live in one flat buffer so that data-parallel training is a
+// ATDNVO in train mode over the T frames of B clips, CLVO_Loss (alpha = 1 unless set_loss chose the composite term), back-propagation
+// through time and through the convolutional encoder, AdamW. Gradients live in one flat buffer so that data-parallel training is a
 // single all-reduce (RCCL) over it between `forward_backward` and `adamw_step`.
 #pragma once
 #include <cstdlib>
@@ -27,6 +27,13 @@ class ClvoTrainer {
   // loss; pred_rot / pred_tr [B][T][3] (device, optional).
   float forward_backward(const float* flows, const float* true_rot, const float* true_tr, float* pred_rot, float* pred_tr,
                          hipStream_t st);
+  // CLVO_Loss(alpha, w) for the iterations that follow. mode 0: the composite term only enters the loss value and alpha scales
+  // the relative-pose gradient (the reference's detached graph); mode 1: the composite term's own gradient is added. alpha == 1
+  // (and a trainer on which this was never called) runs the relative-pose kernel alone: the composite term is not evaluated.
+  void set_loss(float alpha, int w, int mode);
+  bool composite() const { return alpha_ != 1.0f; }
+  // {L, mean_b L_rel, mean_b L_com} of the last forward_backward with alpha != 1
+  const float* loss_terms() const { return terms_valid_ ? terms_ : nullptr; }
   // AdamW over every parameter that received a gradient (polar_norm is never used by forward()); t = 1-based step
   void adamw_step(float lr, float wd, float eps, int t, hipStream_t st);
 
@@ -69,6 +76,10 @@ class ClvoTrainer {
 
   StateDict sd_;
   bool ready_ = false;
+  float alpha_ = 1.0f;           // CLVO_Loss(alpha, w); loss_mode_ 1 = the composite term contributes its gradient
+  int w_ = 3, loss_mode_ = 0;
+  float terms_[3] = {0.f, 0.f, 0.f};
+  bool terms_valid_ = false;
   bool conv16_ = !(getenv("ATDN_TRAIN_CONV16") && getenv("ATDN_TRAIN_CONV16")[0] == '0');  // 16-channel convs on the 16x16x4 MFMA kernel
   // BatchNorm statistics taken in the kernel that writes the layer's input (0: a reduction pass of their own, the A/B partner)
   bool fused_stats_ = !(getenv("ATDN_TRAIN_FUSED_STATS") && getenv("ATDN_TRAIN_FUSED_STATS")[0] == '0');

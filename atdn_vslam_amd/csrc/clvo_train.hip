@@ -1,5 +1,5 @@
 // CLVO training iteration. Reference: train_odometry.py:21-49 (loop body), odometry/network.py:122-146 (forward, train
-// mode), layers/conv.py (Conv = BN(Mish(conv)), ResidualConv), layers/linear.py, odometry/loss.py:25-58,108-118.
+// mode), layers/conv.py (Conv = BN(Mish(conv)), ResidualConv), layers/linear.py, odometry/loss.py:25-118.
 // Convolutions (forward and data gradients) run on the exact-fp32 MFMA implicit-GEMM engine; a strided convolution's
 // data gradient is the stride-1 convolution of the zero-stuffed output gradient with the transposed, flipped kernel.
 #include "clvo_train.h"
@@ -363,7 +363,11 @@ float ClvoTrainer::forward_backward(const float* flows, const float* true_rot, c
 
   // ================= loss and backward
   float* d_out[2] = {dsmall_[0].p, dsmall_[1].p};
-  launch_clvo_loss(out_[0].p, out_[1].p, true_rot, true_tr, B, T, loss_.p, d_out[0], d_out[1], st);
+  if (composite())
+    launch_clvo_loss_composite(out_[0].p, out_[1].p, true_rot, true_tr, B, T, alpha_, w_, loss_mode_ == 1, true, loss_.p, d_out[0],
+                               d_out[1], st);
+  else
+    launch_clvo_loss(out_[0].p, out_[1].p, true_rot, true_tr, B, T, loss_.p, d_out[0], d_out[1], st);
   float* dh2 = dsmall_[2].p;
   float* hs1 = dsmall_[6].p;               // [TB][128]
   float* hs2 = dsmall_[6].p + (long)TB * 128;  // [TB][64]
@@ -448,10 +452,20 @@ float ClvoTrainer::forward_backward(const float* flows, const float* true_rot, c
   launch_conv_wgrad(t1, 4, 3, nimg, H, W, cur, hs_[1], ws_[1], 7, 7, 2, 3, wscratch_.p, A, st);
   launch_stem_combine(A, P(stem_.conv.w), P(dw_w_), P(dw_b_), 49, G(stem_.conv.w), G(dw_w_), G(dw_b_), st);
 
-  float loss = 0.f;
-  ATDN_HIP(hipMemcpyAsync(&loss, loss_.p, sizeof(float), hipMemcpyDeviceToHost, st));
+  float loss[3] = {0.f, 0.f, 0.f};
+  ATDN_HIP(hipMemcpyAsync(loss, loss_.p, (composite() ? 3 : 1) * sizeof(float), hipMemcpyDeviceToHost, st));
   ATDN_HIP(hipStreamSynchronize(st));
-  return loss;
+  terms_valid_ = composite();
+  if (terms_valid_) std::copy(loss, loss + 3, terms_);
+  return loss[0];
+}
+
+void ClvoTrainer::set_loss(float alpha, int w, int mode) {
+  ATDN_CHECK(w >= 1 && w <= T, "set_loss: the composite window needs 1 <= w <= sequence length");
+  ATDN_CHECK(mode == 0 || mode == 1, "set_loss: mode is 0 (reference) or 1 (gradient)");
+  ATDN_CHECK(alpha == alpha, "set_loss: alpha is NaN");
+  alpha_ = alpha; w_ = w; loss_mode_ = mode;
+  terms_valid_ = false;
 }
 
 void ClvoTrainer::adamw_step(float lr, float wd, float eps, int t, hipStream_t st) {

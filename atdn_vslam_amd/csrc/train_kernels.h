@@ -82,6 +82,14 @@ void launch_lstm_bwd(const float* dh, const float* dc_out, const float* act, con
 // ---- loss (odometry/loss.py, alpha = 1): L = mean_b sum_t (delta*|dt|^2 + khi*|dr|^2); also the gradients
 void launch_clvo_loss(const float* pred_rot, const float* pred_tr, const float* true_rot, const float* true_tr, int B, int T,
                       float* loss /*[1]*/, float* d_rot, float* d_tr, hipStream_t st);
+// ---- loss with the composite term (CLVO_Loss(alpha, w); clvo_composite.h): L = mean_b(alpha*L_rel + (1-alpha)*L_com), L_com the
+// same weighted error on the product of every window of w consecutive transforms, converted back to Euler + translation.
+// with_grad false: the composite term leaves the gradients alone, as in the reference's detached graph (d = alpha x the above);
+// true: its hand-derived gradient is added. step_major: predictions and gradients are rows r = t*B + b (the trainer's layout),
+// else [B][T][3] like the targets. loss3 = {L, mean_b L_rel, mean_b L_com} (device). One launch, deterministic; 1 <= w <= T <= 160.
+void launch_clvo_loss_composite(const float* pred_rot, const float* pred_tr, const float* true_rot, const float* true_tr, int B, int T,
+                                float alpha, int w, bool with_grad, bool step_major, float* loss3 /*[3]*/, float* d_rot, float* d_tr,
+                                hipStream_t st);
 
 // ---- AdamW (torch.optim.AdamW, amsgrad off) on a flat range; t = 1-based step
 void launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float wd, float eps, float beta1,

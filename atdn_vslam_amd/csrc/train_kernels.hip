@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <cstdlib>
+#include "clvo_composite.h"
 #include "common.h"
 #include <algorithm>
 #include <cmath>
@@ -1042,6 +1043,85 @@ __global__ void clvo_loss_kernel(const float* __restrict__ pr, const float* __re
 void launch_clvo_loss(const float* pred_rot, const float* pred_tr, const float* true_rot, const float* true_tr, int B, int T,
                       float* loss, float* d_rot, float* d_tr, hipStream_t st) {
   hipLaunchKernelGGL(clvo_loss_kernel, dim3(1), dim3(256), 0, st, pred_rot, pred_tr, true_rot, true_tr, B, T, loss, d_rot, d_tr);
+  ATDN_HIP(hipGetLastError());
+}
+
+// CLVO_Loss(alpha, w) with the composite term (loss.py:25-101; arithmetic and clamps: clvo_composite.h). One workgroup walks the
+// batch in passes of `cpp` clips whose transforms fit in LDS. Per pass: one thread per step builds P_t of the predictions and of
+// the targets; one thread per window chains the w transforms, converts back to Euler + translation, adds the window loss and
+// (with_grad) leaves dl/dC in LDS; one thread per step then writes that step's gradient: alpha x the relative-pose gradient of
+// clvo_loss_kernel, plus (1-alpha)/B x the windows covering the step, summed in ascending window order by that one thread (no
+// atomics: two launches on the same inputs give the same bits). Predictions and gradients are step-major (r = t*B + b) when
+// step_major, else [B][T][3] like the targets. loss3 = {L, mean_b L_rel, mean_b L_com}.
+__global__ void __launch_bounds__(256) clvo_loss_composite_kernel(const float* __restrict__ pr, const float* __restrict__ pt,
+                                                                  const float* __restrict__ tr_,
+                                                                  const float* __restrict__ tt, int B, int T, int w, float alpha,
+                                                                  int with_grad, int step_major, int cpp, float* __restrict__ loss3,
+                                                                  float* __restrict__ d_rot, float* __restrict__ d_tr) {
+  using composite::Affine;
+  extern __shared__ double composite_lds[];
+  __shared__ double red[2][256];
+  Affine* Pp = reinterpret_cast<Affine*>(composite_lds);   // [cpp][T] predictions
+  Affine* Pt = Pp + (long)cpp * T;                         // [cpp][T] targets
+  Affine* Gw = Pt + (long)cpp * T;                         // [cpp][T-w+1] dl/dC per window
+  const int NW = T - w + 1;
+  const float invB = 1.0f / (float)B;
+  const double com_scale = (1.0 - (double)alpha) / (double)B;
+  double s_rel = 0.0, s_com = 0.0;
+  for (int c0 = 0; c0 < B; c0 += cpp) {
+    const int nc = min(cpp, B - c0);
+    for (int idx = threadIdx.x; idx < nc * T; idx += blockDim.x) {
+      const int c = idx / T, t = idx - c * T, b = c0 + c;
+      const long ti = ((long)b * T + t) * 3, pi = step_major ? ((long)t * B + b) * 3 : ti;
+      Pp[idx] = composite::from_pose(pr + pi, pt + pi);
+      Pt[idx] = composite::from_pose(tr_ + ti, tt + ti);
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < nc * NW; idx += blockDim.x) {
+      const int c = idx / NW, j = idx - c * NW;
+      const Affine cp = composite::chain(Pp + (long)c * T, j, w), ct = composite::chain(Pt + (long)c * T, j, w);
+      s_com += composite::window_loss(cp, ct, with_grad ? Gw + idx : nullptr);
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < nc * T; idx += blockDim.x) {
+      const int c = idx / T, t = idx - c * T, b = c0 + c;
+      const long ti = ((long)b * T + t) * 3, pi = step_major ? ((long)t * B + b) * 3 : ti;
+      double gr[3] = {0.0, 0.0, 0.0}, gt[3] = {0.0, 0.0, 0.0};
+      if (with_grad) composite::step_gradient(Pp + (long)c * T, Gw + (long)c * NW, T, w, t, pr + pi, gr, gt);
+      for (int e = 0; e < 3; ++e) {
+        const float dr = pr[pi + e] - tr_[ti + e], dt = pt[pi + e] - tt[ti + e];
+        s_rel += (double)(1.0f * dt * dt) + (double)(100.0f * dr * dr);
+        const float rel_r = alpha * (2.0f * 100.0f * dr * invB), rel_t = alpha * (2.0f * 1.0f * dt * invB);   // (as clvo_loss_kernel)
+        d_rot[pi + e] = with_grad ? (float)((double)rel_r + com_scale * gr[e]) : rel_r;
+        d_tr[pi + e] = with_grad ? (float)((double)rel_t + com_scale * gt[e]) : rel_t;
+      }
+    }
+    __syncthreads();   // the next pass overwrites the transforms
+  }
+  red[0][threadIdx.x] = s_rel;
+  red[1][threadIdx.x] = s_com;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double rel = 0.0, com = 0.0;
+    for (int t = 0; t < blockDim.x; ++t) { rel += red[0][t]; com += red[1][t]; }
+    rel /= (double)B;
+    com /= (double)B;
+    loss3[0] = (float)((double)alpha * rel + (1.0 - (double)alpha) * com);
+    loss3[1] = (float)rel;
+    loss3[2] = (float)com;
+  }
+}
+void launch_clvo_loss_composite(const float* pred_rot, const float* pred_tr, const float* true_rot, const float* true_tr, int B, int T,
+                                float alpha, int w, bool with_grad, bool step_major, float* loss3, float* d_rot, float* d_tr,
+                                hipStream_t st) {
+  constexpr int kLdsSteps = 160;   // transforms resident per pass: 3 x 160 x 96 B = 45 KiB of LDS
+  ATDN_CHECK(B >= 1 && T >= 1, "clvo loss: empty batch or sequence");
+  ATDN_CHECK(w >= 1 && w <= T, "clvo loss: the composite window needs 1 <= w <= sequence length");
+  ATDN_CHECK(T <= kLdsSteps, "clvo loss: sequence length above 160");
+  const int cpp = std::min(B, kLdsSteps / T);
+  const size_t lds = (size_t)3 * cpp * T * sizeof(composite::Affine);
+  hipLaunchKernelGGL(clvo_loss_composite_kernel, dim3(1), dim3(256), lds, st, pred_rot, pred_tr, true_rot, true_tr, B, T, w, alpha,
+                     with_grad ? 1 : 0, step_major ? 1 : 0, cpp, loss3, d_rot, d_tr);
   ATDN_HIP(hipGetLastError());
 }
 

@@ -2,7 +2,7 @@
 
     python -m atdn_vslam_amd.train_odometry --config config.yaml --flow-weights gma-kitti.pth [--geometry slam|crop]
     python -m atdn_vslam_amd.train_odometry --config config.yaml --flows2          # import dataset/flows2 instead
-    ... [--init PATH] [--save-flows2] [--gpus N]
+    ... [--init PATH] [--save-flows2] [--gpus N] [--composite reference|gradient]
 
 The configuration is the reference's YAML (`Arguments`, README): data_path, train_sequences, batch_size, sequence_length,
 epochs, lr, wd, epsilon, stage, weight_file, log_file, augment_flow, alpha, w. The loop is train_odometry.py:59-145:
@@ -13,8 +13,13 @@ and per epoch a loss log `log_file + str(stage-1) + "_" + str(epoch) + ".txt"` a
 and one CLVOTrainer.step.
 
 Targets are computed in float64 (as the reference does) and rounded to fp32 when handed to the trainer, whose contract is
-fp32 targets; the reference subtracts float64 targets from fp32 predictions. `w` is read and unused: with alpha = 1 (the
-only value the trainer implements) the composite term that takes it is multiplied by zero.
+fp32 targets; the reference subtracts float64 targets from fp32 predictions.
+
+`alpha` and `w` (CLVO_Loss): without `--composite` only alpha = 1 is accepted and `w` is read and unused, since the composite
+term that takes it is multiplied by zero. `--composite reference|gradient` hands the YAML's `alpha` and `w` to the trainer:
+"reference" evaluates the composite term for the logged loss only and scales the relative-pose gradient by alpha (the
+reference's detached graph, as the CPU oracle restates it), "gradient" lets the term steer the weights
+(atdn_vslam_amd/training.py). The per-epoch log holds the total loss either way, as the reference's does.
 
 `--gpus N`: N ranks started here (launch.spawn_ranks_if_needed); every rank builds or loads the whole bank and draws the
 same seeded stream, and rank r trains on the contiguous slice [r*B/N, (r+1)*B/N) of each global batch.
@@ -72,10 +77,19 @@ def load_config(path):
     return cfg
 
 
-def check_alpha(cfg):
-    if cfg.alpha != 1:
-        raise NotImplementedError("alpha = %r: CLVOTrainer implements CLVO_Loss(alpha = 1) only (the composite term is "
-                                  "detached in the reference, but alpha still scales the relative-pose gradient)" % (cfg.alpha,))
+def check_alpha(cfg, composite=None):
+    """Without a composite mode only alpha = 1 trains; with one, `w` must fit the clip. Runs before any GPU work."""
+    if composite is None:
+        if cfg.alpha != 1:
+            raise NotImplementedError("alpha = %r: without --composite the trainer runs CLVO_Loss(alpha = 1) only; choose "
+                                      "--composite reference (the composite term is detached, as in the reference, and alpha scales "
+                                      "the relative-pose gradient) or --composite gradient (the term gets its true gradient)"
+                                      % (cfg.alpha,))
+        return
+    from atdn_vslam_amd.training import composite_mode
+    composite_mode(composite)
+    if not 1 <= int(cfg.w) <= int(cfg.sequence_length):
+        raise ValueError("w = %r: the composite window needs 1 <= w <= sequence_length (%d)" % (cfg.w, int(cfg.sequence_length)))
 
 
 def checkpoint_path(cfg):
@@ -140,12 +154,15 @@ def build_bank(cfg, device, flow_weights=None, flows2=False, geometry="slam", ba
     return bank
 
 
-def train(cfg, bank, device, init_state=None, rank=0, world=1, group=None, on_step=None, log=None, save=True):
+def train(cfg, bank, device, init_state=None, rank=0, world=1, group=None, on_step=None, log=None, save=True, composite=None):
     """The epoch loop of train_odometry.py on `bank`. Seeds torch, builds the sampler and the initial weights exactly as
     the reference orders them, then trains; returns (trainer, per-epoch loss lists). `on_step(epoch, batch, seq_idx,
-    clips, reverse, loss)` is called after every iteration with this rank's slice of the batch."""
+    clips, reverse, loss)` is called after every iteration with this rank's slice of the batch. `composite` (None,
+    "reference" or "gradient"): None trains CLVO_Loss(alpha = 1) and refuses any other alpha; a mode hands cfg.alpha and
+    cfg.w to the trainer (training.py)."""
     from atdn_vslam_amd.training import CLVOTrainer
-    check_alpha(cfg)
+    check_alpha(cfg, composite)
+    loss_args = {} if composite is None else dict(alpha=float(cfg.alpha), w=int(cfg.w), composite=composite)
     B, N = int(cfg.batch_size), int(cfg.sequence_length)
     lo, hi = fb.rank_slice(B, world, rank)
     seqs = [bank.sequence(s) for s in cfg.train_sequences]
@@ -156,7 +173,7 @@ def train(cfg, bank, device, init_state=None, rank=0, world=1, group=None, on_st
     if init_state is not None:
         state = init_state
     trainer = CLVOTrainer(state, hi - lo, N, hw=bank.hw, device=device, lr=cfg.lr, weight_decay=cfg.wd, eps=cfg.epsilon,
-                          total_steps=cfg.epochs * len(loader), eta_min=1e-9, group=group)
+                          total_steps=cfg.epochs * len(loader), eta_min=1e-9, group=group, **loss_args)
     buf = torch.empty((hi - lo, N, 2) + bank.hw, dtype=torch.float32, device=device)
     firsts = np.array([s.first for s in seqs], dtype=np.int64)
     history = []
@@ -195,9 +212,11 @@ def main(argv=None):
     ap.add_argument("--flow-batch", type=int, default=16, help="frame pairs per flow-network call while building the bank")
     ap.add_argument("--init", default=None, help="starting weights (overrides the stage rule)")
     ap.add_argument("--gpus", type=int, default=None)
+    ap.add_argument("--composite", default=None, choices=("reference", "gradient"),
+                    help="train with the YAML's alpha and w: the composite term detached as in the reference, or with its gradient")
     a = ap.parse_args(argv)
     cfg = load_config(a.config)
-    check_alpha(cfg)
+    check_alpha(cfg, a.composite)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -223,7 +242,7 @@ def main(argv=None):
     if p is not None:
         log("loading weights from %s" % p)
         init_state = torch.load(p, map_location="cpu")
-    train(cfg, bank, dev, init_state=init_state, rank=rank, world=world, group=group, log=log)
+    train(cfg, bank, dev, init_state=init_state, rank=rank, world=world, group=group, log=log, composite=a.composite)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -167,8 +167,17 @@ void atdn_clvo_destroy(atdn_clvo* h);
 
 /* ---------------------------------------------------------------------------------------------------
  * CLVO training iteration  —  replaces the body of train() in train_odometry.py:21-49 for one batch:
- *   model.train(); T x model(fl[:, j]) with the LSTM state carried; CLVO_Loss(alpha = 1); loss.backward();
+ *   model.train(); T x model(fl[:, j]) with the LSTM state carried; CLVO_Loss(alpha, w); loss.backward();
  *   optimizer.step() (AdamW, train_odometry.py:99); model.reset_lstm().
+ * The loss is CLVO_Loss(alpha = 1) (relative-pose term only) until atdn_clvo_trainer_set_loss chooses the composite term:
+ *   L = mean_b(alpha * L_rel + (1 - alpha) * L_com), L_com summed over every window of w consecutive steps: the w predicted
+ *   transforms chained, likewise the true ones, both products converted back to Euler yxz + translation (matrix2euler), and the
+ *   same 1 * |d tr|^2 + 100 * |d euler|^2 taken (no angle wrapping).
+ *   mode 0 ("reference"): the composite term enters the loss value only; the gradients are alpha x those of alpha = 1 (the
+ *     reference builds its matrices and Euler vectors with torch.tensor(...), which cuts the graph).
+ *   mode 1 ("gradient"): the composite term contributes its true gradient, (1 - alpha)/batch * dL_com/d(pred_rot, pred_tr).
+ *   The radicand 1 - C12^2 of matrix2euler is clamped at 0 for the value and at FLT_EPSILON in the derivative (the reference
+ *   returns NaN there). With alpha == 1 the composite term is not evaluated at all, whatever w and mode say.
  * BatchNorm layers use per-call batch statistics and update their running averages (momentum 0.1), as torch does.
  * Gradients sit in ONE flat device buffer (`atdn_clvo_trainer_gradients`): data-parallel training all-reduces that
  * buffer (RCCL, averaged over ranks) between forward_backward and adamw_step — see atdn_vslam_amd/training.py.
@@ -182,6 +191,15 @@ int atdn_clvo_trainer_finalize(atdn_clvo_trainer* h);
 int atdn_clvo_trainer_forward_backward(atdn_clvo_trainer* h, const float* flows, const float* true_rot, const float* true_tr,
                                        float* pred_rot, float* pred_tr, float* loss_out, void* stream);
 int atdn_clvo_trainer_gradients(atdn_clvo_trainer* h, float** device_ptr, long* count);
+/* Selects the loss of the forward_backward calls that follow (see above). Fails for w < 1, w > sequence_length, mode not 0 / 1. */
+int atdn_clvo_trainer_set_loss(atdn_clvo_trainer* h, float alpha, int w, int mode);
+/* {L, mean_b L_rel, mean_b L_com} of the last forward_backward (host); fails unless that call ran with alpha != 1. */
+int atdn_clvo_trainer_loss_terms(atdn_clvo_trainer* h, float* terms3_host);
+/* The loss on its own: pred_rot, pred_tr, true_rot, true_tr and the gradients d_rot, d_tr are [B, T, 3] device fp32;
+ * loss3_host receives {L, mean_b L_rel, mean_b L_com}. One kernel launch, deterministic (no atomics); synchronises the stream.
+ * Fails for w < 1, w > T, T > 160 or a mode other than 0 / 1. */
+int atdn_clvo_loss(const float* pred_rot, const float* pred_tr, const float* true_rot, const float* true_tr, int B, int T, float alpha,
+                   int w, int mode, float* loss3_host, float* d_rot, float* d_tr, void* stream);
 /* torch.optim.AdamW (betas 0.9 / 0.999) on every parameter forward() uses; step is 1-based */
 int atdn_clvo_trainer_adamw_step(atdn_clvo_trainer* h, float lr, float weight_decay, float eps, int step, void* stream);
 /* copy a named tensor to the host: kind 0 parameter, 1 gradient, 2 BatchNorm running statistic; returns the count or -1 */

@@ -2,6 +2,10 @@
 on one GPU, or data-parallel under torch.distributed.run (one process per GPU, RCCL all-reduce of the flat gradient).
 
     python tools/bench_train.py [--gpus N] [--batch 24] [--seq 6] [--steps 10] [--warmup 2]
+                                [--alpha 1.0] [--w 3] [--composite reference|gradient] [--repeats 1]
+
+`--alpha`, `--w`, `--composite`: time an iteration with the composite pose term (CLVO_Loss(alpha, w), training.py).
+`--repeats R`: R timed legs of `--steps` iterations in one process; the JSON line then carries every leg's time.
 
 `--gpus N` with N > 1 and no launcher around it starts its own N ranks (atdn_vslam_amd/launch.py), exactly as bench.py does.
 """
@@ -32,6 +36,10 @@ def main():
     ap.add_argument("--seq", type=int, default=6)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--alpha", type=float, default=1.0, help="CLVO_Loss alpha (1: relative-pose term only)")
+    ap.add_argument("--w", type=int, default=3, help="CLVO_Loss composite window")
+    ap.add_argument("--composite", default="reference", choices=("reference", "gradient"))
+    ap.add_argument("--repeats", type=int, default=1, help="timed legs of --steps iterations each")
     ap.add_argument("--gpus", type=int, default=None, help="ranks of the data-parallel job (default: WORLD_SIZE, else 1)")
     ap.add_argument("--launch-check", action="store_true", help="launch plumbing only (gloo all-gather of the ranks, no GPU call)")
     a = ap.parse_args()
@@ -54,7 +62,8 @@ def main():
     if world > 1:
         import torch.distributed as dist
         dist.init_process_group("nccl", device_id=dev)
-    tr = CLVOTrainer(syn.to_torch(syn.make_clvo_state(seed=1)), a.batch, a.seq, device=dev, total_steps=a.steps + a.warmup)
+    tr = CLVOTrainer(syn.to_torch(syn.make_clvo_state(seed=1)), a.batch, a.seq, device=dev,
+                     total_steps=a.steps * a.repeats + a.warmup, alpha=a.alpha, w=a.w, composite=a.composite)
     r = np.random.RandomState(7 + rank)
     flows = torch.from_numpy(syn.make_flow(a.batch * a.seq, 376, 1232, seed=50 + rank)).view(a.batch, a.seq, 2, 376, 1232).to(dev)
     rot = torch.from_numpy(r.uniform(-0.02, 0.02, (a.batch, a.seq, 3)).astype(np.float32)).to(dev)
@@ -65,13 +74,16 @@ def main():
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        losses.append(tr.step(flows, rot, trn))
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    dt = time.perf_counter() - t0
+    legs = []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            losses.append(tr.step(flows, rot, trn))
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        legs.append(time.perf_counter() - t0)
+    dt = float(np.median(legs))
     if rank == 0:
         # roofline of the iteration: the head's convolutions are 0.635 GMAC per flow frame forward (SURVEY appendix
         # A) on the exact-fp32 matrix core (v_mfma_f32_16x16x4_f32), the backward pass is two GEMMs of the same size per layer
@@ -84,6 +96,8 @@ def main():
         print(json.dumps({"metric": "CLVO training flow-frames/s (forward + backward + AdamW)", "value": world * a.batch * a.seq * a.steps / dt,
                           "unit": "flow frames/s", "n_gpus": world, "ms_per_iteration": dt * 1e3 / a.steps, "batch_per_gpu": a.batch,
                           "sequence_length": a.seq, "loss_first": losses[0], "loss_last": losses[-1],
+                          "alpha": a.alpha, "w": a.w, "composite": a.composite if a.alpha != 1.0 else None,
+                          "ms_per_iteration_legs": [t * 1e3 / a.steps for t in legs],
                           "roofline": {"bound": "mfma", "achieved": flop / sec / 1e12, "peak": 157.3, "unit": "TFLOP/s",
                                        "frac": flop / sec / 1e12 / 157.3, "algorithmic_flop_per_iteration": flop,
                                        "note": "fp32 MFMA peak (the trainer computes in exact fp32); per GPU"},
