@@ -582,6 +582,9 @@ int atdn_conv2d_nhwc_sf_epi(const float* src, int nimg, int H, int W, int Cin, c
                             float* dst, void* stream) {
   ATDN_API_BEGIN
   ATDN_CHECK(src && weight_host && dst && nimg >= 1 && Cin % 32 == 0, "bad argument (Cin must be a multiple of 32)");
+  ATDN_CHECK(sf_store >= 0 && sf_store <= 7 && (sf_store & 6) != 6, "sf_store: bit 0 names the epilogue, bit 1 or bit 2 the tile form");
+  const int tile_form = (sf_store & 2) ? 1 : (sf_store & 4) ? 2 : 0;   // 1x5 / 5x1: rectangular 8 x 16 x 128 tiles / run tiles
+  sf_store &= 1;
   ATDN_CHECK(!sf_store || Cout % 32 == 0, "the split-f16 store needs Cout % 32 == 0");
   StateDict sd;
   const int64_t ws[4] = {Cout, Cin, KH, KW};
@@ -605,6 +608,7 @@ int atdn_conv2d_nhwc_sf_epi(const float* src, int nimg, int H, int W, int Cin, c
     s.w = L.w; s.ldw = L.ldw; s.N = Cout; s.nimg = nimg;
     const int Ho = conv_out(H, KH, stride, padH), Wo = conv_out(W, KW, stride, padW);
     s.wfrag16 = L.wf16;
+    s.tile_form = tile_form;
     // sf_store: write split-f16 through the SfBias epilogue (the channel-vector sf store of the product's layers), then
     // unpack to fp32; otherwise fp32 output through EpiBias
     if (sf_store) {

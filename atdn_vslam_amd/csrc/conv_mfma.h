@@ -277,6 +277,9 @@ struct ConvShape {  // what the caller describes; ConvGeom is derived from it
   // optional (generation-6 halo kernels with a statistics epilogue only): src0 is the RAW fp32 output of an
   // InstanceNorm'ed layer and these are its per-(image, channel) mean / reciprocal std: the loader normalises + ReLUs
   const float* in_mean = nullptr; const float* in_rstd = nullptr;
+  // tests only (atdn_conv2d_nhwc_sf_epi): 1x5 / 5x1 halo-patch convolutions on the 8 x 16 x 128 rectangular tiles (1) or on the
+  // run tiles where the shape allows them (2) whatever the grid size; 0 = the dispatch rules of the product
+  int tile_form = 0;
 };
 
 inline int conv_out(int in, int k, int stride, int pad) { return (in + 2 * pad - k) / stride + 1; }

@@ -102,9 +102,22 @@ template <class E> struct conv_stamp_kind : std::integral_constant<int, -1> {};
 // (the body: one block of one convolution. `bidx` is the block's index within ITS convolution — blockIdx.x in conv_sf6_kernel, or
 // the index behind the first convolution's blocks in conv_sf6_pair_kernel, which runs two independent convolutions of the same
 // shape class as ONE launch)
-template <int TH, int TW, int BN, int WM, int WN, int KH, int KW, class Epi, bool FAST = false, bool NORM = false, int ABL = 0>
+//
+// RUN (1x5 / 5x1 only, the 8 x 16 x 128 block): the M tile is not a rectangle but 128 CONSECUTIVE pixels of the image in row-major
+// (1x5) or column-major (5x1) order, m = 128 t .. 128 t + 127 with m = y W + x or m = x H + y: a separable pass has its halo along
+// one axis only, so a tile may wrap from one image row (column) — a "run" of L = W (H) pixels — into the next, and only the last
+// tile of an image holds padding pixels (47 x 154: 57 tiles instead of 60). The LDS image is then a flat array of pixel slots:
+// 2 halo slots, the tile's pixels, 2 halo slots, with 8 zero slots between two runs (2 would serve the taps; a gap that is no
+// multiple of 8 slots puts the two parts of the row block that straddles it on the same banks). Halo slots outside the pixel's own
+// run are true zeros, tap t is the slot offset t in both orientations, and every output pixel accumulates the same taps and chunks
+// in the same order as in the rectangular form: the same bits. L >= 43 keeps a tile to at most 3 run boundaries = 156 slots.
+template <int TH, int TW, int BN, int WM, int WN, int KH, int KW, class Epi, bool FAST = false, bool NORM = false, int ABL = 0,
+          bool RUN = false>
 __device__ __forceinline__ void conv_sf6_body(const Conv2Geom& g, const Epi& ep, const int bidx) {
   static_assert(ABL == 0 || !NORM, "ablation builds exist for the plain patch loader");
+  static_assert(!RUN || (((KH == 1 && KW == 5) || (KH == 5 && KW == 1)) && TH == 8 && BN == 128 && WM == 1 && WN == 4 && !NORM &&
+                         ABL == 0 && !Epi::kStats && !epi_flowhead<Epi>::value),
+                "run tiles: separable passes on the 8 x 16 x 128 block, plain loader, epilogues without statistics");
   static_assert(TW == 16, "the 16x16x32 loop is built for 16-pixel tile rows");
   constexpr int NIMG = 2;   // two patch images: a chunk boundary costs one barrier
   constexpr int NW = WM * WN, NT = NW * 64;
@@ -113,7 +126,8 @@ __device__ __forceinline__ void conv_sf6_body(const Conv2Geom& g, const Epi& ep,
   static_assert(32 % TW == 0 || TW % 32 == 0, "a 32-pixel MFMA row tile must cover whole tile rows");
   constexpr int NTAP = KH * KW;
   constexpr int RSTEP = NT / 8;
-  constexpr int PROWS = (TH + KH - 1) * (TW + KW - 1);
+  constexpr int RSLOTS = 160;   // run tiles: pixel slots of the flat image (132 + 8 per run boundary <= 156, whole loader steps)
+  constexpr int PROWS = RUN ? RSLOTS : (TH + KH - 1) * (TW + KW - 1);
   constexpr int PW = TW + KW - 1;
   constexpr int NP = (PROWS + RSTEP - 1) / RSTEP;
   constexpr int ROWB = 160;   // pixel pitch of the patch image
@@ -122,7 +136,7 @@ __device__ __forceinline__ void conv_sf6_body(const Conv2Geom& g, const Epi& ep,
   constexpr bool SWAP = epi_vec4<Epi>::value;
   // two patch images: chunk c+1 is written (from the registers its loads landed in) during the last tap of chunk c,
   // so a chunk boundary costs one barrier, not two
-  constexpr int PSZ = (TH + KH - 1) * RS;
+  constexpr int PSZ = RUN ? RSLOTS * ROWB : (TH + KH - 1) * RS;
   __shared__ __attribute__((aligned(256))) char Pbytes[NIMG * PSZ];
 
   const int tid = threadIdx.x;
@@ -136,6 +150,24 @@ __device__ __forceinline__ void conv_sf6_body(const Conv2Geom& g, const Epi& ep,
   const int ty0 = (tloc / g.tiles_x) * TH, tx0 = (tloc % g.tiles_x) * TW;
   const int n0 = tile_n * BN;
   const int lane = tid & 63, wave = tid >> 6;
+  // run tiles: first flat pixel of the tile, its run and position in the run, and the tile-relative pixels at which the next
+  // runs begin (block-uniform; a pixel's run follows from comparing against them, never from a division per lane)
+  const int rL = KH == 1 ? g.W : g.H, rHW = g.H * g.W;
+  const int rm0 = tloc * (TH * TW);
+  const int rrun0 = RUN ? rm0 / rL : 0, rpos0 = rm0 - rrun0 * rL;
+  const int rb1 = rL - rpos0, rb2 = rb1 + rL, rb3 = rb2 + rL;
+  // output pixel index of tile pixel p (-1: outside the image)
+  auto out_pixel = [&](int p) {
+    if constexpr (RUN) {
+      const int k = (p >= rb1 ? 1 : 0) + (p >= rb2 ? 1 : 0) + (p >= rb3 ? 1 : 0);
+      const int m = rm0 + p;
+      if (m >= rHW) return -1;
+      return KH == 1 ? m : (rpos0 + p - k * rL) * g.W + rrun0 + k;
+    } else {
+      const int oy = ty0 + p / TW, ox = tx0 + p % TW;
+      return (oy < g.Ho && ox < g.Wo) ? oy * g.Wo + ox : -1;
+    }
+  };
 #ifdef ATDN_CONV_STAMP
   constexpr int kStamp = conv_stamp_kind<Epi>::value;
   unsigned long long st_r0 = 0, st_t0 = 0, st_t1 = 0, st_t2 = 0, st_bar = 0;
@@ -151,12 +183,24 @@ __device__ __forceinline__ void conv_sf6_body(const Conv2Geom& g, const Epi& ep,
   const int jrow = (tid >> 3) & 7;
   const int s = tid & 7, r0 = !NORM ? tid >> 3 : ((tid >> 6) << 3) + 2 * (jrow & 1) + ((jrow >> 1) & 1) + 4 * (jrow >> 2);
   // per patch row of this thread: (pixel offset in the image + 1, 0 = zero padding) << 12 | LDS offset / 16
-  static_assert((TH + KH - 1) * RS / 16 <= 4096, "LDS offset field");
+  static_assert(PSZ / 16 <= 4096, "LDS offset field");
   unsigned pmeta[NP];
 #pragma unroll
   for (int k = 0; k < NP; ++k) {
     const int prow = r0 + RSTEP * k;
     unsigned off = 0;
+    if constexpr (RUN) {
+      // slot prow: gap j (8 zero slots) starts at slot 2 + b_j + 8 (j - 1); behind kk gaps the slot holds tile pixel prow - 2 - 8 kk
+      static_assert(PROWS == NP * RSTEP, "every loader step writes slots of the image");
+      const int kk = (prow >= 2 + rb1 ? 1 : 0) + (prow >= 10 + rb2 ? 1 : 0) + (prow >= 18 + rb3 ? 1 : 0);
+      const bool gap = kk > 0 && prow < 2 + rb1 + (kk - 1) * rL + 8 * kk;
+      const int p = prow - 2 - 8 * kk;
+      const int pos = rpos0 + p - kk * rL;   // position in its run: outside [0, L) the slot is a halo slot of another run
+      // (p > 129: slots behind the trailing halo, which no tap reads, stay zero)
+      if (!gap && p < 130 && (unsigned)pos < (unsigned)rL && rm0 + p < rHW) off = (unsigned)(KH == 1 ? rm0 + p : pos * g.W + rrun0 + kk) + 1u;
+      pmeta[k] = (off << 12) | (unsigned)((prow * ROWB + 16 * s) >> 4);
+      continue;
+    }
     const int py = prow / PW, px = prow - py * PW;
     if (prow < PROWS) {
       const int iy = ty0 - g.padH + py, ix = tx0 - g.padW + px;
@@ -230,9 +274,22 @@ __device__ __forceinline__ void conv_sf6_body(const Conv2Geom& g, const Epi& ep,
     }
   {
     const int n16 = lane & 15, g16 = lane >> 4;
-    int a_off[TM];   // first patch row (pixel half 0) of row tile i: pixel n16, slot g16; half 1 is the next patch row
+    // first patch row (pixel half 0) of row tile i: pixel n16, slot g16; half 1 is the next patch row
+    // (run tiles: a 16-pixel row block that straddles a run boundary has lanes on both sides of the gap — one offset per half)
+    int a_off[RUN ? 2 * TM : TM];
 #pragma unroll
-    for (int i = 0; i < TM; ++i) a_off[i] = ((wm * TM + i) * 2) * RS + n16 * ROWB + 16 * g16;
+    for (int i = 0; i < TM; ++i) {
+      if constexpr (RUN) {
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+          const int p = ((wm * TM + i) * 2 + hh) * 16 + n16;
+          const int k = (p >= rb1 ? 1 : 0) + (p >= rb2 ? 1 : 0) + (p >= rb3 ? 1 : 0);
+          a_off[hh * TM + i] = (p + 8 * k) * ROWB + 16 * g16;
+        }
+      } else {
+        a_off[i] = ((wm * TM + i) * 2) * RS + n16 * ROWB + 16 * g16;
+      }
+    }
     const char* Pb = Pbytes;
     // weight fragments of channel block cb of column tile j: [n/16][q][hi | lo][lane] x 16 B
     const int nblk16 = (g.N + 15) >> 4;
@@ -279,11 +336,12 @@ __device__ __forceinline__ void conv_sf6_body(const Conv2Geom& g, const Epi& ep,
 #endif
     f16x8 ah[2][TM], al[2][TM];   // [pixel half][row tile]
     auto read_a = [&](int half, int tap) __attribute__((always_inline)) {
-      const char* arow = Pb + (tap / KW + half) * RS + (tap % KW) * ROWB;
+      const char* arow = RUN ? Pb + tap * ROWB : Pb + (tap / KW + half) * RS + (tap % KW) * ROWB;
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
-        ah[half][i] = *reinterpret_cast<const f16x8*>(arow + a_off[i]);
-        if constexpr (!FAST) al[half][i] = *reinterpret_cast<const f16x8*>(arow + a_off[i] + 64);
+        const int ao = a_off[RUN ? half * TM + i : i];
+        ah[half][i] = *reinterpret_cast<const f16x8*>(arow + ao);
+        if constexpr (!FAST) al[half][i] = *reinterpret_cast<const f16x8*>(arow + ao + 64);
       }
     };
     auto mfma_half = [&](int half, const WFrag& w) __attribute__((always_inline)) {
@@ -424,9 +482,8 @@ __device__ __forceinline__ void conv_sf6_body(const Conv2Geom& g, const Epi& ep,
     // pixel index of row 8q + trow of tile row i (-1: outside the image)
     auto tile_pixel = [&](int i, int q) {
       const int p = (wm * TM + i) * 32 + 8 * q + trow;
-      const int oy = ty0 + p / TW, ox = tx0 + p % TW;
       if constexpr ((ABL & 16) != 0) return p;
-      return (oy < g.Ho && ox < g.Wo) ? oy * g.Wo + ox : -1;
+      return out_pixel(p);
     };
     // one 32-pixel x 32-channel accumulator tile -> the wave's slab [pixel][LDS_LD floats], scaled
     // (RAW: epilogues that fold the weight scale — a power of two — into their first addition take the accumulators as they are)
@@ -653,9 +710,7 @@ __device__ __forceinline__ void conv_sf6_body(const Conv2Geom& g, const Epi& ep,
     int mm[NPX];
 #pragma unroll
     for (int e = 0; e < NPX; ++e) {
-      const int p = pbase + pix_of(e);
-      const int oy = ty0 + p / TW, ox = tx0 + p % TW;
-      mm[e] = (oy < g.Ho && ox < g.Wo) ? oy * g.Wo + ox : -1;
+      mm[e] = out_pixel(pbase + pix_of(e));
     }
     // statistics epilogues (round 5: instruction count — the kernels with this epilogue ran 3.7-5.2 vector instructions per
     // MFMA): what depends on the pixels alone is formed once per row tile, not once per channel column — the valid-pixel count of
@@ -756,6 +811,12 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void conv_sf6_kernel(const Conv2Ge
   conv_sf6_body<TH, TW, BN, WM, WN, KH, KW, Epi, FAST, NORM, ABL>(g, ep, (int)blockIdx.x);
 }
 
+// The run-tile form of the 8 x 16 x 128 block (1x5 / 5x1; see conv_sf6_body): g.tiles_x counts the 128-pixel run tiles of an image.
+template <int KH, int KW, class Epi, bool FAST = false>
+__global__ __launch_bounds__(256, 1) void conv_sf6_run_kernel(const Conv2Geom g, const Epi ep) {
+  conv_sf6_body<8, 16, 128, 1, 4, KH, KW, Epi, FAST, false, 0, true>(g, ep, (int)blockIdx.x);
+}
+
 // Two INDEPENDENT convolutions of the same instantiation as one launch (round 5: convc2 and convf2 of the motion encoder — the
 // correlation branch and the flow branch of update.py:76-92 do not depend on each other). Blocks [0, nblk0) are the first
 // convolution's, the rest the second's; the second starts at a multiple of 8 so that both keep their XCD mapping (blocks of the
@@ -821,6 +882,25 @@ inline void launch_conv_sf6(const ConvShape& s, float wscale, Epi ep, hipStream_
   set_groups(ep, g.tiles_x * g.tiles_y * (TH * TW / 32));
   const int nblk = g.nimg * g.tiles_x * g.tiles_y * g.ntile_n;
   hipLaunchKernelGGL((conv_sf6_kernel<TH, TW, BN, WM, WN, KH, KW, Epi, FAST, NORM, ABL>), dim3(nblk), dim3(WM * WN * 64), 0, st, g, ep);
+  ATDN_HIP(hipGetLastError());
+}
+
+// run tiles serve 'same' separable convolutions whose runs are long enough for a tile to hold at most 3 run boundaries
+template <int KH, int KW>
+inline bool conv_sf6_run_eligible(const ConvShape& s) {
+  if (KH * KW != 5 || s.KH != KH || s.KW != KW || s.stride != 1 || s.in_mean) return false;
+  if (s.padH != KH / 2 || s.padW != KW / 2) return false;
+  const int L = KH == 1 ? s.W : s.H;
+  return (L + 126) / L <= 3;
+}
+
+template <int KH, int KW, class Epi, bool FAST>
+inline void launch_conv_sf6_run(const ConvShape& s, float wscale, Epi ep, hipStream_t st) {
+  Conv2Geom g = conv_sf6_geom<8, 128, 1, 4, KH, KW, Epi, FAST, false, 0>(s, wscale);
+  ATDN_CHECK((conv_sf6_run_eligible<KH, KW>(s)) && g.Ho == g.H && g.Wo == g.W, "shape not served by the run-tile kernel");
+  g.tiles_x = cdiv(g.H * g.W, 128); g.tiles_y = 1;
+  const int nblk = g.nimg * g.tiles_x * g.ntile_n;
+  hipLaunchKernelGGL((conv_sf6_run_kernel<KH, KW, Epi, FAST>), dim3(nblk), dim3(256), 0, st, g, ep);
   ATDN_HIP(hipGetLastError());
 }
 
@@ -914,6 +994,24 @@ inline bool conv_sf6_try_shape(const ConvShape& s, float wscale, const Epi& ep, 
   // Same K order as every other tile shape, so the same bits (tests/test_gpu_parity.py: a pair comes out of an 8-pair launch
   // exactly as out of a single-pair call). Not for the statistics epilogues (their tile height follows from the layer's geometry
   // alone) nor the fused flow head (one block holds all channels of its pixels).
+  // (ConvShape::tile_form, set by the test entry atdn_conv2d_nhwc_sf_epi alone: 1 = the 8 x 16 x 128 halo block and 2 = the run
+  // tiles for a 1x5 / 5x1 convolution at ANY grid size, so that both forms can be compared on small shapes)
+  if constexpr (KH != 3 && !Epi::kStats && !epi_flowhead<Epi>::value) {
+    if (s.tile_form == 1) {
+      *bn_out = 128;
+      launch_conv_sf6_m<8, 128, 1, 4, KH, KW, Epi, FAST, false>(s, wscale, ep, st);
+      return true;
+    }
+    if (s.tile_form == 2 && conv_sf6_run_eligible<KH, KW>(s)) {
+#ifndef ATDN_NO_RUN_TILES
+      *bn_out = 128;
+      launch_conv_sf6_run<KH, KW, Epi, FAST>(s, wscale, ep, st);
+      return true;
+#else
+      ATDN_CHECK(false, "run tiles requested from a library built with ATDN_NO_RUN_TILES");
+#endif
+    }
+  }
   if constexpr (!Epi::kStats && !epi_flowhead<Epi>::value) {
     // (ATDN_CONV_SMALL_TILES=1: the 4 x 16 x 64 form for every 1x5 / 5x1 convolution at ANY grid size — the A/B of DESIGN.md 10.8)
     static const bool force_small = getenv("ATDN_CONV_SMALL_TILES") && getenv("ATDN_CONV_SMALL_TILES")[0] == '1';
@@ -946,6 +1044,12 @@ inline bool conv_sf6_try_shape(const ConvShape& s, float wscale, const Epi& ep, 
     }
   }
   *bn_out = bn;
+#ifndef ATDN_NO_RUN_TILES   // (-DATDN_NO_RUN_TILES: a variant build that keeps the rectangular tiles everywhere, for A/B timing)
+  // 1x5 / 5x1 on the 8 x 16 x 128 block: 128-pixel run tiles, no padding pixels but in an image's last tile
+  if constexpr (KH != 3 && !Epi::kStats && !epi_flowhead<Epi>::value) {
+    if (bn == 128 && conv_sf6_run_eligible<KH, KW>(s)) { launch_conv_sf6_run<KH, KW, Epi, FAST>(s, wscale, ep, st); return true; }
+  }
+#endif
   switch (bn) {
     case 64:  launch_conv_sf6_m<8, 64, 2, 2, KH, KW, Epi, FAST, false>(s, wscale, ep, st); return true;  // 4 waves of 64 px x 32 ch
     case 128: launch_conv_sf6_m<8, 128, 1, 4, KH, KW, Epi, FAST, false>(s, wscale, ep, st); return true;

@@ -31,7 +31,9 @@ struct SfBias {
   }
   // channel-vector form (conv_sf6.h): channels n..n+3 of pixel m
   static constexpr bool kVec4 = true;
-  static constexpr int kGen6 = 1;  // conv_sf6.h kernel shapes: 1 = 3x3, 2 = 1x5 / 5x1
+  // conv_sf6.h kernel shapes: 1 = 3x3, 2 = 1x5 / 5x1. (The plain store also serves 1x5 / 5x1: no layer of the product is such a
+  // convolution — its ACT_NONE layers are 1x1 — but atdn_conv2d_nhwc_sf_epi tests the separable kernels' sf store through it.)
+  static constexpr int kGen6 = ACT == ACT_NONE ? 3 : 1;
   // bias of channels n..n+3, fetched ONCE per channel run by the kernel (a load inside store4 sits between the
   // stores of consecutive pixels and its wait, vmcnt(0), also waits for those stores)
   __device__ __forceinline__ float4 bias4(int n) const {

@@ -357,7 +357,11 @@ int atdn_conv2d_nhwc_sf(const float* src, int nimg, int H, int W, int Cin, const
                         const float* bias_host, int Cout, int KH, int KW, int stride, int padH, int padW, float* dst,
                         void* stream);
 /* ... with the epilogue named: sf_store = 0 writes fp32 (what atdn_conv2d_nhwc_sf does), sf_store = 1 writes the split-f16
- * format through the channel-vector store the product's layers use (Cout % 32 == 0) and decodes it to fp32 `dst`. */
+ * format through the channel-vector store the product's layers use (Cout % 32 == 0) and decodes it to fp32 `dst`.
+ * Tests of the 1x5 / 5x1 halo-patch kernels add one of two bits, which change the tiling and never the result: bit 1 (values 2, 3:
+ * the epilogue of 0, 1) runs them on the rectangular 8 x 16-pixel x 128-channel tiles, bit 2 (values 4, 5) on the 128-pixel run
+ * tiles where the shape allows them (run length >= 43), both whatever the grid size; without them the product's dispatch rules
+ * choose, which take small grids to smaller tiles. Other kernel shapes ignore the bits. */
 int atdn_conv2d_nhwc_sf_epi(const float* src, int nimg, int H, int W, int Cin, const float* weight_host,
                             const float* bias_host, int Cout, int KH, int KW, int stride, int padH, int padW, int sf_store,
                             float* dst, void* stream);
