@@ -79,18 +79,14 @@ def build(force=False, jobs=None, microbench=False, variant=None, defines=()):
     with ThreadPoolExecutor(max_workers=jobs) as ex:
         results = list(ex.map(lambda src: _compile(src, objdir, tuple(defines)), _sources()))
     objs = [o for o, _ in results]
-    if variant:
-        LIBV = lib
-    else:
-        LIBV = LIB
-    if any(changed for _, changed in results) or not os.path.exists(LIBV) or _mtime(LIBV) < max(_mtime(o) for o in objs):
-        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-fno-gpu-rdc", "-o", LIBV] + objs
+    if any(changed for _, changed in results) or not os.path.exists(lib) or _mtime(lib) < max(_mtime(o) for o in objs):
+        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-fno-gpu-rdc", "-o", lib] + objs
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if r.returncode != 0:
             raise RuntimeError("link failed:\n%s" % r.stdout)
     if microbench and not variant:
         build_microbench()
-    return LIBV
+    return lib
 
 
 def build_microbench():

@@ -10,6 +10,7 @@
 // * packed weights carry a per-layer power-of-two scale (max|w'| in [1,2)) so that the lo halves of small
 //   weights stay normal f16 numbers; the accumulator is multiplied by `wscale` = 2^-p before the epilogue.
 #pragma once
+#include <type_traits>
 #include "conv_dispatch.h"
 #include "sf.h"
 
@@ -266,6 +267,13 @@ inline void launch_conv_sf(const ConvShape& s, float wscale, const Epi& ep, hipS
 // Plain-f16 arithmetic (precision mode 2) for the calling thread's sf convolutions: conv_sf_dispatch issues only the
 // hi x hi MFMA of every product while this is set (GmaNet sets it around its forward).
 bool& sf_fast_mode();
+
+// The run-time flag as the kernels' FAST template argument: f(std::true_type{}) or f(std::false_type{}), so that a launch ladder
+// is written once for both arithmetic modes.
+template <class F>
+inline auto with_fast(bool fast, F&& f) {
+  return fast ? f(std::true_type{}) : f(std::false_type{});
+}
 
 // Definitions are explicitly instantiated in conv_sf_inst_*.hip
 template <class Epi>

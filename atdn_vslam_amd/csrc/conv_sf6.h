@@ -18,7 +18,6 @@
 // VMEM instructions. Epilogues without it (InstanceNorm statistics need the pixel-major registers) keep the
 // classic orientation.
 #pragma once
-#include <cstdlib>
 #include <type_traits>
 #include "conv_sf.h"
 
@@ -29,11 +28,10 @@ struct Conv2Geom {
   long sb0, sb1;
   int ld0, ld1, C0, C1;
   int H, W, Ho, Wo;
-  int KH, KW, padH, padW;
-  int PH, PW;            // patch size in pixels
+  int padH, padW;
   int tiles_x, tiles_y;  // per image
   int nimg, ntile_n;
-  const float* w; int ldw; int N;
+  const float* w; int N;
   float wscale;
   // normalise-on-load (NORM): src0 is RAW fp32 [pix][C0] and the patch loader applies
   // relu((x - in_mean[img][c]) * in_rstd[img][c]) before splitting to sf (InstanceNorm + ReLU of the producer)
@@ -828,10 +826,9 @@ __device__ __forceinline__ Conv2Geom conv2_geom_pick(const Conv2Geom& a, const C
   g.src0 = s ? b.src0 : a.src0; g.src1 = s ? b.src1 : a.src1; g.sb0 = s ? b.sb0 : a.sb0; g.sb1 = s ? b.sb1 : a.sb1;
   g.ld0 = s ? b.ld0 : a.ld0; g.ld1 = s ? b.ld1 : a.ld1; g.C0 = s ? b.C0 : a.C0; g.C1 = s ? b.C1 : a.C1;
   g.H = s ? b.H : a.H; g.W = s ? b.W : a.W; g.Ho = s ? b.Ho : a.Ho; g.Wo = s ? b.Wo : a.Wo;
-  g.KH = s ? b.KH : a.KH; g.KW = s ? b.KW : a.KW; g.padH = s ? b.padH : a.padH; g.padW = s ? b.padW : a.padW;
-  g.PH = s ? b.PH : a.PH; g.PW = s ? b.PW : a.PW; g.tiles_x = s ? b.tiles_x : a.tiles_x; g.tiles_y = s ? b.tiles_y : a.tiles_y;
+  g.padH = s ? b.padH : a.padH; g.padW = s ? b.padW : a.padW; g.tiles_x = s ? b.tiles_x : a.tiles_x; g.tiles_y = s ? b.tiles_y : a.tiles_y;
   g.nimg = s ? b.nimg : a.nimg; g.ntile_n = s ? b.ntile_n : a.ntile_n;
-  g.w = s ? b.w : a.w; g.ldw = s ? b.ldw : a.ldw; g.N = s ? b.N : a.N; g.wscale = s ? b.wscale : a.wscale;
+  g.w = s ? b.w : a.w; g.N = s ? b.N : a.N; g.wscale = s ? b.wscale : a.wscale;
   g.in_mean = nullptr; g.in_rstd = nullptr;
   return g;
 }
@@ -854,9 +851,8 @@ inline Conv2Geom conv_sf6_geom(const ConvShape& s, float wscale) {
   Conv2Geom g{};
   g.src0 = s.src0; g.src1 = s.src1; g.sb0 = s.sb0; g.sb1 = s.sb1; g.ld0 = s.ld0; g.ld1 = s.ld1;
   g.C0 = s.C0; g.C1 = s.C1; g.H = s.H; g.W = s.W;
-  g.KH = s.KH; g.KW = s.KW; g.padH = s.padH; g.padW = s.padW;
+  g.padH = s.padH; g.padW = s.padW;
   g.Ho = conv_out(s.H, s.KH, 1, s.padH); g.Wo = conv_out(s.W, s.KW, 1, s.padW);
-  g.PH = TH + s.KH - 1; g.PW = TW + s.KW - 1;
   ATDN_CHECK(s.C0 % 32 == 0 && s.C1 % 32 == 0 && s.C0 > 0 && s.ld0 % 4 == 0, "TAP-mode channel constraints");
   ATDN_CHECK(s.ldw % 4 == 0 && s.ldw >= s.KH * s.KW * (s.C0 + s.C1), "weight rows too short");
   ATDN_CHECK(!epi_vec4<Epi>::value || !Epi::kPrefetch || s.N % 4 == 0, "channel-vector epilogue with operand loads needs N % 4 == 0");
@@ -867,7 +863,7 @@ inline Conv2Geom conv_sf6_geom(const ConvShape& s, float wscale) {
              "per-image slice of 4 GB or more: the 32-bit epilogue offsets would wrap");
   g.tiles_x = cdiv(g.Wo, TW); g.tiles_y = cdiv(g.Ho, TH);
   g.nimg = s.nimg; g.ntile_n = cdiv(s.N, BN);
-  g.w = s.wfrag16; g.ldw = s.ldw; g.N = s.N; g.wscale = wscale;
+  g.w = s.wfrag16; g.N = s.N; g.wscale = wscale;
   g.in_mean = s.in_mean; g.in_rstd = s.in_rstd;
   ATDN_CHECK(NORM == (s.in_mean != nullptr) && (!NORM || (s.in_rstd && s.C1 == 0 && s.ld0 == s.C0)),
              "normalise-on-load: one dense fp32 source with its mean / rstd");
@@ -920,41 +916,31 @@ inline void launch_conv_sf6_pair(const ConvShape& s0, float wscale0, Epi ep0, co
 }
 
 
-// block width the 3x3 dispatch below picks for a layer (the flow-head fusion needs one block to hold all channels)
-inline int conv_sf6_block_width_3x3(const ConvShape& s) {
-  const int Ho = conv_out(s.H, s.KH, 1, s.padH), Wo = conv_out(s.W, s.KW, 1, s.padW);
-  const long tiles = (long)s.nimg * cdiv(Wo, 16) * cdiv(Ho, 8);
-  int bn = 64;
-  if (s.N <= 32) bn = 32;
-  else if (s.N == 96) bn = 96;
-  else {
-    int best = cdiv(s.N, 64) * 64;
-    for (int c : {128, 256})
-      if (cdiv(s.N, c) * c <= best) { best = cdiv(s.N, c) * c; bn = c; }
-  }
-  while (bn > 64 && bn != 96 && tiles * cdiv(s.N, bn) < 300) bn /= 2;
-  return bn;
+// operands every halo-patch kernel needs: the fragment-major weight copy, stride 1, whole 32-channel chunks
+inline bool conv_sf6_operands_ok(const ConvShape& s) {
+  return s.wfrag16 && s.stride == 1 && s.C0 % 32 == 0 && s.C1 % 32 == 0 && s.C0 > 0 && s.ld0 % 4 == 0;
 }
 
-template <int TH, int BN, int WM, int WN, int KH, int KW, class Epi, bool FAST, bool NORM>
-inline void launch_conv_sf6_m(const ConvShape& s, float wscale, const Epi& ep, hipStream_t st) {
-  launch_conv_sf6<TH, BN, WM, WN, KH, KW, Epi, FAST, NORM>(s, wscale, ep, st);
-}
+// The tile a convolution runs with: th x 16 output pixels x bn channels, or (run) 128 consecutive pixels x 128 channels.
+struct Sf6Plan { int th, bn; bool run; };   // th == 0: this path does not serve the shape
 
-// Picks the block shape for N output channels and launches the fragment-major-weight kernel: 8x16-pixel tiles, or
-// 12x16 for the 64- and 96-wide blocks (3 MFMA row tiles per wave: less halo, fewer tile seams; measured
-// 7-10 % faster on the encoder shapes and on N = 192) when the taller tiles pad the image no worse and still
-// cover the chip. Returns false when this path does not serve the shape (the caller falls back to the plain implicit GEMM).
-template <int KH, int KW, class Epi, bool FAST>
-inline bool conv_sf6_try_shape(const ConvShape& s, float wscale, const Epi& ep, hipStream_t st, int* bn_out, int* th_out) {
+// Decides the tile for a KH x KW convolution with epilogue Epi — the ONE place that does: conv_sf6_try launches what it says, and
+// conv_sf6_try_pair asks it whether two convolutions get the same kernel. Host arithmetic on the shape only.
+template <int KH, int KW, class Epi>
+inline Sf6Plan conv_sf6_plan(const ConvShape& s, bool fast) {
+  constexpr bool k3 = KH == 3;
+  // 4-row and run tiles: not for the statistics epilogues (their tile height follows from the layer's geometry alone) nor the
+  // fused flow head (one block holds all channels of its pixels)
+  constexpr bool plain = !Epi::kStats && !epi_flowhead<Epi>::value;
+  constexpr Sf6Plan none{0, 0, false};
   const int Ho = conv_out(s.H, s.KH, 1, s.padH), Wo = conv_out(s.W, s.KW, 1, s.padW);
   const long tiles = (long)s.nimg * cdiv(Wo, 16) * cdiv(Ho, 8);
   // block width: the one of {256, 128, 64} that pads N least (ties: the widest, it shares the patch among more
   // channels); N = 96 has its own 2x3-wave block. Measured (tools/microbench_conv.py, B = 8): N = 256 -> 256-wide
   // 163 us vs 64-wide 174 us; N = 192 -> 64-wide 154 us vs 128- or 256-wide 186 us.
   int bn = 64;
-  if (s.N <= 32 && KH == 3) bn = 32;       // flow head (N = 2): 4 waves of 32 px x 32 ch, half the padding of a 64-wide block
-  else if (s.N == 96 && KH == 3) bn = 96;
+  if (s.N <= 32 && k3) bn = 32;       // flow head (N = 2): 4 waves of 32 px x 32 ch, half the padding of a 64-wide block
+  else if (s.N == 96 && k3) bn = 96;
   else {
     int best = cdiv(s.N, 64) * 64;
     for (int c : {128, 256})
@@ -968,143 +954,118 @@ inline bool conv_sf6_try_shape(const ConvShape& s, float wscale, const Epi& ep, 
   // (Round 5 also measured 64-wide blocks for the gates, 8 x 16 and 12 x 16 pixels, 2 x 2 waves — the shape the 3x3 convolutions
   // of the motion encoder run best with: z|r 3.40 -> 3.52 / 3.63 ms per forward, q 1.94 -> 2.06 / 2.08; the vertical pass worse
   // still, 174 registers = two waves per SIMD without the wider block's patch reuse. profiles/r05_ab_gru_block_width.txt)
-  if constexpr (KH != 3) bn = std::min(bn, 128);
-  *th_out = 8;
+  if (!k3) bn = std::min(bn, 128);
+  // 12 x 16 pixels for the 64- and 96-wide 3x3 blocks (3 MFMA row tiles per wave: less halo, fewer tile seams; measured
+  // 7-10 % faster on the encoder shapes and on N = 192) when the taller tiles pad the image no worse ...
+  const bool fits12 = k3 && (bn == 64 || bn == 96) && cdiv(Ho, 12) * 12 * 100 <= cdiv(Ho, 8) * 8 * 103;
   if (s.in_mean) {   // normalise-on-load: statistics convs of the feature network (3x3, 64 / 96 / 128 channels)
-    if constexpr (Epi::kStats && KH == 3 && !FAST) {
-      // (statistics convolutions: the tile height fixes which 32 pixels form a statistics group, so it must follow from
-      // the layer's geometry alone, never from the number of images in the launch — a clip, a continued clip and single
-      // pairs then produce bit-identical InstanceNorm statistics)
-      const bool tall = (bn == 64 || bn == 96) && cdiv(Ho, 12) * 12 * 100 <= cdiv(Ho, 8) * 8 * 103;
-      *bn_out = bn; *th_out = tall ? 12 : 8;
-      if (bn == 64 && tall) launch_conv_sf6_m<12, 64, 2, 2, KH, KW, Epi, false, true>(s, wscale, ep, st);
-      else if (bn == 64) launch_conv_sf6_m<8, 64, 2, 2, KH, KW, Epi, false, true>(s, wscale, ep, st);
-      else if (bn == 96 && tall) launch_conv_sf6_m<12, 96, 2, 3, KH, KW, Epi, false, true>(s, wscale, ep, st);
-      else if (bn == 96) launch_conv_sf6_m<8, 96, 2, 3, KH, KW, Epi, false, true>(s, wscale, ep, st);
-      else if (bn == 128) launch_conv_sf6_m<8, 128, 1, 4, KH, KW, Epi, false, true>(s, wscale, ep, st);
-      else return false;
-      return true;
-    } else {
-      return false;
-    }
+    if (!Epi::kStats || !k3 || fast || bn == 32 || bn == 256) return none;
+    // (statistics convolutions: the tile height fixes which 32 pixels form a statistics group, so it must follow from
+    // the layer's geometry alone, never from the number of images in the launch — a clip, a continued clip and single
+    // pairs then produce bit-identical InstanceNorm statistics)
+    return {fits12 ? 12 : 8, bn, false};
   }
+  // ConvShape::tile_form, set by the test entry atdn_conv2d_nhwc_sf_epi alone: 1 = the 8 x 16 x 128 halo block and 2 = the run
+  // tiles for a 1x5 / 5x1 convolution at ANY grid size, so that both forms can be compared on small shapes
+  const bool run_ok = !k3 && plain && conv_sf6_run_eligible<KH, KW>(s);
+  if (!k3 && plain && s.tile_form == 1) return {8, 128, false};
+  if (run_ok && s.tile_form == 2) return {8, 128, true};
   // Small grids (round 6: one or two pairs per launch — the reference's per-frame call pattern; 47 x 154 pixels are 60 tiles of
   // 8 x 16): when even 64-wide blocks leave most of the chip's 512 block slots empty, 4 x 16-pixel tiles double the blocks. A
   // block then carries half the MFMAs behind a relatively larger halo, which costs efficiency nobody is short of at this size.
   // Same K order as every other tile shape, so the same bits (tests/test_gpu_parity.py: a pair comes out of an 8-pair launch
-  // exactly as out of a single-pair call). Not for the statistics epilogues (their tile height follows from the layer's geometry
-  // alone) nor the fused flow head (one block holds all channels of its pixels).
-  // (ConvShape::tile_form, set by the test entry atdn_conv2d_nhwc_sf_epi alone: 1 = the 8 x 16 x 128 halo block and 2 = the run
-  // tiles for a 1x5 / 5x1 convolution at ANY grid size, so that both forms can be compared on small shapes)
-  if constexpr (KH != 3 && !Epi::kStats && !epi_flowhead<Epi>::value) {
-    if (s.tile_form == 1) {
-      *bn_out = 128;
-      launch_conv_sf6_m<8, 128, 1, 4, KH, KW, Epi, FAST, false>(s, wscale, ep, st);
-      return true;
-    }
-    if (s.tile_form == 2 && conv_sf6_run_eligible<KH, KW>(s)) {
-#ifndef ATDN_NO_RUN_TILES
-      *bn_out = 128;
-      launch_conv_sf6_run<KH, KW, Epi, FAST>(s, wscale, ep, st);
-      return true;
-#else
-      ATDN_CHECK(false, "run tiles requested from a library built with ATDN_NO_RUN_TILES");
-#endif
-    }
-  }
-  if constexpr (!Epi::kStats && !epi_flowhead<Epi>::value) {
-    // (ATDN_CONV_SMALL_TILES=1: the 4 x 16 x 64 form for every 1x5 / 5x1 convolution at ANY grid size — the A/B of DESIGN.md 10.8)
-    static const bool force_small = getenv("ATDN_CONV_SMALL_TILES") && getenv("ATDN_CONV_SMALL_TILES")[0] == '1';
-    if ((bn == 64 && tiles * cdiv(s.N, 64) < 300) || (force_small && KH != 3)) {
-      *bn_out = 64; *th_out = 4;
-      launch_conv_sf6_m<4, 64, 2, 2, KH, KW, Epi, FAST, false>(s, wscale, ep, st);
-      return true;
-    }
-  }
-  if constexpr (KH != 3 && !Epi::kStats && !epi_flowhead<Epi>::value) {
-    // (ATDN_CONV_SMALL_TILES=2: 4 x 16-pixel x 128-channel blocks for the 1x5 / 5x1 convolutions — half the row tiles per wave of the
-    // shipped 8 x 16 x 128 block, so fewer registers: the A/B of DESIGN.md 10.8)
-    static const bool half128 = getenv("ATDN_CONV_SMALL_TILES") && getenv("ATDN_CONV_SMALL_TILES")[0] == '2';
-    if (half128 && bn == 128) {
-      *bn_out = 128; *th_out = 4;
-      launch_conv_sf6_m<4, 128, 1, 4, KH, KW, Epi, FAST, false>(s, wscale, ep, st);
-      return true;
-    }
-  }
-  if constexpr (KH == 3) {
-    if (bn == 32) { *bn_out = 32; launch_conv_sf6_m<8, 32, 4, 1, KH, KW, Epi, FAST, false>(s, wscale, ep, st); return true; }
-    const long tiles12 = (long)s.nimg * cdiv(Wo, 16) * cdiv(Ho, 12);
-    const bool tall = (bn == 64 || bn == 96) && cdiv(Ho, 12) * 12 * 100 <= cdiv(Ho, 8) * 8 * 103 &&
-                      (Epi::kStats || tiles12 * cdiv(s.N, bn) >= 512);   // (statistics: geometry only, see above)
-    if (tall) {
-      *bn_out = bn; *th_out = 12;
-      if (bn == 64) launch_conv_sf6_m<12, 64, 2, 2, KH, KW, Epi, FAST, false>(s, wscale, ep, st);
-      else launch_conv_sf6_m<12, 96, 2, 3, KH, KW, Epi, FAST, false>(s, wscale, ep, st);
-      return true;
-    }
-  }
-  *bn_out = bn;
-#ifndef ATDN_NO_RUN_TILES   // (-DATDN_NO_RUN_TILES: a variant build that keeps the rectangular tiles everywhere, for A/B timing)
+  // exactly as out of a single-pair call).
+  if (plain && bn == 64 && tiles * cdiv(s.N, 64) < 300) return {4, 64, false};
+  // ... and still cover the chip (statistics: geometry only, see above)
+  const long tiles12 = (long)s.nimg * cdiv(Wo, 16) * cdiv(Ho, 12);
+  if (fits12 && (Epi::kStats || tiles12 * cdiv(s.N, bn) >= 512)) return {12, bn, false};
   // 1x5 / 5x1 on the 8 x 16 x 128 block: 128-pixel run tiles, no padding pixels but in an image's last tile
-  if constexpr (KH != 3 && !Epi::kStats && !epi_flowhead<Epi>::value) {
-    if (bn == 128 && conv_sf6_run_eligible<KH, KW>(s)) { launch_conv_sf6_run<KH, KW, Epi, FAST>(s, wscale, ep, st); return true; }
+  // (profiles/r07_ab_gru_run_tiles.txt)
+  if (run_ok && bn == 128) return {8, 128, true};
+  return {8, bn, false};
+}
+
+// One block shape: the normalise-on-load build of it (NORM) when the source is raw and the epilogue has one — the statistics
+// epilogues' 64 / 96 / 128-wide 3x3 blocks, split-f16 arithmetic only.
+template <int TH, int BN, int WM, int WN, int KH, int KW, class Epi, bool FAST>
+inline void conv_sf6_launch_tile(const ConvShape& s, float wscale, const Epi& ep, hipStream_t st) {
+  if (s.in_mean) {
+    if constexpr (Epi::kStats && KH == 3 && !FAST && TH >= 8 && (BN == 64 || BN == 96 || BN == 128))
+      return launch_conv_sf6<TH, BN, WM, WN, KH, KW, Epi, false, true>(s, wscale, ep, st);
+    ATDN_CHECK(false, "no normalise-on-load kernel for this tile");
   }
-#endif
-  switch (bn) {
-    case 64:  launch_conv_sf6_m<8, 64, 2, 2, KH, KW, Epi, FAST, false>(s, wscale, ep, st); return true;  // 4 waves of 64 px x 32 ch
-    case 128: launch_conv_sf6_m<8, 128, 1, 4, KH, KW, Epi, FAST, false>(s, wscale, ep, st); return true;
-    case 256: launch_conv_sf6_m<8, 256, 1, 8, KH, KW, Epi, FAST, false>(s, wscale, ep, st); return true;
-    default: break;
+  launch_conv_sf6<TH, BN, WM, WN, KH, KW, Epi, FAST, false>(s, wscale, ep, st);
+}
+
+// Maps a plan to its instantiation: every block shape and its wave grid are named here and nowhere else. The guards keep the
+// kernel set: 32-, 96-, 256-wide and 12-row blocks exist for 3x3 only, 4-row and run tiles for the plain epilogues only.
+template <int KH, int KW, class Epi, bool FAST>
+inline void conv_sf6_launch(const Sf6Plan& p, const ConvShape& s, float wscale, const Epi& ep, hipStream_t st) {
+  constexpr bool k3 = KH == 3;
+  constexpr bool plain = !Epi::kStats && !epi_flowhead<Epi>::value;
+  const int th = p.th, bn = p.bn;
+  if (p.run) {
+    if constexpr (!k3 && plain) return launch_conv_sf6_run<KH, KW, Epi, FAST>(s, wscale, ep, st);
+  } else if (th == 4 && bn == 64) {
+    if constexpr (plain) return conv_sf6_launch_tile<4, 64, 2, 2, KH, KW, Epi, FAST>(s, wscale, ep, st);
+  } else if (th == 8 && bn == 64) {   // 4 waves of 64 px x 32 ch
+    return conv_sf6_launch_tile<8, 64, 2, 2, KH, KW, Epi, FAST>(s, wscale, ep, st);
+  } else if (th == 8 && bn == 128) {
+    return conv_sf6_launch_tile<8, 128, 1, 4, KH, KW, Epi, FAST>(s, wscale, ep, st);
+  } else if constexpr (k3) {
+    if (th == 8 && bn == 32) return conv_sf6_launch_tile<8, 32, 4, 1, KH, KW, Epi, FAST>(s, wscale, ep, st);   // 4 waves of 32 px x 32 ch
+    if (th == 8 && bn == 96) return conv_sf6_launch_tile<8, 96, 2, 3, KH, KW, Epi, FAST>(s, wscale, ep, st);
+    if (th == 8 && bn == 256) return conv_sf6_launch_tile<8, 256, 1, 8, KH, KW, Epi, FAST>(s, wscale, ep, st);
+    if (th == 12 && bn == 64) return conv_sf6_launch_tile<12, 64, 2, 2, KH, KW, Epi, FAST>(s, wscale, ep, st);
+    if (th == 12 && bn == 96) return conv_sf6_launch_tile<12, 96, 2, 3, KH, KW, Epi, FAST>(s, wscale, ep, st);
   }
-  if constexpr (KH == 3) {
-    if (bn == 96) { launch_conv_sf6_m<8, 96, 2, 3, KH, KW, Epi, FAST, false>(s, wscale, ep, st); return true; }
-  }
-  return false;
+  ATDN_CHECK(false, "tile plan without a kernel for this epilogue");
 }
 
 // Both convolutions as ONE launch when each of them, alone, would run the 12 x 16-pixel x 64-channel 3x3 kernel with a plain
-// store (the same selection rules as conv_sf6_try_shape<3, 3>: the pair changes the schedule, never the kernel a convolution gets).
+// store (conv_sf6_plan decides: the pair changes the schedule, never the kernel a convolution gets).
 template <class Epi>
 inline bool conv_sf6_try_pair(const ConvShape& s0, float wscale0, const Epi& ep0, const ConvShape& s1, float wscale1, const Epi& ep1,
                               hipStream_t st, bool fast) {
   if constexpr ((epi_gen6<Epi>::value & 1) == 0 || Epi::kStats || epi_flowhead<Epi>::value) {
     return false;
   } else {
-    auto picks_tall64 = [&](const ConvShape& s) {
-      if (!conv_halo_eligible(s) || s.KH != 3 || s.KW != 3 || !s.wfrag16 || s.in_mean) return false;
+    auto picks_12x64 = [&](const ConvShape& s) {
+      if (!conv_halo_eligible(s) || s.KH != 3 || s.KW != 3 || !conv_sf6_operands_ok(s) || s.in_mean) return false;
       if (epi_vec4<Epi>::value && (s.N % 4) != 0) return false;
-      if (s.C0 % 32 != 0 || s.C1 % 32 != 0 || s.C0 <= 0 || s.ld0 % 4 != 0) return false;
-      if (conv_sf6_block_width_3x3(s) != 64) return false;
-      const int Ho = conv_out(s.H, 3, 1, s.padH), Wo = conv_out(s.W, 3, 1, s.padW);
-      const long tiles12 = (long)s.nimg * cdiv(Wo, 16) * cdiv(Ho, 12);
-      return cdiv(Ho, 12) * 12 * 100 <= cdiv(Ho, 8) * 8 * 103 && tiles12 * cdiv(s.N, 64) >= 512;
+      const Sf6Plan p = conv_sf6_plan<3, 3, Epi>(s, fast);
+      return p.th == 12 && p.bn == 64 && !p.run;
     };
-    if (!picks_tall64(s0) || !picks_tall64(s1)) return false;
-    if (fast) launch_conv_sf6_pair<12, 64, 2, 2, 3, 3, Epi, true>(s0, wscale0, ep0, s1, wscale1, ep1, st);
-    else launch_conv_sf6_pair<12, 64, 2, 2, 3, 3, Epi, false>(s0, wscale0, ep0, s1, wscale1, ep1, st);
+    if (!picks_12x64(s0) || !picks_12x64(s1)) return false;
+    with_fast(fast, [&](auto f) {
+      launch_conv_sf6_pair<12, 64, 2, 2, 3, 3, Epi, decltype(f)::value>(s0, wscale0, ep0, s1, wscale1, ep1, st);
+    });
     return true;
   }
+}
+
+// Plans and launches; returns false when this path does not serve the shape (the caller falls back to the plain implicit GEMM).
+template <int KH, int KW, class Epi>
+inline bool conv_sf6_try_taps(const ConvShape& s, float wscale, const Epi& ep, hipStream_t st, int* bn_out, int* th_out, bool fast) {
+  const Sf6Plan p = conv_sf6_plan<KH, KW, Epi>(s, fast);
+  if (p.th == 0) return false;
+  *bn_out = p.bn; *th_out = p.th;
+  with_fast(fast, [&](auto f) { conv_sf6_launch<KH, KW, Epi, decltype(f)::value>(p, s, wscale, ep, st); });
+  return true;
 }
 
 template <class Epi>
 inline bool conv_sf6_try(const ConvShape& s, float wscale, const Epi& ep, hipStream_t st, int* bn_out, int* th_out, bool fast) {
   constexpr int kinds = epi_gen6<Epi>::value;
-  if (kinds == 0 || !s.wfrag16 || s.stride != 1) return false;
+  if (kinds == 0 || !conv_sf6_operands_ok(s)) return false;
   if (epi_vec4<Epi>::value && Epi::kPrefetch && (s.N % 4) != 0) return false;
   if (epi_vec4<Epi>::value && s.N < 4) return false;
-  if (s.C0 % 32 != 0 || s.C1 % 32 != 0 || s.C0 <= 0 || s.ld0 % 4 != 0) return false;
   if constexpr ((kinds & 1) != 0) {
-    if (s.KH == 3 && s.KW == 3)
-      return fast ? conv_sf6_try_shape<3, 3, Epi, true>(s, wscale, ep, st, bn_out, th_out)
-                  : conv_sf6_try_shape<3, 3, Epi, false>(s, wscale, ep, st, bn_out, th_out);
+    if (s.KH == 3 && s.KW == 3) return conv_sf6_try_taps<3, 3>(s, wscale, ep, st, bn_out, th_out, fast);
   }
   if constexpr ((kinds & 2) != 0) {
-    if (s.KH == 1 && s.KW == 5)
-      return fast ? conv_sf6_try_shape<1, 5, Epi, true>(s, wscale, ep, st, bn_out, th_out)
-                  : conv_sf6_try_shape<1, 5, Epi, false>(s, wscale, ep, st, bn_out, th_out);
-    if (s.KH == 5 && s.KW == 1)
-      return fast ? conv_sf6_try_shape<5, 1, Epi, true>(s, wscale, ep, st, bn_out, th_out)
-                  : conv_sf6_try_shape<5, 1, Epi, false>(s, wscale, ep, st, bn_out, th_out);
+    if (s.KH == 1 && s.KW == 5) return conv_sf6_try_taps<1, 5>(s, wscale, ep, st, bn_out, th_out, fast);
+    if (s.KH == 5 && s.KW == 1) return conv_sf6_try_taps<5, 1>(s, wscale, ep, st, bn_out, th_out, fast);
   }
   return false;
 }

@@ -21,19 +21,14 @@ TileChoice conv_sf_dispatch(const ConvShape& s, float wscale, Epi ep, hipStream_
   TileChoice t = choose_tile(s.nimg, Ho * Wo, s.N);
   t.groups_per_img = cdiv(Ho * Wo, t.BM) * (t.BM / 32);
   set_groups(ep, t.groups_per_img);
-  if (sf_fast_mode()) {
-    if (t.BM == 128 && t.BN == 128) launch_conv_sf<2, 2, 2, 2, Epi, true>(s, wscale, ep, st);
-    else if (t.BM == 128 && t.BN == 64) launch_conv_sf<2, 1, 2, 2, Epi, true>(s, wscale, ep, st);
-    else if (t.BM == 128 && t.BN == 96) launch_conv_sf<1, 3, 4, 1, Epi, true>(s, wscale, ep, st);
-    else if (t.BM == 128 && t.BN == 32) launch_conv_sf<1, 1, 4, 1, Epi, true>(s, wscale, ep, st);
-    else launch_conv_sf<1, 1, 2, 2, Epi, true>(s, wscale, ep, st);
-    return t;
-  }
-  if (t.BM == 128 && t.BN == 128) launch_conv_sf<2, 2, 2, 2>(s, wscale, ep, st);
-  else if (t.BM == 128 && t.BN == 64) launch_conv_sf<2, 1, 2, 2>(s, wscale, ep, st);
-  else if (t.BM == 128 && t.BN == 96) launch_conv_sf<1, 3, 4, 1>(s, wscale, ep, st);
-  else if (t.BM == 128 && t.BN == 32) launch_conv_sf<1, 1, 4, 1>(s, wscale, ep, st);
-  else launch_conv_sf<1, 1, 2, 2>(s, wscale, ep, st);
+  with_fast(sf_fast_mode(), [&](auto f) {
+    constexpr bool FAST = decltype(f)::value;
+    if (t.BM == 128 && t.BN == 128) launch_conv_sf<2, 2, 2, 2, Epi, FAST>(s, wscale, ep, st);
+    else if (t.BM == 128 && t.BN == 64) launch_conv_sf<2, 1, 2, 2, Epi, FAST>(s, wscale, ep, st);
+    else if (t.BM == 128 && t.BN == 96) launch_conv_sf<1, 3, 4, 1, Epi, FAST>(s, wscale, ep, st);
+    else if (t.BM == 128 && t.BN == 32) launch_conv_sf<1, 1, 4, 1, Epi, FAST>(s, wscale, ep, st);
+    else launch_conv_sf<1, 1, 2, 2, Epi, FAST>(s, wscale, ep, st);
+  });
   return t;
 }
 

@@ -11,8 +11,9 @@ void launch_flow_head_fused(const ConvShape& s, float wscale, const SfFlowHeadPa
   // 2.35 / 2.37 -> 2.24 / 2.23 ms per forward (profiles/r05_ab_flow_head_128.txt).
   // (the f16 fast mode measures 4 % better on the old 256-wide block — 1.155 against 1.20 ms per forward; one shape for both modes)
   ATDN_CHECK(ep.gstride > 0, "two channel blocks per pixel tile write two copies of G");
-  if (sf_fast_mode()) launch_conv_sf6_m<8, 128, 1, 4, 3, 3, SfFlowHeadPartial, true, false>(s, wscale, ep, st);
-  else launch_conv_sf6_m<8, 128, 1, 4, 3, 3, SfFlowHeadPartial, false, false>(s, wscale, ep, st);
+  with_fast(sf_fast_mode(), [&](auto f) {
+    launch_conv_sf6<8, 128, 1, 4, 3, 3, SfFlowHeadPartial, decltype(f)::value>(s, wscale, ep, st);
+  });
 }
 // (always the 128-wide block, whatever the batch: results must not depend on how many pairs share a launch — at one pair it
 // covers the chip worse than the 64-wide blocks the dispatch would pick, a few us per iteration of the single-pair forward)

@@ -21,7 +21,7 @@
 // Ring of two slots by tick parity: a workgroup can overwrite slot s & 1 (tick s + 2) only after it has swept tick s + 1, which
 // every workgroup publishes only after ITS sweep of tick s has completed. All polled words are zeroed by a memset node in front
 // of every launch (tag 0 never matches: tags start at 1).
-// Where a tick's 2.0 us go (tools/scan_time.py, ablation modes; profiles/r06_scan_*.txt): barriers + publish 0.4, arithmetic
+// Where a tick's 2.0 us go (ablation runs of round 6: profiles/r06_scan_*.txt): barriers + publish 0.4, arithmetic
 // 0.55, the exchange 1.1 (store -> visible ~0.45 + one polling pass ~0.6). Steps on the way (us per tick): first version, every
 // wave storing its own granules and loading its own input-projection terms 3.09 | one store per workgroup, terms by LDS-DMA 2.85
 // | gate batch, packed FMAs, interleaved reductions 2.55-2.68 | first poll delayed until the data is about to be visible 2.02.
@@ -89,7 +89,7 @@ struct ScanArgs {
   unsigned long long* xch;           // [2 slots][workgroup][h1 | lin | h2][unit of the workgroup]: 3 x 512 granules per slot
   unsigned int* abort_word;          // behind the granules
   int T;
-  int mode;                          // diagnostics (ATDN_SCAN_MODE): bits 0-3 initial poll delay, 16 no arithmetic, 32 no sweep (both: timing only), 64 the 64-workgroup form
+  int test_abort;                    // ATDN_SCAN_TEST_ABORT: the launch gives up at once (the test of the verified-launch path)
 };
 
 constexpr int PD = 6;                // ticks the input-projection terms are fetched ahead (LDS-DMA ring of 8 slots)
@@ -124,7 +124,7 @@ __global__ __launch_bounds__((NWV + 1) * 64) void lstm_scan_kernel(const ScanArg
 #pragma unroll
     for (int t = 0; t < PD; ++t) fetch_p1(t);
     barrier_lds();
-    if (a.mode & 128) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; }   // test hook: the launch gives up at once
+    if (a.test_abort) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; }   // test hook: the launch gives up at once
     const unsigned dead_addr = (unsigned)(unsigned long)(__attribute__((address_space(3))) int*)dead;
     for (int s = 0; s < T + 2; ++s) {
       fetch_p1(s + PD);
@@ -177,15 +177,15 @@ __global__ __launch_bounds__((NWV + 1) * 64) void lstm_scan_kernel(const ScanArg
   constexpr int XB = (256 / NWV) * GPW;   // the same units + 256
   barrier_lds();
 
-  bool failed = (a.mode & 128) != 0;   // ATDN_SCAN_TEST_ABORT: behave like a launch whose spins ran out
+  bool failed = a.test_abort != 0;   // ATDN_SCAN_TEST_ABORT: behave like a launch whose spins ran out
   if (failed && threadIdx.x == 0) __hip_atomic_store(abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  int dly = (a.mode & 15) ? (a.mode & 15) : 8, streak = 0;   // sweepers: delay of the first poll in units of 128 clocks (adaptive)
+  int dly = 8, streak = 0;   // sweepers: delay of the first poll in units of 128 clocks (adaptive)
   for (int s = 0; s < T + 2 && !failed; ++s) {
     const int par = s & 1;
     float* img = lds + par * NGRAN;
     const bool doA = s < T, doC = s >= 2;   // (lstm_linear is live in ticks 1 .. T; nothing of it is carried)
     // ---- sweep: everything tick s - 1 published carries tag s
-    if (wave < 3 && s >= 1 && !(a.mode & 32)) {
+    if (wave < 3 && s >= 1) {
       gu64* g = xch + (long)((s - 1) & 1) * NGRAN + wave * 512 + lane;
       unsigned v[8];
       // The first pass is held back until the stores of tick s - 1 are about to be visible: a pass that comes too early costs a
@@ -232,52 +232,47 @@ __global__ __launch_bounds__((NWV + 1) * 64) void lstm_scan_kernel(const ScanArg
     // ONE v_rcp_f32 for the nine of them, one more pair for the two tanh(c'). (Every lane evaluating every function itself, as
     // the first version of this kernel did, spent 24 quarter-rate instructions per tick and wave.)
     // Stages that are not live in this tick (pipeline fill and drain) compute on whatever the image holds and are discarded.
-    float h1n = 0.f, linv = 0.f, h2n = 0.f;
-    if (!(a.mode & 16)) {
-      const float4 xa = *reinterpret_cast<const float4*>(img + xo), xb = *reinterpret_cast<const float4*>(img + XB + xo);
-      const float4 ya = *reinterpret_cast<const float4*>(img + NWV + xo), yb = *reinterpret_cast<const float4*>(img + XB + NWV + xo);
-      const float4 za = *reinterpret_cast<const float4*>(img + 2 * NWV + xo), zb = *reinterpret_cast<const float4*>(img + XB + 2 * NWV + xo);
-      const float p1v = p1s[(s & 7) * 32 + p1idx];
-      float sv[9];
+    const float4 xa = *reinterpret_cast<const float4*>(img + xo), xb = *reinterpret_cast<const float4*>(img + XB + xo);
+    const float4 ya = *reinterpret_cast<const float4*>(img + NWV + xo), yb = *reinterpret_cast<const float4*>(img + XB + NWV + xo);
+    const float4 za = *reinterpret_cast<const float4*>(img + 2 * NWV + xo), zb = *reinterpret_cast<const float4*>(img + XB + 2 * NWV + xo);
+    const float p1v = p1s[(s & 7) * 32 + p1idx];
+    float sv[9];
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        sv[g] = dot8(w1[g][0], w1[g][1], xa, xb);
-        sv[5 + g] = dot8b(wi[g][0], wi[g][1], ya, yb, wh[g][0], wh[g][1], za, zb);
-      }
-      sv[4] = dot8(wl[0], wl[1], xa, xb);
-#define ATDN_DPP_STEP(ctrl, rmask) _Pragma("unroll") for (int k = 0; k < 9; ++k) \
-        sv[k] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sv[k]), ctrl, rmask, 0xF, false))
-      ATDN_DPP_STEP(0x111, 0xF); ATDN_DPP_STEP(0x112, 0xF); ATDN_DPP_STEP(0x114, 0xF); ATDN_DPP_STEP(0x118, 0xF);
-      ATDN_DPP_STEP(0x142, 0xA); ATDN_DPP_STEP(0x143, 0xC);
-#undef ATDN_DPP_STEP
-      // the totals (lane 63) as scalars FIRST, pinned in uniform control flow: written as `lane == k ? readlane(..) : gv` the
-      // compiler turned the selects into branches and sank a total's last DPP addition into its branch, where only lane k
-      // executes it — lane 63, the one the readlane reads, kept the sum without it
-      int tot[9];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        tot[k] = __builtin_amdgcn_readlane(__float_as_int(sv[k]), 63);
-        asm volatile("" : "+s"(tot[k]));
-      }
-      float gv = 0.f;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) gv = lane == k ? __int_as_float(tot[k]) : gv;
-      const float x = (gv + bvec) + (lane < 4 ? p1v : 0.f);
-      const float e = __builtin_amdgcn_exp2f((lane == 4 ? fminf(x, 20.0f) : x) * kvec);
-      const float t = e * (e + 2.0f);
-      const float r = __builtin_amdgcn_rcpf(lane == 4 ? t + 2.0f : 1.0f + e);
-      const float out = lane == 4 ? (x > 20.0f ? x : x * t * r) : istanh ? __builtin_fmaf(2.0f, r, -1.0f) : r;
-      auto at = [&](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
-      const float cnA = at(out, 1) * c1 + at(out, 0) * at(out, 2);
-      const float cnC = at(out, 6) * c2 + at(out, 5) * at(out, 7);
-      const float y = lane == 0 ? cnA : cnC;
-      const float th = __builtin_fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y * -2.8853900817779268f)), -1.0f);
-      h1n = at(out, 3) * at(th, 0);
-      linv = at(out, 4);
-      h2n = at(out, 8) * at(th, 1);
-      if (doA) { c1 = cnA; h1_last = h1n; }
-      if (doC) { c2 = cnC; h2_last = h2n; }
+    for (int g = 0; g < 4; ++g) {
+      sv[g] = dot8(w1[g][0], w1[g][1], xa, xb);
+      sv[5 + g] = dot8b(wi[g][0], wi[g][1], ya, yb, wh[g][0], wh[g][1], za, zb);
     }
+    sv[4] = dot8(wl[0], wl[1], xa, xb);
+#define ATDN_DPP_STEP(ctrl, rmask) _Pragma("unroll") for (int k = 0; k < 9; ++k) \
+      sv[k] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sv[k]), ctrl, rmask, 0xF, false))
+    ATDN_DPP_STEP(0x111, 0xF); ATDN_DPP_STEP(0x112, 0xF); ATDN_DPP_STEP(0x114, 0xF); ATDN_DPP_STEP(0x118, 0xF);
+    ATDN_DPP_STEP(0x142, 0xA); ATDN_DPP_STEP(0x143, 0xC);
+#undef ATDN_DPP_STEP
+    // the totals (lane 63) as scalars FIRST, pinned in uniform control flow: written as `lane == k ? readlane(..) : gv` the
+    // compiler turned the selects into branches and sank a total's last DPP addition into its branch, where only lane k
+    // executes it — lane 63, the one the readlane reads, kept the sum without it
+    int tot[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      tot[k] = __builtin_amdgcn_readlane(__float_as_int(sv[k]), 63);
+      asm volatile("" : "+s"(tot[k]));
+    }
+    float gv = 0.f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) gv = lane == k ? __int_as_float(tot[k]) : gv;
+    const float x = (gv + bvec) + (lane < 4 ? p1v : 0.f);
+    const float e = __builtin_amdgcn_exp2f((lane == 4 ? fminf(x, 20.0f) : x) * kvec);
+    const float t = e * (e + 2.0f);
+    const float r = __builtin_amdgcn_rcpf(lane == 4 ? t + 2.0f : 1.0f + e);
+    const float out = lane == 4 ? (x > 20.0f ? x : x * t * r) : istanh ? __builtin_fmaf(2.0f, r, -1.0f) : r;
+    auto at = [&](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
+    const float cnA = at(out, 1) * c1 + at(out, 0) * at(out, 2);
+    const float cnC = at(out, 6) * c2 + at(out, 5) * at(out, 7);
+    const float y = lane == 0 ? cnA : cnC;
+    const float th = __builtin_fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y * -2.8853900817779268f)), -1.0f);
+    const float h1n = at(out, 3) * at(th, 0), linv = at(out, 4), h2n = at(out, 8) * at(th, 1);
+    if (doA) { c1 = cnA; h1_last = h1n; }
+    if (doC) { c2 = cnC; h2_last = h2n; }
     // ---- publish: the workgroup's 24 results as ONE store instruction of wave 4 (tag = tick + 1), and the output row
     if (lane == 0) { pub[wave] = h1n; pub[NWV + wave] = linv; pub[2 * NWV + wave] = h2n; }
     barrier_lds();
@@ -324,11 +319,10 @@ void launch_lstm_scan(const float* pre1, const float* Whh1, const float* bhh1, c
   ScanArgs a{pre1, Whh1, bhh1, Wlin, blin, Wih2, bih2, Whh2, bhh2, state, h2seq,
              reinterpret_cast<unsigned long long*>(exchange),
              reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(exchange) + (long)(2 * NGRAN) * 8), T,
-             (getenv("ATDN_SCAN_MODE") ? atoi(getenv("ATDN_SCAN_MODE")) : 0) | (getenv("ATDN_SCAN_TEST_ABORT") ? 128 : 0)};
+             getenv("ATDN_SCAN_TEST_ABORT") ? 1 : 0};
   // 128 workgroups of 4 units: one arithmetic wave per SIMD (64 of 8 units: two waves share a SIMD's vector ALU; 2.44 against
-  // 2.02 us per tick at each form's best poll delay). ATDN_SCAN_MODE bit 6 selects the 64-workgroup form for comparison.
-  if (a.mode & 64) hipLaunchKernelGGL(lstm_scan_kernel<8>, dim3(HD / 8), dim3(9 * 64), 0, st, a);
-  else hipLaunchKernelGGL(lstm_scan_kernel<4>, dim3(HD / 4), dim3(5 * 64), 0, st, a);
+  // 2.02 us per tick at each form's best poll delay)
+  hipLaunchKernelGGL(lstm_scan_kernel<4>, dim3(HD / 4), dim3(5 * 64), 0, st, a);
   ATDN_HIP(hipGetLastError());
 }
 

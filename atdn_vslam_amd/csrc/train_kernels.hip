@@ -4,7 +4,6 @@
 #include "train_kernels.h"
 
 #include <cstdint>
-#include <cstdlib>
 #include "clvo_composite.h"
 #include "common.h"
 #include <algorithm>
@@ -737,13 +736,12 @@ static void wgrad16_mfma_launch(const float* x, int nimg, int H, int W, const fl
 void launch_conv_wgrad(const float* x, int Cpix, int Cin, int nimg, int H, int W, const float* dz, int Ho, int Wo, int KH,
                        int KW, int stride, int pad, float* scratch, float* dW, hipStream_t st) {
   ATDN_CHECK(Cpix >= Cin && Cpix % 4 == 0, "conv_wgrad: channel layout");
-  static const bool mfma = !(getenv("ATDN_TRAIN_WGRAD_MFMA") && getenv("ATDN_TRAIN_WGRAD_MFMA")[0] == '0');
-  if (mfma && Cin == 16 && Cpix == 16) {
+  if (Cin == 16 && Cpix == 16) {
     if (KH == 3 && KW == 3 && stride == 1) return wgrad16_mfma_launch<1, 3, 8>(x, nimg, H, W, dz, Ho, Wo, pad, scratch, dW, st);
     if (KH == 3 && KW == 3 && stride == 2) return wgrad16_mfma_launch<2, 3, 4>(x, nimg, H, W, dz, Ho, Wo, pad, scratch, dW, st);
     if (KH == 1 && KW == 1 && stride == 2) return wgrad16_mfma_launch<2, 1, 4>(x, nimg, H, W, dz, Ho, Wo, pad, scratch, dW, st);
   }
-  if (mfma && Cin == 3 && Cpix == 4 && KH == 7 && KW == 7 && stride == 2 && pad == 3) {
+  if (Cin == 3 && Cpix == 4 && KH == 7 && KW == 7 && stride == 2 && pad == 3) {
     const long items = (long)nimg * cdiv(Ho, SW_R) * cdiv(Wo, WG_TW);
     const int nblk = (int)std::min<long>(items, WG_MFMA_BLOCKS);
     hipLaunchKernelGGL(stem_wgrad_mfma_kernel, dim3(nblk), dim3(256), 0, st, x, nimg, H, W, dz, Ho, Wo, scratch, nblk * 4);

@@ -1,5 +1,5 @@
 """Wall time of the CLVO head's recurrent scan over a KITTI-00-length sequence (4,540 steps, one batch row): the per-step kernel
-(ATDN_SCAN_PERSISTENT=0) against the persistent kernel (csrc/lstm_scan.hip), and the latter's experiment modes (ATDN_SCAN_MODE)."""
+(ATDN_SCAN_PERSISTENT=0) against the persistent kernel (csrc/lstm_scan.hip)."""
 import os
 import sys
 import time
@@ -41,8 +41,6 @@ f = torch.from_numpy((r.normal(0, 0.12, (1, 512)) + np.cumsum(r.normal(0, 0.01, 
 per, one = head(False), head(True)
 ms, ref = run(per, f)
 print("per-step kernel              %7.2f ms  (%.2f us per step)" % (ms, ms * 1e3 / T))
-for mode in [int(m) for m in os.environ.get("MODES", "0,1,2,3,4,5,6,7").split(",")]:
-    os.environ["ATDN_SCAN_MODE"] = str(mode)
-    ms, out = run(one, f)
-    print("persistent, mode %d           %7.2f ms  (%.2f us per step)  max |rot - per-step| %.2e  finite %s"
-          % (mode, ms, ms * 1e3 / T, float((out - ref).abs().max()), bool(torch.isfinite(out).all())))
+ms, out = run(one, f)
+print("persistent kernel            %7.2f ms  (%.2f us per step)  max |rot - per-step| %.2e  finite %s"
+      % (ms, ms * 1e3 / T, float((out - ref).abs().max()), bool(torch.isfinite(out).all())))
