@@ -11,6 +11,7 @@
 #include "frontend.h"
 #include "conv_sf.h"
 #include "epilogues_sf.h"
+#include "warm_start_host.h"
 
 namespace atdn {
 extern template TileChoice conv_dispatch<MODE_TAP, EpiBias<ACT_NONE>>(const ConvShape&, EpiBias<ACT_NONE>, hipStream_t);
@@ -379,6 +380,17 @@ int atdn_pose_accumulate_f32(float* pose16, const float* rot, const float* tr) {
   make_transform(rot, tr, m);
   matmul4(pose16, m, o);
   for (int i = 0; i < 16; ++i) pose16[i] = o[i];
+  ATDN_API_END
+}
+
+// ------------------------------------------------------------------ warm start (host twin of warm_start.hip)
+int atdn_flow_forward_interpolate_host(const float* flow_low, int B, int h, int w, float* out) {
+  ATDN_API_BEGIN
+  ATDN_CHECK(flow_low && out, "null argument");
+  ATDN_CHECK(B >= 1 && h >= 1 && w >= 1 && (long)h * w <= (1L << 24), "bad batch or grid size");
+  const long count = (long)B * 2 * h * w;
+  ATDN_CHECK(flow_low + count <= out || out + count <= flow_low, "input and output overlap");
+  forward_interpolate_host(flow_low, B, h, w, out);
   ATDN_API_END
 }
 

@@ -164,6 +164,7 @@ class RAFTGMA(_NativeModule):
         self.saturation_fallback = bool(saturation_fallback)
         self.low_latency = bool(low_latency) or os.environ.get("ATDN_LOW_LATENCY") == "1"   # (the variable: experiments only)
         self._stream_tail = None        # forward_consecutive: (last frame tensor, its version, handle) of the chain in progress
+        self._warm_low = None           # forward_consecutive(warm_start=True): flow_low of the chain's last call
         self.fell_back = False
         self.saturation_check_every = int(saturation_check_every)
         self.saturation_checks = 0      # how many times the counter has been read (tests)
@@ -189,7 +190,7 @@ class RAFTGMA(_NativeModule):
 
     def _drop_handles(self):
         super()._drop_handles()
-        self._stream_tail = None
+        self._stream_tail = self._warm_low = None
         self._sat_pending = True        # new weights (load_state_dict / .to()): the next forward is checked again
 
     def check_saturation(self, raise_on_clamp=True):
@@ -282,7 +283,7 @@ class RAFTGMA(_NativeModule):
         `flow_predictions` (network.py:106-129) — a list of `iters` tensors [B,2,H,W], the upsampled flow after every iteration;
         values only (this module is inference-only: the list carries no autograd graph)."""
         self._require_input(image1, "RAFTGMA.forward")
-        self._stream_tail = None   # pair mode overwrites the handle's feature maps: a forward_consecutive chain ends here
+        self._stream_tail = self._warm_low = None   # pair mode overwrites the handle's feature maps: a forward_consecutive chain ends here
         if image1.shape != image2.shape or image1.dim() != 4 or image1.shape[1] != 3:
             raise RuntimeError("expected two [B,3,H,W] frames, got %s and %s" % (tuple(image1.shape), tuple(image2.shape)))
         B, _, H, W = image1.shape
@@ -321,7 +322,7 @@ class RAFTGMA(_NativeModule):
         Same bits as the non-continued call and as pair mode (round 3: the kernels' statistics grouping no longer depends on
         how many images share a launch; tests/test_gpu_round3.py)."""
         self._require_input(frames, "RAFTGMA.forward_sequence")
-        self._stream_tail = None
+        self._stream_tail = self._warm_low = None
         if frames.dim() != 4 or frames.shape[1] != 3 or frames.shape[0] < 2:
             raise RuntimeError("expected frames [B+1,3,H,W] with B >= 1, got %s" % (tuple(frames.shape),))
         if self.precision not in ("split_f16", "f16"):
@@ -345,28 +346,46 @@ class RAFTGMA(_NativeModule):
         return flow_low, flow_up
 
     @torch.no_grad()
-    def forward_consecutive(self, prev, cur, iters=12):
+    def forward_consecutive(self, prev, cur, iters=12, warm_start=False):
         """`flow_net(prev[None], cur[None], iters, test_mode=True)` for a caller that walks a sequence one frame per call
         (NeuralSLAM.__call__, neural_slam.py:192-227: frame t is image2 of one pair and image1 of the next): when `prev` IS the
         tensor that was `cur` of the previous call of this method — same object, not modified since, same handle, nothing else
         run on the module in between — its features are still in the handle and only `cur` goes through the feature network
         (atdn_gma_forward_sequence_continued with one pair). The continued form gives the bits of pair mode
         (tests/test_gpu_round3.py), so this is pair mode minus one feature-network pass; anything that breaks the chain (another
-        forward, new weights, .to(), another frame size) just makes the next call encode both frames again."""
+        forward, new weights, .to(), another frame size) just makes the next call encode both frames again.
+        `warm_start=True`: the module keeps the flow_low of this call, and while the chain is unbroken (the same rule) the next
+        warm call starts its refinement from `transforms.forward_interpolate` of it, passed as `flow_init` — what the flow
+        package's evaluate.py does for video (whl:GMA/core/utils/utils.py:28-56), with the interpolation on the device. A first
+        call and a call after a broken chain run cold, exactly as with warm_start=False; so does a warm call that follows a
+        warm_start=False call (nothing was kept). Works in every precision: only `flow_init` is fed."""
         self._require_input(cur, "RAFTGMA.forward_consecutive")
         if prev.shape != cur.shape or cur.dim() != 3 or cur.shape[0] != 3:
             raise RuntimeError("expected two [3,H,W] frames, got %s and %s" % (tuple(prev.shape), tuple(cur.shape)))
-        if self.precision not in ("split_f16", "f16"):
+        sf = self.precision in ("split_f16", "f16")
+        if not sf and not warm_start:
             return self.forward(prev[None], cur[None], iters=iters, test_mode=True)
         key = self._key(cur.shape[1], cur.shape[2])
         ent, tail = self._handles.get(key), self._stream_tail
         cont = (tail is not None and ent is not None and tail[0] is prev and tail[1] == prev._version and tail[2] == ent[0].value
                 and ent[1] == self._fingerprint())
-        low, up = self.forward_sequence(torch.stack([prev, cur]), iters=iters, continued=cont)
+        fi = None
+        if warm_start and cont and self._warm_low is not None:
+            from .transforms import forward_interpolate
+            fi = forward_interpolate(self._warm_low)
+        if sf:
+            low, up = self.forward_sequence(torch.stack([prev, cur]), iters=iters, flow_init=fi, continued=cont)
+        else:   # (the exact-fp32 mode has no sequence form: the chain only carries the kept flow)
+            low, up = self.forward(prev[None], cur[None], iters=iters, flow_init=fi, test_mode=True)
         ent = self._handles.get(key)
-        if ent is not None and not self.fell_back:
+        if ent is not None and (not self.fell_back or not sf):
             self._stream_tail = (cur, cur._version, ent[0].value)   # (holds `cur`: its storage cannot be handed to another tensor)
+            self._warm_low = low if warm_start else None
         return low, up
+
+    def break_chain(self):
+        """Ends a forward_consecutive chain: the next call encodes both frames and, with warm_start, runs cold."""
+        self._stream_tail = self._warm_low = None
 
     def _read_counter(self, handle, who):
         """Reads (and resets) the device's saturation counter through `handle` and publishes a non-zero count in the per-device

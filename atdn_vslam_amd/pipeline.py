@@ -211,7 +211,11 @@ class OdometryPipeline:
 class VisualOdometry:
     """Frame-at-a-time odometry with the reference's call pattern: `pose = vo(frame)`."""
 
-    def __init__(self, gma_state, clvo_state, device="cuda:0", iters=12):
+    def __init__(self, gma_state, clvo_state, device="cuda:0", iters=12, warm_start=False):
+        """`warm_start=True`: every pair after the first of an unbroken run of calls starts its refinement from the previous
+        pair's flow, forward-interpolated on the device (RAFTGMA.forward_consecutive); meant to be combined with a smaller
+        `iters`, which is the caller's choice. `reset()` makes the next pair run cold again."""
+        self.warm_start = bool(warm_start)
         # one pair per call: the low-latency form of the flow network (modules.RAFTGMA)
         self.pipe = OdometryPipeline(gma_state, clvo_state, device=device, max_batch=1, iters=iters, low_latency=True)
         # frame-by-frame caller: every call ends in a device synchronisation anyway (the pose goes to the host), so the
@@ -224,6 +228,7 @@ class VisualOdometry:
         self._prev = None
         self.current_pose = torch.eye(4, dtype=torch.float32)
         self.pipe.head.reset_lstm()
+        self.pipe.flow_net.break_chain()   # a new sequence: no features or flow carried over
 
     @torch.no_grad()
     def __call__(self, im):
@@ -234,7 +239,7 @@ class VisualOdometry:
         im = self.pipe.padder.pad(im)[0]
         if self._prev is not None:
             # (pair mode's bits; the previous frame's features are reused when the chain of calls is unbroken)
-            _, flow = self.pipe.flow_net.forward_consecutive(self._prev, im, iters=self.pipe.iters)
+            _, flow = self.pipe.flow_net.forward_consecutive(self._prev, im, iters=self.pipe.iters, warm_start=self.warm_start)
             rot, tr = self.pipe.head(flow)
             rt = torch.cat([rot.reshape(-1), tr.reshape(-1)]).cpu()   # one trip to the host for both vectors
             self.current_pose = transforms.accumulate(self.current_pose, rt[:3], rt[3:])

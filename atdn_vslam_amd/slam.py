@@ -75,13 +75,17 @@ class NeuralSLAM:
     sit in HBM banks, a relocalisation query searches them in one launch and takes the keyframe image from the bank instead
     of its file, and `relocalize_batch` answers several queries per call. Files on disk and return values are the same; with
     the default (False) nothing changes.
+    `warm_start=True`: in odometry mode every pair of an unbroken run of calls starts from the previous pair's flow, pushed forward
+    on the device (RAFTGMA.forward_consecutive; 12 iterations as before). The relocalisation refinement always runs cold: a
+    keyframe and a query are not consecutive frames.
     """
 
     FLOW_CHECKPOINT = "atdn_vslam/checkpoints/gma-kitti.pth"  # utils/gma_parameters.py
 
     def __init__(self, args, odometry_weights=None, start_mode=None, flow_weights=None, mapping_weights=None,
-                 precision=None, map_options=None, resident_map=False):
+                 precision=None, map_options=None, resident_map=False, warm_start=False):
         self._args = args
+        self._warm_start = bool(warm_start)   # odometry mode only; relocalisation pairs are not consecutive frames
         self._map_options = dict(map_options or {})   # keyword arguments of mapping.create_map (e.g. num_epochs)
         self._base = args.keyframes_path
         self._device = torch.device(args.device if getattr(args, "device", None) not in (None, "cpu") else "cuda:0")
@@ -174,7 +178,7 @@ class NeuralSLAM:
             if self._image_buffer is not None:
                 im2 = self._padder.pad(im)[0]
                 # (pair mode's bits, one feature-network pass per frame while the chain of odometry calls is unbroken)
-                _, flow = self._flow_net.forward_consecutive(self._image_buffer, im2, iters=12)
+                _, flow = self._flow_net.forward_consecutive(self._image_buffer, im2, iters=12, warm_start=self._warm_start)
                 pred_rot, pred_tr = self._odometry_net(flow)
                 rot, tr = pred_rot.squeeze().cpu(), pred_tr.squeeze().cpu()
                 pred_mat = transforms.transform(rot, tr)

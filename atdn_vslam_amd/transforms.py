@@ -60,6 +60,28 @@ def kitti_rows(poses):
     return p[:, :3, :].reshape(p.shape[0], 12)
 
 
+def forward_interpolate(flow):
+    """forward_interpolate(flow_low) of the flow package (whl:GMA/core/utils/utils.py:28-56): the 1/8-resolution flow of one
+    pair pushed forward along itself, the `flow_init` that warm-starts the next pair of a video. `flow` is [2,h,w] or [B,2,h,w];
+    returns float32 of the same shape. A device tensor goes through libatdn_hip's kernel on the current stream and the result
+    stays on the device (the wheel's function goes to the host and calls scipy's griddata twice); a CPU tensor goes through the
+    library's float64 host form. Nearest valid source in float64, ties to the lowest source index, all zeros when no source
+    lands inside the grid (the wheel raises there): include/atdn_hip.h, atdn_flow_forward_interpolate."""
+    if flow.dim() not in (3, 4) or flow.shape[-3] != 2:
+        raise RuntimeError("expected a flow [2,h,w] or [B,2,h,w], got %s" % (tuple(flow.shape),))
+    src = flow.detach().float().contiguous()
+    B = src.shape[0] if src.dim() == 4 else 1
+    h, w = src.shape[-2:]
+    out = torch.empty_like(src)
+    if src.is_cuda:
+        with torch.cuda.device(src.device):
+            _lib.check(_lib.lib().atdn_flow_forward_interpolate(C.c_void_p(src.data_ptr()), B, h, w, C.c_void_p(out.data_ptr()),
+                                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    else:
+        _lib.check(_lib.lib().atdn_flow_forward_interpolate_host(C.c_void_p(src.data_ptr()), B, h, w, C.c_void_p(out.data_ptr())))
+    return out
+
+
 class InputPadder:
     """Replicate-pads frames to multiples of 8 ('sintel' mode splits the padding on both sides)."""
 

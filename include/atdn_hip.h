@@ -294,6 +294,25 @@ int atdn_flow_gather_clips(const uint16_t* bank, int n_flows, int H, int W, cons
                            float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Warm start  —  replaces forward_interpolate of the flow package (whl:GMA/core/utils/utils.py:28-56; its evaluate.py feeds
+ * the result to the next pair as flow_init, network.py:103-104)
+ * ------------------------------------------------------------------------------------------------- */
+
+/* forward_interpolate(flow_low[b]) for every b (utils.py:28-56, which leaves the device and calls scipy's
+ * griddata(method='nearest') twice): the flow pushed forward along itself.
+ *   flow_low, out [B,2,h,w] fp32 DEVICE, not overlapping; channel 0 = dx, 1 = dy; batches are independent.
+ * Source i = y*w + x sits at (x + dx_i, y + dy_i), formed in float64, and is valid when 0 < x1 < w and 0 < y1 < h (all strict;
+ * NaN / infinite flows are invalid). out at grid point (qx, qy) = (dx_j, dy_j) of the valid source j nearest to it:
+ * (qx - x1)^2 + (qy - y1)^2 in float64, every operation rounded separately, equal distances to the lowest j (scipy leaves ties
+ * unspecified). Outputs are bit copies of inputs. With NO valid source out is all zeros — the wheel's function raises there
+ * (griddata on an empty point set). One launch on `stream`: asynchronous, capturable, no atomics, no workspace, the same bits on
+ * every call. B <= 65535, h * w <= 2^24. */
+int atdn_flow_forward_interpolate(const float* flow_low, int B, int h, int w, float* out, void* stream);
+/* The same function (utils.py:28-56) on HOST buffers in plain C++, float64, by the same rules and with the same results:
+ * serves CPU tensors, needs no GPU. */
+int atdn_flow_forward_interpolate_host(const float* flow_low, int B, int h, int w, float* out);
+
+/* ---------------------------------------------------------------------------------------------------
  * Keyframe map  —  replaces the keyframe list of NeuralSLAM's relocalisation (keyframe_map.py)
  *   embeddings: Frame.embedding, one MappingVAE call per keyframe (slam_framework/neural_slam.py:88-103,158-164)
  *   search:     the per-keyframe torch.norm loop, torch.stack and argmin (neural_slam.py:374-383)
