@@ -11,6 +11,7 @@
 #include "frontend.h"
 #include "conv_sf.h"
 #include "epilogues_sf.h"
+#include "flow_consistency_host.h"
 #include "warm_start_host.h"
 
 namespace atdn {
@@ -22,6 +23,9 @@ extern template TileChoice conv_dispatch<MODE_TAP, EpiScale>(const ConvShape&, E
 
 extern template TileChoice conv_sf_dispatch<EpiBias<ACT_NONE>>(const ConvShape&, float, EpiBias<ACT_NONE>, hipStream_t);
 extern template TileChoice conv_sf_dispatch<SfBias<ACT_NONE>>(const ConvShape&, float, SfBias<ACT_NONE>, hipStream_t);
+
+void flow_consistency_check_args(const float* flow_fw, const float* flow_bw, int B, int H, int W, double alpha1, double alpha2,
+                                 const unsigned char* mask, const int* count);   // flow_consistency.hip
 
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& msg) { g_last_error = msg; }
@@ -391,6 +395,15 @@ int atdn_flow_forward_interpolate_host(const float* flow_low, int B, int h, int 
   const long count = (long)B * 2 * h * w;
   ATDN_CHECK(flow_low + count <= out || out + count <= flow_low, "input and output overlap");
   forward_interpolate_host(flow_low, B, h, w, out);
+  ATDN_API_END
+}
+
+// ------------------------------------------------------------------ flow consistency (host twin of flow_consistency.hip)
+int atdn_flow_consistency_host(const float* flow_fw, const float* flow_bw, int B, int H, int W, double alpha1, double alpha2,
+                               unsigned char* mask, int* count) {
+  ATDN_API_BEGIN
+  flow_consistency_check_args(flow_fw, flow_bw, B, H, W, alpha1, alpha2, mask, count);
+  flow_consistency_host(flow_fw, flow_bw, B, H, W, alpha1, alpha2, mask, count);
   ATDN_API_END
 }
 

@@ -253,7 +253,7 @@ class KeyframeMap:
         return search_bank(self.embedding_bank[:self.n], self.rows(queries_mu), top_k)
 
     @torch.no_grad()
-    def relocalize(self, images, flow_net, odometry_net, mapping_net, top_k=1, refine=True):
+    def relocalize(self, images, flow_net, odometry_net, mapping_net, top_k=1, refine=True, verify=False):
         """Answer Q relocalisation queries at once (neural_slam.py:355-399 for a batch). images [Q,3,H,W] (or [3,H,W]),
         values 0..255. Returns host tensors `distances` [Q,K], `indices` [Q,top_k] (int64), `initial` [Q,4,4] (the pose of
         the nearest keyframe) and `refined` [Q,4,4] (= initial @ the odometry step from that keyframe's image to the query;
@@ -264,7 +264,21 @@ class KeyframeMap:
         Pose-head state: every query is evaluated from the reset (zero) LSTM state, and the state `odometry_net` carries
         between its own calls is neither read nor changed. The reference's single-query call starts from whatever state
         earlier calls left behind (neural_slam.py:396); a batch has no such order. `NeuralSLAM.__call__` keeps the
-        reference's semantics."""
+        reference's semantics.
+
+        `verify=True` (needs `refine`; ValueError otherwise) puts evidence behind the answer: ALL Q * top_k candidates are
+        refined, pair p = q * top_k + r being (keyframe indices[q, r], query q). The pairs go through
+        `flow_net.forward_backward` in chunks of max(1, max_batch // 2) pairs, `transforms.flow_consistency` (alpha1 = 0.01,
+        alpha2 = 0.5) scores each chunk, the pose head's encoder runs on the forward flows, and ONE recurrent step runs with
+        Q * top_k independent sequences from the reset state (the carried state is untouched, as above). Returns the 6-tuple
+        `(distances, indices, initial, refined, scores, chosen)`: `scores` [Q,top_k] float32 (host), the share of pixels whose
+        forward and backward flow agree — near 0 when the two images show different places; `chosen` [Q] int64, the rank r
+        with the largest integer count of such pixels, ties to the lower rank; `initial` and `refined` are those of the chosen
+        candidate. With top_k = 1 the poses are those of verify=False (the flows come from batches of another composition:
+        equal within rounding, not bit for bit) and `scores` is the confidence. With verify=False the code path, the 4-tuple
+        and its bits are unchanged."""
+        if verify and not refine:
+            raise ValueError("verify=True scores the flows of the refinement: it needs refine=True")
         q = images.to(self.device)
         if q.dim() == 3:
             q = q.unsqueeze(0)
@@ -276,6 +290,8 @@ class KeyframeMap:
             mu, _ = mapping_net.encode_rows(q)
             dist, idx = self.search(mu, top_k)
             indices = idx.cpu().long()
+            if verify:
+                return self._relocalize_verified(q, dist, indices, flow_net, odometry_net)
             best = indices[:, 0]
             initial = self.poses[best].clone()
             if not refine:
@@ -290,3 +306,28 @@ class KeyframeMap:
             rot, tr = rot[0].cpu(), tr[0].cpu()
         refined = torch.stack([initial[i] @ transforms.transform(rot[i], tr[i]) for i in range(Q)], dim=0)
         return dist.cpu(), indices, initial, refined
+
+    def _relocalize_verified(self, q, dist, indices, flow_net, odometry_net):
+        """The verify=True half of `relocalize` (called under its device and no_grad): q [Q,3,H,W] fp32 on the device, `dist`
+        the device distances, `indices` [Q,top_k] int64 on the host."""
+        Q, top_k = int(indices.shape[0]), int(indices.shape[1])
+        n = self.hw[0] * self.hw[1]
+        flat = indices.reshape(-1)                                   # pair p = q * top_k + r
+        keyframes = self.images(flat)
+        queries = q.repeat_interleave(top_k, dim=0) if top_k > 1 else q
+        chunk = max(1, int(getattr(flow_net, "max_batch", 1)) // 2)     # 2 * chunk images per flow call
+        feats, counts = [], []
+        for a in range(0, Q * top_k, chunk):
+            fw, bw = flow_net.forward_backward(keyframes[a:a + chunk], queries[a:a + chunk], iters=12)
+            counts.append(transforms._flow_consistency_counts(fw, bw, 0.01, 0.5)[1])
+            feats.append(odometry_net.encode(fw))
+        rot, tr, _ = odometry_net.scan(torch.cat(feats, dim=0)[None], state=None, hw=self.hw)
+        rot, tr = rot[0].cpu(), tr[0].cpu()
+        counts = torch.cat(counts).cpu().long().view(Q, top_k)
+        scores = (counts.double() / float(n)).float()
+        chosen = torch.tensor([row.index(max(row)) for row in counts.tolist()], dtype=torch.int64)   # ties: the lower rank
+        rows = torch.arange(Q)
+        initial = self.poses[indices[rows, chosen]].clone()
+        pick = (rows * top_k + chosen).tolist()
+        refined = torch.stack([initial[i] @ transforms.transform(rot[p], tr[p]) for i, p in enumerate(pick)], dim=0)
+        return dist.cpu(), indices, initial, refined, scores, chosen

@@ -367,10 +367,13 @@ class RAFTGMA(_NativeModule):
             return self.forward(prev[None], cur[None], iters=iters, test_mode=True)
         key = self._key(cur.shape[1], cur.shape[2])
         ent, tail = self._handles.get(key), self._stream_tail
-        cont = (tail is not None and ent is not None and tail[0] is prev and tail[1] == prev._version and tail[2] == ent[0].value
-                and ent[1] == self._fingerprint())
+        chain = (tail is not None and ent is not None and tail[0] is prev and tail[1] == prev._version and tail[2] == ent[0].value
+                 and ent[1] == self._fingerprint())
+        # (tail[3] is False after forward_backward: the chain stands, but the handle's feature maps went to that call, so both
+        # frames are encoded again — the bits of the continued form, tests/test_gpu_low_latency.py)
+        cont = chain and tail[3]
         fi = None
-        if warm_start and cont and self._warm_low is not None:
+        if warm_start and chain and self._warm_low is not None:
             from .transforms import forward_interpolate
             fi = forward_interpolate(self._warm_low)
         if sf:
@@ -379,9 +382,43 @@ class RAFTGMA(_NativeModule):
             low, up = self.forward(prev[None], cur[None], iters=iters, flow_init=fi, test_mode=True)
         ent = self._handles.get(key)
         if ent is not None and (not self.fell_back or not sf):
-            self._stream_tail = (cur, cur._version, ent[0].value)   # (holds `cur`: its storage cannot be handed to another tensor)
+            self._stream_tail = (cur, cur._version, ent[0].value, True)   # (holds `cur`: its storage cannot be handed to another tensor)
             self._warm_low = low if warm_start else None
         return low, up
+
+    @torch.no_grad()
+    def forward_backward(self, image1, image2, iters=12, flow_init=None):
+        """Both flows of B pairs: `(flow_fw, flow_bw)`, each [B,2,H,W] — flow_fw from image1 to image2, flow_bw from image2 to
+        image1 — what `transforms.flow_consistency` takes. Defined as `forward(test_mode=True)` on the concatenation
+        (image1 || image2, image2 || image1): ONE call of 2B pairs when 2B <= max_batch, two calls of B pairs otherwise, and the
+        bits are whatever those calls return. `flow_init` [B,2,H/8,W/8] starts the forward half only (the backward half, and
+        both when it is None, start from zero). The saturation guard acts as in `forward`. A `forward_consecutive` chain in
+        progress is neither used nor ended: its kept flow survives, and the next call of the chain encodes both of its frames
+        again (the handle's feature maps went to this call), which gives the bits of the continued form. Every image passes
+        the feature network twice (2 of the 4 passes could be shared; DESIGN.md, "Verified relocalisation")."""
+        self._require_input(image1, "RAFTGMA.forward_backward")
+        if image1.shape != image2.shape or image1.dim() != 4 or image1.shape[1] != 3:
+            raise RuntimeError("expected two [B,3,H,W] frames, got %s and %s" % (tuple(image1.shape), tuple(image2.shape)))
+        B, _, H, W = image1.shape
+        tail, warm_low, fell_back = self._stream_tail, self._warm_low, self.fell_back
+        if 2 * B <= self.max_batch:
+            fi = None
+            if flow_init is not None:
+                fi = flow_init.to(image1.device).float()
+                if tuple(fi.shape) != (B, 2, H // 8, W // 8):
+                    raise RuntimeError("flow_init must be [B,2,H/8,W/8]")
+                fi = torch.cat([fi, torch.zeros_like(fi)], dim=0)     # (a zero flow_init is no flow_init: coords1 + 0)
+            _, up = self.forward(torch.cat([image1, image2], dim=0), torch.cat([image2, image1], dim=0), iters=iters, flow_init=fi,
+                                 test_mode=True)
+            fw, bw = up[:B], up[B:]
+        else:
+            _, fw = self.forward(image1, image2, iters=iters, flow_init=flow_init, test_mode=True)
+            _, bw = self.forward(image2, image1, iters=iters, test_mode=True)
+        if tail is not None and self.fell_back == fell_back:
+            ent = self._handles.get(self._key(tail[0].shape[1], tail[0].shape[2]))
+            if ent is not None and ent[1] == self._fingerprint():
+                self._stream_tail, self._warm_low = (tail[0], tail[1], ent[0].value, False), warm_low
+        return fw, bw
 
     def break_chain(self):
         """Ends a forward_consecutive chain: the next call encodes both frames and, with warm_start, runs cold."""

@@ -276,13 +276,17 @@ class NeuralSLAM:
         return self._batch_flow_net
 
     @torch.no_grad()
-    def relocalize_batch(self, images, top_k=1, refine=True):
+    def relocalize_batch(self, images, top_k=1, refine=True, verify=False):
         """Several relocalisation queries per call (resident map only): `KeyframeMap.relocalize` with this object's
         networks. images [Q,3,376,1232] (or a list of [3,376,1232] frames). Returns host tensors `distances` [Q,K],
         `indices` [Q,top_k] (nearest first), `initial` [Q,4,4], `refined` [Q,4,4]. Every query is refined from the reset
         (zero) state of the pose head, and the state the head carries between `slam(image)` calls is neither read nor
         changed. The flow network runs on a second handle with the same weights (batches of at most 16), created on the
-        first call."""
+        first call.
+        `verify=True` (needs `refine`): every one of the Q * top_k candidates is refined and scored by the forward-backward
+        consistency of its two flows; returns `(distances, indices, initial, refined, scores, chosen)` with `scores`
+        [Q,top_k] (near 0: the keyframe and the query do not show the same place), `chosen` [Q] the rank with the most
+        consistent pixels, and `initial` / `refined` those of the chosen candidate (`KeyframeMap.relocalize`)."""
         if getattr(self, "_map", None) is None:
             raise RuntimeError("relocalize_batch needs the keyframe map in device memory: construct "
                                "NeuralSLAM(..., resident_map=True)")
@@ -291,7 +295,7 @@ class NeuralSLAM:
         if isinstance(images, (list, tuple)):
             images = torch.stack([torch.as_tensor(im) for im in images], dim=0)
         return self._map.relocalize(images, self._flow_for_batches(), self._odometry_net, self._mapping_net, top_k=top_k,
-                                    refine=refine)
+                                    refine=refine, verify=verify)
 
     def _relocalize(self, image):
         mu = self._mapping_net(image)[0]

@@ -82,6 +82,50 @@ def forward_interpolate(flow):
     return out
 
 
+def _flow_consistency_counts(flow_fw, flow_bw, alpha1, alpha2):
+    """(mask uint8 [B,1,H,W], count int32 [B]) of two flows [B,2,H,W] on one device (atdn_flow_consistency / its host twin)."""
+    if flow_fw.dim() != 4 or flow_fw.shape[1] != 2:
+        raise RuntimeError("expected flows [B,2,H,W], got %s" % (tuple(flow_fw.shape),))
+    if flow_bw.shape != flow_fw.shape:
+        raise RuntimeError("flow_fw is %s but flow_bw is %s" % (tuple(flow_fw.shape), tuple(flow_bw.shape)))
+    if flow_bw.device != flow_fw.device:
+        raise RuntimeError("flow_fw on %s but flow_bw on %s" % (flow_fw.device, flow_bw.device))
+    fw = flow_fw.detach().float().contiguous()
+    bw = flow_bw.detach().float().contiguous()
+    B, _, H, W = fw.shape
+    mask = torch.empty((B, 1, H, W), dtype=torch.uint8, device=fw.device)
+    count = torch.empty((B,), dtype=torch.int32, device=fw.device)
+    L = _lib.lib()
+    if fw.is_cuda:
+        with torch.cuda.device(fw.device):
+            _lib.check(L.atdn_flow_consistency(C.c_void_p(fw.data_ptr()), C.c_void_p(bw.data_ptr()), B, H, W, float(alpha1),
+                                               float(alpha2), C.c_void_p(mask.data_ptr()), C.c_void_p(count.data_ptr()),
+                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    else:
+        _lib.check(L.atdn_flow_consistency_host(C.c_void_p(fw.data_ptr()), C.c_void_p(bw.data_ptr()), B, H, W, float(alpha1),
+                                                float(alpha2), C.c_void_p(mask.data_ptr()), C.c_void_p(count.data_ptr())))
+    return mask, count
+
+
+def flow_consistency(flow_fw, flow_bw, alpha1=0.01, alpha2=0.5):
+    """Forward-backward consistency of a flow pair (UnFlow / ARFlow): `flow_fw` is the flow from image 1 to image 2, `flow_bw`
+    the flow from image 2 to image 1, both [B,2,H,W] (or [2,H,W]), channel 0 = x. Returns `(mask, score)`: `mask` uint8
+    [B,1,H,W] ([1,H,W] for 3-d inputs), 1 where following flow_fw and then flow_bw (bilinear, where flow_fw lands) returns to
+    the start within alpha1 * (|fw|^2 + |bw|^2) + alpha2 — the pixels that are visible in both images and whose two flows agree —
+    and 0 elsewhere (occluded, left the image, or the flows contradict each other; any NaN or infinity involved); `score`
+    float32 [B] (0-d for 3-d inputs) = the share of ones, an exact integer count divided by H * W in float64, then rounded. Two
+    images of different places give flows that are noise in both directions and a score near 0. Device tensors go through
+    libatdn_hip's kernel on the current stream and the results stay on the device (no synchronisation); CPU tensors go through
+    the library's host form. The rule is float64 and stated in full in include/atdn_hip.h, atdn_flow_consistency; the same
+    inputs give the same bits on every call and on both paths."""
+    if flow_fw.dim() not in (3, 4) or flow_bw.dim() != flow_fw.dim():
+        raise RuntimeError("expected two flows [2,H,W] or [B,2,H,W], got %s and %s" % (tuple(flow_fw.shape), tuple(flow_bw.shape)))
+    single = flow_fw.dim() == 3
+    mask, count = _flow_consistency_counts(flow_fw[None] if single else flow_fw, flow_bw[None] if single else flow_bw, alpha1, alpha2)
+    score = (count.double() / float(mask.shape[-2] * mask.shape[-1])).float()
+    return (mask[0], score[0]) if single else (mask, score)
+
+
 class InputPadder:
     """Replicate-pads frames to multiples of 8 ('sintel' mode splits the padding on both sides)."""
 

@@ -313,6 +313,40 @@ int atdn_flow_forward_interpolate(const float* flow_low, int B, int h, int w, fl
 int atdn_flow_forward_interpolate_host(const float* flow_low, int B, int h, int w, float* out);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Flow consistency  —  no counterpart in the reference or the flow package: the forward-backward check of UnFlow (Meister et
+ * al., AAAI 2018, eq. 2) and ARFlow, which relocalisation uses to tell "same place" from "different place" (keyframe_map.py,
+ * verify=True) and which is the usual occlusion mask of a flow pair
+ * ------------------------------------------------------------------------------------------------- */
+
+/* mask[b,0,y,x] = 1 where following flow_fw from (x, y) and then flow_bw from where it lands returns to the start, else 0;
+ * count[b] = the number of ones of mask[b].
+ *   flow_fw, flow_bw [B,2,H,W] fp32 DEVICE, channel 0 = x; mask [B,1,H,W] uint8 DEVICE, count [B] int32 DEVICE; mask and count
+ *   overlap neither each other nor the inputs. alpha1, alpha2 finite and >= 0 (UnFlow: 0.01, 0.5). B <= 65535, H * W <= 2^24.
+ * The rule, for pixel (x, y), everything in float64 and every operation rounded on its own (no fused multiply-add), in exactly
+ * this order:
+ *   x1 = x + fw_x, y1 = y + fw_y                                 (exact in float64)
+ *   inside = 0 <= x1 <= W-1 && 0 <= y1 <= H-1                    (closed intervals; a NaN fails)
+ *   not inside: mask = 0, and flow_bw is not read for this pixel
+ *   x0 = floor(x1), ax = x1 - x0; y0 = floor(y1), ay = y1 - y0
+ *   taps t00, t10, t01, t11 of flow_bw at (x0, y0), (min(x0+1, W-1), y0), (x0, min(y0+1, H-1)), (min(x0+1, W-1), min(y0+1, H-1));
+ *   all four are always read, zero-weight ones too (0 * NaN and 0 * inf are NaN and reach the result)
+ *   per channel: top = t00*(1-ax) + t10*ax, bot = t01*(1-ax) + t11*ax, b = top*(1-ay) + bot*ay
+ *   sx = fw_x + b_x, sy = fw_y + b_y, diff = sx*sx + sy*sy
+ *   mag = (fw_x*fw_x + fw_y*fw_y) + (b_x*b_x + b_y*b_y), thr = alpha1*mag + alpha2
+ *   mask = inside && diff <= thr && diff <= DBL_MAX              (plain comparisons: any NaN gives 0)
+ * The last clause keeps a pixel with an INFINITE flow_bw tap of non-zero weight at 0 (there diff = thr = +inf, and inf <= inf
+ * holds); finite fp32 inputs always give a finite diff, so it changes nothing for them. A NaN or an infinity in flow_fw at a
+ * pixel or in one of its four taps therefore gives 0 at that pixel, and touches no other pixel than those that read it.
+ * A memset of `count` and one launch on `stream`: asynchronous, capturable, no host synchronisation, no workspace. The count
+ * is an integer sum (wave ballots, LDS, one integer atomic add per workgroup; no float atomics): the same bits on every call. */
+int atdn_flow_consistency(const float* flow_fw, const float* flow_bw, int B, int H, int W, double alpha1, double alpha2,
+                          unsigned char* mask, int* count, void* stream);
+/* The same function on HOST buffers in plain C++ float64 (csrc/flow_consistency_host.h, the per-pixel function the kernel
+ * calls too): serves CPU tensors, needs no GPU, the same bits. */
+int atdn_flow_consistency_host(const float* flow_fw, const float* flow_bw, int B, int H, int W, double alpha1, double alpha2,
+                               unsigned char* mask, int* count);
+
+/* ---------------------------------------------------------------------------------------------------
  * Keyframe map  —  replaces the keyframe list of NeuralSLAM's relocalisation (keyframe_map.py)
  *   embeddings: Frame.embedding, one MappingVAE call per keyframe (slam_framework/neural_slam.py:88-103,158-164)
  *   search:     the per-keyframe torch.norm loop, torch.stack and argmin (neural_slam.py:374-383)

@@ -5,6 +5,7 @@ directory and removes it).
     python tools/bench_reloc.py --leg search [--K 455,4096,16384] [--Q 1,16] [--reps 200] [--no-loop]
     python tools/bench_reloc.py --leg e2e    [--keyframes 455] [--reps 200]
     python tools/bench_reloc.py --leg all --out profiles/reloc_bench.json
+    python tools/bench_reloc.py --leg verify [--parent-lib PATH/libatdn_hip.so]     (writes profiles/reloc_verify_bench.json)
 
 search: `atdn_map_search` (distances + top-1) on a bank of K embeddings of 15,360 floats, Q queries per call, against the
 per-keyframe `torch.norm` loop of the default relocalisation path on the same embeddings (one query). The two alternate in
@@ -19,6 +20,11 @@ e2e: one relocalisation query from the image to the host pose (embedding + searc
 algebra): the default path (`NeuralSLAM(...)`: torch.norm loop, keyframe image read from its file, batch 1), the resident
 map's single query (`resident_map=True`), and `relocalize_batch` at 16 queries per call, per query. Host clock; every call
 ends with host tensors, i.e. synchronised.
+
+verify (not part of `all`): what `relocalize_batch(verify=True)` costs — ms per query against verify=False at Q = 1, 16 and
+top_k = 1, 3 with 455 keyframes, every timing process a child of its own, alternating with the same verify=False leg on the
+parent commit's library when --parent-lib names one — and `atdn_flow_consistency` alone by device events at 376 x 1232,
+B = 1, 16, against bytes / 8 TB/s. See leg_verify.
 """
 import argparse
 import json
@@ -168,9 +174,166 @@ def leg_e2e(a):
     return row
 
 
+HBM_TBPS = 8.0                 # peak HBM3E bandwidth of the MI355X: the floor bytes / 8 TB/s of the consistency kernel
+VERIFY_CONFIGS = [(1, 1), (1, 3), (16, 1), (16, 3)]      # (Q, top_k)
+
+
+def _verify_directory(root, K, vsd, distinct):
+    kf = os.path.join(root, "kf")
+    os.makedirs(os.path.join(kf, "rgb"))
+    for i in range(K):
+        im = distinct[i % 16].clone()
+        im[:, :2, :16] = torch.tensor([(i >> b) & 1 for b in range(16)], dtype=torch.uint8) * 255
+        torch.save(im, os.path.join(kf, "rgb", "%06d.pth" % i))
+    poses = torch.eye(4).flatten()[:12].repeat(K, 1)
+    poses[:, 3] = torch.arange(K, dtype=torch.float32)
+    torch.save(poses, os.path.join(kf, "poses.pth"))
+    torch.save(vsd, os.path.join(kf, "MappingVAE_weights.pth"))
+    return kf
+
+
+def leg_verify_child(a):
+    """One process of the verify leg, on whatever library ATDN_LIB_PATH names: ms per query of relocalize_batch(verify=False)
+    and — with --with-verify — of verify=True, host clock around calls that end with host tensors, the variants alternating in
+    rounds. The processes that compare the two libraries time verify=False alone, so that both do exactly the same work (the
+    heavy verify=True batches in between would leave the card in another clock and thermal state). --parent-abi: the library
+    is the parent commit's, which lacks the two flow-consistency entry points; they are taken out of the ctypes table before it
+    loads (verify=False never calls them)."""
+    from atdn_vslam_amd import _lib
+    if a.parent_abi:
+        for name in ("atdn_flow_consistency", "atdn_flow_consistency_host"):
+            _lib.SIGNATURES.pop(name)
+    from atdn_vslam_amd.slam import NeuralSLAM
+    gsd = syn.to_torch(syn.make_gma_state(seed=1))
+    hsd = syn.to_torch(syn.make_clvo_state(seed=1))
+    vsd = syn.to_torch(syn.make_vae_state(seed=2))
+    distinct = torch.from_numpy(syn.make_frames(17, 376, 1232, seed=5)).byte()
+    root = tempfile.mkdtemp(prefix="reloc_verify_")
+    try:
+        kf = _verify_directory(root, a.keyframes, vsd, distinct)
+        slam = NeuralSLAM(_Args(kf), odometry_weights=hsd, flow_weights=gsd, start_mode="relocalization", resident_map=True)
+        batches = {1: distinct[16:17].float(), 16: torch.stack([distinct[(3 * j) % 17].float() for j in range(16)])}
+        variants = [(Q, k, False) for Q, k in VERIFY_CONFIGS]
+        if a.with_verify:
+            variants += [(Q, k, True) for Q, k in VERIFY_CONFIGS]
+        for Q, k, v in variants:                               # warm-up: every shape of the timed window, twice
+            for _ in range(2):
+                slam.relocalize_batch(batches[Q], top_k=k, verify=v)
+        t = {v: [] for v in variants}
+        for _ in range(ROUNDS):
+            for Q, k, v in variants:
+                reps = max(1, (a.reps // ROUNDS) // (1 if Q == 1 else 8))
+                t[(Q, k, v)].append(_host(lambda: slam.relocalize_batch(batches[Q], top_k=k, verify=v), reps) / Q)
+        rows = [{"Q": Q, "top_k": k, "verify": v, "ms_per_query": round(sorted(x)[len(x) // 2], 4),
+                 "min": round(min(x), 4), "max": round(max(x), 4)} for (Q, k, v), x in t.items()]
+        scores = None
+        if a.with_verify:
+            scores = slam.relocalize_batch(batches[16], top_k=3, verify=True)[4].tolist()
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+    res = {"library": _lib.LIB_PATH, "parent_abi": bool(a.parent_abi), "keyframes": a.keyframes, "rows": rows,
+           "scores_q16_top3_synthetic_weights": scores}
+    with open(a.child_out, "w") as f:
+        json.dump(res, f)
+    return res
+
+
+def _consistency_kernel(a):
+    """atdn_flow_consistency alone at 376 x 1232, B = 1 and 16: device events over `reps` launches (5 rounds), against the
+    bytes it must move (16 read + 1 written per pixel; the count and the re-read taps are not counted) over 8 TB/s. Back-to-back
+    launches re-read the same 59 MB (B = 16) from the 256 MiB Infinity Cache, so this is the kernel's own rate, not HBM's."""
+    from atdn_vslam_amd import transforms
+    out = []
+    g = torch.Generator(device=DEV).manual_seed(11)
+    y, x = torch.meshgrid(torch.arange(376.0, device=DEV), torch.arange(1232.0, device=DEV), indexing="ij")
+    for B in (1, 16):
+        # smooth forward flows of ~2 px, backward = -forward + noise: both outcomes occur, the taps are local
+        ph = torch.rand((B, 1, 1), generator=g, device=DEV) * 6.28
+        fw = torch.stack([2.0 * torch.sin(x / 130.0 + y / 170.0 + ph), 2.0 * torch.cos(x / 210.0 - y / 90.0 + ph)], dim=1).contiguous()
+        bw = -fw + 0.45 * torch.randn(fw.shape, generator=g, device=DEV)
+        for _ in range(10):
+            transforms._flow_consistency_counts(fw, bw, 0.01, 0.5)
+        per = max(1, a.reps // ROUNDS)
+        ev = [_events(lambda: transforms._flow_consistency_counts(fw, bw, 0.01, 0.5), per) for _ in range(ROUNDS)]
+        ms = sorted(ev)[len(ev) // 2]
+        nbytes = B * 376 * 1232 * 17
+        floor_ms = nbytes / (HBM_TBPS * 1e12) * 1e3
+        row = {"B": B, "H": 376, "W": 1232, "launches": per * ROUNDS, "bytes": nbytes, "ms_events": round(ms, 5),
+               "ms_events_min": round(min(ev), 5), "ms_events_max": round(max(ev), 5), "floor_ms_at_8TBps": round(floor_ms, 5),
+               "times_the_floor": round(ms / floor_ms, 2), "tbps": round(nbytes / (ms * 1e-3) / 1e12, 3),
+               "consistent_share": [round(float(s), 4) for s in transforms.flow_consistency(fw, bw)[1].tolist()[:2]]}
+        print(json.dumps(row), flush=True)
+        out.append(row)
+    return out
+
+
+def leg_verify(a):
+    """Price of verify=True. Every timing process is a child of its own (a process loads ONE library). With --parent-lib:
+    verify=False alone on the parent commit's library and on this one, alternating (parent, new, parent, new, ...),
+    `--verify-runs` of each — the new library's figures must lie inside the spread of the parent's own runs. Then two processes
+    on this library that alternate verify=False and verify=True: the ratio of the two in the same process (expected: about
+    2 * top_k flow passes per query instead of one, plus noise)."""
+    import subprocess
+    here = os.path.abspath(__file__)
+    tmp = tempfile.mkdtemp(prefix="reloc_verify_out_")
+    runs = {"new": [], "parent": [], "full": []}
+    try:
+        order = (["parent", "new"] * a.verify_runs if a.parent_lib else []) + ["full"] * min(2, a.verify_runs)
+        for i, which in enumerate(order):
+            out = os.path.join(tmp, "%d.json" % i)
+            env = dict(os.environ)
+            cmd = [sys.executable, here, "--leg", "verify-child", "--child-out", out, "--keyframes", str(a.keyframes),
+                   "--reps", str(a.reps)]
+            if which == "parent":
+                env["ATDN_LIB_PATH"] = os.path.abspath(a.parent_lib)
+                cmd.append("--parent-abi")
+            else:
+                env.pop("ATDN_LIB_PATH", None)
+                if which == "full":
+                    cmd.append("--with-verify")
+            subprocess.run(cmd, env=env, check=True, timeout=a.child_timeout)
+            with open(out) as f:
+                runs[which].append(json.load(f))
+            print(json.dumps({"run": i, "library": which, "rows": runs[which][-1]["rows"]}), flush=True)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+    def med(which, Q, k, v):
+        return [r["ms_per_query"] for run in runs[which] for r in run["rows"] if (r["Q"], r["top_k"], r["verify"]) == (Q, k, v)]
+
+    table = []
+    for Q, k in VERIFY_CONFIGS:
+        new_off, par = med("new", Q, k, False), med("parent", Q, k, False)
+        full_off, full_on = med("full", Q, k, False), med("full", Q, k, True)
+        row = {"Q": Q, "top_k": k, "verify_false_ms_per_query_new": new_off if new_off else "not measured (no --parent-lib)",
+               "same_process": {"verify_false_ms_per_query": full_off, "verify_true_ms_per_query": full_on},
+               "verify_true_over_false": [round(x / y, 2) for x, y in zip(full_on, full_off)],
+               "flow_passes_per_query": {"verify_false": 1, "verify_true": 2 * k},
+               "verify_false_ms_per_query_parent": par if par else "not measured (no --parent-lib)"}
+        if par:
+            # the spread of the parent's runs: every per-round figure of every parent process, not only their medians
+            lo = min(r["min"] for run in runs["parent"] for r in run["rows"] if (r["Q"], r["top_k"], r["verify"]) == (Q, k, False))
+            hi = max(r["max"] for run in runs["parent"] for r in run["rows"] if (r["Q"], r["top_k"], r["verify"]) == (Q, k, False))
+            row["parent_spread_ms"] = [lo, hi]
+            row["new_inside_parent_spread"] = all(lo <= x <= hi for x in new_off)
+        table.append(row)
+    res = {"leg": "verify", "keyframes": a.keyframes, "runs_per_library": a.verify_runs, "end_to_end": table,
+           "kernel": _consistency_kernel(a),
+           "scores_q16_top3_synthetic_weights": runs["full"][-1]["scores_q16_top3_synthetic_weights"] if runs["full"] else None,
+           "note": "synthetic weights: the scores show that the mechanism runs, not that it ranks candidates correctly"}
+    print(json.dumps(res), flush=True)
+    return res
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("search", "e2e", "all"), default="all")
+    ap.add_argument("--leg", choices=("search", "e2e", "all", "verify", "verify-child"), default="all")
+    ap.add_argument("--parent-lib", default=None, help="verify: the parent commit's libatdn_hip.so, for the alternating comparison")
+    ap.add_argument("--verify-runs", type=int, default=2, help="verify: processes per library (0: the kernel alone)")
+    ap.add_argument("--child-timeout", type=int, default=240)
+    ap.add_argument("--parent-abi", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--with-verify", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--child-out", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--K", type=lambda s: [int(x) for x in s.split(",")], default=[455, 4096, 16384])
     ap.add_argument("--Q", type=lambda s: [int(x) for x in s.split(",")], default=[1, 16])
     ap.add_argument("--reps", type=int, default=200)
@@ -185,6 +348,11 @@ if __name__ == "__main__":
         res["search"] = leg_search(a)
     if a.leg in ("e2e", "all"):
         res["e2e"] = leg_e2e(a)
+    if a.leg == "verify-child":
+        leg_verify_child(a)
+    if a.leg == "verify":
+        res["verify"] = leg_verify(a)
+        a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "reloc_verify_bench.json")
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
