@@ -8,6 +8,7 @@
 #include "gma.h"
 #include "vae.h"
 #include "clvo_train.h"
+#include "train_kernels.h"  // launch_clvo_loss_composite
 #include "frontend.h"
 #include "conv_sf.h"
 #include "epilogues_sf.h"

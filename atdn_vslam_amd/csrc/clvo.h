@@ -1,7 +1,6 @@
 // CLVO pose head `ATDNVO` (atdn_vslam/odometry/network.py:122-146): stateless CNN encoder (shardable over
 // frame pairs) + the sequential LSTM/MLP tail with explicit state.
 #pragma once
-#include "conv_dispatch.h"
 #include "kernels.h"
 #include "weights.h"
 #include "gma.h"  // DeviceBuf
@@ -23,10 +22,11 @@ class ClvoNet {
   int H, W, maxB;
 
  private:
-  // raw_*: the layer's OIHW weights and bias as the state dict holds them, for the 16x16x4 MFMA kernels (conv16)
-  struct ConvBN { PackedConv conv; long sc_off = -1, sh_off = -1; const float* sc = nullptr; const float* sh = nullptr;
-                  long raw_w_off = -1, raw_b_off = -1; const float* raw_w = nullptr; const float* raw_b = nullptr; };
-  struct Res { ConvBN a, b; PackedConv skip; long sc_off = -1, sh_off = -1; const float* sc = nullptr; const float* sh = nullptr;
+  // w, b: the layer's OIHW weights and bias as the state dict holds them (the conv16 kernels read that layout); sc, sh: the
+  // folded eval-mode BatchNorm affine
+  struct ConvBN { long sc_off = -1, sh_off = -1; const float* sc = nullptr; const float* sh = nullptr;
+                  long w_off = -1, b_off = -1; const float* w = nullptr; const float* b = nullptr; };
+  struct Res { ConvBN a, b; long sc_off = -1, sh_off = -1; const float* sc = nullptr; const float* sh = nullptr;
                long skip_w_off = -1, skip_b_off = -1; const float* skip_w = nullptr; const float* skip_b = nullptr; };
   ConvBN pack_convbn(const std::string& p);
 

@@ -3,14 +3,11 @@
 // through time and through the convolutional encoder, AdamW. Gradients live in one flat buffer so that data-parallel training is a
 // single all-reduce (RCCL) over it between `forward_backward` and `adamw_step`.
 #pragma once
-#include <cstdlib>
 #include <map>
 #include <string>
 #include <vector>
 
-#include "conv_dispatch.h"
 #include "gma.h"  // DeviceBuf
-#include "train_kernels.h"
 #include "weights.h"
 
 namespace atdn {
@@ -46,10 +43,9 @@ class ClvoTrainer {
 
  private:
   struct Slot { long off = -1, n = 0; };
-  struct ConvL {   // convolution + its packed forward / transposed weights
+  struct ConvL {   // the kernels read the OIHW weights straight from the parameter buffer
     Slot w, b;
-    int cin = 16, cpix = 16, kh = 3, kw = 3, stride = 1, pad = 1;
-    long fwd_off = 0, bwd_off = 0;  // into packed_
+    int cin = 16, kh = 3, kw = 3, stride = 1, pad = 1;
   };
   struct BnL { Slot gamma, beta; long rm = -1, rv = -1; long stat_off = 0; };  // stat_off: mean/rstd [G][16] x 2
   struct ConvBlock { ConvL conv; BnL bn; };
@@ -62,12 +58,13 @@ class ClvoTrainer {
   BnL make_bn(const std::string& p);
   Lin make_lin(const std::string& p, bool bias = true);
 
-  void pack_weights(hipStream_t st);
-  int conv_fwd(const ConvL& c, const float* x, int h, int w, float* z, hipStream_t st, bool with_stats = false);
-  void conv_bwd_data(const ConvL& c, const float* dz, int h_in, int w_in, int ho, int wo, float* dx, int ldd, hipStream_t st,
+  // Every convolution runs on the conv16 family (conv16.h); a shape it does not serve raises an Error.
+  // with_stats: the kernel leaves the BatchNorm statistics of Mish(z) in part_; returns their partial rows per group (else 0)
+  int conv_fwd(const ConvL& c, const float* x, int h, int w, float* z, hipStream_t st, bool with_stats);
+  void conv_bwd_data(const ConvL& c, const float* dz, int h_in, int w_in, int ho, int wo, float* dx, hipStream_t st,
                      bool accumulate = false);
-  int bn_fwd(const BnL& bn, const float* z, long P, bool mish, const float* add, float* y, hipStream_t st, int rows_done = 0,
-             bool stats_next = false);
+  // y = BN(Mish(z)) (+ add) from the `rows` partial rows per group that the kernel producing z left in part_
+  int bn_fwd(const BnL& bn, const float* z, long P, const float* add, float* y, hipStream_t st, int rows, bool stats_next = false);
   // dy -> dz (through BN and the activation); adds dgamma/dbeta; bias gradient of the producing conv into db (optional)
   void bn_bwd(const BnL& bn, const float* dy, const float* z, long P, bool mish, float* dz, float* db, hipStream_t st);
 
@@ -80,14 +77,11 @@ class ClvoTrainer {
   int w_ = 3, loss_mode_ = 0;
   float terms_[3] = {0.f, 0.f, 0.f};
   bool terms_valid_ = false;
-  bool conv16_ = !(getenv("ATDN_TRAIN_CONV16") && getenv("ATDN_TRAIN_CONV16")[0] == '0');  // 16-channel convs on the 16x16x4 MFMA kernel
-  // BatchNorm statistics taken in the kernel that writes the layer's input (0: a reduction pass of their own, the A/B partner)
-  bool fused_stats_ = !(getenv("ATDN_TRAIN_FUSED_STATS") && getenv("ATDN_TRAIN_FUSED_STATS")[0] == '0');
   std::map<std::string, Slot> pindex_;
   std::map<std::string, long> sindex_;
   long n_params_ = 0, n_stats_ = 0;
   std::vector<std::pair<long, long>> trained_;  // (offset, count) ranges AdamW walks
-  DeviceBuf params_, grads_, m_, v_, stats_, packed_, bnstat_, part_, sums_, wscratch_, loss_;
+  DeviceBuf params_, grads_, m_, v_, stats_, bnstat_, part_, sums_, wscratch_, loss_;
 
   Slot dw_w_, dw_b_;
   ConvBlock stem_, last_;
@@ -95,7 +89,7 @@ class ClvoTrainer {
   Lin fc_, lin_, rot_[3], tr_[3];
   Slot l1_wih_, l1_whh_, l1_bih_, l1_bhh_, l2_wih_, l2_whh_, l2_bih_, l2_bhh_;
   int hs_[7], ws_[7];  // map sizes: [0] input, [1] stem out, [2..5] res outs, [6] last conv out
-  long packed_n_ = 0, bnstat_n_ = 0;
+  long bnstat_n_ = 0;
 
   // activations kept for the backward pass
   DeviceBuf flow_, x0_, z1_, y1_;

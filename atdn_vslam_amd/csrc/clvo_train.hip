@@ -1,18 +1,20 @@
 // CLVO training iteration. Reference: train_odometry.py:21-49 (loop body), odometry/network.py:122-146 (forward, train
 // mode), layers/conv.py (Conv = BN(Mish(conv)), ResidualConv), layers/linear.py, odometry/loss.py:25-118.
-// Convolutions (forward and data gradients) run on the exact-fp32 MFMA implicit-GEMM engine; a strided convolution's
-// data gradient is the stride-1 convolution of the zero-stuffed output gradient with the transposed, flipped kernel.
+// Convolutions (forward and data gradients) run on the conv16 family (conv16.h: exact fp32, v_mfma_f32_16x16x4_f32) with the
+// weights read straight from the parameter buffer. The stride-2 data gradients have a kernel of their own; that of the stride-3
+// last convolution is the stride-1 convolution of the zero-stuffed output gradient with the transposed, flipped kernel.
 #include "clvo_train.h"
 
 #include <algorithm>
 #include <cstring>
 #include <utility>
 
+#include "conv16.h"
+#include "conv_mfma.h"  // conv_out
 #include "kernels.h"
+#include "train_kernels.h"
 
 namespace atdn {
-
-extern template TileChoice conv_dispatch<MODE_ROW, EpiBias<ACT_NONE>>(const ConvShape&, EpiBias<ACT_NONE>, hipStream_t);
 
 namespace {
 // [B][T][...] <-> [T][B][...] with `inner` contiguous floats per (b, t) item
@@ -49,7 +51,7 @@ ClvoTrainer::ClvoTrainer(int H_, int W_, int B_, int T_) : H(H_), W(W_), B(B_), 
 }
 
 ClvoTrainer::~ClvoTrainer() {
-  for (DeviceBuf* b : {&params_, &grads_, &m_, &v_, &stats_, &packed_, &bnstat_, &part_, &sums_, &wscratch_, &loss_, &flow_, &x0_,
+  for (DeviceBuf* b : {&params_, &grads_, &m_, &v_, &stats_, &bnstat_, &part_, &sums_, &wscratch_, &loss_, &flow_, &x0_,
                        &z1_, &y1_, &z6_, &y6_, &flat_, &zf_, &feat_, &pre1_, &act1_, &c1_, &tc1_, &h1_, &zl_, &x2_, &pre2_, &act2_,
                        &c2_, &tc2_, &h2_, &out_[0], &out_[1], &ga_, &gb_, &gc_, &stuffed_})
     b->release();
@@ -75,12 +77,8 @@ ClvoTrainer::ConvL ClvoTrainer::make_conv(const std::string& p, int stride, int 
   const HostTensor& w = sd_.get(p + ".weight");
   ATDN_CHECK((int)w.shape[0] == 16, "encoder convolutions have 16 output channels");
   c.cin = (int)w.shape[1]; c.kh = (int)w.shape[2]; c.kw = (int)w.shape[3];
-  c.cpix = c.cin <= 4 ? 4 : 16;
+  ATDN_CHECK(c.kh == c.kw, "encoder convolutions have square kernels");
   c.stride = stride; c.pad = pad;
-  c.fwd_off = packed_n_;
-  packed_n_ += (long)16 * c.kh * round_up(c.kw * c.cpix, 32);
-  c.bwd_off = packed_n_;
-  packed_n_ += (long)c.cin * c.kh * round_up(c.kw * 16, 32);
   return c;
 }
 ClvoTrainer::BnL ClvoTrainer::make_bn(const std::string& p) {
@@ -155,11 +153,10 @@ void ClvoTrainer::finalize() {
   // ---- buffers
   const long nimg = (long)T * B, TB = nimg;
   auto px = [&](int l) { return (long)hs_[l] * ws_[l]; };
-  packed_.alloc(packed_n_);
   bnstat_.alloc(bnstat_n_);
   const long Pmax = (long)B * px(1);
   // partial rows of the BatchNorm reductions: per group, one per reduction block, per persistent block of a producing convolution
-  // (<= 1024: train_kernels.hip) or per block of bn_apply
+  // (<= 1024: conv16.hip) or per block of bn_apply
   part_.alloc((long)T * std::max<long>(std::max<long>(bn_partial_blocks(Pmax), bn_apply_partial_rows(Pmax)), 1024) * 2 * 16 + 64);
   sums_.alloc((long)T * 2 * 16);
   wscratch_.alloc(std::max(wgrad_scratch_floats(0, 0, 16, 3, 3), wgrad_scratch_floats(0, 0, 3, 7, 7)));
@@ -210,40 +207,22 @@ long ClvoTrainer::read(const std::string& key, int kind, float* host, long capac
 }
 
 // ---------------------------------------------------------------------------------------------------- building blocks
-void ClvoTrainer::pack_weights(hipStream_t st) {
-  auto pack = [&](const ConvL& c) {
-    launch_pack_row(P(c.w), 16, c.cin, c.cpix, c.kh, c.kw, false, packed_.p + c.fwd_off, st);
-    launch_pack_row(P(c.w), 16, c.cin, 16, c.kh, c.kw, true, packed_.p + c.bwd_off, st);
-  };
-  pack(stem_.conv); pack(last_.conv);
-  for (auto& r : res_) { pack(r.a.conv); pack(r.b.conv); pack(r.skip); }
-}
-
-// Returns the partial rows per group of the BatchNorm statistics of Mish(z) the kernel left in part_ (with_stats, 16-channel
-// kernels only), or 0: the caller's bn_fwd then reduces z itself.
 int ClvoTrainer::conv_fwd(const ConvL& c, const float* x, int h, int w, float* z, hipStream_t st, bool with_stats) {
   Conv16Stats cs;
-  cs.part = with_stats && fused_stats_ ? part_.p : nullptr; cs.group_imgs = B; cs.capacity = part_.n;
-  if (c.cin == 16 && conv16_) {   // 16 -> 16 channels: the 16x16x4 fp32 MFMA kernel, weights straight from the parameters
+  cs.part = with_stats ? part_.p : nullptr; cs.group_imgs = B; cs.capacity = part_.n;
+  if (c.cin == 16) {   // 16 -> 16 channels
     launch_conv16(x, T * B, h, w, P(c.w), false, P(c.b), c.kh, c.stride, c.pad, z, st, false, &cs);
-    return cs.rows;
-  }
-  if (c.cin == 2 && c.cpix == 4 && c.kh == 7 && c.kw == 7 && c.stride == 2 && c.pad == 3 && conv16_) {
+  } else {             // the stem: 2 -> 16 channels on the NHWC4 input
+    ATDN_CHECK(c.cin == 2 && c.kh == 7 && c.stride == 2 && c.pad == 3, "conv_fwd: no kernel for this convolution shape");
     launch_stem16(x, T * B, h, w, P(c.w), P(c.b), z, st, nullptr, &cs);
-    return cs.rows;
   }
-  ConvShape s;
-  s.src0 = x; s.ld0 = c.cpix; s.sb0 = (long)h * w * c.cpix; s.C0 = c.cpix; s.H = h; s.W = w;
-  s.KH = c.kh; s.KW = c.kw; s.stride = c.stride; s.padH = c.pad; s.padW = c.pad;
-  s.w = packed_.p + c.fwd_off; s.ldw = c.kh * round_up(c.kw * c.cpix, 32); s.N = 16; s.nimg = T * B;
-  const int oh = conv_out(h, c.kh, c.stride, c.pad), ow = conv_out(w, c.kw, c.stride, c.pad);
-  conv_dispatch<MODE_ROW>(s, EpiBias<ACT_NONE>{P(c.b), z, (long)oh * ow * 16, 16, 1.f}, st);
-  return 0;
+  return cs.rows;
 }
 
-void ClvoTrainer::conv_bwd_data(const ConvL& c, const float* dz, int h_in, int w_in, int ho, int wo, float* dx, int ldd,
-                                hipStream_t st, bool accumulate) {
-  if (c.cin == 16 && ldd == 16 && conv16_ && c.stride == 2) {   // no zero-stuffed map: parity classes of the output
+void ClvoTrainer::conv_bwd_data(const ConvL& c, const float* dz, int h_in, int w_in, int ho, int wo, float* dx, hipStream_t st,
+                                bool accumulate) {
+  ATDN_CHECK(c.cin == 16, "conv_bwd_data: 16-channel convolutions only (no data gradient of the stem is ever formed)");
+  if (c.stride == 2) {   // no zero-stuffed map: parity classes of the output
     launch_tconv16_s2(dz, T * B, ho, wo, P(c.w), c.kh, c.pad, h_in, w_in, accumulate, dx, st);
     return;
   }
@@ -256,37 +235,21 @@ void ClvoTrainer::conv_bwd_data(const ConvL& c, const float* dz, int h_in, int w
   } else {
     ATDN_CHECK(Hs == ho && Ws == wo, "stride-1 data gradient expects same-size maps");
   }
-  if (c.cin == 16 && ldd == 16 && conv16_) {
-    ATDN_CHECK(Hs + c.kh - 1 - 2 * c.pad == h_in && Ws + c.kw - 1 - 2 * c.pad == w_in, "data-gradient geometry");
-    launch_conv16(src, T * B, Hs, Ws, P(c.w), true, nullptr, c.kh, 1, c.kh - 1 - c.pad, dx, st, accumulate);
-    return;
-  }
-  ConvShape s;
-  s.src0 = src; s.ld0 = 16; s.sb0 = (long)Hs * Ws * 16; s.C0 = 16; s.H = Hs; s.W = Ws;
-  s.KH = c.kh; s.KW = c.kw; s.stride = 1; s.padH = c.kh - 1 - c.pad; s.padW = c.kw - 1 - c.pad;
-  s.w = packed_.p + c.bwd_off; s.ldw = c.kh * round_up(c.kw * 16, 32); s.N = c.cin; s.nimg = T * B;
-  ATDN_CHECK(conv_out(Hs, c.kh, 1, s.padH) == h_in && conv_out(Ws, c.kw, 1, s.padW) == w_in, "data-gradient geometry");
-  ATDN_CHECK(!accumulate, "conv_bwd_data: accumulation needs the 16-channel kernels");
-  conv_dispatch<MODE_ROW>(s, EpiBias<ACT_NONE>{nullptr, dx, (long)h_in * w_in * ldd, ldd, 1.f}, st);
+  ATDN_CHECK(Hs + c.kh - 1 - 2 * c.pad == h_in && Ws + c.kw - 1 - 2 * c.pad == w_in, "data-gradient geometry");
+  launch_conv16(src, T * B, Hs, Ws, P(c.w), true, nullptr, c.kh, 1, c.kh - 1 - c.pad, dx, st, accumulate);
 }
 
-// rows_done > 0: part_ already holds that many partial rows per group of this layer's statistics (left there by the kernel that
-// produced z). stats_next: this pass also leaves the statistics of Mish(y) in part_ for the BatchNorm that follows y directly;
-// returns their rows per group (part_ is free again by then: the finalize that read it is earlier in the stream).
-int ClvoTrainer::bn_fwd(const BnL& bn, const float* z, long Pg, bool mish, const float* add, float* y, hipStream_t st, int rows_done,
+// part_ holds `rows` partial rows per group of this layer's statistics, those of Mish(z), left there by the kernel that produced z.
+// stats_next: this pass also leaves the statistics of Mish(y) in part_ for the BatchNorm that follows y directly; returns their
+// rows per group (part_ is free again by then: the finalize that read it is earlier in the stream).
+int ClvoTrainer::bn_fwd(const BnL& bn, const float* z, long Pg, const float* add, float* y, hipStream_t st, int rows,
                         bool stats_next) {
+  ATDN_CHECK(rows > 0, "bn_fwd: the kernel that produced z takes the statistics");
   float* mean = bnstat_.p + bn.stat_off;
   float* rstd = mean + (long)T * 16;
-  if (rows_done > 0) {
-    ATDN_CHECK(mish, "fused statistics are those of Mish(z)");
-    launch_bn_finalize_rows(part_.p, T, rows_done, Pg, stats_.p + bn.rm, stats_.p + bn.rv, mean, rstd, sums_.p, st);
-  } else {
-    launch_bn_stats(z, T, Pg, mish, part_.p, st);
-    launch_bn_finalize(part_.p, T, Pg, stats_.p + bn.rm, stats_.p + bn.rv, mean, rstd, sums_.p, st);   // (sums_: idle in the forward)
-  }
-  const bool next = stats_next && fused_stats_;
-  launch_bn_apply(z, T, Pg, mish, mean, rstd, P(bn.gamma), P(bn.beta), add, y, st, next ? part_.p : nullptr);
-  return next ? bn_apply_partial_rows(Pg) : 0;
+  launch_bn_finalize(part_.p, T, rows, Pg, stats_.p + bn.rm, stats_.p + bn.rv, mean, rstd, sums_.p, st);   // (sums_: idle in the forward)
+  launch_bn_apply(z, T, Pg, true, mean, rstd, P(bn.gamma), P(bn.beta), add, y, st, stats_next ? part_.p : nullptr);
+  return stats_next ? bn_apply_partial_rows(Pg) : 0;
 }
 
 void ClvoTrainer::bn_bwd(const BnL& bn, const float* dy, const float* z, long Pg, bool mish, float* dz, float* db, hipStream_t st) {
@@ -306,7 +269,6 @@ float ClvoTrainer::forward_backward(const float* flows, const float* true_rot, c
   auto px = [&](int l) { return (long)hs_[l] * ws_[l]; };
   auto Pg = [&](int l) { return (long)B * px(l); };
   ATDN_HIP(hipMemsetAsync(grads_.p, 0, n_params_ * sizeof(float), st));
-  pack_weights(st);
 
   // ================= forward (train mode)
   launch_swap_bt(flows, B, T, 2 * px(0), true, flow_.p, st);   // [B][T] clip layout -> step-major [T][B]
@@ -314,21 +276,21 @@ float ClvoTrainer::forward_backward(const float* flows, const float* true_rot, c
   // (round 5: every BatchNorm's statistics come out of the kernel that writes its input — the convolution, or for out_block the
   // pass that forms zo — instead of a reduction pass of their own; part_ carries them to the finalize right behind)
   int rows = conv_fwd(stem_.conv, x0_.p, H, W, z1_.p, st, true);
-  bn_fwd(stem_.bn, z1_.p, Pg(1), true, nullptr, y1_.p, st, rows);
+  bn_fwd(stem_.bn, z1_.p, Pg(1), nullptr, y1_.p, st, rows);
   const float* x = y1_.p;
   for (int k = 0; k < 4; ++k) {
     ResBlock& r = res_[k]; ResAct& A = ract_[k];
     const int h = hs_[k + 1], w = ws_[k + 1];
     rows = conv_fwd(r.a.conv, x, h, w, A.za.p, st, true);
-    bn_fwd(r.a.bn, A.za.p, Pg(k + 1), true, nullptr, A.ua.p, st, rows);
+    bn_fwd(r.a.bn, A.za.p, Pg(k + 1), nullptr, A.ua.p, st, rows);
     rows = conv_fwd(r.b.conv, A.ua.p, h, w, A.zb.p, st, true);
     conv_fwd(r.skip, x, h, w, A.s.p, st, false);
-    rows = bn_fwd(r.b.bn, A.zb.p, Pg(k + 2), true, A.s.p, A.zo.p, st, rows, true);    // zo = BN_b(mish(zb)) + skip
-    bn_fwd(r.out, A.zo.p, Pg(k + 2), true, nullptr, A.o.p, st, rows);
+    rows = bn_fwd(r.b.bn, A.zb.p, Pg(k + 2), A.s.p, A.zo.p, st, rows, true);    // zo = BN_b(mish(zb)) + skip
+    bn_fwd(r.out, A.zo.p, Pg(k + 2), nullptr, A.o.p, st, rows);
     x = A.o.p;
   }
   rows = conv_fwd(last_.conv, x, hs_[5], ws_[5], z6_.p, st, true);
-  bn_fwd(last_.bn, z6_.p, Pg(6), true, nullptr, y6_.p, st, rows);
+  bn_fwd(last_.bn, z6_.p, Pg(6), nullptr, y6_.p, st, rows);
   launch_nhwc_to_chw(y6_.p, nimg, (int)px(6), flat_.p, st);         // nn.Flatten order (C, H, W)
   launch_gemm(false, true, TB, 512, 832, flat_.p, 832, P(fc_.w), 832, zf_.p, 512, 0.f, P(fc_.b), st);
   launch_mish_fwd(zf_.p, feat_.p, (long)TB * 512, st);
@@ -422,7 +384,7 @@ float ClvoTrainer::forward_backward(const float* flows, const float* true_rot, c
   launch_chw_to_nhwc(dsmall_[7].p, nimg, (int)px(6), cur, st);
   bn_bwd(last_.bn, cur, z6_.p, Pg(6), true, cur, G(last_.conv.b), st);
   launch_conv_wgrad(ract_[3].o.p, 16, 16, nimg, hs_[5], ws_[5], cur, hs_[6], ws_[6], 3, 3, 3, 0, wscratch_.p, G(last_.conv.w), st);
-  conv_bwd_data(last_.conv, cur, hs_[5], ws_[5], hs_[6], ws_[6], t1, 16, st);
+  conv_bwd_data(last_.conv, cur, hs_[5], ws_[5], hs_[6], ws_[6], t1, st);
   std::swap(cur, t1);
   for (int k = 3; k >= 0; --k) {
     ResBlock& r = res_[k]; ResAct& A = ract_[k];
@@ -430,19 +392,14 @@ float ClvoTrainer::forward_backward(const float* flows, const float* true_rot, c
     const float* xin = k == 0 ? y1_.p : ract_[k - 1].o.p;
     bn_bwd(r.out, cur, A.zo.p, Pg(k + 2), true, cur, G(r.skip.b), st);                      // cur = dzo; db_skip = sum dzo
     launch_conv_wgrad(xin, 16, 16, nimg, h, w, cur, oh, ow, 1, 1, 2, 0, wscratch_.p, G(r.skip.w), st);
-    conv_bwd_data(r.skip, cur, h, w, oh, ow, t2, 16, st);                                   // t2 = dx through the skip conv
+    conv_bwd_data(r.skip, cur, h, w, oh, ow, t2, st);                                       // t2 = dx through the skip conv
     bn_bwd(r.b.bn, cur, A.zb.p, Pg(k + 2), true, cur, G(r.b.conv.b), st);                   // cur = dzb
     launch_conv_wgrad(A.ua.p, 16, 16, nimg, h, w, cur, oh, ow, 3, 3, 2, 1, wscratch_.p, G(r.b.conv.w), st);
-    conv_bwd_data(r.b.conv, cur, h, w, oh, ow, t1, 16, st);                                 // t1 = dua
+    conv_bwd_data(r.b.conv, cur, h, w, oh, ow, t1, st);                                     // t1 = dua
     bn_bwd(r.a.bn, t1, A.za.p, Pg(k + 1), true, t1, G(r.a.conv.b), st);                     // t1 = dza
     launch_conv_wgrad(xin, 16, 16, nimg, h, w, t1, h, w, 3, 3, 1, 1, wscratch_.p, G(r.a.conv.w), st);
-    if (conv16_) {
-      conv_bwd_data(r.a.conv, t1, h, w, h, w, t2, 16, st, true);                            // t2 += dx through conv a
-      std::swap(cur, t2);
-    } else {
-      conv_bwd_data(r.a.conv, t1, h, w, h, w, cur, 16, st);                                 // cur = dx through conv a
-      launch_add_inplace(cur, t2, (long)nimg * h * w * 16, st);
-    }
+    conv_bwd_data(r.a.conv, t1, h, w, h, w, t2, st, true);                                  // t2 += dx through conv a
+    std::swap(cur, t2);
   }
   bn_bwd(stem_.bn, cur, z1_.p, Pg(1), true, cur, G(stem_.conv.b), st);                      // cur = dz1
   // stem weights and the depthwise 1x1 in front of it: one weight-gradient pass on (xn0, xn1, 1), then a combine

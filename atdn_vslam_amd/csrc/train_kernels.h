@@ -1,31 +1,23 @@
-// Kernels of the CLVO training step that are not convolutions (clvo_train.hip): train-mode BatchNorm + Mish forward
-// and backward on NHWC16 maps with per-call statistics groups, zero-stuffing for transposed convolutions, weight
-// gradients of the thin convolutions, small dense GEMMs, LSTM cell forward/backward, loss and AdamW.
+// Kernels of the CLVO training step other than the 16-channel convolutions' forward and data-gradient passes (conv16.h):
+// train-mode BatchNorm + Mish forward and backward on NHWC16 maps with per-call statistics groups, zero-stuffing for the
+// stride-3 transposed convolution, weight gradients of the thin convolutions, small dense GEMMs, LSTM cell forward/backward,
+// loss and AdamW. Used by clvo_train.hip.
 // Reference semantics: torch.nn.BatchNorm2d (training), nn.Mish, nn.LSTMCell, odometry/loss.py, torch.optim.AdamW.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace atdn {
 
-// ---- weight packing for the ROW-mode conv engine, on the device (weights change every iteration)
-// forward:   dst[n][ky*ldr + kx*Cpix + c] = w[n][c][ky][kx]                         rows = N
-// transposed (for the data gradient): dst[c][ky*ldr + kx*Cpix + n] = w[n][c][KH-1-ky][KW-1-kx]   rows = Cin
-// ldr = round_up(KW*Cpix, 32); every other entry of dst is written as 0.
-void launch_pack_row(const float* w, int N, int Cin, int Cpix, int KH, int KW, bool transposed, float* dst, hipStream_t st);
-
 // ---- train-mode BatchNorm over NHWC16 maps; G statistic groups of P pixels each (a group = one forward() call)
 constexpr int BN_C = 16;
-int bn_partial_blocks(long P);  // blocks per group the reduction kernels use
-// part[G][nblk][2][16]: sum and sum of squares of a = mish(z) (mish=true) or of z itself
-void launch_bn_stats(const float* z, int G, long P, bool mish, float* part, hipStream_t st);
+int bn_partial_blocks(long P);  // blocks per group the backward reduction kernels use
+// Forward statistics are taken by the kernel that writes the layer's input: part[G][rows][2][16] holds per-group partial sums
+// and sums of squares of mish(z), `rows` of them per group (Conv16Stats::rows, or bn_apply_partial_rows(P) after
+// launch_bn_apply(..., next_part)).
 // mean/rstd [G][16]; running stats updated sequentially over the G calls (momentum 0.1, unbiased variance)
 // (var_scratch: [G][16] floats, the groups' unbiased variances between the two launches)
-void launch_bn_finalize(const float* part, int G, long P, float* running_mean, float* running_var, float* mean,
+void launch_bn_finalize(const float* part, int G, int rows, long P, float* running_mean, float* running_var, float* mean,
                         float* rstd, float* var_scratch, hipStream_t st);
-// the same with the partial rows counted by the caller (statistics taken in a producing kernel: Conv16Stats::rows, or
-// bn_apply_partial_rows(P) after launch_bn_apply(..., next_part))
-void launch_bn_finalize_rows(const float* part, int G, int rows, long P, float* running_mean, float* running_var, float* mean,
-                             float* rstd, float* var_scratch, hipStream_t st);
 // y = (act(z) - mean) * rstd * gamma + beta (+ add), act = mish or identity.
 // next_part (optional, [G][bn_apply_partial_rows(P)][2][16]): sums of Mish(y), Mish(y)^2 — the statistics of a BatchNorm that
 // follows y directly (ResidualConv.out_block: bn(mish(x + skip)), layers/conv.py:78-80,88)
@@ -95,38 +87,4 @@ void launch_clvo_loss_composite(const float* pred_rot, const float* pred_tr, con
 void launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float wd, float eps, float beta1,
                   float beta2, int t, hipStream_t st);
 
-}  // namespace atdn
-
-namespace atdn {
-// ---- 16 -> 16 channel convolution on NHWC16 maps with v_mfma_f32_16x16x4_f32 (exact fp32): the thin convolutions of
-// the CLVO encoder fill a 32x32 MFMA tile to a quarter (N = 16, K rows padded 48 -> 64); here N is exactly one
-// 16-column tile, K = KH*KW*16 needs no padding, the whole weight tensor sits in operand registers for the lifetime
-// of the block and the input is read from an LDS halo patch with one ds_read_b128 per tap and 16-pixel tile.
-// w: OIHW [16][16][K][K]; transposed = use w[c][n][K-1-ky][K-1-kx] instead (data gradient of a convolution).
-// z[img][oy][ox][n] = bias[n] + sum x[img][oy*S - pad + ky][ox*S - pad + kx][c] * w(n, c, ky, kx)
-// the 7x7 stride-2 pad-3 stem (2 -> 16 channels) on NHWC4 input, same MFMA; w: OIHW [16][2][7][7]
-// eval-mode tail fused into the store (inference head): BN(Mish(.)) with the folded affine sc/sh, and with `skip`
-// ([nimg][Ho][Wo][16]) the ResidualConv tail BN2(Mish(BN1(Mish(.)) + skip))
-struct Conv16Tail {
-  const float* sc = nullptr; const float* sh = nullptr;
-  const float* skip = nullptr; const float* sc2 = nullptr; const float* sh2 = nullptr;
-};
-// Training forward only: BatchNorm statistics of Mish(z) taken in the producing kernel (see c16_stat_flush in train_kernels.hip).
-// `part` [groups][rows][2][16] with `capacity` floats; the launcher zeroes what it uses and sets `rows` (partial rows per group) for
-// launch_bn_finalize_rows. group_imgs = images per statistics group (the images of one time step).
-struct Conv16Stats {
-  float* part = nullptr; int group_imgs = 1; long capacity = 0; int rows = 0;
-};
-void launch_stem16(const float* x4, int nimg, int H, int W, const float* w, const float* bias, float* z, hipStream_t st,
-                   const Conv16Tail* tail = nullptr, Conv16Stats* stat = nullptr);
-// data gradient of a stride-2 16 -> 16 convolution (w OIHW, K = 3 pad 1 or K = 1 pad 0): dx [nimg][H][W][16] from
-// dz [nimg][Ho][Wo][16]; accumulate: dx += instead of dx =
-void launch_tconv16_s2(const float* dz, int nimg, int Ho, int Wo, const float* w, int K, int pad, int H, int W, bool accumulate,
-                       float* dx, hipStream_t st);
-void launch_conv16(const float* x, int nimg, int H, int W, const float* w, bool transposed, const float* bias, int K, int S,
-                   int pad, float* z, hipStream_t st, bool accumulate = false,   // accumulate: z += instead of z =
-                   Conv16Stats* stat = nullptr);
-// the same convolution with an eval-mode tail: K = 3 with S = 1 or 3 (Conv blocks), K = 3, S = 2 with tail.skip (ResidualConv)
-void launch_conv16_eval(const float* x, int nimg, int H, int W, const float* w, const float* bias, int K, int S, int pad,
-                        const Conv16Tail& tail, float* z, hipStream_t st);
 }  // namespace atdn

@@ -141,14 +141,6 @@ def test_training_iteration_matches_the_fp64_oracle(sd, oracle, hw, bt):
     _run_case(sd, oracle, hw[0], hw[1], bt[0], bt[1])
 
 
-@pytest.mark.parametrize("switch", ["ATDN_TRAIN_CONV16", "ATDN_TRAIN_FUSED_STATS"])
-def test_training_switches_match_the_fp64_oracle(sd, oracle, monkeypatch, switch):
-    """The two implementation switches still in the tree (read when the trainer is constructed), each turned off, against
-    the fp64 oracle rather than only against each other."""
-    monkeypatch.setenv(switch, "0")
-    _run_case(sd, oracle, 370, 1226, 3, 2, tag="/%s=0" % switch)
-
-
 def test_adamw_over_four_steps_matches_fp64_adamw_on_the_trainers_gradients(sd):
     """Four iterations at 370x1226 with total_steps = 5 (the cosine rate moves every step) and weight decay 1e-2. After each
     optimizer_step every parameter element equals an fp64 AdamW step (fp64 m / v carried from step 1) applied to the
