@@ -13,6 +13,7 @@
 #include "conv_sf.h"
 #include "epilogues_sf.h"
 #include "flow_consistency_host.h"
+#include "two_view_host.h"
 #include "warm_start_host.h"
 
 namespace atdn {
@@ -27,6 +28,8 @@ extern template TileChoice conv_sf_dispatch<SfBias<ACT_NONE>>(const ConvShape&, 
 
 void flow_consistency_check_args(const float* flow_fw, const float* flow_bw, int B, int H, int W, double alpha1, double alpha2,
                                  const unsigned char* mask, const int* count);   // flow_consistency.hip
+void two_view_check_args(const float* flow, const float* pose, const unsigned char* mask, int B, int H, int W,
+                         const TwoViewCamera& cam, const float* depth, const int* counts);   // two_view.hip
 
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& msg) { g_last_error = msg; }
@@ -405,6 +408,17 @@ int atdn_flow_consistency_host(const float* flow_fw, const float* flow_bw, int B
   ATDN_API_BEGIN
   flow_consistency_check_args(flow_fw, flow_bw, B, H, W, alpha1, alpha2, mask, count);
   flow_consistency_host(flow_fw, flow_bw, B, H, W, alpha1, alpha2, mask, count);
+  ATDN_API_END
+}
+
+// ------------------------------------------------------------------ two-view depth (host twin of two_view.hip)
+int atdn_flow_two_view_depth_host(const float* flow, const float* pose, const unsigned char* mask, int B, int H, int W, double fx,
+                                  double fy, double cx, double cy, double max_epipolar, double min_sin2, double max_depth,
+                                  float* depth, int* counts) {
+  ATDN_API_BEGIN
+  const TwoViewCamera cam{fx, fy, cx, cy, max_epipolar, min_sin2, max_depth};
+  two_view_check_args(flow, pose, mask, B, H, W, cam, depth, counts);
+  two_view_depth_host(flow, pose, mask, B, H, W, cam, depth, counts);
   ATDN_API_END
 }
 

@@ -211,11 +211,21 @@ class OdometryPipeline:
 class VisualOdometry:
     """Frame-at-a-time odometry with the reference's call pattern: `pose = vo(frame)`."""
 
-    def __init__(self, gma_state, clvo_state, device="cuda:0", iters=12, warm_start=False):
+    def __init__(self, gma_state, clvo_state, device="cuda:0", iters=12, warm_start=False, calib=None):
         """`warm_start=True`: every pair after the first of an unbroken run of calls starts its refinement from the previous
         pair's flow, forward-interpolated on the device (RAFTGMA.forward_consecutive); meant to be combined with a smaller
-        `iters`, which is the caller's choice. `reset()` makes the next pair run cold again."""
+        `iters`, which is the caller's choice. `reset()` makes the next pair run cold again.
+        `calib`: (fx, fy, cx, cy) or a 3x3 / 3x4 calibration matrix of the 376 x 1232 grid (depth.resize_calib takes a camera's
+        calibration there). Every pair then also leaves `last_depth` [1,1,376,1232] and `last_counts` [1,3] on the device
+        (transforms.two_view_depth of that pair's flow and the pose just predicted: the depth of the pair's FIRST frame), one
+        small copy and one launch more per frame and no further synchronisation; `epipolar_score()` reads the score. Without it
+        the calls and the poses are what they were."""
+        from .depth import intrinsics
         self.warm_start = bool(warm_start)
+        self.calib = None if calib is None else intrinsics(calib)
+        # the pose goes back to the device through pinned memory: the copy is asynchronous, and the buffer is free again by
+        # the next frame, whose own trip to the host waits for everything before it
+        self._pose_host = torch.empty(12, dtype=torch.float32).pin_memory() if calib is not None else None
         # one pair per call: the low-latency form of the flow network (modules.RAFTGMA)
         self.pipe = OdometryPipeline(gma_state, clvo_state, device=device, max_batch=1, iters=iters, low_latency=True)
         # frame-by-frame caller: every call ends in a device synchronisation anyway (the pose goes to the host), so the
@@ -226,6 +236,8 @@ class VisualOdometry:
 
     def reset(self):
         self._prev = None
+        self.last_depth = None
+        self.last_counts = None
         self.current_pose = torch.eye(4, dtype=torch.float32)
         self.pipe.head.reset_lstm()
         self.pipe.flow_net.break_chain()   # a new sequence: no features or flow carried over
@@ -243,5 +255,17 @@ class VisualOdometry:
             rot, tr = self.pipe.head(flow)
             rt = torch.cat([rot.reshape(-1), tr.reshape(-1)]).cpu()   # one trip to the host for both vectors
             self.current_pose = transforms.accumulate(self.current_pose, rt[:3], rt[3:])
+            if self.calib is not None:
+                self._pose_host.copy_(transforms.transform(rt[:3], rt[3:])[:3].reshape(12))
+                pose = self._pose_host.to(self.device, non_blocking=True)[None]
+                self.last_depth, self.last_counts = transforms.two_view_depth(flow, pose, self.calib)
         self._prev = im
         return self.current_pose
+
+    def epipolar_score(self):
+        """The share of the last pair's correspondences that lie within 1 px of the epipolar line its predicted pose gives them
+        (transforms.epipolar_score of `last_counts`), as a Python float: the one call here that waits for the device. None
+        before the first pair or without a calibration."""
+        if self.last_counts is None:
+            return None
+        return float(transforms.epipolar_score(self.last_counts)[0])

@@ -78,13 +78,21 @@ class NeuralSLAM:
     `warm_start=True`: in odometry mode every pair of an unbroken run of calls starts from the previous pair's flow, pushed forward
     on the device (RAFTGMA.forward_consecutive; 12 iterations as before). The relocalisation refinement always runs cold: a
     keyframe and a query are not consecutive frames.
+    `calib`: (fx, fy, cx, cy) or a 3x3 / 3x4 calibration matrix of the 376 x 1232 grid (depth.resize_calib). In odometry mode the
+    pair whose first frame is a keyframe then gives that keyframe its depth (transforms.two_view_depth of the pair's flow and
+    predicted pose): `<keyframes_path>/depth/%06d.pth`, float32 [1,376,1232], 0 = no depth, written on the call after the one
+    that stored the keyframe — a keyframe that never gets a successor has no file — and `keyframe_points(i)` returns its valid
+    pixels as points of the world frame. Without it nothing on disk or in any return value changes.
     """
 
     FLOW_CHECKPOINT = "atdn_vslam/checkpoints/gma-kitti.pth"  # utils/gma_parameters.py
 
     def __init__(self, args, odometry_weights=None, start_mode=None, flow_weights=None, mapping_weights=None,
-                 precision=None, map_options=None, resident_map=False, warm_start=False):
+                 precision=None, map_options=None, resident_map=False, warm_start=False, calib=None):
+        from .depth import intrinsics
         self._args = args
+        self._calib = None if calib is None else intrinsics(calib)
+        self._depth_pending = None   # index of the keyframe that is the first frame of the next pair
         self._warm_start = bool(warm_start)   # odometry mode only; relocalisation pairs are not consecutive frames
         self._map_options = dict(map_options or {})   # keyword arguments of mapping.create_map (e.g. num_epochs)
         self._base = args.keyframes_path
@@ -120,6 +128,11 @@ class NeuralSLAM:
         else:
             os.makedirs(os.path.join(self._base, "rgb"), exist_ok=True)
             for f in glob.glob(os.path.join(self._base, "rgb", "*")):
+                os.remove(f)
+            # keyframe depths of an earlier session go like its frames; the directory itself appears only with a calibration
+            if self._calib is not None:
+                os.makedirs(os.path.join(self._base, "depth"), exist_ok=True)
+            for f in glob.glob(os.path.join(self._base, "depth", "*")):
                 os.remove(f)
             # a cold start owns the directory: poses and map weights of an earlier session go too
             for stale in ("poses.pth", "MappingVAE_weights.pth"):
@@ -183,16 +196,25 @@ class NeuralSLAM:
                 rot, tr = pred_rot.squeeze().cpu(), pred_tr.squeeze().cpu()
                 pred_mat = transforms.transform(rot, tr)
                 self._current_pose = transforms.accumulate(self._current_pose, rot, tr)  # float32 pose @ pred_mat
+                if self._depth_pending is not None:
+                    # the previous frame is a keyframe: this pair's flow starts at its pixels, so the depth is the keyframe's
+                    depth, _ = transforms.two_view_depth(flow, pred_mat[None].to(self._device), self._calib)
+                    torch.save(depth[0].to("cpu"), os.path.join(self._base, "depth", "%06d.pth" % self._depth_pending))
+                    self._depth_pending = None
                 if self._policy(pred_mat):
                     name = os.path.join(self._base, "rgb", "%06d.pth" % len(self._keyframes))
                     self._store_keyframe(im2, name)
                     self._keyframes.append(Frame(name, self._current_pose))
+                    if self._calib is not None:
+                        self._depth_pending = len(self._keyframes) - 1
                 self._image_buffer = im2
             else:
                 self._image_buffer = self._padder.pad(im)[0]
                 name = os.path.join(self._base, "rgb", "000000.pth")
                 self._store_keyframe(im, name)
                 self._keyframes.append(Frame(name, self._current_pose))
+                if self._calib is not None:
+                    self._depth_pending = 0
             return self._current_pose
         if self._mode == "relocalization":
             q = im.to(self._device).float()
@@ -221,6 +243,23 @@ class NeuralSLAM:
 
     def __len__(self):
         return len(self._keyframes)
+
+    @torch.no_grad()
+    def keyframe_points(self, index):
+        """[3,N] float32 on the device: the pixels of keyframe `index` that have a depth, as points of the world frame — its
+        depth file back-projected (depth.project_depth) and moved by the keyframe's pose. Needs `calib`; a keyframe without a
+        depth file (no successor yet) raises FileNotFoundError."""
+        from .depth import project_depth
+        if self._calib is None:
+            raise RuntimeError("keyframe_points needs the calibration: construct NeuralSLAM(..., calib=...)")
+        kf = self._keyframes[index]
+        number = os.path.splitext(os.path.basename(kf.rgb_file_name))[0]
+        depth = torch.load(os.path.join(self._base, "depth", number + ".pth")).to(self._device)
+        points = project_depth(depth, self._calib)
+        points = points[:, depth[0] > 0]
+        pose = torch.as_tensor(kf.pose, dtype=torch.float32).to(self._device)
+        # (three products and three sums per coordinate, element-wise: no GEMM for a 3 x 3 matrix)
+        return (pose[:3, 0:1] * points[0:1] + pose[:3, 1:2] * points[1:2]) + (pose[:3, 2:3] * points[2:3] + pose[:3, 3:4])
 
     # ------------------------------------------------------------------ internals
     def _set_mapping_net(self, weights):

@@ -126,6 +126,73 @@ def flow_consistency(flow_fw, flow_bw, alpha1=0.01, alpha2=0.5):
     return (mask[0], score[0]) if single else (mask, score)
 
 
+def _pose_rows(pose, B, device):
+    """[B,4,4], [B,3,4] or [B,12] (one pose without the batch axis when B == 1) -> contiguous float32 [B,12] on `device`."""
+    p = torch.as_tensor(pose)
+    if B == 1 and (tuple(p.shape) in ((4, 4), (3, 4), (12,))):
+        p = p[None]
+    if p.dim() == 3 and tuple(p.shape[1:]) in ((4, 4), (3, 4)):
+        p = p[:, :3, :].reshape(p.shape[0], 12)
+    if p.dim() != 2 or tuple(p.shape) != (B, 12):
+        raise RuntimeError("expected %d poses [B,4,4], [B,3,4] or [B,12], got %s" % (B, tuple(torch.as_tensor(pose).shape)))
+    return p.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def two_view_depth(flow, pose, calib, mask=None, max_epipolar=1.0, min_parallax_deg=0.05, max_depth=80.0):
+    """Depth and epipolar agreement of a flow and a relative pose under a calibration. `flow` [B,2,H,W] (or [2,H,W]) is the flow
+    from image 1 to image 2, channel 0 = x; `pose` [B,4,4], [B,3,4] or [B,12] the relative pose with X1 = R X2 + t — what
+    `transform(rot, tr)` of the pose head returns, the matrix a running pose is multiplied by; `calib` is (fx, fy, cx, cy) or a 3x3
+    / 3x4 calibration matrix without skew, of the grid the flow lives on (depth.resize_calib). `mask` (uint8 or bool, [B,1,H,W],
+    [B,H,W] or [H,W]; e.g. the mask of `flow_consistency`) removes the pixels where it is 0. Returns `(depth, counts)` on the flow's
+    device: `depth` float32 [B,1,H,W] ([1,H,W] for a 3-d flow), the triangulated depth of every pixel in camera 1 and 0 where there
+    is none; `counts` int32 [B,3] ([3]) = (correspondences that land inside image 2, those within `max_epipolar` pixels of their
+    epipolar line, those with a valid depth: an inlier whose two rays meet at an angle of at least `min_parallax_deg` degrees, in
+    front of both cameras, no farther than `max_depth`). `epipolar_score(counts)` is the share of inliers. Device tensors go through
+    libatdn_hip's kernel on the current stream and the results stay on the device (no synchronisation); CPU tensors go through the
+    library's host form. The rule is float64 and stated in full in include/atdn_hip.h, atdn_flow_two_view_depth; the same inputs
+    give the same bits on every call and on both paths."""
+    import math
+    from .depth import intrinsics
+    if flow.dim() not in (3, 4) or flow.shape[-3] != 2:
+        raise RuntimeError("expected a flow [2,H,W] or [B,2,H,W], got %s" % (tuple(flow.shape),))
+    single = flow.dim() == 3
+    f = (flow[None] if single else flow).detach().float().contiguous()
+    B, _, H, W = f.shape
+    p = _pose_rows(pose, B, f.device)
+    fx, fy, cx, cy = intrinsics(calib)
+    m = None
+    if mask is not None:
+        m = torch.as_tensor(mask)
+        if m.numel() != B * H * W or tuple(m.shape[-2:]) != (H, W):
+            raise RuntimeError("expected a mask of %d x %d x %d values, got %s" % (B, H, W, tuple(m.shape)))
+        if m.device != f.device:
+            raise RuntimeError("flow on %s but mask on %s" % (f.device, m.device))
+        m = (m != 0).to(torch.uint8) if m.dtype != torch.uint8 else m
+        m = m.detach().contiguous()
+    min_sin2 = math.sin(math.radians(float(min_parallax_deg))) ** 2
+    depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=f.device)
+    counts = torch.empty((B, 3), dtype=torch.int32, device=f.device)
+    L = _lib.lib()
+    args = (C.c_void_p(f.data_ptr()), C.c_void_p(p.data_ptr()), C.c_void_p(m.data_ptr()) if m is not None else None, B, H, W,
+            fx, fy, cx, cy, float(max_epipolar), min_sin2, float(max_depth), C.c_void_p(depth.data_ptr()),
+            C.c_void_p(counts.data_ptr()))
+    if f.is_cuda:
+        with torch.cuda.device(f.device):
+            _lib.check(L.atdn_flow_two_view_depth(*args, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    else:
+        _lib.check(L.atdn_flow_two_view_depth_host(*args))
+    return (depth[0], counts[0]) if single else (depth, counts)
+
+
+def epipolar_score(counts):
+    """float32 inliers / inside of the `counts` [B,3] (or [3]) of `two_view_depth`, 0 where no correspondence is inside: the
+    share of the flow's correspondences that lie within `max_epipolar` pixels of the epipolar line the pose gives them. Exact
+    integer counts divided in float64, then rounded; stays on the counts' device."""
+    c = torch.as_tensor(counts)
+    inside, inliers = c[..., 0].double(), c[..., 1].double()
+    return torch.where(inside > 0, inliers / inside.clamp(min=1.0), torch.zeros_like(inside)).float()
+
+
 class InputPadder:
     """Replicate-pads frames to multiples of 8 ('sintel' mode splits the padding on both sides)."""
 

@@ -347,6 +347,67 @@ int atdn_flow_consistency_host(const float* flow_fw, const float* flow_bw, int B
                                unsigned char* mask, int* count);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Two-view geometry  —  what a flow and a relative pose determine at every pixel once the camera calibration is known: how far
+ * the correspondence lies from its epipolar line (the share of pixels that agree scores the pose against its own flow, without
+ * ground truth) and, by triangulation, the depth of the pixel. The reference has no producer of depth; atdn_depth_backproject
+ * is the device form of project_depth of its utils/depth.py:23-46 for a calibration without skew
+ * ------------------------------------------------------------------------------------------------- */
+
+/* depth[b,0,y,x] = the triangulated depth of pixel (x, y) of image 1 in camera 1, 0 where there is none; counts[b] = (number of
+ * correspondences inside image 2, number of epipolar inliers among them, number of valid depths among those).
+ *   flow [B,2,H,W] fp32 DEVICE, frame 1 -> frame 2, channel 0 = x. pose [B,12] fp32 DEVICE: the rows of [R|t] with
+ *   X1 = R X2 + t, i.e. r_ij = pose[b][4*i + j], t_i = pose[b][4*i + 3] — the first three rows of transform(rot, tr) of the pose
+ *   head, the matrix a running pose is multiplied by (atdn_pose_transform_f32). mask [B,H,W] uint8 DEVICE or NULL: pixels whose
+ *   byte is 0 are skipped (the mask of atdn_flow_consistency fits). depth [B,1,H,W] fp32 DEVICE, counts [B,3] int32 DEVICE; depth
+ *   and counts overlap neither each other nor an input. fx, fy finite and > 0; cx, cy finite; max_epipolar (pixels) and min_sin2
+ *   finite and >= 0; max_depth finite and > 0. B <= 65535, H * W <= 2^24. Anything else fails before a launch.
+ * The rule, for pixel (x, y) with flow (u, v), everything in float64 and every operation rounded on its own (no fused
+ * multiply-add), in exactly this order:
+ *   mask given and mask[y,x] == 0: depth 0, counted nowhere
+ *   x2 = x + u, y2 = y + v                                        (exact in float64)
+ *   inside = 0 <= x2 <= W-1 && 0 <= y2 <= H-1                     (closed intervals; a NaN fails); not inside: depth 0, counted nowhere
+ *   a0 = (x - cx)/fx, a1 = (y - cy)/fy                            (the ray of the pixel; a2 = 1)
+ *   q0 = (x2 - cx)/fx, q1 = (y2 - cy)/fy                          (the ray of the correspondence in camera 2; q2 = 1)
+ *   b_i = (r_i0*q0 + r_i1*q1) + r_i2                  i = 0,1,2   (b = R q)
+ *   n0 = t1 - t2*a1, n1 = t2*a0 - t0, n2 = t0*a1 - t1*a0          (n = t x a)
+ *   res = (n0*b0 + n1*b1) + n2*b2
+ *   m0 = (r00*n0 + r10*n1) + r20*n2, m1 = (r01*n0 + r11*n1) + r21*n2, l0 = m0/fx, l1 = m1/fy
+ *   epi2 = (res*res) / (l0*l0 + l1*l1)                            (squared pixel distance of (x2, y2) from its epipolar line in image 2)
+ *   inlier = epi2 <= max_epipolar*max_epipolar                    (plain comparison: 0/0 from t = 0 is NaN and fails)
+ *   aa = (a0*a0 + a1*a1) + 1, bb = (b0*b0 + b1*b1) + b2*b2, ab = (a0*b0 + a1*b1) + b2
+ *   at = (a0*t0 + a1*t1) + t2, bt = (b0*t0 + b1*t1) + b2*t2
+ *   p = aa*bb, det = p - ab*ab, sin2 = det/p                      (sin^2 of the angle between the two rays)
+ *   z1 = (bb*at - ab*bt)/det, z2 = (ab*at - aa*bt)/det            (least-squares solution of z1*a - z2*b = t)
+ *   valid = inlier && sin2 >= min_sin2 && z1 >= FLT_MIN && z2 > 0 && z1 <= max_depth
+ *   depth = valid ? (float)z1 : 0
+ * No square root and no transcendental: + - * / and comparisons, all correctly rounded, so the device, the host form and any
+ * IEEE float64 restatement agree bit for bit. `z1 >= FLT_MIN` (2^-126) stands where `z1 > 0` would: a smaller positive z1 rounds
+ * to a float32 zero or subnormal, and a pixel counted valid would carry the value that means "no depth"; with it every valid
+ * depth is a normal positive float32 and counts[b][2] is the number of non-zero depths. Parallel rays (det = 0: no parallax, or a
+ * pixel at the epipole) give z1 = +-inf or NaN and are never valid, whatever min_sin2 is; t = 0 gives no inliers. A NaN or an
+ * infinity in the flow of a pixel gives depth 0 there and touches no other pixel; one in the pose fails every comparison it reaches.
+ * A memset of `counts` and one launch on `stream`: asynchronous, capturable, no host synchronisation, no workspace. The counts
+ * are integer sums (wave ballots, LDS, one integer atomic add per workgroup and counter; no float atomics): the same bits on
+ * every call. */
+int atdn_flow_two_view_depth(const float* flow, const float* pose, const unsigned char* mask, int B, int H, int W, double fx,
+                             double fy, double cx, double cy, double max_epipolar, double min_sin2, double max_depth, float* depth,
+                             int* counts, void* stream);
+/* The same function on HOST buffers in plain C++ float64 (csrc/two_view_host.h, the per-pixel function the kernel calls too):
+ * serves CPU tensors, needs no GPU, the same bits. */
+int atdn_flow_two_view_depth_host(const float* flow, const float* pose, const unsigned char* mask, int B, int H, int W, double fx,
+                                  double fy, double cx, double cy, double max_epipolar, double min_sin2, double max_depth,
+                                  float* depth, int* counts);
+
+/* points[b] = [3,H,W] fp32: the pinhole back-projection of depth[b] (project_depth of utils/depth.py:23-46 with
+ * calib = [[fx,0,cx],[0,fy,cy],[0,0,1]]): for z = depth[b,0,y,x],
+ *   X = (z*(x - cx))/fx, Y = (z*(y - cy))/fy, Z = z
+ * each formed in float64 (every operation rounded on its own) and rounded to fp32 once — the reference inverts the fp32 matrix and
+ * multiplies in fp32. depth [B,1,H,W], points [B,3,H,W] fp32 DEVICE, not overlapping; fx, fy finite and > 0, cx, cy finite;
+ * B <= 65535, H * W <= 2^24. One launch on `stream`: asynchronous, capturable. */
+int atdn_depth_backproject(const float* depth, int B, int H, int W, double fx, double fy, double cx, double cy, float* points,
+                           void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Keyframe map  —  replaces the keyframe list of NeuralSLAM's relocalisation (keyframe_map.py)
  *   embeddings: Frame.embedding, one MappingVAE call per keyframe (slam_framework/neural_slam.py:88-103,158-164)
  *   search:     the per-keyframe torch.norm loop, torch.stack and argmin (neural_slam.py:374-383)
