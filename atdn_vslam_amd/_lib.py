@@ -77,6 +77,10 @@ SIGNATURES = {
     "atdn_flow_two_view_depth_host": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                                 C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp]),
     "atdn_depth_backproject": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp]),
+    "atdn_flow_track_step": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double,
+                                       C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "atdn_flow_track_step_host": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, C.c_double,
+                                            C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp]),
     "atdn_map_search": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "atdn_map_gather_images_u8": (C.c_int, [_vp, C.c_int, C.c_long, _vp, C.c_int, _vp, _vp]),
     "atdn_corr_lookup": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),

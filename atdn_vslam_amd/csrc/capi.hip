@@ -13,6 +13,7 @@
 #include "conv_sf.h"
 #include "epilogues_sf.h"
 #include "flow_consistency_host.h"
+#include "flow_track_host.h"
 #include "two_view_host.h"
 #include "warm_start_host.h"
 
@@ -30,6 +31,9 @@ void flow_consistency_check_args(const float* flow_fw, const float* flow_bw, int
                                  const unsigned char* mask, const int* count);   // flow_consistency.hip
 void two_view_check_args(const float* flow, const float* pose, const unsigned char* mask, int B, int H, int W,
                          const TwoViewCamera& cam, const float* depth, const int* counts);   // two_view.hip
+void flow_track_check_args(const float* flow, const unsigned char* mask, const float* acc_in, const unsigned char* alive_in, int B,
+                           int H, int W, const float* acc_out, const unsigned char* alive_out, const float* pose,
+                           const TwoViewCamera& cam, const float* depth, const int* counts);   // flow_track.hip
 
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& msg) { g_last_error = msg; }
@@ -419,6 +423,18 @@ int atdn_flow_two_view_depth_host(const float* flow, const float* pose, const un
   const TwoViewCamera cam{fx, fy, cx, cy, max_epipolar, min_sin2, max_depth};
   two_view_check_args(flow, pose, mask, B, H, W, cam, depth, counts);
   two_view_depth_host(flow, pose, mask, B, H, W, cam, depth, counts);
+  ATDN_API_END
+}
+
+// ------------------------------------------------------------------ flow track (host twin of flow_track.hip)
+int atdn_flow_track_step_host(const float* flow, const unsigned char* mask, const float* acc_in, const unsigned char* alive_in,
+                              int B, int H, int W, float* acc_out, unsigned char* alive_out, const float* pose, double fx,
+                              double fy, double cx, double cy, double max_epipolar, double min_sin2, double max_depth, float* depth,
+                              int* counts) {
+  ATDN_API_BEGIN
+  const TwoViewCamera cam{fx, fy, cx, cy, max_epipolar, min_sin2, max_depth};
+  flow_track_check_args(flow, mask, acc_in, alive_in, B, H, W, acc_out, alive_out, pose, cam, depth, counts);
+  flow_track_step_host(flow, mask, acc_in, alive_in, B, H, W, acc_out, alive_out, pose, cam, depth, counts);
   ATDN_API_END
 }
 

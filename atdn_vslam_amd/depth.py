@@ -74,3 +74,65 @@ def project_depth(depth, calib, device=None):
     x = torch.arange(W, dtype=torch.float64).view(1, W)
     y = torch.arange(H, dtype=torch.float64).view(H, 1)
     return torch.stack([(z * (x - cx)) / fx, (z * (y - cy)) / fy, z]).float()
+
+
+class FlowTrack:
+    """The state of one anchor frame's flow track (transforms.flow_track_step) on the device: `acc` [B,2,H,W] float32, the flow
+    from the anchor to the latest frame on the anchor's grid; `alive` [B,H,W] uint8; `depth` [B,1,H,W] float32, at every pixel the
+    triangulation of the last step at which it was valid (0 = none yet); `counts` [B,4] int32 of the last step = (alive, inside,
+    inliers, valid); `pose` [B,4,4] float64 on the host, anchor <- latest frame; `steps`, the number of pairs since the anchor.
+    `calib` is that of the grid the flows live on (`resize_calib`); `thresholds` are max_epipolar, min_parallax_deg and max_depth
+    of `transforms.two_view_depth`. `start()` begins a track at a new anchor, `extend(flow, pred_mat)` carries it over one pair.
+    The pose goes to the device as 12 float32 through pinned memory, asynchronously; no call synchronises with the host."""
+
+    def __init__(self, hw, calib, device, batch=1, **thresholds):
+        unknown = set(thresholds) - {"max_epipolar", "min_parallax_deg", "max_depth"}
+        if unknown:
+            raise TypeError("unknown threshold(s): %s" % ", ".join(sorted(unknown)))
+        H, W = int(hw[0]), int(hw[1])
+        B = int(batch)
+        self.calib = intrinsics(calib)
+        self.device = torch.device(device)
+        self.thresholds = dict(thresholds)
+        self.acc = torch.zeros((B, 2, H, W), dtype=torch.float32, device=self.device)
+        self.alive = torch.ones((B, H, W), dtype=torch.uint8, device=self.device)
+        self.depth = torch.zeros((B, 1, H, W), dtype=torch.float32, device=self.device)
+        self.counts = torch.zeros((B, 4), dtype=torch.int32, device=self.device)
+        self._pose_dev = torch.zeros((B, 12), dtype=torch.float32, device=self.device)
+        self.pose = torch.eye(4, dtype=torch.float64).repeat(B, 1, 1)
+        self.steps = 0
+
+    def to(self, device):
+        """Move the device state, a running track included; the pose and `steps` stay on the host. Returns self."""
+        self.device = torch.device(device)
+        for name in ("acc", "alive", "depth", "counts", "_pose_dev"):
+            setattr(self, name, getattr(self, name).to(self.device))
+        return self
+
+    def start(self):
+        """Begin a track at a new anchor: acc and depth zero, every pixel alive, identity pose."""
+        self.acc.zero_()
+        self.depth.zero_()
+        self.alive.fill_(1)
+        self.counts.zero_()
+        self.pose = torch.eye(4, dtype=torch.float64).repeat(self.pose.shape[0], 1, 1)
+        self.steps = 0
+
+    def extend(self, flow, pred_mat, mask=None):
+        """Carry the track over the pair frame k -> k+1: `flow` [B,2,H,W] on the track's device, `pred_mat` [4,4] or [B,4,4] the
+        pair's relative pose (X_k = R X_k+1 + t, what `transforms.transform` returns), `mask` as for `transforms.flow_track_step`.
+        pose <- pose @ pred_mat in float64, then one in-place step. Returns `counts`."""
+        from . import transforms
+        B = self.pose.shape[0]
+        step = torch.as_tensor(pred_mat).detach().to("cpu", torch.float64)
+        if tuple(step.shape) not in ((4, 4), (B, 4, 4)):
+            raise RuntimeError("expected a relative pose [4,4] or [%d,4,4], got %s" % (B, tuple(step.shape)))
+        self.pose = self.pose @ step
+        # a pinned buffer of the caching host allocator per step: it is handed out again only after the copy that reads it is done
+        rows = torch.empty((B, 12), dtype=torch.float32, pin_memory=self.device.type == "cuda")
+        rows.copy_(self.pose[:, :3, :].reshape(B, 12))
+        self._pose_dev.copy_(rows, non_blocking=True)
+        transforms.flow_track_step(flow, self.acc, self.alive, pose=self._pose_dev, calib=self.calib, mask=mask, depth=self.depth,
+                                   out=(self.acc, self.alive, self.counts), **self.thresholds)
+        self.steps += 1
+        return self.counts

@@ -83,15 +83,27 @@ class NeuralSLAM:
     predicted pose): `<keyframes_path>/depth/%06d.pth`, float32 [1,376,1232], 0 = no depth, written on the call after the one
     that stored the keyframe — a keyframe that never gets a successor has no file — and `keyframe_points(i)` returns its valid
     pixels as points of the world frame. Without it nothing on disk or in any return value changes.
+    `keyframe_depth`: "pair" (the default) is the depth just described. "track" (needs `calib`) uses the whole keyframe interval
+    instead of its first pair: a depth.FlowTrack starts at every keyframe and is extended by every pair up to and including the one
+    that registers the next keyframe, so each pixel's depth is triangulated over the longest baseline its track survives. The file
+    has the same name, shape and dtype; it is written when the next keyframe is registered, or by `end_odometry()` for the last
+    keyframe if any pair followed it. Poses and `rgb/` files do not depend on the choice.
     """
 
     FLOW_CHECKPOINT = "atdn_vslam/checkpoints/gma-kitti.pth"  # utils/gma_parameters.py
 
     def __init__(self, args, odometry_weights=None, start_mode=None, flow_weights=None, mapping_weights=None,
-                 precision=None, map_options=None, resident_map=False, warm_start=False, calib=None):
+                 precision=None, map_options=None, resident_map=False, warm_start=False, calib=None, keyframe_depth="pair"):
         from .depth import intrinsics
+        if keyframe_depth not in ("pair", "track"):
+            raise ValueError('keyframe_depth is "pair" or "track", got %r' % (keyframe_depth,))
+        if keyframe_depth == "track" and calib is None:
+            raise ValueError('keyframe_depth="track" needs the calibration: pass calib=')
         self._args = args
         self._calib = None if calib is None else intrinsics(calib)
+        self._track_depth = keyframe_depth == "track"
+        self._track = None           # depth.FlowTrack of the latest keyframe (keyframe_depth="track"), created with the first frame
+        self._track_index = None     # index of the keyframe the track is anchored at
         self._depth_pending = None   # index of the keyframe that is the first frame of the next pair
         self._warm_start = bool(warm_start)   # odometry mode only; relocalisation pairs are not consecutive frames
         self._map_options = dict(map_options or {})   # keyword arguments of mapping.create_map (e.g. num_epochs)
@@ -156,6 +168,7 @@ class NeuralSLAM:
         neural_slam.py:160 does; skipped only when `mapping_weights` is given explicitly), embed every keyframe and
         enter relocalization."""
         if self._mode == "odometry" and len(self._keyframes) > 0:
+            self._flush_track()
             poses = torch.stack([kf.pose.flatten()[:12] for kf in self._keyframes], dim=0)
             torch.save(poses, os.path.join(self._base, "poses.pth"))
             self._mode = "mapping"
@@ -196,6 +209,8 @@ class NeuralSLAM:
                 rot, tr = pred_rot.squeeze().cpu(), pred_tr.squeeze().cpu()
                 pred_mat = transforms.transform(rot, tr)
                 self._current_pose = transforms.accumulate(self._current_pose, rot, tr)  # float32 pose @ pred_mat
+                if self._track_index is not None:
+                    self._track.extend(flow, pred_mat)
                 if self._depth_pending is not None:
                     # the previous frame is a keyframe: this pair's flow starts at its pixels, so the depth is the keyframe's
                     depth, _ = transforms.two_view_depth(flow, pred_mat[None].to(self._device), self._calib)
@@ -205,7 +220,10 @@ class NeuralSLAM:
                     name = os.path.join(self._base, "rgb", "%06d.pth" % len(self._keyframes))
                     self._store_keyframe(im2, name)
                     self._keyframes.append(Frame(name, self._current_pose))
-                    if self._calib is not None:
+                    if self._track_depth:
+                        self._flush_track()
+                        self._start_track(len(self._keyframes) - 1)
+                    elif self._calib is not None:
                         self._depth_pending = len(self._keyframes) - 1
                 self._image_buffer = im2
             else:
@@ -213,7 +231,9 @@ class NeuralSLAM:
                 name = os.path.join(self._base, "rgb", "000000.pth")
                 self._store_keyframe(im, name)
                 self._keyframes.append(Frame(name, self._current_pose))
-                if self._calib is not None:
+                if self._track_depth:
+                    self._start_track(0)
+                elif self._calib is not None:
                     self._depth_pending = 0
             return self._current_pose
         if self._mode == "relocalization":
@@ -234,6 +254,8 @@ class NeuralSLAM:
         if self._mapping_net is not None:
             self._mapping_net = self._mapping_net.to(device)
         self._batch_flow_net = None   # (a resident keyframe map stays where it was built: its search names both devices)
+        if self._track is not None:
+            self._track.to(self._device)   # keyframe_depth="track": a running track goes along with the networks
 
     def get_keyframe(self, index):
         return self._keyframes[index]
@@ -262,6 +284,20 @@ class NeuralSLAM:
         return (pose[:3, 0:1] * points[0:1] + pose[:3, 1:2] * points[1:2]) + (pose[:3, 2:3] * points[2:3] + pose[:3, 3:4])
 
     # ------------------------------------------------------------------ internals
+    def _start_track(self, index):
+        """keyframe_depth="track": the flow track of keyframe `index` begins with the next pair."""
+        if self._track is None:
+            from .depth import FlowTrack
+            self._track = FlowTrack(SLAM_SIZE, self._calib, self._device)
+        self._track.start()
+        self._track_index = index
+
+    def _flush_track(self):
+        """Write the depth of the keyframe the track is anchored at, if any pair has extended it."""
+        if self._track_index is not None and self._track.steps > 0:
+            torch.save(self._track.depth[0].to("cpu"), os.path.join(self._base, "depth", "%06d.pth" % self._track_index))
+        self._track_index = None
+
     def _set_mapping_net(self, weights):
         self._mapping_net = MappingVAE()
         self._mapping_net.load_state_dict(_load_weights(weights))

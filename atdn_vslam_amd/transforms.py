@@ -193,6 +193,102 @@ def epipolar_score(counts):
     return torch.where(inside > 0, inliers / inside.clamp(min=1.0), torch.zeros_like(inside)).float()
 
 
+def flow_track_step(flow, acc, alive, pose=None, calib=None, mask=None, depth=None, max_epipolar=1.0, min_parallax_deg=0.05,
+                    max_depth=80.0, out=None):
+    """One step of a flow track: the correspondences of an anchor frame's pixels carried one frame further and, given a pose,
+    triangulated over the whole interval. `acc` [B,2,H,W] (or [2,H,W]) is the flow from the anchor to frame k on the anchor's grid
+    (zeros at the start of a track), `alive` (uint8 or bool, [B,H,W], [B,1,H,W] or [H,W]) says which pixels still have a track,
+    `flow` [B,2,H,W] (or [2,H,W]) is the flow from frame k to frame k+1, channel 0 = x. The step reads `flow` bilinearly where each
+    track stands and adds it: acc(k+1) = acc(k) + flow(p + acc(k)). A track dies — for good — when it leaves the image, meets a
+    NaN or an infinity, or stands (nearest pixel) where `mask` (as for `two_view_depth`, on frame k's grid; e.g. the mask of
+    `flow_consistency` of that pair) is 0; a dead pixel keeps its `acc`. With `pose` — anchor <- frame k+1, X_anchor = R X + t, in
+    any form `two_view_depth` takes, the product of the pairs' relative poses — and `calib`, the new `acc` is triangulated by the
+    two-view rule and the depth is written where it is valid; elsewhere `depth` keeps what it had, so after several steps every
+    pixel carries the triangulation of the last step at which it was valid. `depth` (float32 contiguous [B,1,H,W], or [1,H,W]) is
+    updated in place; None starts from zeros. Without `pose` the chain alone is advanced (`depth` and `calib` must be None).
+    Returns `(acc, alive, depth or None, counts)`: acc float32, alive uint8 [B,H,W] of 0 and 1, counts int32 [B,4] = (alive,
+    inside, inliers, valid), the last three as in `two_view_depth` (0 without a pose); a 3-d flow gives [2,H,W], [H,W], [1,H,W], [4].
+    `out=(acc_out, alive_out)` or `(acc_out, alive_out, counts_out)` names the tensors to write (float32 / uint8 / int32,
+    contiguous); `out=(acc, alive)` updates the state in place. Device tensors go through libatdn_hip's kernel on the current stream
+    and the results stay on the device (no synchronisation); CPU tensors go through the library's host form. The rule is float64
+    and stated in full in include/atdn_hip.h, atdn_flow_track_step; the same inputs give the same bits on every call and on
+    both paths."""
+    import math
+    from .depth import intrinsics
+    if flow.dim() not in (3, 4) or flow.shape[-3] != 2:
+        raise RuntimeError("expected a flow [2,H,W] or [B,2,H,W], got %s" % (tuple(flow.shape),))
+    single = flow.dim() == 3
+    f = (flow[None] if single else flow).detach().float().contiguous()
+    B, _, H, W = f.shape
+    dev = f.device
+
+    def same_device(t, what):
+        if t.device != dev:
+            raise RuntimeError("flow on %s but %s on %s" % (dev, what, t.device))
+        return t
+
+    def bytes_of(t, what):
+        t = same_device(torch.as_tensor(t), what)
+        if t.numel() != B * H * W or tuple(t.shape[-2:]) != (H, W):
+            raise RuntimeError("expected %s of %d x %d x %d values, got %s" % (what, B, H, W, tuple(t.shape)))
+        t = (t != 0).to(torch.uint8) if t.dtype != torch.uint8 else t
+        return t.detach().contiguous()
+
+    a = same_device(torch.as_tensor(acc), "acc")
+    if tuple(a.shape) != ((2, H, W) if single else (B, 2, H, W)):
+        raise RuntimeError("expected acc of the flow's shape %s, got %s" % (tuple(flow.shape), tuple(a.shape)))
+    a = a.detach().float().contiguous()
+    live = bytes_of(alive, "alive")
+    m = None if mask is None else bytes_of(mask, "a mask")
+    if pose is None:
+        if depth is not None or calib is not None:
+            raise RuntimeError("depth and calib need a pose: without one only the chain is advanced")
+        p, d = None, None
+        fx = fy = cx = cy = min_sin2 = 0.0
+    else:
+        if calib is None:
+            raise RuntimeError("a pose needs the calibration")
+        p = _pose_rows(pose, B, dev)
+        fx, fy, cx, cy = intrinsics(calib)
+        min_sin2 = math.sin(math.radians(float(min_parallax_deg))) ** 2
+        if depth is None:
+            d = torch.zeros((B, 1, H, W), dtype=torch.float32, device=dev)
+        else:
+            d = same_device(depth, "depth")
+            if d.dtype != torch.float32 or not d.is_contiguous() or d.numel() != B * H * W or tuple(d.shape[-2:]) != (H, W):
+                raise RuntimeError("depth is updated in place: expected contiguous float32 [%d,1,%d,%d], got %s %s"
+                                   % (B, H, W, d.dtype, tuple(d.shape)))
+    if out is None:
+        a_out = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev)
+        l_out = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+        counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    else:
+        if len(out) not in (2, 3):
+            raise RuntimeError("out is (acc_out, alive_out) or (acc_out, alive_out, counts_out)")
+        a_out, l_out = out[0], out[1]
+        counts = out[2] if len(out) == 3 else torch.empty((B, 4), dtype=torch.int32, device=dev)
+        for t, dt, count, what in ((a_out, torch.float32, B * 2 * H * W, "acc_out"), (l_out, torch.uint8, B * H * W, "alive_out"),
+                                   (counts, torch.int32, B * 4, "counts_out")):
+            same_device(t, what)
+            if t.dtype != dt or not t.is_contiguous() or t.numel() != count:
+                raise RuntimeError("%s must be contiguous %s of %d values, got %s %s" % (what, dt, count, t.dtype, tuple(t.shape)))
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+    L = _lib.lib()
+    args = (ptr(f), ptr(m), ptr(a), ptr(live), B, H, W, ptr(a_out), ptr(l_out), ptr(p), fx, fy, cx, cy, float(max_epipolar),
+            min_sin2, float(max_depth), ptr(d), ptr(counts))
+    if f.is_cuda:
+        with torch.cuda.device(dev):
+            _lib.check(L.atdn_flow_track_step(*args, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    else:
+        _lib.check(L.atdn_flow_track_step_host(*args))
+    d_ret = depth if depth is not None else (None if d is None else (d[0] if single else d))
+    if out is not None:
+        return a_out, l_out, d_ret, counts
+    if single:
+        return a_out[0], l_out[0], d_ret, counts[0]
+    return a_out, l_out, d_ret, counts
+
+
 class InputPadder:
     """Replicate-pads frames to multiples of 8 ('sintel' mode splits the padding on both sides)."""
 

@@ -407,6 +407,56 @@ int atdn_flow_two_view_depth_host(const float* flow, const float* pose, const un
 int atdn_depth_backproject(const float* depth, int B, int H, int W, double fx, double fy, double cx, double cy, float* points,
                            void* stream);
 
+/* One step of a flow track: the correspondence of every pixel of an ANCHOR frame carried one frame further, and its depth over
+ * the whole baseline. acc is the flow from the anchor to frame k on the anchor's grid, alive says which pixels still have a track;
+ * the step composes acc with the flow k -> k+1, read bilinearly where each track stands — p(k+1) = p(k) + flow_k(p(k)) — and, given
+ * the accumulated pose anchor <- frame k+1, triangulates the composed correspondence by the rule of atdn_flow_two_view_depth and
+ * writes the depth over the anchor's depth map where it is valid (the latest valid triangulation wins).
+ *   flow [B,2,H,W] fp32 DEVICE, frame k -> k+1 on frame k's grid, channel 0 = x. mask [B,H,W] uint8 DEVICE or NULL, on frame k's
+ *   grid: 0 = do not trust the flow here (the mask of atdn_flow_consistency of that pair fits). acc_in, acc_out [B,2,H,W] fp32
+ *   DEVICE: the flow anchor -> frame k, and anchor -> frame k+1, on the anchor's grid. alive_in, alive_out [B,H,W] uint8 DEVICE:
+ *   any non-zero byte in = alive; out is exactly 0 or 1. pose [B,12] fp32 DEVICE or NULL: anchor <- frame k+1 in the convention of
+ *   atdn_flow_two_view_depth (X_anchor = R X + t). depth [B,1,H,W] fp32 DEVICE, in/out. counts [B,4] int32 DEVICE = (alive_out,
+ *   inside, inliers, valid), the last three those of the two-view rule.
+ *   acc_out == acc_in and alive_out == alive_in (the same pointer) are allowed: a pixel's own state is read before it is written
+ *   and no other pixel's is read. Every other overlap of an output with an input or another output is refused.
+ *   pose == NULL is the chain-only form: depth must be NULL, counts[b][1..3] = 0, and fx .. max_depth are ignored. With a pose:
+ *   depth not NULL; fx, fy finite and > 0; cx, cy finite; max_epipolar and min_sin2 finite and >= 0; max_depth finite and > 0.
+ *   B <= 65535, H * W <= 2^24, B, H, W >= 1. Anything else fails before a launch.
+ * The rule, for pixel (x, y) of image b, everything in float64 and every operation rounded on its own (no fused multiply-add), in
+ * exactly this order ("dead" = alive_out 0, acc_out = acc_in bit for bit, depth untouched, counted nowhere):
+ *   alive_in == 0: dead
+ *   x1 = x + acc_x, y1 = y + acc_y                                (exact in float64)
+ *   inside = 0 <= x1 <= W-1 && 0 <= y1 <= H-1                     (closed intervals; a NaN fails); not inside: dead
+ *   x0 = floor(x1), ax = x1 - x0; y0 = floor(y1), ay = y1 - y0
+ *   taps t00, t10, t01, t11 of flow at (x0, y0), (min(x0+1, W-1), y0), (x0, min(y0+1, H-1)), (min(x0+1, W-1), min(y0+1, H-1));
+ *   all four are always read, zero-weight ones too (0 * NaN and 0 * inf are NaN and reach the result)
+ *   per channel: top = t00*(1-ax) + t10*ax, bot = t01*(1-ax) + t11*ax, s = top*(1-ay) + bot*ay
+ *   n_x = acc_x + s_x, n_y = acc_y + s_y; finite = |n_x| <= DBL_MAX && |n_y| <= DBL_MAX
+ *   trusted = mask == NULL || mask[floor(y1 + 0.5)][floor(x1 + 0.5)] != 0       (always inside the image, given `inside`)
+ *   alive_out = inside && finite && trusted; otherwise dead
+ *   acc_out = ((float)n_x, (float)n_y), one rounding each; a value that rounds to a float32 infinity makes the pixel dead
+ *   alive and pose != NULL: the rule of atdn_flow_two_view_depth for pixel (x, y) with the flow acc_out (the fp32 values), this
+ *   pose and no mask -> inside2, inlier, valid, z1; valid: depth = (float)z1; otherwise depth untouched
+ *   counts = (number of alive_out, of inside2, of inlier, of valid)
+ * So: a dead track never comes back. A NaN or an infinity in acc_in at a pixel, or in one of its four taps, makes that pixel dead
+ * and touches no other pixel; one in the pose fails every comparison it reaches, so the chain is unaffected and no depth is
+ * written. The depth at a pixel is the triangulation of the LAST step at which it was valid: the caller zeroes depth (and acc,
+ * and sets alive) at the start of a track. Only + - * /, floor, comparisons and one double -> float conversion, all correctly
+ * rounded: the device, the host form and any IEEE float64 restatement agree bit for bit.
+ * A memset of `counts` and one launch on `stream`: asynchronous, capturable, no host synchronisation, no workspace. The counts
+ * are integer sums (wave ballots, LDS, one integer atomic add per workgroup and counter; no float atomics): the same bits on
+ * every call. */
+int atdn_flow_track_step(const float* flow, const unsigned char* mask, const float* acc_in, const unsigned char* alive_in, int B,
+                         int H, int W, float* acc_out, unsigned char* alive_out, const float* pose, double fx, double fy, double cx,
+                         double cy, double max_epipolar, double min_sin2, double max_depth, float* depth, int* counts, void* stream);
+/* The same function on HOST buffers in plain C++ float64 (csrc/flow_track_host.h, the per-pixel function the kernel calls too):
+ * serves CPU tensors, needs no GPU, the same bits. */
+int atdn_flow_track_step_host(const float* flow, const unsigned char* mask, const float* acc_in, const unsigned char* alive_in,
+                              int B, int H, int W, float* acc_out, unsigned char* alive_out, const float* pose, double fx,
+                              double fy, double cx, double cy, double max_epipolar, double min_sin2, double max_depth, float* depth,
+                              int* counts);
+
 /* ---------------------------------------------------------------------------------------------------
  * Keyframe map  —  replaces the keyframe list of NeuralSLAM's relocalisation (keyframe_map.py)
  *   embeddings: Frame.embedding, one MappingVAE call per keyframe (slam_framework/neural_slam.py:88-103,158-164)
