@@ -12,6 +12,7 @@
 #include "frontend.h"
 #include "conv_sf.h"
 #include "epilogues_sf.h"
+#include "flow_args.h"
 #include "flow_consistency_host.h"
 #include "flow_track_host.h"
 #include "two_view_host.h"
@@ -27,14 +28,6 @@ extern template TileChoice conv_dispatch<MODE_TAP, EpiScale>(const ConvShape&, E
 extern template TileChoice conv_sf_dispatch<EpiBias<ACT_NONE>>(const ConvShape&, float, EpiBias<ACT_NONE>, hipStream_t);
 extern template TileChoice conv_sf_dispatch<SfBias<ACT_NONE>>(const ConvShape&, float, SfBias<ACT_NONE>, hipStream_t);
 
-void flow_consistency_check_args(const float* flow_fw, const float* flow_bw, int B, int H, int W, double alpha1, double alpha2,
-                                 const unsigned char* mask, const int* count);   // flow_consistency.hip
-void two_view_check_args(const float* flow, const float* pose, const unsigned char* mask, int B, int H, int W,
-                         const TwoViewCamera& cam, const float* depth, const int* counts);   // two_view.hip
-void flow_track_check_args(const float* flow, const unsigned char* mask, const float* acc_in, const unsigned char* alive_in, int B,
-                           int H, int W, const float* acc_out, const unsigned char* alive_out, const float* pose,
-                           const TwoViewCamera& cam, const float* depth, const int* counts);   // flow_track.hip
-
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& msg) { g_last_error = msg; }
 }  // namespace atdn
@@ -46,17 +39,6 @@ struct atdn_clvo { ClvoNet net; atdn_clvo(int H, int W, int B) : net(H, W, B) {}
 struct atdn_vae { VaeEncoder net; atdn_vae(int H, int W, int B) : net(H, W, B) {} };
 struct atdn_ingest { FrameIngest in; atdn_ingest(int a, int b, int c, int d, int n, int aa) : in(a, b, c, d, n, aa) {} };
 struct atdn_clvo_trainer { ClvoTrainer net; atdn_clvo_trainer(int H, int W, int B, int T) : net(H, W, B, T) {} };
-
-#define ATDN_API_BEGIN try {
-#define ATDN_API_END                                      \
-  return 0;                                               \
-  } catch (const std::exception& e) {                     \
-    set_last_error(e.what());                             \
-    return 1;                                             \
-  } catch (...) {                                         \
-    set_last_error("unknown error");                      \
-    return 1;                                             \
-  }
 
 // host pose algebra helpers
 template <class T>
@@ -400,8 +382,8 @@ int atdn_flow_forward_interpolate_host(const float* flow_low, int B, int h, int 
   ATDN_API_BEGIN
   ATDN_CHECK(flow_low && out, "null argument");
   ATDN_CHECK(B >= 1 && h >= 1 && w >= 1 && (long)h * w <= (1L << 24), "bad batch or grid size");
-  const long count = (long)B * 2 * h * w;
-  ATDN_CHECK(flow_low + count <= out || out + count <= flow_low, "input and output overlap");
+  const long bytes = (long)B * 2 * h * w * 4;
+  ATDN_CHECK(disjoint(flow_low, bytes, out, bytes), "input and output overlap");
   forward_interpolate_host(flow_low, B, h, w, out);
   ATDN_API_END
 }

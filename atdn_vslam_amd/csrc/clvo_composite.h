@@ -13,11 +13,7 @@
 #include <cfloat>
 #include <cmath>
 
-#if defined(__HIPCC__)
-#define ATDN_HD __host__ __device__
-#else
-#define ATDN_HD
-#endif
+#include "pixel_rule.h"   // ATDN_HD
 
 namespace atdn {
 namespace composite {

@@ -35,6 +35,25 @@ struct Error : std::runtime_error {
     }                                                                                       \
   } while (0)
 
+// The body of an extern "C" entry point that returns 0, or 1 with the message left for atdn_last_error().
+#define ATDN_API_BEGIN try {
+#define ATDN_API_END                                      \
+  return 0;                                               \
+  } catch (const std::exception& e) {                     \
+    ::atdn::set_last_error(e.what());                     \
+    return 1;                                             \
+  } catch (...) {                                         \
+    ::atdn::set_last_error("unknown error");              \
+    return 1;                                             \
+  }
+
+// the byte ranges [a, a + a_bytes) and [b, b + b_bytes) do not meet
+inline bool disjoint(const void* a, long a_bytes, const void* b, long b_bytes) {
+  const char* p = (const char*)a;
+  const char* q = (const char*)b;
+  return p + a_bytes <= q || q + b_bytes <= p;
+}
+
 // makes `dev` current for a scope (destructors of handles that own memory on ONE device: the caller's current device
 // may be another one — multi-GPU processes)
 struct DeviceGuard {

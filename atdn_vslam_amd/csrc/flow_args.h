@@ -1,0 +1,39 @@
+// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip), shared by each device
+// entry point and its host twin in capi.hip.
+#pragma once
+#include <cmath>
+
+#include "common.h"
+#include "two_view_host.h"
+
+namespace atdn {
+
+// [B, ., H, W] planes walked by pixel_quads.h: B is gridDim.y, and a flat index of a plane times four fits an int. The host forms
+// of flow_consistency and two_view have never had the gridDim.y limit (grid_limit = false); their device entry points check it.
+inline void check_plane_batch(int B, int H, int W, bool grid_limit = true) {
+  ATDN_CHECK(B >= 1 && H >= 1 && W >= 1, "bad batch or image size");
+  if (grid_limit) ATDN_CHECK(B <= 65535, "batch too large (B <= 65535)");
+  ATDN_CHECK((long)H * W <= (1L << 24), "image too large (H * W <= 2^24)");
+}
+
+inline void check_pinhole(double fx, double fy, double cx, double cy) {
+  ATDN_CHECK(std::isfinite(fx) && std::isfinite(fy) && fx > 0.0 && fy > 0.0, "fx and fy must be finite and > 0");
+  ATDN_CHECK(std::isfinite(cx) && std::isfinite(cy), "cx and cy must be finite");
+}
+
+inline void check_two_view_camera(const TwoViewCamera& cam) {
+  check_pinhole(cam.fx, cam.fy, cam.cx, cam.cy);
+  ATDN_CHECK(std::isfinite(cam.max_epipolar) && cam.max_epipolar >= 0.0, "max_epipolar must be finite and >= 0");
+  ATDN_CHECK(std::isfinite(cam.min_sin2) && cam.min_sin2 >= 0.0, "min_sin2 must be finite and >= 0");
+  ATDN_CHECK(std::isfinite(cam.max_depth) && cam.max_depth > 0.0, "max_depth must be finite and > 0");
+}
+
+void flow_consistency_check_args(const float* flow_fw, const float* flow_bw, int B, int H, int W, double alpha1, double alpha2,
+                                 const unsigned char* mask, const int* count);
+void two_view_check_args(const float* flow, const float* pose, const unsigned char* mask, int B, int H, int W,
+                         const TwoViewCamera& cam, const float* depth, const int* counts);
+void flow_track_check_args(const float* flow, const unsigned char* mask, const float* acc_in, const unsigned char* alive_in, int B,
+                           int H, int W, const float* acc_out, const unsigned char* alive_out, const float* pose,
+                           const TwoViewCamera& cam, const float* depth, const int* counts);
+
+}  // namespace atdn

@@ -9,11 +9,9 @@
 // flow_fw, flow_bw [2, H, W] float32, channel 0 = x. For pixel (x, y), everything in float64, every operation rounded on its
 // own (fp contraction off), in exactly this order:
 //   x1 = x + fw_x, y1 = y + fw_y                                  (exact in float64)
-//   inside = 0 <= x1 <= W-1 && 0 <= y1 <= H-1                     (closed; a NaN fails); not inside: mask 0, nothing more is read
-//   x0 = floor(x1), ax = x1 - x0; y0 = floor(y1), ay = y1 - y0
-//   taps of flow_bw at (x0, y0), (min(x0+1, W-1), y0), (x0, min(y0+1, H-1)), (min(x0+1, W-1), min(y0+1, H-1)): all four are
-//   always read, zero-weight ones too (a NaN or an infinity there reaches the result)
-//   per channel: top = t00*(1-ax) + t10*ax, bot = t01*(1-ax) + t11*ax, b = top*(1-ay) + bot*ay
+//   inside, b = bilinear_flow(flow_bw at (x1, y1))                (pixel_rule.h states it line by line: the closed inside test,
+//                                                                  four taps always read, the order of the products and sums);
+//                                                                  not inside: mask 0, nothing more is read
 //   sx = fw_x + b_x, sy = fw_y + b_y, diff = sx*sx + sy*sy
 //   mag = (fw_x*fw_x + fw_y*fw_y) + (b_x*b_x + b_y*b_y), thr = alpha1*mag + alpha2
 //   mask = inside && diff <= thr && diff <= DBL_MAX               (plain comparisons: any NaN gives 0)
@@ -24,37 +22,18 @@
 #include <cfloat>
 #include <cmath>
 
-#if defined(__HIPCC__)
-#define ATDN_FC_HD __host__ __device__
-#else
-#define ATDN_FC_HD
-#endif
+#include "pixel_rule.h"
 
 namespace atdn {
 
 // fw_x, fw_y: the forward flow at (x, y); bx, by: the two planes [H * W] of the backward flow.
-ATDN_FC_HD inline bool flow_consistent_pixel(float fw_x, float fw_y, const float* bx, const float* by, int H, int W, int x, int y,
-                                             double alpha1, double alpha2) {
+ATDN_HD inline bool flow_consistent_pixel(float fw_x, float fw_y, const float* bx, const float* by, int H, int W, int x, int y,
+                                          double alpha1, double alpha2) {
 #pragma clang fp contract(off)
   const double fx = (double)fw_x, fy = (double)fw_y;
   const double x1 = (double)x + fx, y1 = (double)y + fy;
-  const bool inside = x1 >= 0.0 && x1 <= (double)(W - 1) && y1 >= 0.0 && y1 <= (double)(H - 1);
-  if (!inside) return false;
-  const double xf = floor(x1), yf = floor(y1);
-  const double ax = x1 - xf, ay = y1 - yf;
-  const int x0 = (int)xf, y0 = (int)yf;                       // in [0, W-1] x [0, H-1]: inside
-  const int xn = x0 + 1 < W ? x0 + 1 : W - 1, yn = y0 + 1 < H ? y0 + 1 : H - 1;
-  const long r0 = (long)y0 * W, r1 = (long)yn * W;
-  const double wx = 1.0 - ax, wy = 1.0 - ay;
   double b[2];
-  for (int c = 0; c < 2; ++c) {
-    const float* p = c ? by : bx;
-    const double t00 = (double)p[r0 + x0], t10 = (double)p[r0 + xn], t01 = (double)p[r1 + x0], t11 = (double)p[r1 + xn];
-    const double top_l = t00 * wx, top_r = t10 * ax, bot_l = t01 * wx, bot_r = t11 * ax;
-    const double top = top_l + top_r, bot = bot_l + bot_r;
-    const double up = top * wy, dn = bot * ay;
-    b[c] = up + dn;
-  }
+  if (!bilinear_flow(x1, y1, bx, by, H, W, b)) return false;
   const double sx = fx + b[0], sy = fy + b[1];
   const double sxx = sx * sx, syy = sy * sy;
   const double diff = sxx + syy;

@@ -14,11 +14,9 @@
 //   alive_in == 0: dead                                           (dead: alive_out = 0, acc_out = acc_in bit for bit, depth untouched,
 //                                                                  counted nowhere)
 //   x1 = x + acc_x, y1 = y + acc_y                                (exact in float64)
-//   inside = 0 <= x1 <= W-1 && 0 <= y1 <= H-1                     (closed; a NaN fails); not inside: dead, nothing more is read
-//   x0 = floor(x1), ax = x1 - x0; y0 = floor(y1), ay = y1 - y0
-//   taps of flow at (x0, y0), (min(x0+1, W-1), y0), (x0, min(y0+1, H-1)), (min(x0+1, W-1), min(y0+1, H-1)): all four are always
-//   read, zero-weight ones too (a NaN or an infinity there reaches the result)
-//   per channel: top = t00*(1-ax) + t10*ax, bot = t01*(1-ax) + t11*ax, s = top*(1-ay) + bot*ay
+//   inside, s = bilinear_flow(flow at (x1, y1))                   (pixel_rule.h states it line by line: the closed inside test,
+//                                                                  four taps always read, the order of the products and sums);
+//                                                                  not inside: dead, nothing more is read
 //   n_x = acc_x + s_x, n_y = acc_y + s_y, finite = |n_x| <= DBL_MAX && |n_y| <= DBL_MAX
 //   trusted = mask == null || mask[floor(y1 + 0.5)][floor(x1 + 0.5)] != 0       (inside the image, given `inside`)
 //   alive_out = inside && finite && trusted && neither n_x nor n_y rounds to a float32 infinity; otherwise dead
@@ -41,32 +39,17 @@ enum { FT_ALIVE = 8 };   // beside TV_INSIDE, TV_INLIER, TV_VALID
 // FT_ALIVE | the TV_* bits of the pixel; *out_x, *out_y = acc_out (the input's bits when dead); *z = the depth where TV_VALID is
 // set, untouched otherwise. DEPTH = false is the chain-only form: P and cam are not read, no TV_* bit is set.
 template <bool DEPTH>
-ATDN_TV_HD inline int flow_track_pixel(float acc_x, float acc_y, bool alive_in, const float* fx, const float* fy,
-                                       const unsigned char* mask, int H, int W, int x, int y, const TwoViewPose* P,
-                                       const TwoViewCamera* cam, float* out_x, float* out_y, float* z) {
+ATDN_HD inline int flow_track_pixel(float acc_x, float acc_y, bool alive_in, const float* fx, const float* fy,
+                                    const unsigned char* mask, int H, int W, int x, int y, const TwoViewPose* P,
+                                    const TwoViewCamera* cam, float* out_x, float* out_y, float* z) {
 #pragma clang fp contract(off)
   *out_x = acc_x;
   *out_y = acc_y;
   if (!alive_in) return 0;
   const double ux = (double)acc_x, uy = (double)acc_y;
   const double x1 = (double)x + ux, y1 = (double)y + uy;
-  const bool inside = x1 >= 0.0 && x1 <= (double)(W - 1) && y1 >= 0.0 && y1 <= (double)(H - 1);
-  if (!inside) return 0;
-  const double xf = floor(x1), yf = floor(y1);
-  const double ax = x1 - xf, ay = y1 - yf;
-  const int x0 = (int)xf, y0 = (int)yf;                       // in [0, W-1] x [0, H-1]: inside
-  const int xn = x0 + 1 < W ? x0 + 1 : W - 1, yn = y0 + 1 < H ? y0 + 1 : H - 1;
-  const long r0 = (long)y0 * W, r1 = (long)yn * W;
-  const double wx = 1.0 - ax, wy = 1.0 - ay;
   double s[2];
-  for (int c = 0; c < 2; ++c) {
-    const float* p = c ? fy : fx;
-    const double t00 = (double)p[r0 + x0], t10 = (double)p[r0 + xn], t01 = (double)p[r1 + x0], t11 = (double)p[r1 + xn];
-    const double top_l = t00 * wx, top_r = t10 * ax, bot_l = t01 * wx, bot_r = t11 * ax;
-    const double top = top_l + top_r, bot = bot_l + bot_r;
-    const double up = top * wy, dn = bot * ay;
-    s[c] = up + dn;
-  }
+  if (!bilinear_flow(x1, y1, fx, fy, H, W, s)) return 0;
   const double nx = ux + s[0], ny = uy + s[1];
   const bool finite = fabs(nx) <= DBL_MAX && fabs(ny) <= DBL_MAX;
   bool trusted = true;

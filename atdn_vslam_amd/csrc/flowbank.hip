@@ -74,21 +74,10 @@ __global__ __launch_bounds__(256) void flow_gather_kernel(const _Float16* __rest
 
 using namespace atdn;
 
-#define FB_API_BEGIN try {
-#define FB_API_END                                        \
-  return 0;                                               \
-  } catch (const std::exception& e) {                     \
-    set_last_error(e.what());                             \
-    return 1;                                             \
-  } catch (...) {                                         \
-    set_last_error("unknown error");                      \
-    return 1;                                             \
-  }
-
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int atdn_flow_pack_f16(const float* flow_up, int B, int H, int Wsrc, int x0, int W, uint16_t* dst, void* stream) {
-  FB_API_BEGIN
+  ATDN_API_BEGIN
   ATDN_CHECK(flow_up && dst && B >= 1 && H >= 1 && W >= 8, "bad argument");
   ATDN_CHECK(W % 8 == 0, "the bank width must be a multiple of 8");
   ATDN_CHECK(x0 >= 0 && (long)x0 + W <= Wsrc, "column window [x0, x0+W) outside the source rows");
@@ -102,12 +91,12 @@ int atdn_flow_pack_f16(const float* flow_up, int B, int H, int Wsrc, int x0, int
   if (al) hipLaunchKernelGGL((flow_pack_f16_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, flow_up, rows, Wsrc, x0, W, d);
   else hipLaunchKernelGGL((flow_pack_f16_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, flow_up, rows, Wsrc, x0, W, d);
   ATDN_HIP(hipGetLastError());
-  FB_API_END
+  ATDN_API_END
 }
 
 int atdn_flow_gather_clips(const uint16_t* bank, int n_flows, int H, int W, const int* start, const int* reverse, int B, int T,
                            float* out, void* stream) {
-  FB_API_BEGIN
+  ATDN_API_BEGIN
   ATDN_CHECK(bank && start && reverse && out && n_flows >= 1 && H >= 1 && W >= 1 && B >= 1 && T >= 1, "bad argument");
   const long per = 2L * H * W;
   ATDN_CHECK(per % 8 == 0, "H * W must be a multiple of 4 (16-byte frames)");
@@ -136,5 +125,5 @@ int atdn_flow_gather_clips(const uint16_t* bank, int n_flows, int H, int W, cons
                        per, tab, out + f0 * per);
     ATDN_HIP(hipGetLastError());
   }
-  FB_API_END
+  ATDN_API_END
 }

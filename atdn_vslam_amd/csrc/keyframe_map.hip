@@ -200,21 +200,10 @@ static void launch_search(int QB, dim3 grid, hipStream_t st, const float* bank, 
 
 using namespace atdn;
 
-#define KM_API_BEGIN try {
-#define KM_API_END                                        \
-  return 0;                                               \
-  } catch (const std::exception& e) {                     \
-    set_last_error(e.what());                             \
-    return 1;                                             \
-  } catch (...) {                                         \
-    set_last_error("unknown error");                      \
-    return 1;                                             \
-  }
-
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int atdn_map_search(const float* bank, int K, int D, const float* queries, int Q, int topk, float* dist, int* idx, void* stream) {
-  KM_API_BEGIN
+  ATDN_API_BEGIN
   ATDN_CHECK(K >= 1, "the map holds no keyframe");
   ATDN_CHECK(Q >= 1, "no query");
   ATDN_CHECK(D >= 4 && D % 4 == 0, "the embedding length must be a multiple of 4 (16-byte vectors)");
@@ -237,11 +226,11 @@ int atdn_map_search(const float* bank, int K, int D, const float* queries, int Q
   }
   hipLaunchKernelGGL(map_topk_kernel, dim3((unsigned)Q), dim3(TK_THREADS), 0, st, dist, K, topk, idx);
   ATDN_HIP(hipGetLastError());
-  KM_API_END
+  ATDN_API_END
 }
 
 int atdn_map_gather_images_u8(const uint8_t* bank, int K, long plane_bytes, const int* index_host, int n, float* out, void* stream) {
-  KM_API_BEGIN
+  ATDN_API_BEGIN
   ATDN_CHECK(bank && index_host && out, "null pointer");
   ATDN_CHECK(K >= 1 && n >= 1, "bad argument");
   ATDN_CHECK(plane_bytes >= 16 && plane_bytes % 16 == 0, "the image size in bytes must be a multiple of 16");
@@ -263,5 +252,5 @@ int atdn_map_gather_images_u8(const uint8_t* bank, int K, long plane_bytes, cons
                        out + (long)j0 * plane_bytes);
     ATDN_HIP(hipGetLastError());
   }
-  KM_API_END
+  ATDN_API_END
 }

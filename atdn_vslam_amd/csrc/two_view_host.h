@@ -34,11 +34,7 @@
 #include <cfloat>
 #include <cmath>
 
-#if defined(__HIPCC__)
-#define ATDN_TV_HD __host__ __device__
-#else
-#define ATDN_TV_HD
-#endif
+#include "pixel_rule.h"
 
 namespace atdn {
 
@@ -50,7 +46,7 @@ struct TwoViewPose {   // X1 = R X2 + t
   double r[3][3], t[3];
 };
 
-ATDN_TV_HD inline TwoViewPose two_view_load_pose(const float* pose12) {
+ATDN_HD inline TwoViewPose two_view_load_pose(const float* pose12) {
   TwoViewPose P;
   for (int i = 0; i < 3; ++i) {
     for (int j = 0; j < 3; ++j) P.r[i][j] = (double)pose12[4 * i + j];
@@ -62,8 +58,8 @@ ATDN_TV_HD inline TwoViewPose two_view_load_pose(const float* pose12) {
 enum { TV_INSIDE = 1, TV_INLIER = 2, TV_VALID = 4 };
 
 // u, v: the flow at (x, y). Returns the depth (0 = none) and sets `flags` to the TV_* bits of the pixel.
-ATDN_TV_HD inline float two_view_pixel(float u, float v, const TwoViewPose& P, const TwoViewCamera& c, int H, int W, int x, int y,
-                                       int* flags) {
+ATDN_HD inline float two_view_pixel(float u, float v, const TwoViewPose& P, const TwoViewCamera& c, int H, int W, int x, int y,
+                                    int* flags) {
 #pragma clang fp contract(off)
   *flags = 0;
   const double xd = (double)x, yd = (double)y;

@@ -85,21 +85,14 @@ __global__ __launch_bounds__(WS_QPB* WS_SPLIT) void forward_interpolate_kernel(c
 using namespace atdn;
 
 int atdn_flow_forward_interpolate(const float* flow_low, int B, int h, int w, float* out, void* stream) {
-  try {
-    ATDN_CHECK(flow_low && out, "null argument");
-    ATDN_CHECK(B >= 1 && B <= 65535 && h >= 1 && w >= 1, "bad batch or grid size");
-    ATDN_CHECK((long)h * w <= (1L << 24), "grid too large (h * w <= 2^24)");
-    const long n = (long)h * w;
-    ATDN_CHECK(flow_low + (long)B * 2 * n <= out || out + (long)B * 2 * n <= flow_low, "input and output overlap");
-    hipLaunchKernelGGL(forward_interpolate_kernel, dim3((unsigned)cdivl(n, WS_QPB), (unsigned)B), dim3(WS_QPB * WS_SPLIT), 0,
-                       (hipStream_t)stream, flow_low, h, w, out);
-    ATDN_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    set_last_error(e.what());
-    return 1;
-  } catch (...) {
-    set_last_error("unknown error");
-    return 1;
-  }
+  ATDN_API_BEGIN
+  ATDN_CHECK(flow_low && out, "null argument");
+  ATDN_CHECK(B >= 1 && B <= 65535 && h >= 1 && w >= 1, "bad batch or grid size");
+  ATDN_CHECK((long)h * w <= (1L << 24), "grid too large (h * w <= 2^24)");
+  const long n = (long)h * w;
+  ATDN_CHECK(disjoint(flow_low, (long)B * 2 * n * 4, out, (long)B * 2 * n * 4), "input and output overlap");
+  hipLaunchKernelGGL(forward_interpolate_kernel, dim3((unsigned)cdivl(n, WS_QPB), (unsigned)B), dim3(WS_QPB * WS_SPLIT), 0,
+                     (hipStream_t)stream, flow_low, h, w, out);
+  ATDN_HIP(hipGetLastError());
+  ATDN_API_END
 }

@@ -1,6 +1,7 @@
 """Pose algebra of the odometry path (atdn_vslam/utils/transforms.py) and the frame padder
 (whl:GMA/core/utils/utils.py:8-25), host side of libatdn_hip."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -13,6 +14,23 @@ def _np32(x):
         x = x.detach().to("cpu")
         x = x.numpy()
     return np.ascontiguousarray(np.asarray(x, dtype=np.float32))
+
+
+def _stream():
+    """The current stream of the current device, as the library's `void* stream` argument."""
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _byte_plane(t, what, B, H, W):
+    """A mask or liveness tensor (uint8 or bool, B * H * W values whose last two axes are H, W) -> contiguous uint8."""
+    if t.numel() != B * H * W or tuple(t.shape[-2:]) != (H, W):
+        raise RuntimeError("expected %s of %d x %d x %d values, got %s" % (what, B, H, W, tuple(t.shape)))
+    t = (t != 0).to(torch.uint8) if t.dtype != torch.uint8 else t
+    return t.detach().contiguous()
+
+
+def _min_sin2(min_parallax_deg):
+    return math.sin(math.radians(float(min_parallax_deg))) ** 2
 
 
 def transform(rot, tr):
@@ -76,7 +94,7 @@ def forward_interpolate(flow):
     if src.is_cuda:
         with torch.cuda.device(src.device):
             _lib.check(_lib.lib().atdn_flow_forward_interpolate(C.c_void_p(src.data_ptr()), B, h, w, C.c_void_p(out.data_ptr()),
-                                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                                                _stream()))
     else:
         _lib.check(_lib.lib().atdn_flow_forward_interpolate_host(C.c_void_p(src.data_ptr()), B, h, w, C.c_void_p(out.data_ptr())))
     return out
@@ -99,8 +117,7 @@ def _flow_consistency_counts(flow_fw, flow_bw, alpha1, alpha2):
     if fw.is_cuda:
         with torch.cuda.device(fw.device):
             _lib.check(L.atdn_flow_consistency(C.c_void_p(fw.data_ptr()), C.c_void_p(bw.data_ptr()), B, H, W, float(alpha1),
-                                               float(alpha2), C.c_void_p(mask.data_ptr()), C.c_void_p(count.data_ptr()),
-                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                               float(alpha2), C.c_void_p(mask.data_ptr()), C.c_void_p(count.data_ptr()), _stream()))
     else:
         _lib.check(L.atdn_flow_consistency_host(C.c_void_p(fw.data_ptr()), C.c_void_p(bw.data_ptr()), B, H, W, float(alpha1),
                                                 float(alpha2), C.c_void_p(mask.data_ptr()), C.c_void_p(count.data_ptr())))
@@ -151,7 +168,6 @@ def two_view_depth(flow, pose, calib, mask=None, max_epipolar=1.0, min_parallax_
     libatdn_hip's kernel on the current stream and the results stay on the device (no synchronisation); CPU tensors go through the
     library's host form. The rule is float64 and stated in full in include/atdn_hip.h, atdn_flow_two_view_depth; the same inputs
     give the same bits on every call and on both paths."""
-    import math
     from .depth import intrinsics
     if flow.dim() not in (3, 4) or flow.shape[-3] != 2:
         raise RuntimeError("expected a flow [2,H,W] or [B,2,H,W], got %s" % (tuple(flow.shape),))
@@ -162,14 +178,10 @@ def two_view_depth(flow, pose, calib, mask=None, max_epipolar=1.0, min_parallax_
     fx, fy, cx, cy = intrinsics(calib)
     m = None
     if mask is not None:
-        m = torch.as_tensor(mask)
-        if m.numel() != B * H * W or tuple(m.shape[-2:]) != (H, W):
-            raise RuntimeError("expected a mask of %d x %d x %d values, got %s" % (B, H, W, tuple(m.shape)))
+        m = _byte_plane(torch.as_tensor(mask), "a mask", B, H, W)
         if m.device != f.device:
             raise RuntimeError("flow on %s but mask on %s" % (f.device, m.device))
-        m = (m != 0).to(torch.uint8) if m.dtype != torch.uint8 else m
-        m = m.detach().contiguous()
-    min_sin2 = math.sin(math.radians(float(min_parallax_deg))) ** 2
+    min_sin2 = _min_sin2(min_parallax_deg)
     depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=f.device)
     counts = torch.empty((B, 3), dtype=torch.int32, device=f.device)
     L = _lib.lib()
@@ -178,7 +190,7 @@ def two_view_depth(flow, pose, calib, mask=None, max_epipolar=1.0, min_parallax_
             C.c_void_p(counts.data_ptr()))
     if f.is_cuda:
         with torch.cuda.device(f.device):
-            _lib.check(L.atdn_flow_two_view_depth(*args, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            _lib.check(L.atdn_flow_two_view_depth(*args, _stream()))
     else:
         _lib.check(L.atdn_flow_two_view_depth_host(*args))
     return (depth[0], counts[0]) if single else (depth, counts)
@@ -213,7 +225,6 @@ def flow_track_step(flow, acc, alive, pose=None, calib=None, mask=None, depth=No
     and the results stay on the device (no synchronisation); CPU tensors go through the library's host form. The rule is float64
     and stated in full in include/atdn_hip.h, atdn_flow_track_step; the same inputs give the same bits on every call and on
     both paths."""
-    import math
     from .depth import intrinsics
     if flow.dim() not in (3, 4) or flow.shape[-3] != 2:
         raise RuntimeError("expected a flow [2,H,W] or [B,2,H,W], got %s" % (tuple(flow.shape),))
@@ -228,11 +239,7 @@ def flow_track_step(flow, acc, alive, pose=None, calib=None, mask=None, depth=No
         return t
 
     def bytes_of(t, what):
-        t = same_device(torch.as_tensor(t), what)
-        if t.numel() != B * H * W or tuple(t.shape[-2:]) != (H, W):
-            raise RuntimeError("expected %s of %d x %d x %d values, got %s" % (what, B, H, W, tuple(t.shape)))
-        t = (t != 0).to(torch.uint8) if t.dtype != torch.uint8 else t
-        return t.detach().contiguous()
+        return _byte_plane(same_device(torch.as_tensor(t), what), what, B, H, W)
 
     a = same_device(torch.as_tensor(acc), "acc")
     if tuple(a.shape) != ((2, H, W) if single else (B, 2, H, W)):
@@ -250,7 +257,7 @@ def flow_track_step(flow, acc, alive, pose=None, calib=None, mask=None, depth=No
             raise RuntimeError("a pose needs the calibration")
         p = _pose_rows(pose, B, dev)
         fx, fy, cx, cy = intrinsics(calib)
-        min_sin2 = math.sin(math.radians(float(min_parallax_deg))) ** 2
+        min_sin2 = _min_sin2(min_parallax_deg)
         if depth is None:
             d = torch.zeros((B, 1, H, W), dtype=torch.float32, device=dev)
         else:
@@ -278,7 +285,7 @@ def flow_track_step(flow, acc, alive, pose=None, calib=None, mask=None, depth=No
             min_sin2, float(max_depth), ptr(d), ptr(counts))
     if f.is_cuda:
         with torch.cuda.device(dev):
-            _lib.check(L.atdn_flow_track_step(*args, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            _lib.check(L.atdn_flow_track_step(*args, _stream()))
     else:
         _lib.check(L.atdn_flow_track_step_host(*args))
     d_ret = depth if depth is not None else (None if d is None else (d[0] if single else d))
@@ -320,8 +327,7 @@ class InputPadder:
         planes = int(src.numel() // (H * W))
         with torch.cuda.device(src.device):
             _lib.check(_lib.lib().atdn_pad_frames(C.c_void_p(src.data_ptr()), planes, H, W, l, r, t, b,
-                                                  C.c_void_p(out.data_ptr()),
-                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                                  C.c_void_p(out.data_ptr()), _stream()))
         return out
 
     def unpad(self, x):
