@@ -15,6 +15,7 @@
 #include "flow_args.h"
 #include "flow_consistency_host.h"
 #include "flow_track_host.h"
+#include "pnp_host.h"
 #include "two_view_host.h"
 #include "warm_start_host.h"
 
@@ -417,6 +418,31 @@ int atdn_flow_track_step_host(const float* flow, const unsigned char* mask, cons
   const TwoViewCamera cam{fx, fy, cx, cy, max_epipolar, min_sin2, max_depth};
   flow_track_check_args(flow, mask, acc_in, alive_in, B, H, W, acc_out, alive_out, pose, cam, depth, counts);
   flow_track_step_host(flow, mask, acc_in, alive_in, B, H, W, acc_out, alive_out, pose, cam, depth, counts);
+  ATDN_API_END
+}
+
+// ------------------------------------------------------------------ pose from depth and flow (host twins of pnp.hip)
+int atdn_pnp_terms_host(const float* depth, const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W,
+                        double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, double* sums,
+                        int* counts) {
+  ATDN_API_BEGIN
+  const void* out[2] = {sums, counts};
+  const long out_bytes[2] = {(long)B * PNP_TERMS * 8, (long)B * 12};
+  pnp_check_args(depth, flow, mask, pose, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z, false, out, out_bytes, 2);
+  pnp_terms_host(depth, flow, mask, pose, B, H, W, pnp_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, H, W), sums, counts);
+  ATDN_API_END
+}
+
+int atdn_pnp_solve_host(const float* depth, const float* flow, const unsigned char* mask, const float* pose_init, int B, int H,
+                        int W, double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, int iters,
+                        float* pose_out, double* cost, int* counts) {
+  ATDN_API_BEGIN
+  const void* out[3] = {pose_out, cost, counts};
+  const long out_bytes[3] = {(long)B * 48, (long)B * 8, (long)B * 16};
+  pnp_check_args(depth, flow, mask, pose_init, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z, false, out, out_bytes, 3);
+  ATDN_CHECK(iters >= 0 && iters <= 64, "iters must be in [0, 64]");
+  pnp_solve_host(depth, flow, mask, pose_init, B, H, W, pnp_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, H, W), iters,
+                 pose_out, cost, counts);
   ATDN_API_END
 }
 

@@ -116,7 +116,9 @@ void ClvoNet::finalize() {
   in4_.alloc((long)maxB * H * W * 4);
   bufA_.alloc((long)maxB * h1 * w1 * 16);
   bufB_.alloc((long)maxB * h1 * w1 * 16);
-  bufS_.alloc((long)maxB * h1 * w1 * 16 / 4 + 64);
+  // the skip convolution (1x1, stride 2) of the first residual block writes ceil(h1/2) x ceil(w1/2) pixels: more than h1*w1/4 when
+  // h1 or w1 is odd (353 x 1217 -> 177 x 609 -> 89 x 305)
+  bufS_.alloc((long)maxB * conv_out(h1, 1, 2, 0) * conv_out(w1, 1, 2, 0) * 16 + 64);
   flat_.alloc((long)maxB * 832);
   ready_ = true;
 }

@@ -1,4 +1,4 @@
-// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip), shared by each device
+// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip), shared by each device
 // entry point and its host twin in capi.hip.
 #pragma once
 #include <cmath>
@@ -35,5 +35,9 @@ void two_view_check_args(const float* flow, const float* pose, const unsigned ch
 void flow_track_check_args(const float* flow, const unsigned char* mask, const float* acc_in, const unsigned char* alive_in, int B,
                            int H, int W, const float* acc_out, const unsigned char* alive_out, const float* pose,
                            const TwoViewCamera& cam, const float* depth, const int* counts);
+// out[i] of out_bytes[i], i < n_out: the outputs (a workspace among them); none may be null or overlap an input or another output
+void pnp_check_args(const float* depth, const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W,
+                    double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, bool grid_limit,
+                    const void* const* out, const long* out_bytes, int n_out);
 
 }  // namespace atdn

@@ -1,0 +1,265 @@
+// Pose from depth and flow on the device: the reprojection terms of a pose (atdn_pnp_terms) and a Levenberg-Marquardt solve over
+// them (atdn_pnp_solve), batched over problems. The rule — float64, every operation rounded on its own — is pnp_pixel,
+// pnp_lm_update, pnp_lm_step and pnp_output of pnp_host.h, which these kernels call, so the kernels and the host form evaluate
+// one function, and the ORDER of every sum is part of the rule (include/atdn_hip.h): the same bits on every call and on both paths.
+//
+// Two launches per evaluation, nothing else on the stream (no memset, no atomics, no host synchronisation; capturable):
+//   pnp_terms_kernel     (chunks, B) workgroups of pixel_quads.h with off = 0: workgroup c of plane b owns the flat indices
+//                        1024 c .. 1024 c + 1023, a thread four consecutive ones. It streams 13 bytes per pixel (depth, two planes
+//                        of flow, mask), keeps the 28 sums of its pixels in 56 VGPRs, reduces them by the fixed binary tree — wave
+//                        shuffles for the strides 1 .. 32, LDS for (w0 + w1) + (w2 + w3) — and stores them in ITS slot of the
+//                        workspace (store-and-sum: cdna_hip_programming.md, Guideline 12).
+//   pnp_finalise_kernel  one wave per problem: thread e < 28 adds the chunk sums of term e in chunk order (coalesced: the 28
+//                        terms of a chunk are contiguous), threads 32 .. 34 the integer counts; thread 0 then either writes the
+//                        sums out (atdn_pnp_terms) or takes the Levenberg-Marquardt decision and the next step (a 6 x 6 LDL^T,
+//                        fully unrolled, in registers) on the problem's PnpState in the workspace.
+// The pose of evaluation 0 is read from the caller's float32 pose by both kernels; later ones from the state.
+#include "../../include/atdn_hip.h"
+
+#include <cmath>
+#include <cstdint>
+
+#include "flow_args.h"
+#include "pixel_quads.h"
+#include "pnp_host.h"
+
+namespace atdn {
+
+static_assert(PNP_CHUNK == 4 * PQ_THREADS && PNP_CHUNK_THREADS == PQ_THREADS, "a chunk is one workgroup of pixel_quads.h");
+static_assert(sizeof(PnpState) % 8 == 0, "the chunk sums follow the states in the workspace");
+
+constexpr int PNP_FIN_THREADS = 64;
+
+struct PnpWorkspace {
+  PnpState* state;   // [B]
+  double* sums;      // [B, chunks, 28]
+  int* counts;       // [B, chunks, 4] (three used)
+};
+
+inline long pnp_chunks(int H, int W) { return cdivl((long)H * W, PNP_CHUNK); }
+
+inline size_t pnp_workspace_size(int B, int H, int W) {
+  const size_t chunks = (size_t)pnp_chunks(H, W);
+  return (size_t)B * (sizeof(PnpState) + chunks * (PNP_TERMS * sizeof(double) + 4 * sizeof(int)));
+}
+
+inline PnpWorkspace pnp_carve(void* workspace, int B, int H, int W) {
+  const size_t chunks = (size_t)pnp_chunks(H, W);
+  PnpWorkspace ws;
+  ws.state = (PnpState*)workspace;
+  ws.sums = (double*)(ws.state + B);
+  ws.counts = (int*)(ws.sums + (size_t)B * chunks * PNP_TERMS);
+  return ws;
+}
+
+// pose32 != nullptr: the public float32 poses [B,12]; otherwise the trial pose of the problem's state
+template <bool MASKED>
+__global__ __launch_bounds__(PQ_THREADS) void pnp_terms_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
+                                                               const unsigned char* __restrict__ mask,
+                                                               const float* __restrict__ pose32,
+                                                               const PnpState* __restrict__ state, int H, int W, PnpParams cam,
+                                                               double* __restrict__ csums, int* __restrict__ ccounts) {
+#pragma clang fp contract(off)
+  __shared__ double part[PQ_WAVES][PNP_TERMS];
+  __shared__ int ipart[PQ_WAVES][3];
+  const int n = H * W;
+  const int b = blockIdx.y;
+  const float* fu = flow + (long)b * 2 * n;
+  const float* fv = fu + n;
+  const Quad q = quad_of(n, 0);
+  double P[12];
+  if (pose32) {
+    pnp_internal_pose(pose32 + 12 * b, P);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) P[i] = state[b].trial[i];
+  }
+  double acc[PNP_TERMS];
+#pragma unroll
+  for (int e = 0; e < PNP_TERMS; ++e) acc[e] = 0.0;
+  float z[4] = {0.0f, 0.0f, 0.0f, 0.0f}, u[4] = {0.0f, 0.0f, 0.0f, 0.0f}, v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  bool keep[4] = {true, true, true, true};
+  if (q.lo < q.hi) {
+    quad_load(q, depth + (long)b * n, z);
+    quad_load(q, fu, u);
+    quad_load(q, fv, v);
+    if (MASKED) quad_load(q, mask + (long)b * n, keep);
+  }
+  int y = q.lo / W, x = q.lo - y * W;                          // of index lo; the quad may cross the end of a row
+  int cnt[3] = {0, 0, 0};
+  // One pixel at a time (not unrolled: four pixels in flight would take every register of the file and leave one workgroup per
+  // CU); the four values of the quad are picked by selects so that the arrays stay in registers.
+#pragma nounroll
+  for (int k = 0; k < 4; ++k) {
+    const float zk = k == 0 ? z[0] : k == 1 ? z[1] : k == 2 ? z[2] : z[3];
+    const float uk = k == 0 ? u[0] : k == 1 ? u[1] : k == 2 ? u[2] : u[3];
+    const float vk = k == 0 ? v[0] : k == 1 ? v[1] : k == 2 ? v[2] : v[3];
+    const bool kk = k == 0 ? keep[0] : k == 1 ? keep[1] : k == 2 ? keep[2] : keep[3];
+    double t[PNP_TERMS];
+    int flags = 0;
+    if (q.has(k)) {
+      flags = pnp_pixel(zk, uk, vk, kk, P, cam, H, W, x, y, t);
+      if (++x == W) { x = 0; ++y; }
+    } else {
+#pragma unroll
+      for (int e = 0; e < PNP_TERMS; ++e) t[e] = 0.0;
+    }
+#pragma unroll
+    for (int e = 0; e < PNP_TERMS; ++e) acc[e] = k == 0 ? t[e] : acc[e] + t[e];   // ((t0 + t1) + t2) + t3
+#pragma unroll
+    for (int j = 0; j < 3; ++j) cnt[j] += __popcll(__ballot(flags & (1 << j)));   // the wave's count, in every lane
+  }
+  // strides 1 .. 32 inside the wave: lane i (a multiple of 2 * stride) takes v[i] + v[i + stride]; the other lanes hold values
+  // that nobody reads
+#pragma unroll
+  for (int e = 0; e < PNP_TERMS; ++e) {
+#pragma unroll
+    for (int stride = 1; stride < 64; stride *= 2) acc[e] = acc[e] + __shfl_down(acc[e], stride, 64);
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int e = 0; e < PNP_TERMS; ++e) part[wave][e] = acc[e];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) ipart[wave][j] = cnt[j];
+  }
+  __syncthreads();
+  const long slot = (long)b * gridDim.x + blockIdx.x;
+  if (threadIdx.x < PNP_TERMS) {
+    const int e = threadIdx.x;
+    const double lo = part[0][e] + part[1][e], hi = part[2][e] + part[3][e];     // strides 64 and 128
+    csums[slot * PNP_TERMS + e] = lo + hi;
+  } else if (threadIdx.x >= 32 && threadIdx.x < 35) {
+    const int j = threadIdx.x - 32;
+    ccounts[slot * 4 + j] = (ipart[0][j] + ipart[1][j]) + (ipart[2][j] + ipart[3][j]);
+  }
+}
+
+// k < 0: atdn_pnp_terms (the plane sums go to sums_out / counts_out). k >= 0: evaluation k of a solve of `iters` steps.
+__global__ __launch_bounds__(PNP_FIN_THREADS) void pnp_finalise_kernel(const double* __restrict__ csums,
+                                                                        const int* __restrict__ ccounts, int chunks, int k, int iters,
+                                                                        PnpState* __restrict__ state,
+                                                                        const float* __restrict__ pose_init,
+                                                                        double* __restrict__ sums_out, int* __restrict__ counts_out,
+                                                                        float* __restrict__ pose_out, double* __restrict__ cost_out) {
+#pragma clang fp contract(off)
+  __shared__ double S[PNP_TERMS];
+  __shared__ int Cn[3];
+  const int b = blockIdx.x;
+  const int t = threadIdx.x;
+  if (t < PNP_TERMS) {
+    const double* p = csums + (long)b * chunks * PNP_TERMS + t;
+    double s = p[0];
+    int ch = 1;
+    for (; ch + 8 <= chunks; ch += 8) {                        // eight loads in flight, the adds in chunk order
+      double v[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v[i] = p[(long)(ch + i) * PNP_TERMS];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) s = s + v[i];
+    }
+    for (; ch < chunks; ++ch) s = s + p[(long)ch * PNP_TERMS];
+    S[t] = s;
+  } else if (t >= 32 && t < 35) {
+    const int* p = ccounts + (long)b * chunks * 4 + (t - 32);
+    int s = 0;
+    for (int ch = 0; ch < chunks; ++ch) s += p[(long)ch * 4];
+    Cn[t - 32] = s;
+  }
+  __syncthreads();
+  if (k < 0) {
+    if (t < PNP_TERMS) sums_out[(long)b * PNP_TERMS + t] = S[t];
+    if (t < 3) counts_out[3 * b + t] = Cn[t];
+    return;
+  }
+  if (t != 0) return;
+  PnpState& s = state[b];
+  if (k == 0) pnp_internal_pose(pose_init + 12 * b, s.trial);
+  pnp_lm_update(s, S, Cn, k);
+  if (k < iters)
+    pnp_lm_step(s);
+  else
+    pnp_output(s, pose_init + 12 * b, pose_out + 12 * b, cost_out + b, counts_out + 4 * b);
+}
+
+static void pnp_launch_terms(const float* depth, const float* flow, const unsigned char* mask, const float* pose32,
+                             const PnpWorkspace& ws, int B, int H, int W, const PnpParams& cam, hipStream_t stream) {
+  const dim3 grid((unsigned)pnp_chunks(H, W), (unsigned)B);
+  if (mask)
+    hipLaunchKernelGGL(pnp_terms_kernel<true>, grid, dim3(PQ_THREADS), 0, stream, depth, flow, mask, pose32, ws.state, H, W, cam,
+                       ws.sums, ws.counts);
+  else
+    hipLaunchKernelGGL(pnp_terms_kernel<false>, grid, dim3(PQ_THREADS), 0, stream, depth, flow, mask, pose32, ws.state, H, W, cam,
+                       ws.sums, ws.counts);
+  ATDN_HIP(hipGetLastError());
+}
+
+// Argument rules shared by the device entry points below and the host ones (capi.hip). out[i] of out_bytes[i]: the outputs
+// (a workspace among them), none of which may overlap an input or another output.
+void pnp_check_args(const float* depth, const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W,
+                    double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, bool grid_limit,
+                    const void* const* out, const long* out_bytes, int n_out) {
+  ATDN_CHECK(depth && flow && pose, "null argument");
+  for (int i = 0; i < n_out; ++i) ATDN_CHECK(out[i], "null argument");
+  check_plane_batch(B, H, W, grid_limit);
+  check_pinhole(fx, fy, cx, cy);
+  ATDN_CHECK(std::isfinite(scale_px) && scale_px > 0.0, "scale_px must be finite and > 0");
+  ATDN_CHECK(std::isfinite(inlier_px) && inlier_px > 0.0, "inlier_px must be finite and > 0");
+  ATDN_CHECK(std::isfinite(min_z) && min_z > 0.0, "min_z must be finite and > 0");
+  const long n = (long)H * W;
+  const void* in[4] = {depth, flow, mask, pose};
+  const long in_bytes[4] = {(long)B * n * 4, (long)B * 2 * n * 4, (long)B * n, (long)B * 48};
+  for (int i = 0; i < n_out; ++i) {
+    for (int k = 0; k < 4; ++k)
+      if (in[k]) ATDN_CHECK(disjoint(in[k], in_bytes[k], out[i], out_bytes[i]), "an output overlaps an input");
+    for (int j = 0; j < i; ++j) ATDN_CHECK(disjoint(out[j], out_bytes[j], out[i], out_bytes[i]), "two outputs overlap");
+  }
+}
+
+}  // namespace atdn
+
+using namespace atdn;
+
+long atdn_pnp_workspace_bytes(int B, int H, int W) {
+  if (B < 1 || H < 1 || W < 1 || (long)H * W > (1L << 24)) return 0;
+  return (long)pnp_workspace_size(B, H, W);
+}
+
+int atdn_pnp_terms(const float* depth, const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W,
+                   double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, double* sums,
+                   int* counts, void* workspace, void* stream) {
+  ATDN_API_BEGIN
+  check_plane_batch(B, H, W);
+  const void* out[3] = {sums, counts, workspace};
+  const long out_bytes[3] = {(long)B * PNP_TERMS * 8, (long)B * 12, (long)pnp_workspace_size(B, H, W)};
+  pnp_check_args(depth, flow, mask, pose, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z, true, out, out_bytes, 3);
+  ATDN_CHECK(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)sums & 7) == 0, "workspace and sums must be 8-byte aligned");
+  const PnpParams cam = pnp_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, H, W);
+  const PnpWorkspace ws = pnp_carve(workspace, B, H, W);
+  pnp_launch_terms(depth, flow, mask, pose, ws, B, H, W, cam, (hipStream_t)stream);
+  hipLaunchKernelGGL(pnp_finalise_kernel, dim3((unsigned)B), dim3(PNP_FIN_THREADS), 0, (hipStream_t)stream, ws.sums, ws.counts,
+                     (int)pnp_chunks(H, W), -1, 0, ws.state, pose, sums, counts, (float*)nullptr, (double*)nullptr);
+  ATDN_HIP(hipGetLastError());
+  ATDN_API_END
+}
+
+int atdn_pnp_solve(const float* depth, const float* flow, const unsigned char* mask, const float* pose_init, int B, int H, int W,
+                   double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, int iters,
+                   float* pose_out, double* cost, int* counts, void* workspace, void* stream) {
+  ATDN_API_BEGIN
+  check_plane_batch(B, H, W);
+  const void* out[4] = {pose_out, cost, counts, workspace};
+  const long out_bytes[4] = {(long)B * 48, (long)B * 8, (long)B * 16, (long)pnp_workspace_size(B, H, W)};
+  pnp_check_args(depth, flow, mask, pose_init, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z, true, out, out_bytes, 4);
+  ATDN_CHECK(iters >= 0 && iters <= 64, "iters must be in [0, 64]");
+  ATDN_CHECK(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)cost & 7) == 0, "workspace and cost must be 8-byte aligned");
+  const PnpParams cam = pnp_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, H, W);
+  const PnpWorkspace ws = pnp_carve(workspace, B, H, W);
+  for (int k = 0; k <= iters; ++k) {
+    pnp_launch_terms(depth, flow, mask, k == 0 ? pose_init : nullptr, ws, B, H, W, cam, (hipStream_t)stream);
+    hipLaunchKernelGGL(pnp_finalise_kernel, dim3((unsigned)B), dim3(PNP_FIN_THREADS), 0, (hipStream_t)stream, ws.sums, ws.counts,
+                       (int)pnp_chunks(H, W), k, iters, ws.state, pose_init, (double*)nullptr, counts, pose_out, cost);
+    ATDN_HIP(hipGetLastError());
+  }
+  ATDN_API_END
+}

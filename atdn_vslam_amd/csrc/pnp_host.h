@@ -1,0 +1,343 @@
+// Pose from depth and flow (robust PnP), the rule in plain C++ float64 (no HIP needed). A depth map of image 1 gives a 3-D point
+// per pixel, the flow image 1 -> image 2 gives that point's pixel in image 2: pnp_pixel is the contribution of one pixel to the
+// Gauss-Newton normal equations of the reprojection error under the Geman-McClure loss, pnp_plane_host the fixed-order sum of
+// a plane (chunks of 1024 pixels), pnp_lm_update / pnp_lm_step one Levenberg-Marquardt decision and step, pnp_terms_host /
+// pnp_solve_host the host forms behind atdn_pnp_terms_host / atdn_pnp_solve_host (capi.hip), which serve CPU tensors. The
+// kernels of pnp.hip call the same functions, so the two cannot drift apart; the independent statement the tests compare both
+// with is tests/pnp_ref.py (NumPy). The rule is stated in full in include/atdn_hip.h, atdn_pnp_terms and atdn_pnp_solve; only
+// + - * / and comparisons, every operation rounded on its own (fp contraction off).
+#pragma once
+#include <cfloat>
+#include <cmath>
+#include <vector>
+
+#include "pixel_rule.h"
+
+namespace atdn {
+
+constexpr int PNP_TERMS = 28;          // 21 upper-triangle Hessian entries (row-major), 6 gradient entries, the cost
+constexpr int PNP_CHUNK = 1024;        // flat indices per chunk: 256 threads x 4
+constexpr int PNP_CHUNK_THREADS = 256;
+enum { PNP_CAND = 1, PNP_USED = 2, PNP_INLIER = 4 };
+
+struct PnpParams {
+  double fx, fy, cx, cy;
+  double c2;           // scale_px * scale_px
+  double thr;          // inlier_px * inlier_px
+  double min_z;
+  double rho_behind;   // the cost of a candidate behind the camera: rho at e2 = (H + W)^2
+};
+
+inline PnpParams pnp_params(double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, int H,
+                            int W) {
+#pragma clang fp contract(off)
+  PnpParams p{fx, fy, cx, cy, scale_px * scale_px, inlier_px * inlier_px, min_z, 0.0};
+  const double eb = (double)(H + W);
+  const double e2 = eb * eb;
+  const double q = e2 / p.c2;
+  const double s = 1.0 + q;
+  const double h = 0.5 * e2;
+  p.rho_behind = h / s;
+  return p;
+}
+
+// The solver's state of one problem. Poses are INTERNAL: p[0..8] = Rc (row-major), p[9..11] = tc, X2 = Rc X1 + tc.
+struct PnpState {
+  double acc[12];            // the accepted pose
+  double trial[12];          // the pose of the next (or the current) evaluation
+  double sums[PNP_TERMS];    // H, g and cost at the accepted pose
+  double lambda;
+  int counts[3];             // (candidates, used, inliers) at the accepted pose
+  int accepted;              // number of accepted steps
+};
+
+// public pose (12 float32, rows of [R|t], X1 = R X2 + t) -> internal pose
+ATDN_HD inline void pnp_internal_pose(const float* pose12, double p[12]) {
+#pragma clang fp contract(off)
+  double r[3][3], t[3];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) r[i][j] = (double)pose12[4 * i + j];
+    t[i] = (double)pose12[4 * i + 3];
+  }
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) p[3 * i + j] = r[j][i];
+    const double a = r[0][i] * t[0], b = r[1][i] * t[1], c = r[2][i] * t[2];
+    const double ab = a + b;
+    const double s = ab + c;
+    p[9 + i] = -s;
+  }
+}
+
+// internal pose -> public pose, rounded to float32
+ATDN_HD inline void pnp_public_pose(const double p[12], float* pose12) {
+#pragma clang fp contract(off)
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) pose12[4 * i + j] = (float)p[3 * j + i];
+    const double a = p[i] * p[9], b = p[3 + i] * p[10], c = p[6 + i] * p[11];
+    const double ab = a + b;
+    const double s = ab + c;
+    pose12[4 * i + 3] = (float)(-s);
+  }
+}
+
+// The 28 terms of pixel (x, y): z its depth, (u, v) its flow, keep its mask. Returns the PNP_* bits; t is always written
+// (+0.0 where the pixel contributes nothing).
+ATDN_HD inline int pnp_pixel(float zf, float u, float v, bool keep, const double* P, const PnpParams& c, int H, int W, int x,
+                             int y, double t[PNP_TERMS]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < PNP_TERMS; ++i) t[i] = 0.0;
+  const double xd = (double)x, yd = (double)y, z = (double)zf;
+  const double x2 = xd + (double)u, y2 = yd + (double)v;
+  const bool inside = x2 >= 0.0 && x2 <= (double)(W - 1) && y2 >= 0.0 && y2 <= (double)(H - 1);
+  const bool cand = keep && z > 0.0 && z <= (double)FLT_MAX && inside;
+  if (!cand) return 0;
+  const double dx = xd - c.cx, dy = yd - c.cy;
+  const double zx = z * dx, zy = z * dy;
+  const double X1 = zx / c.fx, Y1 = zy / c.fy;
+  double Xc[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double a = P[3 * i] * X1, b = P[3 * i + 1] * Y1, d = P[3 * i + 2] * z;
+    const double ab = a + b;
+    const double abd = ab + d;
+    Xc[i] = abd + P[9 + i];
+  }
+  const double X = Xc[0], Y = Xc[1], Z = Xc[2];
+  if (!(Z >= c.min_z)) {
+    t[27] = c.rho_behind;
+    return PNP_CAND;
+  }
+  const double iz = 1.0 / Z;
+  const double fX = c.fx * X, fY = c.fy * Y;
+  const double px = fX * iz, py = fY * iz;
+  const double pxc = px + c.cx, pyc = py + c.cy;
+  const double rx = pxc - x2, ry = pyc - y2;
+  const double rxx = rx * rx, ryy = ry * ry;
+  const double e2 = rxx + ryy;
+  const double q = e2 / c.c2;
+  const double s = 1.0 + q;
+  const double ss = s * s;
+  const double w = 1.0 / ss;
+  const double he = 0.5 * e2;
+  const double rho = he / s;
+  const double a = c.fx * iz, k = c.fy * iz;
+  const double pxiz = px * iz, pyiz = py * iz;
+  const double b = -pxiz, d = -pyiz;
+  const double aZ = a * Z, bX = b * X, aY = a * Y, dY = d * Y, kZ = k * Z, dX = d * X;
+  const double Jx[6] = {b * Y, aZ - bX, -aY, a, 0.0, b};
+  const double Jy[6] = {dY - kZ, -dX, k * X, 0.0, k, d};
+  int n = 0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    const double wx = w * Jx[i], wy = w * Jy[i];
+#pragma unroll
+    for (int j = i; j < 6; ++j) {
+      const double hx = wx * Jx[j], hy = wy * Jy[j];
+      t[n++] = hx + hy;
+    }
+    const double gx = wx * rx, gy = wy * ry;
+    t[21 + i] = gx + gy;
+  }
+  t[27] = rho;
+  return PNP_CAND | PNP_USED | (e2 <= c.thr ? PNP_INLIER : 0);
+}
+
+// After evaluation k (k = 0: the initial pose) with the plane sums `sums` and counts `counts` at s.trial: accept or reject.
+ATDN_HD inline void pnp_lm_update(PnpState& s, const double* sums, const int* counts, int k) {
+#pragma clang fp contract(off)
+  const bool accept = k == 0 || sums[27] < s.sums[27];
+  if (accept) {
+    for (int i = 0; i < 12; ++i) s.acc[i] = s.trial[i];
+    for (int i = 0; i < PNP_TERMS; ++i) s.sums[i] = sums[i];
+    for (int i = 0; i < 3; ++i) s.counts[i] = counts[i];
+  }
+  if (k == 0) {
+    s.lambda = 1e-3;
+    s.accepted = 0;
+  } else if (accept) {
+    const double l = s.lambda / 3.0;
+    s.lambda = l > 1e-9 ? l : 1e-9;
+    s.accepted += 1;
+  } else {
+    const double l = 4.0 * s.lambda;
+    s.lambda = l < 1e6 ? l : 1e6;
+  }
+}
+
+// The damped step from the accepted point: s.trial = retract(s.acc, delta), or s.acc again where the factorisation fails.
+ATDN_HD inline void pnp_lm_step(PnpState& s) {
+#pragma clang fp contract(off)
+  double A[6][6], L[6][6], D[6], dl[6];
+  int n = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) {
+      A[i][j] = s.sums[n];
+      A[j][i] = s.sums[n];
+      ++n;
+    }
+  for (int i = 0; i < 6; ++i) {
+    const double l = s.lambda * A[i][i];
+    A[i][i] = A[i][i] + l;
+  }
+  // no early exit: after a failed pivot the remaining values are garbage that is computed and never used
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double dj = A[j][j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) {
+      const double ld = L[j][k] * D[k];
+      const double lld = L[j][k] * ld;
+      dj = dj - lld;
+    }
+    ok = ok && dj > 0.0;
+    D[j] = dj;
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double l = A[i][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) {
+        const double ld = L[j][k] * D[k];
+        const double lld = L[i][k] * ld;
+        l = l - lld;
+      }
+      L[i][j] = l / dj;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double y = -s.sums[21 + i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) {
+      const double ly = L[i][k] * dl[k];
+      y = y - ly;
+    }
+    dl[i] = y;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) dl[i] = dl[i] / D[i];
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    double y = dl[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; ++k) {
+      const double ly = L[k][i] * dl[k];
+      y = y - ly;
+    }
+    dl[i] = y;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) ok = ok && dl[i] >= -DBL_MAX && dl[i] <= DBL_MAX;
+  if (!ok) {
+    for (int i = 0; i < 12; ++i) s.trial[i] = s.acc[i];
+    return;
+  }
+  const double h[3] = {0.5 * dl[0], 0.5 * dl[1], 0.5 * dl[2]};
+  const double h00 = h[0] * h[0], h11 = h[1] * h[1], h22 = h[2] * h[2];
+  const double h01 = h00 + h11;
+  const double n2 = h01 + h22;
+  const double den = 1.0 + n2;
+  const double f = 2.0 / den;
+  const double K[3][3] = {{0.0, -h[2], h[1]}, {h[2], 0.0, -h[0]}, {-h[1], h[0], 0.0}};
+  double E[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double hh = h[i] * h[j];
+      const double m = i == j ? hh - n2 : K[i][j] + hh;
+      const double fm = f * m;
+      E[i][j] = i == j ? 1.0 + fm : fm;
+    }
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) {
+      const double a = E[i][0] * s.acc[j], b = E[i][1] * s.acc[3 + j], c = E[i][2] * s.acc[6 + j];
+      const double ab = a + b;
+      s.trial[3 * i + j] = ab + c;
+    }
+    const double a = E[i][0] * s.acc[9], b = E[i][1] * s.acc[10], c = E[i][2] * s.acc[11];
+    const double ab = a + b;
+    const double abc = ab + c;
+    s.trial[9 + i] = abc + dl[3 + i];
+  }
+}
+
+// The outputs of a finished solve.
+ATDN_HD inline void pnp_output(const PnpState& s, const float* pose_in, float* pose_out, double* cost, int* counts4) {
+  if (s.accepted == 0) {
+    for (int i = 0; i < 12; ++i) pose_out[i] = pose_in[i];
+  } else {
+    pnp_public_pose(s.acc, pose_out);
+  }
+  *cost = s.sums[27];
+  for (int i = 0; i < 3; ++i) counts4[i] = s.counts[i];
+  counts4[3] = s.accepted;
+}
+
+// The sums of one plane at the internal pose P: chunks of 1024 flat indices; inside a chunk, thread j owns the indices
+// 4j .. 4j + 3 and sums them as ((t0 + t1) + t2) + t3, the 256 thread values go through the binary tree of strides 1 .. 128
+// (v[i] += v[i + stride] for i a multiple of 2 * stride); the chunk sums are added in chunk order.
+inline void pnp_plane_host(const float* depth, const float* fu, const float* fv, const unsigned char* mask, const double* P,
+                           const PnpParams& c, int H, int W, double sums[PNP_TERMS], int counts[3]) {
+#pragma clang fp contract(off)
+  const long n = (long)H * W;
+  const long chunks = (n + PNP_CHUNK - 1) / PNP_CHUNK;
+  std::vector<double> v((size_t)PNP_CHUNK_THREADS * PNP_TERMS);
+  double t[PNP_TERMS];
+  counts[0] = counts[1] = counts[2] = 0;
+  for (long ch = 0; ch < chunks; ++ch) {
+    for (int j = 0; j < PNP_CHUNK_THREADS; ++j) {
+      double* a = &v[(size_t)j * PNP_TERMS];
+      for (int k = 0; k < 4; ++k) {
+        const long i = ch * PNP_CHUNK + 4 * j + k;
+        int flags = 0;
+        if (i < n) {
+          const int y = (int)(i / W), x = (int)(i - (long)y * W);
+          flags = pnp_pixel(depth[i], fu[i], fv[i], mask ? mask[i] != 0 : true, P, c, H, W, x, y, t);
+        } else {
+          for (int e = 0; e < PNP_TERMS; ++e) t[e] = 0.0;
+        }
+        for (int e = 0; e < PNP_TERMS; ++e) a[e] = k == 0 ? t[e] : a[e] + t[e];
+        counts[0] += (flags & PNP_CAND) ? 1 : 0;
+        counts[1] += (flags & PNP_USED) ? 1 : 0;
+        counts[2] += (flags & PNP_INLIER) ? 1 : 0;
+      }
+    }
+    for (int stride = 1; stride < PNP_CHUNK_THREADS; stride *= 2)
+      for (int i = 0; i < PNP_CHUNK_THREADS; i += 2 * stride)
+        for (int e = 0; e < PNP_TERMS; ++e) v[(size_t)i * PNP_TERMS + e] = v[(size_t)i * PNP_TERMS + e] + v[(size_t)(i + stride) * PNP_TERMS + e];
+    for (int e = 0; e < PNP_TERMS; ++e) sums[e] = ch == 0 ? v[e] : sums[e] + v[e];
+  }
+}
+
+// depth [B,H,W], flow [B,2,H,W], mask [B,H,W] uint8 or null, pose [B,12] -> sums [B,28], counts [B,3]
+inline void pnp_terms_host(const float* depth, const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W,
+                           const PnpParams& c, double* sums, int* counts) {
+  const long n = (long)H * W;
+  for (int b = 0; b < B; ++b) {
+    double P[12];
+    pnp_internal_pose(pose + 12L * b, P);
+    pnp_plane_host(depth + b * n, flow + 2 * b * n, flow + (2 * b + 1) * n, mask ? mask + b * n : nullptr, P, c, H, W,
+                   sums + (long)PNP_TERMS * b, counts + 3L * b);
+  }
+}
+
+// iters Levenberg-Marquardt steps (iters + 1 evaluations) from pose_init -> pose_out [B,12], cost [B], counts [B,4]
+inline void pnp_solve_host(const float* depth, const float* flow, const unsigned char* mask, const float* pose_init, int B, int H,
+                           int W, const PnpParams& c, int iters, float* pose_out, double* cost, int* counts) {
+  const long n = (long)H * W;
+  for (int b = 0; b < B; ++b) {
+    PnpState s;
+    pnp_internal_pose(pose_init + 12L * b, s.trial);
+    for (int k = 0; k <= iters; ++k) {
+      double sums[PNP_TERMS];
+      int cnt[3];
+      pnp_plane_host(depth + b * n, flow + 2 * b * n, flow + (2 * b + 1) * n, mask ? mask + b * n : nullptr, s.trial, c, H, W,
+                     sums, cnt);
+      pnp_lm_update(s, sums, cnt, k);
+      if (k < iters) pnp_lm_step(s);
+    }
+    pnp_output(s, pose_init + 12L * b, pose_out + 12L * b, cost + b, counts + 4L * b);
+  }
+}
+
+}  // namespace atdn

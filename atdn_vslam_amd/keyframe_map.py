@@ -13,7 +13,10 @@ embedding, and answers a relocalisation query with a loop of `torch.norm(kf.embe
 * `search` is `atdn_map_search`: every distance of every query in one pass over the bank, and the top_k nearest keyframes
   per query;
 * `relocalize` answers a batch of queries: one encoder call, one search, one image gather, the flow network and the pose
-  head at batch Q.
+  head at batch Q;
+* the depth bank is one fp32 device buffer [capacity,H,W] (allocated by the first `set_depth`; zeros = no depth): with
+  `relocalize(geometric=True)` the keyframe's depth and the keyframe -> query flow give a second, geometric pose
+  (`transforms.pose_from_depth`) next to the pose head's.
 
 Poses live on the host ([K,4,4] float32), as in the reference.
 """
@@ -114,6 +117,7 @@ class KeyframeMap:
         self.D = self.embedding_hw[0] * self.embedding_hw[1] * 128
         self.image_bank = torch.empty((self.capacity, 3) + self.hw, dtype=torch.uint8, device=self.device)
         self.embedding_bank = None          # [capacity, D] fp32, allocated by the first embed()
+        self.depth_bank = None              # [capacity, H, W] fp32, allocated by the first set_depth(); zeros = no depth
         self._poses = torch.zeros((self.capacity, 4, 4), dtype=torch.float32)
         self.n = 0
         self.n_embedded = 0
@@ -137,6 +141,10 @@ class KeyframeMap:
             emb = torch.empty((cap, self.D), dtype=torch.float32, device=self.device)
             emb[:self.n_embedded].copy_(self.embedding_bank[:self.n_embedded])
             self.embedding_bank = emb
+        if self.depth_bank is not None:
+            depth = torch.zeros((cap,) + self.hw, dtype=torch.float32, device=self.device)
+            depth[:self.n].copy_(self.depth_bank[:self.n])
+            self.depth_bank = depth
         poses = torch.zeros((cap, 4, 4), dtype=torch.float32)
         poses[:self.n] = self._poses[:self.n]
         self._poses = poses
@@ -160,10 +168,33 @@ class KeyframeMap:
         self.n += 1
         return self.n - 1
 
+    def set_depth(self, k, depth):
+        """Give keyframe k its depth map: [H,W] or [1,H,W] float32 in the map's own scale, 0 = no depth (what
+        `transforms.two_view_depth` and `depth.FlowTrack` produce), on any device; it replaces an earlier one. The bank is
+        allocated, as zeros, by the first call; a keyframe that never got a depth holds zeros."""
+        if not 0 <= int(k) < self.n:
+            raise IndexError("keyframe %d of %d" % (k, self.n))
+        d = torch.as_tensor(depth)
+        d = d[0] if d.dim() == 3 and d.shape[0] == 1 else d
+        if tuple(d.shape) != self.hw:
+            raise ValueError("keyframe depth must be [%d,%d] or [1,%d,%d], got %s" % (self.hw + self.hw + (tuple(depth.shape),)))
+        if self.depth_bank is None:
+            self.depth_bank = torch.zeros((self.capacity,) + self.hw, dtype=torch.float32, device=self.device)
+        self.depth_bank[int(k)].copy_(d.detach().to(self.device, torch.float32))
+
+    def depths(self, indices):
+        """fp32 [n,H,W] on the device: the depth maps of the keyframes `indices` (a host sequence), zeros where there is none."""
+        ix = [int(i) for i in indices]
+        if any(not 0 <= i < self.n for i in ix):
+            raise IndexError("keyframe index outside [0, %d)" % self.n)
+        if self.depth_bank is None:
+            return torch.zeros((len(ix),) + self.hw, dtype=torch.float32, device=self.device)
+        return self.depth_bank.index_select(0, torch.tensor(ix, dtype=torch.int64).to(self.device, non_blocking=True))
+
     @classmethod
     def from_directory(cls, keyframes_path, device, mapping_net=None):
         """The map of a keyframe directory as the reference and slam.NeuralSLAM write it: `rgb/*.pth` (sorted; uint8
-        [3,H,W]) and `poses.pth` ([K,12]). Every file is read once; the directory is validated (poses.pth present, as many
+        [3,H,W]), `poses.pth` ([K,12]) and, where a keyframe has one, `depth/<the frame's name>` (float32 [1,H,W]). Every file is read once; the directory is validated (poses.pth present, as many
         poses as frames, all frames of the first one's size) before anything touches the device.
         With `mapping_net` the keyframes are embedded too."""
         poses_file = os.path.join(keyframes_path, "poses.pth")
@@ -190,6 +221,10 @@ class KeyframeMap:
         m = cls(device, hw=hw, capacity=len(files))
         for im, pose in zip(frames, poses):
             m.append(im, pose)
+        for k, f in enumerate(files):
+            depth_file = os.path.join(keyframes_path, "depth", os.path.basename(f))
+            if os.path.exists(depth_file):
+                m.set_depth(k, torch.load(depth_file, map_location="cpu"))
         if mapping_net is not None:
             m.embed(mapping_net)
         return m
@@ -253,7 +288,8 @@ class KeyframeMap:
         return search_bank(self.embedding_bank[:self.n], self.rows(queries_mu), top_k)
 
     @torch.no_grad()
-    def relocalize(self, images, flow_net, odometry_net, mapping_net, top_k=1, refine=True, verify=False):
+    def relocalize(self, images, flow_net, odometry_net, mapping_net, top_k=1, refine=True, verify=False, geometric=False,
+                   calib=None):
         """Answer Q relocalisation queries at once (neural_slam.py:355-399 for a batch). images [Q,3,H,W] (or [3,H,W]),
         values 0..255. Returns host tensors `distances` [Q,K], `indices` [Q,top_k] (int64), `initial` [Q,4,4] (the pose of
         the nearest keyframe) and `refined` [Q,4,4] (= initial @ the odometry step from that keyframe's image to the query;
@@ -276,9 +312,21 @@ class KeyframeMap:
         with the largest integer count of such pixels, ties to the lower rank; `initial` and `refined` are those of the chosen
         candidate. With top_k = 1 the poses are those of verify=False (the flows come from batches of another composition:
         equal within rounding, not bit for bit) and `scores` is the confidence. With verify=False the code path, the 4-tuple
-        and its bits are unchanged."""
+        and its bits are unchanged.
+
+        `geometric=True` (needs `refine` and `calib`, the calibration of the map's grid; ValueError otherwise) adds a pose from
+        geometry: for every refined pair, `transforms.pose_from_depth` on the keyframe's depth (`set_depth`; zeros where it
+        has none) and the forward flow, started at the pose head's relative pose, with the consistency mask as its mask when
+        `verify` is on; all pairs of a flow chunk in one batch, nothing synchronises until the results are fetched. Two items
+        are appended to the tuple: `refined_geo` [Q,4,4] = initial @ that pose and `geo_counts` [Q,4] int32 = (candidates,
+        used, inliers, accepted steps), both of the chosen candidate with `verify`. A keyframe without depth gives
+        refined_geo == refined and zero counts. With geometric=False the code paths, the tuples and their bits are unchanged."""
         if verify and not refine:
             raise ValueError("verify=True scores the flows of the refinement: it needs refine=True")
+        if geometric and not refine:
+            raise ValueError("geometric=True solves for the pose of the refinement's flow: it needs refine=True")
+        if geometric and calib is None:
+            raise ValueError("geometric=True needs the calibration of the map's grid: pass calib=")
         q = images.to(self.device)
         if q.dim() == 3:
             q = q.unsqueeze(0)
@@ -291,38 +339,65 @@ class KeyframeMap:
             dist, idx = self.search(mu, top_k)
             indices = idx.cpu().long()
             if verify:
-                return self._relocalize_verified(q, dist, indices, flow_net, odometry_net)
+                return self._relocalize_verified(q, dist, indices, flow_net, odometry_net, calib if geometric else None)
             best = indices[:, 0]
             initial = self.poses[best].clone()
             if not refine:
                 return dist.cpu(), indices, initial, initial.clone()
             keyframes = self.images(best)
             chunk = max(1, min(int(getattr(flow_net, "max_batch", 1)), 16))
-            feats = []
+            feats, flows = [], []
             for a in range(0, Q, chunk):
                 _, flow = flow_net(keyframes[a:a + chunk], q[a:a + chunk], iters=12, test_mode=True)
                 feats.append(odometry_net.encode(flow))
+                if geometric:
+                    flows.append(flow)
             rot, tr, _ = odometry_net.scan(torch.cat(feats, dim=0)[None], state=None, hw=self.hw)
             rot, tr = rot[0].cpu(), tr[0].cpu()
+            if geometric:
+                geo, geo_counts = self._geometric(best.tolist(), flows, None, rot, tr, calib)
         refined = torch.stack([initial[i] @ transforms.transform(rot[i], tr[i]) for i in range(Q)], dim=0)
+        if geometric:
+            return dist.cpu(), indices, initial, refined, torch.stack([initial[i] @ geo[i] for i in range(Q)], dim=0), geo_counts
         return dist.cpu(), indices, initial, refined
 
-    def _relocalize_verified(self, q, dist, indices, flow_net, odometry_net):
+    def _geometric(self, keyframe_indices, flows, masks, rot, tr, calib):
+        """The geometric leg of `relocalize`: `flows` (and `masks`, or None) are the forward flows (consistency masks) of the
+        pairs, chunk by chunk, `keyframe_indices` the keyframe of every pair, `rot` / `tr` the pose head's answers on the host.
+        Returns host tensors: the PnP poses [P,4,4] and counts [P,4]."""
+        head = torch.stack([transforms.transform(rot[p], tr[p]) for p in range(len(keyframe_indices))], dim=0)
+        poses, counts, a = [], [], 0
+        for c, flow in enumerate(flows):
+            b = int(flow.shape[0])
+            pose, _, cnt = transforms.pose_from_depth(self.depths(keyframe_indices[a:a + b]), flow, head[a:a + b], calib,
+                                                      mask=None if masks is None else masks[c])
+            poses.append(pose)
+            counts.append(cnt)
+            a += b
+        return torch.cat(poses).cpu(), torch.cat(counts).cpu()
+
+    def _relocalize_verified(self, q, dist, indices, flow_net, odometry_net, calib=None):
         """The verify=True half of `relocalize` (called under its device and no_grad): q [Q,3,H,W] fp32 on the device, `dist`
-        the device distances, `indices` [Q,top_k] int64 on the host."""
+        the device distances, `indices` [Q,top_k] int64 on the host; `calib` not None: with the geometric leg."""
         Q, top_k = int(indices.shape[0]), int(indices.shape[1])
         n = self.hw[0] * self.hw[1]
         flat = indices.reshape(-1)                                   # pair p = q * top_k + r
         keyframes = self.images(flat)
         queries = q.repeat_interleave(top_k, dim=0) if top_k > 1 else q
         chunk = max(1, int(getattr(flow_net, "max_batch", 1)) // 2)     # 2 * chunk images per flow call
-        feats, counts = [], []
+        feats, counts, flows, masks = [], [], [], []
         for a in range(0, Q * top_k, chunk):
             fw, bw = flow_net.forward_backward(keyframes[a:a + chunk], queries[a:a + chunk], iters=12)
-            counts.append(transforms._flow_consistency_counts(fw, bw, 0.01, 0.5)[1])
+            mask, count = transforms._flow_consistency_counts(fw, bw, 0.01, 0.5)
+            counts.append(count)
             feats.append(odometry_net.encode(fw))
+            if calib is not None:
+                flows.append(fw)
+                masks.append(mask)
         rot, tr, _ = odometry_net.scan(torch.cat(feats, dim=0)[None], state=None, hw=self.hw)
         rot, tr = rot[0].cpu(), tr[0].cpu()
+        if calib is not None:
+            geo, geo_counts = self._geometric(flat.tolist(), flows, masks, rot, tr, calib)
         counts = torch.cat(counts).cpu().long().view(Q, top_k)
         scores = (counts.double() / float(n)).float()
         chosen = torch.tensor([row.index(max(row)) for row in counts.tolist()], dtype=torch.int64)   # ties: the lower rank
@@ -330,4 +405,7 @@ class KeyframeMap:
         initial = self.poses[indices[rows, chosen]].clone()
         pick = (rows * top_k + chosen).tolist()
         refined = torch.stack([initial[i] @ transforms.transform(rot[p], tr[p]) for i, p in enumerate(pick)], dim=0)
+        if calib is not None:
+            refined_geo = torch.stack([initial[i] @ geo[p] for i, p in enumerate(pick)], dim=0)
+            return dist.cpu(), indices, initial, refined, scores, chosen, refined_geo, geo_counts[pick]
         return dist.cpu(), indices, initial, refined, scores, chosen

@@ -215,6 +215,8 @@ class NeuralSLAM:
                     # the previous frame is a keyframe: this pair's flow starts at its pixels, so the depth is the keyframe's
                     depth, _ = transforms.two_view_depth(flow, pred_mat[None].to(self._device), self._calib)
                     torch.save(depth[0].to("cpu"), os.path.join(self._base, "depth", "%06d.pth" % self._depth_pending))
+                    if self._map is not None:
+                        self._map.set_depth(self._depth_pending, depth[0])
                     self._depth_pending = None
                 if self._policy(pred_mat):
                     name = os.path.join(self._base, "rgb", "%06d.pth" % len(self._keyframes))
@@ -296,6 +298,8 @@ class NeuralSLAM:
         """Write the depth of the keyframe the track is anchored at, if any pair has extended it."""
         if self._track_index is not None and self._track.steps > 0:
             torch.save(self._track.depth[0].to("cpu"), os.path.join(self._base, "depth", "%06d.pth" % self._track_index))
+            if self._map is not None:
+                self._map.set_depth(self._track_index, self._track.depth[0])
         self._track_index = None
 
     def _set_mapping_net(self, weights):
@@ -351,7 +355,7 @@ class NeuralSLAM:
         return self._batch_flow_net
 
     @torch.no_grad()
-    def relocalize_batch(self, images, top_k=1, refine=True, verify=False):
+    def relocalize_batch(self, images, top_k=1, refine=True, verify=False, geometric=False):
         """Several relocalisation queries per call (resident map only): `KeyframeMap.relocalize` with this object's
         networks. images [Q,3,376,1232] (or a list of [3,376,1232] frames). Returns host tensors `distances` [Q,K],
         `indices` [Q,top_k] (nearest first), `initial` [Q,4,4], `refined` [Q,4,4]. Every query is refined from the reset
@@ -361,7 +365,11 @@ class NeuralSLAM:
         `verify=True` (needs `refine`): every one of the Q * top_k candidates is refined and scored by the forward-backward
         consistency of its two flows; returns `(distances, indices, initial, refined, scores, chosen)` with `scores`
         [Q,top_k] (near 0: the keyframe and the query do not show the same place), `chosen` [Q] the rank with the most
-        consistent pixels, and `initial` / `refined` those of the chosen candidate (`KeyframeMap.relocalize`)."""
+        consistent pixels, and `initial` / `refined` those of the chosen candidate (`KeyframeMap.relocalize`).
+        `geometric=True` (needs `refine` and a `calib` at construction) appends `refined_geo` [Q,4,4] and `geo_counts` [Q,4]:
+        the pose that the keyframe's depth map and the keyframe -> query flow determine (`transforms.pose_from_depth`, started
+        at the pose head's answer, masked by the consistency mask with `verify`), as initial @ pose, and its (candidates,
+        used, inliers, accepted steps). A keyframe without a depth gives refined_geo == refined and zero counts."""
         if getattr(self, "_map", None) is None:
             raise RuntimeError("relocalize_batch needs the keyframe map in device memory: construct "
                                "NeuralSLAM(..., resident_map=True)")
@@ -369,8 +377,10 @@ class NeuralSLAM:
             raise Exception("SLAM called in invalid state!")
         if isinstance(images, (list, tuple)):
             images = torch.stack([torch.as_tensor(im) for im in images], dim=0)
+        if geometric and self._calib is None:
+            raise ValueError("geometric=True needs the calibration: construct NeuralSLAM(..., calib=...)")
         return self._map.relocalize(images, self._flow_for_batches(), self._odometry_net, self._mapping_net, top_k=top_k,
-                                    refine=refine, verify=verify)
+                                    refine=refine, verify=verify, geometric=geometric, calib=self._calib if geometric else None)
 
     def _relocalize(self, image):
         mu = self._mapping_net(image)[0]

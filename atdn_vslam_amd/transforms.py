@@ -205,6 +205,99 @@ def epipolar_score(counts):
     return torch.where(inside > 0, inliers / inside.clamp(min=1.0), torch.zeros_like(inside)).float()
 
 
+def _pnp_inputs(depth, flow, pose, calib, mask, scale_px, inlier_px, min_z):
+    """The checked, contiguous inputs of `reprojection_terms` and `pose_from_depth`, with the batch axis added to 3-d forms."""
+    from .depth import intrinsics
+    if flow.dim() not in (3, 4) or flow.shape[-3] != 2:
+        raise RuntimeError("expected a flow [2,H,W] or [B,2,H,W], got %s" % (tuple(flow.shape),))
+    single = flow.dim() == 3
+    f = (flow[None] if single else flow).detach().float().contiguous()
+    B, _, H, W = f.shape
+    d = torch.as_tensor(depth)
+    if d.numel() != B * H * W or tuple(d.shape[-2:]) != (H, W):
+        raise RuntimeError("expected a depth of %d x %d x %d values, got %s" % (B, H, W, tuple(d.shape)))
+    if d.device != f.device:
+        raise RuntimeError("flow on %s but depth on %s" % (f.device, d.device))
+    d = d.detach().float().contiguous()
+    p = _pose_rows(pose, B, f.device)
+    m = None
+    if mask is not None:
+        m = _byte_plane(torch.as_tensor(mask), "a mask", B, H, W)
+        if m.device != f.device:
+            raise RuntimeError("flow on %s but mask on %s" % (f.device, m.device))
+    ptr = (C.c_void_p(d.data_ptr()), C.c_void_p(f.data_ptr()), C.c_void_p(m.data_ptr()) if m is not None else None,
+           C.c_void_p(p.data_ptr()), B, H, W) + tuple(intrinsics(calib)) + (float(scale_px), float(inlier_px), float(min_z))
+    return single, (d, f, m, p), ptr, B, H, W
+
+
+def _pnp_workspace(B, H, W, device):
+    n = int(_lib.lib().atdn_pnp_workspace_bytes(B, H, W))
+    return torch.empty((max(n, 8) + 7) // 8, dtype=torch.float64, device=device)
+
+
+def reprojection_terms(depth, flow, pose, calib, mask=None, scale_px=4.0, inlier_px=2.0, min_z=0.1):
+    """How well a pose explains a depth map and a flow. `depth` [B,H,W] ([B,1,H,W] or [H,W]) is the depth of every pixel of
+    image 1 in camera 1 (0 = none; what `two_view_depth` and the keyframe depth maps hold), `flow` [B,2,H,W] (or [2,H,W]) the flow
+    from image 1 to image 2, `pose`, `calib` and `mask` as for `two_view_depth` (X1 = R X2 + t). Every pixel with a depth whose
+    flow lands inside image 2 is a candidate; its 3-D point is moved into camera 2, projected, and compared with where the flow
+    says it is. Returns `(sums, counts)` on the flow's device: `sums` float64 [B,28] ([28]) = the 21 upper-triangle entries of the
+    Gauss-Newton Hessian, the 6 gradient entries and the cost of the reprojection error under the Geman-McClure loss of scale
+    `scale_px`; `counts` int32 [B,3] ([3]) = (candidates, those at least `min_z` in front of camera 2, those within `inlier_px`
+    pixels). `reprojection_score(counts)` is the share of inliers. Device tensors go through libatdn_hip's kernels on the current
+    stream and the results stay on the device (no synchronisation); CPU tensors go through the library's host form. The rule is
+    float64, fixes the order of every sum and is stated in full in include/atdn_hip.h, atdn_pnp_terms; the same inputs give the
+    same bits on every call and on both paths."""
+    single, keep, ptr, B, H, W = _pnp_inputs(depth, flow, pose, calib, mask, scale_px, inlier_px, min_z)
+    dev = keep[1].device
+    sums = torch.empty((B, 28), dtype=torch.float64, device=dev)
+    counts = torch.empty((B, 3), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    out = (C.c_void_p(sums.data_ptr()), C.c_void_p(counts.data_ptr()))
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            ws = _pnp_workspace(B, H, W, dev)
+            _lib.check(L.atdn_pnp_terms(*ptr, *out, C.c_void_p(ws.data_ptr()), _stream()))
+    else:
+        _lib.check(L.atdn_pnp_terms_host(*ptr, *out))
+    return (sums[0], counts[0]) if single else (sums, counts)
+
+
+def reprojection_score(counts):
+    """float32 inliers / candidates of the `counts` [B,3] or [B,4] (or [3], [4]) of `reprojection_terms` / `pose_from_depth`, 0
+    where there is no candidate: the share of the depth's points that the pose projects within `inlier_px` pixels of where the
+    flow puts them. Exact integer counts divided in float64, then rounded; stays on the counts' device."""
+    c = torch.as_tensor(counts)
+    cand, inliers = c[..., 0].double(), c[..., 2].double()
+    return torch.where(cand > 0, inliers / cand.clamp(min=1.0), torch.zeros_like(cand)).float()
+
+
+def pose_from_depth(depth, flow, pose_init, calib, mask=None, iters=16, scale_px=4.0, inlier_px=2.0, min_z=0.1):
+    """The relative pose that a depth map and a flow determine (robust PnP): `iters` Levenberg-Marquardt steps from `pose_init` on
+    the terms of `reprojection_terms`, every problem of the batch on its own, all on the device. Arguments as for
+    `reprojection_terms`. Returns `(pose, cost, counts)` on the flow's device: `pose` float32 [B,4,4] ([4,4] for a 3-d flow) with
+    X1 = R X2 + t, `cost` float64 [B] and `counts` int32 [B,4] = (candidates, used, inliers, accepted steps) at it. Where no step
+    was accepted — a depth map of zeros, say — `pose` holds the bits of `pose_init`. 2 * (iters + 1) launches on the current
+    stream and no synchronisation; CPU tensors go through the library's host form. The rule is stated in full in
+    include/atdn_hip.h, atdn_pnp_solve; the same inputs give the same bits on every call and on both paths."""
+    single, keep, ptr, B, H, W = _pnp_inputs(depth, flow, pose_init, calib, mask, scale_px, inlier_px, min_z)
+    dev = keep[1].device
+    pose = torch.zeros((B, 4, 4), dtype=torch.float32, device=dev)
+    pose[:, 3, 3] = 1.0
+    rows = torch.empty((B, 12), dtype=torch.float32, device=dev)
+    cost = torch.empty((B,), dtype=torch.float64, device=dev)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    out = (int(iters), C.c_void_p(rows.data_ptr()), C.c_void_p(cost.data_ptr()), C.c_void_p(counts.data_ptr()))
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            ws = _pnp_workspace(B, H, W, dev)
+            _lib.check(L.atdn_pnp_solve(*ptr, *out, C.c_void_p(ws.data_ptr()), _stream()))
+    else:
+        _lib.check(L.atdn_pnp_solve_host(*ptr, *out))
+    pose[:, :3, :] = rows.view(B, 3, 4)
+    return (pose[0], cost[0], counts[0]) if single else (pose, cost, counts)
+
+
 def flow_track_step(flow, acc, alive, pose=None, calib=None, mask=None, depth=None, max_epipolar=1.0, min_parallax_deg=0.05,
                     max_depth=80.0, out=None):
     """One step of a flow track: the correspondences of an anchor frame's pixels carried one frame further and, given a pose,

@@ -458,6 +458,92 @@ int atdn_flow_track_step_host(const float* flow, const unsigned char* mask, cons
                               int* counts);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Pose from depth and flow (robust PnP)  —  a depth map of image 1 gives a 3-D point per pixel, the flow image 1 -> image 2 gives
+ * that point's pixel in image 2: the pose that explains the correspondences, by Levenberg-Marquardt on the reprojection error
+ * under the Geman-McClure loss, batched over problems, all on the device. atdn_pnp_terms is one evaluation (the normal
+ * equations, the cost and the share of reprojection inliers of a given pose: the depth-aware sibling of the epipolar score),
+ * atdn_pnp_solve the solver. The reference has nothing like it.
+ * ------------------------------------------------------------------------------------------------- */
+
+/* Bytes of the workspace of atdn_pnp_terms / atdn_pnp_solve for B planes of H x W (0 for sizes they refuse): one solver state per
+ * problem and, per chunk of 1024 pixels, 28 float64 sums and four int32. No call reads what an earlier call left there. */
+long atdn_pnp_workspace_bytes(int B, int H, int W);
+
+/* sums[b] = the 28 reprojection terms of pose[b] summed over the plane, counts[b] = (candidates, used, inliers).
+ *   depth [B,H,W] fp32 DEVICE: the depth of every pixel of image 1 in camera 1, 0 = none. flow [B,2,H,W] fp32 DEVICE, image 1 ->
+ *   image 2, channel 0 = x. mask [B,H,W] uint8 DEVICE or NULL: pixels whose byte is 0 are skipped. pose [B,12] fp32 DEVICE: the
+ *   rows of [R|t] with X1 = R X2 + t, as for atdn_flow_two_view_depth. sums [B,28] float64 DEVICE, counts [B,3] int32 DEVICE,
+ *   workspace: atdn_pnp_workspace_bytes(B, H, W) bytes DEVICE, 8-byte aligned like sums; no output (the workspace is one)
+ *   overlaps an input or another output. fx, fy finite and > 0; cx, cy finite; scale_px, inlier_px (pixels) and min_z finite and
+ *   > 0. B <= 65535, H * W <= 2^24, B, H, W >= 1. Anything else fails before a launch.
+ * The rule: everything in float64, every operation rounded on its own (no fused multiply-add), only + - * / and comparisons, in
+ * exactly this order.
+ * Internal pose (X2 = Rc X1 + tc): Rc = R^T (a copy), tc_i = -((r_0i*t_0 + r_1i*t_1) + r_2i*t_2).
+ * Constants: c2 = scale_px*scale_px, thr = inlier_px*inlier_px, e = (double)(H + W), rho_behind = (0.5*(e*e)) / (1 + (e*e)/c2).
+ * Pixel (x, y) with z = depth, (u, v) = flow:
+ *   x2 = x + u, y2 = y + v                                        (exact in float64)
+ *   cand = mask byte != 0 && 0 < z <= FLT_MAX && 0 <= x2 <= W-1 && 0 <= y2 <= H-1      (closed; a NaN fails)
+ *   X1 = (z*(x - cx))/fx, Y1 = (z*(y - cy))/fy
+ *   X = ((rc_00*X1 + rc_01*Y1) + rc_02*z) + tc_0, Y and Z likewise with rows 1 and 2 of Rc
+ *   used = cand && Z >= min_z
+ *   iz = 1/Z, px = (fx*X)*iz, py = (fy*Y)*iz
+ *   rx = (px + cx) - x2, ry = (py + cy) - y2, e2 = rx*rx + ry*ry
+ *   s = 1 + e2/c2, w = 1/(s*s), rho = (0.5*e2)/s                  (Geman-McClure: redescending, no square root)
+ *   inlier = used && e2 <= thr
+ *   a = fx*iz, b = -(px*iz), k = fy*iz, d = -(py*iz)
+ *   Jx = (b*Y, a*Z - b*X, -(a*Y), a, 0, b), Jy = (d*Y - k*Z, -(d*X), k*X, 0, k, d)
+ *     (the Jacobian of (rx, ry) with respect to (w0, w1, w2, v0, v1, v2) for X2 <- X2 + w x X2 + v)
+ *   terms 0..20: H_ij = (w*Jx_i)*Jx_j + (w*Jy_i)*Jy_j for i <= j, row by row (00, 01, .., 05, 11, .., 55); the products with the
+ *     structural zeros of Jx and Jy are formed like any other
+ *   terms 21..26: g_i = (w*Jx_i)*rx + (w*Jy_i)*ry;  term 27: rho
+ *   cand && !used (the point is behind camera 2, or a NaN pose): term 27 = rho_behind, the others +0.0 — without it a step that
+ *     pushes points behind the camera would lower the cost
+ *   !cand: +0.0 in all 28 terms
+ * Sums (their order is part of the rule; + is the float64 addition):
+ *   a plane is cut into chunks of 1024 consecutive flat indices i = y*W + x; indices >= H*W contribute +0.0 to every term;
+ *   inside a chunk, thread j = 0..255 owns the indices 4j .. 4j+3 and forms v[j] = ((t0 + t1) + t2) + t3; then for stride = 1, 2,
+ *   4, .., 128: v[i] = v[i] + v[i + stride] for every i that is a multiple of 2*stride; the chunk sum is v[0];
+ *   the plane sum is the chunk sums added in chunk order, starting from chunk 0's.
+ * The three counts are integer sums over the plane. No atomics and no memset: every workgroup writes its own slot of the
+ * workspace and a second launch adds the slots in order, so the same inputs give the same bits on every call. Two launches on
+ * `stream`: asynchronous, capturable, no host synchronisation. */
+int atdn_pnp_terms(const float* depth, const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W,
+                   double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, double* sums,
+                   int* counts, void* workspace, void* stream);
+/* The same function on HOST buffers in plain C++ float64 (csrc/pnp_host.h, the functions the kernels call too): serves CPU
+ * tensors, needs no GPU and no workspace, the same bits. */
+int atdn_pnp_terms_host(const float* depth, const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W,
+                        double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, double* sums,
+                        int* counts);
+
+/* pose_out[b] = the pose after `iters` Levenberg-Marquardt steps from pose_init[b] on the terms above; cost[b] and
+ * counts[b] = (candidates, used, inliers, accepted steps) at it. Arguments as for atdn_pnp_terms; pose_init, pose_out [B,12]
+ * fp32 DEVICE, cost [B] float64 DEVICE (8-byte aligned), counts [B,4] int32 DEVICE, 0 <= iters <= 64.
+ * State per problem: the accepted pose, the trial pose, the accepted terms, lambda, the accepted counts, the number of accepted
+ * steps. Evaluation 0 is at the internal form of pose_init and always becomes the accepted point, with lambda = 1e-3. After
+ * evaluation k >= 1 (at the trial pose): accepted iff cost_trial < cost_accepted (a NaN fails); on accept the pose, terms and
+ * counts are the trial's and lambda = max(lambda/3, 1e-9); on reject lambda = min(4*lambda, 1e6). Then, unless k = iters:
+ *   A = H of the accepted terms with A_ii = H_ii + lambda*H_ii
+ *   LDL^T without pivoting, for j = 0..5:  d_j = A_jj - sum_{k<j} L_jk*(L_jk*d_k)   (subtracted one by one, k ascending)
+ *                                           L_ij = (A_ij - sum_{k<j} L_ik*(L_jk*d_k)) / d_j  for i > j, likewise
+ *   y_i = -g_i - sum_{k<i} L_ik*y_k (k ascending);  y_i = y_i/d_i;  delta_i = y_i - sum_{k>i} L_ki*delta_k (i = 5..0, k ascending)
+ *   some d_j > 0 fails, or some |delta_i| <= DBL_MAX fails: the trial is the accepted pose again
+ *   retraction (rational, exactly orthonormal in exact arithmetic): h = 0.5*delta_w, n2 = (h0*h0 + h1*h1) + h2*h2, f = 2/(1 + n2),
+ *     M_ii = h_i*h_i - n2, M_ij = K_ij + h_i*h_j with K = [h]x = ((0, -h2, h1), (h2, 0, -h0), (-h1, h0, 0)),
+ *     E_ii = 1 + f*M_ii, E_ij = f*M_ij;  Rc'_ij = (E_i0*Rc_0j + E_i1*Rc_1j) + E_i2*Rc_2j,
+ *     tc'_i = ((E_i0*tc_0 + E_i1*tc_1) + E_i2*tc_2) + delta_v_i
+ * `iters` steps are iters + 1 evaluations, two launches each (the terms; the order-fixed sum with the decision and the step, one
+ * workgroup per problem); no host synchronisation, capturable. Output: R = Rc^T, t_i = -((rc_0i*tc_0 + rc_1i*tc_1) + rc_2i*tc_2)
+ * of the accepted pose, each rounded to fp32 once; when no step was accepted pose_out holds the bits of pose_init — a plane
+ * without depth returns exactly what it was given, cost +0.0 and zero counts. */
+int atdn_pnp_solve(const float* depth, const float* flow, const unsigned char* mask, const float* pose_init, int B, int H, int W,
+                   double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, int iters,
+                   float* pose_out, double* cost, int* counts, void* workspace, void* stream);
+int atdn_pnp_solve_host(const float* depth, const float* flow, const unsigned char* mask, const float* pose_init, int B, int H,
+                        int W, double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, int iters,
+                        float* pose_out, double* cost, int* counts);
+
+/* ---------------------------------------------------------------------------------------------------
  * Keyframe map  —  replaces the keyframe list of NeuralSLAM's relocalisation (keyframe_map.py)
  *   embeddings: Frame.embedding, one MappingVAE call per keyframe (slam_framework/neural_slam.py:88-103,158-164)
  *   search:     the per-keyframe torch.norm loop, torch.stack and argmin (neural_slam.py:374-383)
