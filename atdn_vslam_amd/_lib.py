@@ -44,6 +44,8 @@ SIGNATURES = {
     "atdn_vae_finalize": (C.c_int, [_vp]),
     "atdn_vae_embedding_shape": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "atdn_vae_encode": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
+    "atdn_vae_scratch_floats": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_int)]),
+    "atdn_vae_debug_stage": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_long, _vp]),
     "atdn_vae_destroy": (None, [_vp]),
     "atdn_clvo_trainer_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int]),
     "atdn_clvo_trainer_load": (C.c_int, [_vp, C.c_char_p, _vp, _i64p, C.c_int]),

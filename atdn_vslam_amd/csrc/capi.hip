@@ -266,6 +266,21 @@ int atdn_vae_encode(atdn_vae* h, const float* images, int B, float* mu, void* st
   h->net.encode(images, B, mu, (hipStream_t)stream);
   ATDN_API_END
 }
+int atdn_vae_debug_stage(atdn_vae* h, const float* images, int B, int stage, float* out, long capacity, void* stream) {
+  ATDN_API_BEGIN
+  ATDN_CHECK(h && images && out, "null argument");
+  h->net.debug_stage(images, B, stage, out, capacity, (hipStream_t)stream);
+  ATDN_API_END
+}
+int atdn_vae_scratch_floats(int H, int W, long* floats, int* stages) {
+  ATDN_API_BEGIN
+  ATDN_CHECK(floats && stages, "null argument");
+  ATDN_CHECK(H >= 1 && W >= 1 && (long)H * W <= (1L << 24), "frame size out of range");
+  const VaePlan p = vae_plan(H, W);
+  floats[0] = p.in4; floats[1] = p.bufA; floats[2] = p.bufB; floats[3] = p.bufS;
+  for (int k = 0; k < kVaeStages; ++k) { stages[3 * k] = p.h[k]; stages[3 * k + 1] = p.w[k]; stages[3 * k + 2] = p.ld[k]; }
+  ATDN_API_END
+}
 void atdn_vae_destroy(atdn_vae* h) { delete h; }
 
 int atdn_clvo_trainer_create(atdn_clvo_trainer** out, int H, int W, int batch, int sequence_length) {

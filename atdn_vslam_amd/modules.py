@@ -679,6 +679,27 @@ class MappingVAE(_NativeModule):
             _lib.check(_lib.lib().atdn_vae_encode(h, _ptr(im), B, _ptr(out), _stream()))
         return out, (oh.value, ow.value)
 
+    @staticmethod
+    def layer_plan(H, W):
+        """`atdn_vae_scratch_floats`: ([(h, w, floats per pixel) of stage 0..6], {buffer: floats per image}) for H x W frames.
+        Host only."""
+        floats, stages = (C.c_long * 4)(), (C.c_int * 21)()
+        _lib.check(_lib.lib().atdn_vae_scratch_floats(int(H), int(W), floats, stages))
+        return ([tuple(stages[3 * k:3 * k + 3]) for k in range(7)], dict(zip(("in4", "bufA", "bufB", "bufS"), floats)))
+
+    @torch.no_grad()
+    def debug_stage(self, images, k):
+        """Output of stage k (0 = stem, 1..6 = residual blocks) as the next layer reads it: [B,h,w,floats per pixel] channels-last,
+        pad lane included (parity tests)."""
+        self._require_input(images, "MappingVAE.debug_stage")
+        B, _, H, W = images.shape
+        h, w, ld = self.layer_plan(H, W)[0][k]
+        with torch.cuda.device(images.device):
+            im = images.float().contiguous()
+            out = torch.empty((B, h, w, ld), dtype=torch.float32, device=images.device)
+            _lib.check(_lib.lib().atdn_vae_debug_stage(self._handle(H, W, B), _ptr(im), B, int(k), _ptr(out), out.numel(), _stream()))
+        return out
+
     @torch.no_grad()
     def forward(self, image):
         self._require_input(image, "MappingVAE.forward")

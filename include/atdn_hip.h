@@ -220,6 +220,15 @@ int atdn_vae_finalize(atdn_vae* h);
 int atdn_vae_embedding_shape(const atdn_vae* h, int* out_h, int* out_w);
 /* images [B,3,H,W] float32 with values 0..255 (device) -> mu [B][out_h*out_w][128] channels-last (device) */
 int atdn_vae_encode(atdn_vae* h, const float* images, int B, float* mu, void* stream);
+/* The encoder's layer plan for H x W frames (host only, no handle, no GPU): stages[3k .. 3k+2] = height, width and floats per
+ * pixel of what stage k writes (k = 0: the 7x7 stem, 1..6: the stride-2 residual blocks; 3 channels travel as 4, pad lane 0),
+ * floats[0..3] = floats per image of the four scratch buffers of a handle: the normalised frames, the stem / block outputs,
+ * the first convolution of a block (at the block's input size), the skip convolution. A stride-2 layer writes
+ * ceil(h/2) x ceil(w/2) pixels, so odd sizes need more than H*W*4. floats [4], stages [21]; 1 <= H, W and H*W <= 2^24. */
+int atdn_vae_scratch_floats(int H, int W, long* floats, int* stages);
+/* Tests only: runs the encoder up to stage k and copies that stage's output, as the next layer reads it, to out (DEVICE,
+ * `capacity` floats >= B * stages[3k] * stages[3k+1] * stages[3k+2]): channels-last [B][h][w][floats per pixel]. */
+int atdn_vae_debug_stage(atdn_vae* h, const float* images, int B, int stage, float* out, long capacity, void* stream);
 void atdn_vae_destroy(atdn_vae* h);
 
 /* ---------------------------------------------------------------------------------------------------
