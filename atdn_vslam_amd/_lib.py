@@ -33,6 +33,7 @@ SIGNATURES = {
     "atdn_range_probe_launch": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
     "atdn_gma_workspace_bytes": (C.c_size_t, [_vp]),
     "atdn_gma_destroy": (None, [_vp]),
+    "atdn_device_bytes_live": (C.c_int64, []),
     "atdn_clvo_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int]),
     "atdn_clvo_load": (C.c_int, [_vp, C.c_char_p, _vp, _i64p, C.c_int]),
     "atdn_clvo_finalize": (C.c_int, [_vp]),

@@ -182,19 +182,13 @@ int atdn_range_probe(const float* x, int64_t rows, int64_t cols, int64_t ld, flo
   ATDN_API_BEGIN
   ATDN_CHECK(x && max_abs && over && nonfinite, "null argument");
   hipStream_t st = (hipStream_t)stream;
-  RangeSlot* slot = nullptr;
+  DeviceArray<RangeSlot> slot;
   RangeSlot host{};
-  ATDN_HIP(hipMalloc(&slot, sizeof(RangeSlot)));
-  try {
-    ATDN_HIP(hipMemsetAsync(slot, 0, sizeof(RangeSlot), st));
-    launch_range_probe(x, (long)rows, (long)cols, (long)ld, slot, st);
-    ATDN_HIP(hipMemcpyAsync(&host, slot, sizeof(RangeSlot), hipMemcpyDeviceToHost, st));
-    ATDN_HIP(hipStreamSynchronize(st));
-  } catch (...) {
-    (void)hipFree(slot);
-    throw;
-  }
-  (void)hipFree(slot);
+  slot.alloc(1);
+  ATDN_HIP(hipMemsetAsync(slot.p, 0, sizeof(RangeSlot), st));
+  launch_range_probe(x, (long)rows, (long)cols, (long)ld, slot.p, st);
+  ATDN_HIP(hipMemcpyAsync(&host, slot.p, sizeof(RangeSlot), hipMemcpyDeviceToHost, st));
+  ATDN_HIP(hipStreamSynchronize(st));
   memcpy(max_abs, &host.max_bits, sizeof(float));
   *over = (int64_t)host.over;
   *nonfinite = (int64_t)host.nonfinite;
@@ -202,6 +196,7 @@ int atdn_range_probe(const float* x, int64_t rows, int64_t cols, int64_t ld, flo
 }
 size_t atdn_gma_workspace_bytes(atdn_gma* h) { return h ? h->net.workspace_bytes() : 0; }
 void atdn_gma_destroy(atdn_gma* h) { delete h; }
+int64_t atdn_device_bytes_live(void) { return (int64_t)device_bytes_live.load(); }
 
 int atdn_clvo_create(atdn_clvo** out, int H, int W, int max_batch) {
   ATDN_API_BEGIN
@@ -344,12 +339,9 @@ int atdn_clvo_loss(const float* pred_rot, const float* pred_tr, const float* tru
   hipStream_t st = (hipStream_t)stream;
   DeviceBuf loss3;
   loss3.alloc(4);
-  try {
-    launch_clvo_loss_composite(pred_rot, pred_tr, true_rot, true_tr, B, T, alpha, w, mode == 1, false, loss3.p, d_rot, d_tr, st);
-    ATDN_HIP(hipMemcpyAsync(loss3_host, loss3.p, 3 * sizeof(float), hipMemcpyDeviceToHost, st));
-    ATDN_HIP(hipStreamSynchronize(st));
-  } catch (...) { loss3.release(); throw; }
-  loss3.release();
+  launch_clvo_loss_composite(pred_rot, pred_tr, true_rot, true_tr, B, T, alpha, w, mode == 1, false, loss3.p, d_rot, d_tr, st);
+  ATDN_HIP(hipMemcpyAsync(loss3_host, loss3.p, 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+  ATDN_HIP(hipStreamSynchronize(st));
   ATDN_API_END
 }
 long atdn_clvo_trainer_read(atdn_clvo_trainer* h, const char* key, int kind, float* host, long capacity, void* stream) {
@@ -506,72 +498,57 @@ int atdn_corr_lookup_bricks(const float* fmap1, const float* fmap2, int B, int H
   const long n8 = (long)B * N;
   BrickPyramid bp;
   bp.N = N; bp.NPB = brick_pixel_blocks(N);
-  DeviceBuf f1, f2, plain[3], fbrick[4], pyr[4], scratch, outsf;
-  DeviceBuf* all[] = {&f1, &f2, &plain[0], &plain[1], &plain[2], &fbrick[0], &fbrick[1], &fbrick[2], &fbrick[3],
-                      &pyr[0], &pyr[1], &pyr[2], &pyr[3], &scratch, &outsf};
   WeightArena A;
-  try {
-    sf_counter_attach();
-    f1.alloc(n8 * 256); f2.alloc(n8 * 256);
-    launch_to_sf(fmap1, f1.p, n8, 256, st);
-    launch_to_sf(fmap2, f2.p, n8, 256, st);
-    float* rowmajor[4] = {pyr0, pyr1, pyr2, pyr3};
-    int pH[4], pW[4];
-    for (int l = 0; l < 4; ++l) {   // the same sequence as GmaNet::run_body_sf
-      pH[l] = H8 >> l; pW[l] = W8 >> l;
-      bp.H[l] = pH[l]; bp.W[l] = pW[l]; bp.BW[l] = cdiv(pW[l], 8); bp.BH[l] = cdiv(pH[l], 4); bp.NB[l] = bp.BW[l] * bp.BH[l] * 32;
-      const float* src = f2.p;
-      long src_sb = (long)N * 256;
-      if (l > 0) {
-        const float* prev = l == 1 ? f2.p : plain[l - 2].p;
-        const long prev_sb = l == 1 ? (long)N * 256 : (long)pH[l - 1] * pW[l - 1] * 256;
-        src_sb = (long)pH[l] * pW[l] * 256;
-        plain[l - 1].alloc((long)B * src_sb);
-        launch_pool_features_sf(prev, B, pH[l - 1], pW[l - 1], 256, prev_sb, plain[l - 1].p, src_sb, st);
-        src = plain[l - 1].p;
-      }
-      fbrick[l].alloc((long)B * bp.NB[l] * 256);
-      launch_brick_rows(src, src_sb, B, pH[l], pW[l], 256, fbrick[l].p, (long)bp.NB[l] * 256, st);
-      pyr[l].alloc((long)B * bp.NPB * kBrickPixelBlock * bp.NB[l]);
-      launch_corr_bricks(f1.p, (long)N * 256, fbrick[l].p, (long)bp.NB[l] * 256, B, N, bp.NB[l], 1.0f / sqrtf(256.0f), pyr[l].p, false, st);
-      bp.base[l] = pyr[l].p;
-      if (rowmajor[l]) launch_unbrick(pyr[l].p, bp.NB[l], N, pH[l], pW[l], n8, rowmajor[l], st);
+  DeviceBuf f1, f2, plain[3], fbrick[4], pyr[4], scratch, outsf, csf;
+  sf_counter_attach();
+  f1.alloc(n8 * 256); f2.alloc(n8 * 256);
+  launch_to_sf(fmap1, f1.p, n8, 256, st);
+  launch_to_sf(fmap2, f2.p, n8, 256, st);
+  float* rowmajor[4] = {pyr0, pyr1, pyr2, pyr3};
+  int pH[4], pW[4];
+  for (int l = 0; l < 4; ++l) {   // the same sequence as GmaNet::run_body_sf
+    pH[l] = H8 >> l; pW[l] = W8 >> l;
+    bp.H[l] = pH[l]; bp.W[l] = pW[l]; bp.BW[l] = cdiv(pW[l], 8); bp.BH[l] = cdiv(pH[l], 4); bp.NB[l] = bp.BW[l] * bp.BH[l] * 32;
+    const float* src = f2.p;
+    long src_sb = (long)N * 256;
+    if (l > 0) {
+      const float* prev = l == 1 ? f2.p : plain[l - 2].p;
+      const long prev_sb = l == 1 ? (long)N * 256 : (long)pH[l - 1] * pW[l - 1] * 256;
+      src_sb = (long)pH[l] * pW[l] * 256;
+      plain[l - 1].alloc((long)B * src_sb);
+      launch_pool_features_sf(prev, B, pH[l - 1], pW[l - 1], 256, prev_sb, plain[l - 1].p, src_sb, st);
+      src = plain[l - 1].p;
     }
-    if (samples) {   // lookup_conv_kernel<FUSED = false>: the sampling code of the fused kernel, samples to memory
-      outsf.alloc(n8 * 352);
-      launch_lookup_bricks(bp, coords, n8, outsf.p, st);
-      scratch.alloc(n8 * 352);
-      launch_from_sf(outsf.p, scratch.p, n8, 352, st);
-      ATDN_HIP(hipMemcpy2DAsync(samples, 324 * sizeof(float), scratch.p, 352 * sizeof(float), 324 * sizeof(float), (size_t)n8,
-                                hipMemcpyDeviceToDevice, st));
-    }
-    if (cor1) {      // lookup_conv_kernel<FUSED = true>: what GmaNet::iteration_sf launches
-      StateDict sd;
-      const int64_t ws[4] = {256, 324, 1, 1}, bs[1] = {256};
-      sd.put("c.weight", convc1_weight_host, ws, 4);
-      sd.put("c.bias", convc1_bias_host, bs, 1);
-      PackedConv L = pack_conv_sf(A, sd, {"c"});
-      pack_fragment_major16(A, L);
-      A.upload();
-      resolve(A, L);
-      DeviceBuf csf;
-      csf.alloc(n8 * 256);
-      try {
-        launch_lookup_conv(bp, coords, n8, nullptr, L.wf16, L.wscale, L.b, csf.p, false, st);
-        launch_from_sf(csf.p, cor1, n8, 256, st);
-        ATDN_HIP(hipStreamSynchronize(st));
-      } catch (...) { csf.release(); throw; }
-      csf.release();
-    }
-    ATDN_HIP(hipStreamSynchronize(st));
-  } catch (...) {
-    (void)hipDeviceSynchronize();
-    for (auto* b : all) b->release();
-    A.release();
-    throw;
+    fbrick[l].alloc((long)B * bp.NB[l] * 256);
+    launch_brick_rows(src, src_sb, B, pH[l], pW[l], 256, fbrick[l].p, (long)bp.NB[l] * 256, st);
+    pyr[l].alloc((long)B * bp.NPB * kBrickPixelBlock * bp.NB[l]);
+    launch_corr_bricks(f1.p, (long)N * 256, fbrick[l].p, (long)bp.NB[l] * 256, B, N, bp.NB[l], 1.0f / sqrtf(256.0f), pyr[l].p, false, st);
+    bp.base[l] = pyr[l].p;
+    if (rowmajor[l]) launch_unbrick(pyr[l].p, bp.NB[l], N, pH[l], pW[l], n8, rowmajor[l], st);
   }
-  for (auto* b : all) b->release();
-  A.release();
+  if (samples) {   // lookup_conv_kernel<FUSED = false>: the sampling code of the fused kernel, samples to memory
+    outsf.alloc(n8 * 352);
+    launch_lookup_bricks(bp, coords, n8, outsf.p, st);
+    scratch.alloc(n8 * 352);
+    launch_from_sf(outsf.p, scratch.p, n8, 352, st);
+    ATDN_HIP(hipMemcpy2DAsync(samples, 324 * sizeof(float), scratch.p, 352 * sizeof(float), 324 * sizeof(float), (size_t)n8,
+                              hipMemcpyDeviceToDevice, st));
+  }
+  if (cor1) {      // lookup_conv_kernel<FUSED = true>: what GmaNet::iteration_sf launches
+    StateDict sd;
+    const int64_t ws[4] = {256, 324, 1, 1}, bs[1] = {256};
+    sd.put("c.weight", convc1_weight_host, ws, 4);
+    sd.put("c.bias", convc1_bias_host, bs, 1);
+    PackedConv L = pack_conv_sf(A, sd, {"c"});
+    pack_fragment_major16(A, L);
+    A.upload();
+    resolve(A, L);
+    csf.alloc(n8 * 256);
+    launch_lookup_conv(bp, coords, n8, nullptr, L.wf16, L.wscale, L.b, csf.p, false, st);
+    launch_from_sf(csf.p, cor1, n8, 256, st);
+    ATDN_HIP(hipStreamSynchronize(st));
+  }
+  ATDN_HIP(hipStreamSynchronize(st));
   ATDN_API_END
 }
 
@@ -598,20 +575,14 @@ int atdn_conv2d_nhwc(const float* src, int nimg, int H, int W, int Cin, const fl
   s.w = L.w; s.ldw = L.ldw; s.N = Cout; s.nimg = nimg;
   const int Ho = conv_out(H, KH, stride, padH), Wo = conv_out(W, KW, stride, padW);
   hipStream_t st = (hipStream_t)stream;
-  try {
-    if (row) {
-      if (relu) conv_dispatch<MODE_ROW>(s, EpiBias<ACT_RELU>{L.b, dst, (long)Ho * Wo * Cout, Cout, 1.f}, st);
-      else conv_dispatch<MODE_ROW>(s, EpiBias<ACT_NONE>{L.b, dst, (long)Ho * Wo * Cout, Cout, 1.f}, st);
-    } else {
-      if (relu) conv_dispatch<MODE_TAP>(s, EpiBias<ACT_RELU>{L.b, dst, (long)Ho * Wo * Cout, Cout, 1.f}, st);
-      else conv_dispatch<MODE_TAP>(s, EpiBias<ACT_NONE>{L.b, dst, (long)Ho * Wo * Cout, Cout, 1.f}, st);
-    }
-    ATDN_HIP(hipStreamSynchronize(st));
-  } catch (...) {
-    A.release();
-    throw;
+  if (row) {
+    if (relu) conv_dispatch<MODE_ROW>(s, EpiBias<ACT_RELU>{L.b, dst, (long)Ho * Wo * Cout, Cout, 1.f}, st);
+    else conv_dispatch<MODE_ROW>(s, EpiBias<ACT_NONE>{L.b, dst, (long)Ho * Wo * Cout, Cout, 1.f}, st);
+  } else {
+    if (relu) conv_dispatch<MODE_TAP>(s, EpiBias<ACT_RELU>{L.b, dst, (long)Ho * Wo * Cout, Cout, 1.f}, st);
+    else conv_dispatch<MODE_TAP>(s, EpiBias<ACT_NONE>{L.b, dst, (long)Ho * Wo * Cout, Cout, 1.f}, st);
   }
-  A.release();
+  ATDN_HIP(hipStreamSynchronize(st));
   ATDN_API_END
 }
 
@@ -676,44 +647,29 @@ int atdn_conv2d_nhwc_sf_epi(const float* src, int nimg, int H, int W, int Cin, c
   A.upload();
   resolve(A, L);
   hipStream_t st = (hipStream_t)stream;
-  float* tmp = nullptr;
+  DeviceBuf tmp, osf;
   const long rows = (long)nimg * H * W;
-  ATDN_HIP(hipMalloc(&tmp, (size_t)rows * Cin * sizeof(float)));
-  try {
-    launch_to_sf(src, tmp, rows, Cin, st);
-    ConvShape s;
-    s.src0 = tmp; s.ld0 = Cin; s.sb0 = (long)H * W * Cin; s.C0 = L.C; s.H = H; s.W = W;
-    s.KH = KH; s.KW = KW; s.stride = stride; s.padH = padH; s.padW = padW;
-    s.w = L.w; s.ldw = L.ldw; s.N = Cout; s.nimg = nimg;
-    const int Ho = conv_out(H, KH, stride, padH), Wo = conv_out(W, KW, stride, padW);
-    s.wfrag16 = L.wf16;
-    s.tile_form = tile_form;
-    // sf_store: write split-f16 through the SfBias epilogue (the channel-vector sf store of the product's layers), then
-    // unpack to fp32; otherwise fp32 output through EpiBias
-    if (sf_store) {
-      float* osf = nullptr;
-      const long orows = (long)nimg * Ho * Wo;
-      ATDN_HIP(hipMalloc(&osf, (size_t)orows * Cout * sizeof(float)));
-      try {
-        conv_sf_dispatch(s, L.wscale, SfBias<ACT_NONE>{L.b, osf, (long)Ho * Wo * Cout, Cout}, st);
-        launch_from_sf(osf, dst, orows, Cout, st);
-        ATDN_HIP(hipStreamSynchronize(st));
-      } catch (...) {
-        (void)hipFree(osf);
-        throw;
-      }
-      (void)hipFree(osf);
-    } else {
-      conv_sf_dispatch(s, L.wscale, EpiBias<ACT_NONE>{L.b, dst, (long)Ho * Wo * Cout, Cout, 1.f}, st);
-      ATDN_HIP(hipStreamSynchronize(st));
-    }
-  } catch (...) {
-    (void)hipFree(tmp);
-    A.release();
-    throw;
+  tmp.alloc(rows * Cin);
+  launch_to_sf(src, tmp.p, rows, Cin, st);
+  ConvShape s;
+  s.src0 = tmp.p; s.ld0 = Cin; s.sb0 = (long)H * W * Cin; s.C0 = L.C; s.H = H; s.W = W;
+  s.KH = KH; s.KW = KW; s.stride = stride; s.padH = padH; s.padW = padW;
+  s.w = L.w; s.ldw = L.ldw; s.N = Cout; s.nimg = nimg;
+  const int Ho = conv_out(H, KH, stride, padH), Wo = conv_out(W, KW, stride, padW);
+  s.wfrag16 = L.wf16;
+  s.tile_form = tile_form;
+  // sf_store: write split-f16 through the SfBias epilogue (the channel-vector sf store of the product's layers), then
+  // unpack to fp32; otherwise fp32 output through EpiBias
+  if (sf_store) {
+    const long orows = (long)nimg * Ho * Wo;
+    osf.alloc(orows * Cout);
+    conv_sf_dispatch(s, L.wscale, SfBias<ACT_NONE>{L.b, osf.p, (long)Ho * Wo * Cout, Cout}, st);
+    launch_from_sf(osf.p, dst, orows, Cout, st);
+    ATDN_HIP(hipStreamSynchronize(st));
+  } else {
+    conv_sf_dispatch(s, L.wscale, EpiBias<ACT_NONE>{L.b, dst, (long)Ho * Wo * Cout, Cout, 1.f}, st);
+    ATDN_HIP(hipStreamSynchronize(st));
   }
-  (void)hipFree(tmp);
-  A.release();
   ATDN_API_END
 }
 

@@ -1,9 +1,9 @@
 // CLVO pose head `ATDNVO` (atdn_vslam/odometry/network.py:122-146): stateless CNN encoder (shardable over
 // frame pairs) + the sequential LSTM/MLP tail with explicit state.
 #pragma once
+#include "device_buf.h"
 #include "kernels.h"
 #include "weights.h"
-#include "gma.h"  // DeviceBuf
 #include <set>
 
 namespace atdn {
@@ -11,6 +11,8 @@ namespace atdn {
 class ClvoNet {
  public:
   ClvoNet(int H, int W, int max_batch);
+  // Order matters: the body synchronises the device and destroys the scan graphs, the capture stream and the pinned abort
+  // word; the buffers and the weight arena are members, so they are freed after it.
   ~ClvoNet();
   StateDict& state() { return sd_; }
   void finalize();

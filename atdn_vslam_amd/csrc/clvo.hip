@@ -29,8 +29,6 @@ ClvoNet::~ClvoNet() {
   for (auto& kv : scan_graphs_) (void)hipGraphExecDestroy(kv.second);
   if (cap_stream_) (void)hipStreamDestroy(cap_stream_);
   if (scan_abort_host_) (void)hipHostFree(scan_abort_host_);
-  for (DeviceBuf* b : {&in4_, &bufA_, &bufB_, &bufS_, &flat_, &pre_, &hseq_, &x2seq_, &hseq2_, &cstate_, &scan_xch_, &scan_state0_}) b->release();
-  arena_.release();
 }
 
 ClvoNet::ConvBN ClvoNet::pack_convbn(const std::string& p) {
@@ -152,13 +150,12 @@ void ClvoNet::encode(const float* flow, int B, float* feat, hipStream_t st) {
 }
 
 void ClvoNet::ensure_scan(long rows, int Bs) {
-  bool grown = false;
-  auto grow = [&](DeviceBuf& b, long n) { if (b.n < n) { b.release(); b.alloc(n); grown = true; } };
-  grow(pre_, rows * 2048);
-  grow(hseq_, (rows + Bs) * 512);
-  grow(x2seq_, rows * 512);
-  grow(hseq2_, (rows + Bs) * 512);
-  grow(cstate_, 2L * Bs * 512);
+  // (a growth that fails leaves its buffer empty, so the next call grows again and reaches the branch below before any replay)
+  bool grown = pre_.reserve(rows * 2048);
+  grown |= hseq_.reserve((rows + Bs) * 512);
+  grown |= x2seq_.reserve(rows * 512);
+  grown |= hseq2_.reserve((rows + Bs) * 512);
+  grown |= cstate_.reserve(2L * Bs * 512);
   if (grown) {   // captured graphs hold the old addresses
     (void)hipDeviceSynchronize();
     for (auto& kv : scan_graphs_) (void)hipGraphExecDestroy(kv.second);

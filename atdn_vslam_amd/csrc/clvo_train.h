@@ -7,7 +7,7 @@
 #include <string>
 #include <vector>
 
-#include "gma.h"  // DeviceBuf
+#include "device_buf.h"
 #include "weights.h"
 
 namespace atdn {
@@ -15,7 +15,6 @@ namespace atdn {
 class ClvoTrainer {
  public:
   ClvoTrainer(int H, int W, int B, int T);
-  ~ClvoTrainer();
   StateDict& state() { return sd_; }
   void finalize();
 

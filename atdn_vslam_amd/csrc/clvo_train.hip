@@ -50,16 +50,6 @@ ClvoTrainer::ClvoTrainer(int H_, int W_, int B_, int T_) : H(H_), W(W_), B(B_), 
   ATDN_CHECK(hs_[6] * ws_[6] * 16 == 832, "ATDNVO needs a flow size that reduces to a 16x4x13 map");
 }
 
-ClvoTrainer::~ClvoTrainer() {
-  for (DeviceBuf* b : {&params_, &grads_, &m_, &v_, &stats_, &bnstat_, &part_, &sums_, &wscratch_, &loss_, &flow_, &x0_,
-                       &z1_, &y1_, &z6_, &y6_, &flat_, &zf_, &feat_, &pre1_, &act1_, &c1_, &tc1_, &h1_, &zl_, &x2_, &pre2_, &act2_,
-                       &c2_, &tc2_, &h2_, &out_[0], &out_[1], &ga_, &gb_, &gc_, &stuffed_})
-    b->release();
-  for (auto& r : ract_) for (DeviceBuf* b : {&r.za, &r.ua, &r.zb, &r.s, &r.zo, &r.o}) b->release();
-  for (int i = 0; i < 2; ++i) for (int j = 0; j < 2; ++j) { hz_[i][j].release(); ha_[i][j].release(); }
-  for (auto& b : dsmall_) b.release();
-}
-
 ClvoTrainer::Slot ClvoTrainer::param(const std::string& key) {
   auto it = pindex_.find(key);
   if (it == pindex_.end()) throw Error("missing parameter: " + key);

@@ -1,7 +1,7 @@
 // Frame front-end: resize (antialiased or plain bilinear, uint8 or fp32 source), replicate padding, and the
 // host-uint8 -> device-fp32 ingest with its own copy stream (frontend.hip).
 #pragma once
-#include "common.h"
+#include "device_buf.h"
 
 namespace atdn {
 
@@ -29,7 +29,7 @@ class FrameIngest {
   const int Hin, Win, Hout, Wout, max_frames, antialias;
 
  private:
-  unsigned char* stage_[2] = {nullptr, nullptr};
+  DeviceArray<unsigned char> stage_[2];   // freed after the destructor body has synchronised
   hipEvent_t copied_[2] = {nullptr, nullptr}, consumed_[2] = {nullptr, nullptr};
   bool used_[2] = {false, false};
   int next_ = 0;

@@ -96,6 +96,7 @@ const ResizePlanRef resize_plan(int Hin, int Win, int Hout, int Wout, int antial
       return {p.ty, p.tx};
   Plan p{dev, Hin, Win, Hout, Wout, antialias, nullptr, nullptr};
   const auto ty = make_table(Hin, Hout, antialias), tx = make_table(Win, Wout, antialias);
+  // process-lifetime blocks, never freed on purpose: the cache hands these addresses to every caller
   ATDN_HIP(hipMalloc(&p.ty, ty.size() * sizeof(ResizeTable)));
   ATDN_HIP(hipMalloc(&p.tx, tx.size() * sizeof(ResizeTable)));
   ATDN_HIP(hipMemcpy(p.ty, ty.data(), ty.size() * sizeof(ResizeTable), hipMemcpyHostToDevice));
@@ -238,7 +239,7 @@ FrameIngest::FrameIngest(int Hin_, int Win_, int Hout_, int Wout_, int max_frame
   (void)resize_plan(Hin, Win, Hout, Wout, antialias);   // builds the tables (and validates the ratio) now
   const size_t bytes = (size_t)max_frames * 3 * Hin * Win;
   for (int s = 0; s < 2; ++s) {
-    ATDN_HIP(hipMalloc(&stage_[s], bytes));
+    stage_[s].alloc((long)bytes);
     ATDN_HIP(hipEventCreateWithFlags(&copied_[s], hipEventDisableTiming));
     ATDN_HIP(hipEventCreateWithFlags(&consumed_[s], hipEventDisableTiming));
   }
@@ -249,7 +250,6 @@ FrameIngest::~FrameIngest() {
   DeviceGuard dg(dev_);
   (void)hipDeviceSynchronize();
   for (int s = 0; s < 2; ++s) {
-    if (stage_[s]) (void)hipFree(stage_[s]);
     if (copied_[s]) (void)hipEventDestroy(copied_[s]);
     if (consumed_[s]) (void)hipEventDestroy(consumed_[s]);
   }
@@ -265,10 +265,10 @@ void FrameIngest::ingest(const unsigned char* host_frames, int n, float* dst, hi
   if (used_[s]) ATDN_HIP(hipEventSynchronize(copied_[s]));
   // the slot's previous contents must have been read by the resize kernel that used them
   if (used_[s]) ATDN_HIP(hipStreamWaitEvent(copy_stream_, consumed_[s], 0));
-  ATDN_HIP(hipMemcpyAsync(stage_[s], host_frames, (size_t)n * 3 * Hin * Win, hipMemcpyHostToDevice, copy_stream_));
+  ATDN_HIP(hipMemcpyAsync(stage_[s].p, host_frames, (size_t)n * 3 * Hin * Win, hipMemcpyHostToDevice, copy_stream_));
   ATDN_HIP(hipEventRecord(copied_[s], copy_stream_));
   ATDN_HIP(hipStreamWaitEvent(st, copied_[s], 0));
-  launch_resize<unsigned char>(stage_[s], n * 3, Hin, Win, Hout, Wout, antialias, dst, st);
+  launch_resize<unsigned char>(stage_[s].p, n * 3, Hin, Win, Hout, Wout, antialias, dst, st);
   ATDN_HIP(hipEventRecord(consumed_[s], st));
   used_[s] = true;
 }

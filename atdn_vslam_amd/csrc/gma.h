@@ -6,6 +6,7 @@
 
 #include "attention.h"
 #include "conv_dispatch.h"
+#include "device_buf.h"
 #include "kernels.h"
 #include "range_probe.h"
 #include "weights.h"
@@ -18,21 +19,12 @@ struct EncoderWeights {
   PackedConv head;
 };
 
-class DeviceBuf {
- public:
-  float* p = nullptr;
-  long n = 0;
-  void alloc(long count) {
-    n = count;
-    ATDN_HIP(hipMalloc(&p, (size_t)count * sizeof(float)));
-  }
-  void release() { if (p) { (void)hipFree(p); p = nullptr; } }
-};
-
 class GmaNet {
  public:
   // precision: 0 = exact-fp32 MFMA everywhere; 1 = split-f16 (3 x f16 MFMA, fp32-grade) for every TAP-mode GEMM
   GmaNet(int H, int W, int max_batch, int precision);
+  // Order matters: the body synchronises the device and destroys graphs, streams and events; the buffers and the weight
+  // arena are members, so they are freed after it.
   ~GmaNet();
   StateDict& state() { return sd_; }
   void finalize();  // pack + upload weights, allocate the workspace
@@ -104,7 +96,7 @@ class GmaNet {
  private:
   bool probe_ = false;
   int probe_it_ = -1;                 // iteration the rows being recorded belong to (-1: outside the loop)
-  RangeSlot* probe_slots_ = nullptr;  // [kProbeMaxRows] device slots, zeroed on the stream at the start of a probed forward
+  DeviceArray<RangeSlot> probe_slots_;  // [kProbeMaxRows] device slots, zeroed on the stream at the start of a probed forward
   std::vector<ProbeRow> probe_rows_;
   void probe_begin(hipStream_t st);
   void probe_end(hipStream_t st);     // one copy of the slot table back, then the stream is synchronised

@@ -168,15 +168,6 @@ GmaNet::~GmaNet() {
   if (cap_stream_) (void)hipStreamDestroy(cap_stream_);
   if (par_stream_) (void)hipStreamDestroy(par_stream_);
   for (auto& e : par_events_) (void)hipEventDestroy(e);
-  DeviceBuf* all[] = {&img4_, &enc_[0], &enc_[1], &enc_[2], &enc_[3], &scratch_, &pcnt_, &fin_, &fmap_, &psum_, &pm2_, &mean_[0], &mean_[1], &mean_[2], &rstd_[0],
-                      &rstd_[1], &rstd_[2], &pyr_[0], &pyr_[1], &pyr_[2], &pyr_[3], &h_[0], &h_[1], &x_, &qk_, &attn_, &vT_,
-                      &corrfeat_, &cor1_, &corflo_, &flo1_, &z_, &rh_, &fh_, &mask_, &coords1_, &flow4_, &pre_zr_[0],
-                      &pre_zr_[1], &pre_q_[0], &pre_q_[1], &rowmax_, &rinv_,
-                      &fbrick_[0], &fbrick_[1], &fbrick_[2], &fbrick_[3], &fplain_[0], &fplain_[1], &fplain_[2], &coords_used_, &fhG_,
-                      &attn_part_, &enc2_[0], &enc2_[1], &enc2_[2], &enc2_[3]};
-  for (auto* b : all) b->release();
-  if (probe_slots_) (void)hipFree(probe_slots_);
-  arena_.release();
 }
 
 // ---------------------------------------------------------------- range probe (gma.h)
@@ -188,22 +179,22 @@ void GmaNet::set_probe(bool on) {
 }
 
 void GmaNet::probe_begin(hipStream_t st) {
-  if (!probe_slots_) ATDN_HIP(hipMalloc(&probe_slots_, kProbeMaxRows * sizeof(RangeSlot)));
-  ATDN_HIP(hipMemsetAsync(probe_slots_, 0, kProbeMaxRows * sizeof(RangeSlot), st));
+  probe_slots_.reserve(kProbeMaxRows);
+  ATDN_HIP(hipMemsetAsync(probe_slots_.p, 0, kProbeMaxRows * sizeof(RangeSlot), st));
   probe_rows_.clear();
   probe_it_ = -1;
 }
 
 void GmaNet::probe(const std::string& name, bool limited, const float* p, long rows, long cols, long ld, hipStream_t st) {
   ATDN_CHECK((int)probe_rows_.size() < kProbeMaxRows, "range probe: slot table full");
-  launch_range_probe(p, rows, cols, ld, probe_slots_ + probe_rows_.size(), st);
+  launch_range_probe(p, rows, cols, ld, probe_slots_.p + probe_rows_.size(), st);
   probe_rows_.push_back({name, probe_it_, limited, 0.f, 0, 0});
 }
 
 void GmaNet::probe_end(hipStream_t st) {
   std::vector<RangeSlot> host(probe_rows_.size());
   if (!host.empty())
-    ATDN_HIP(hipMemcpyAsync(host.data(), probe_slots_, host.size() * sizeof(RangeSlot), hipMemcpyDeviceToHost, st));
+    ATDN_HIP(hipMemcpyAsync(host.data(), probe_slots_.p, host.size() * sizeof(RangeSlot), hipMemcpyDeviceToHost, st));
   ATDN_HIP(hipStreamSynchronize(st));
   for (size_t i = 0; i < host.size(); ++i) {
     ProbeRow& r = probe_rows_[i];
@@ -991,7 +982,7 @@ long GmaNet::debug_read(const char* name, float* host, long capacity, hipStream_
     // bricked level -> the reference's row-major [pixel][H_l * W_l]
     const int l = k[3] - '0';
     const long rows = (long)maxB * N, total = rows * pyrH_[l] * pyrW_[l];
-    if (scratch_.n < total) { scratch_.release(); scratch_.alloc(total); }
+    scratch_.reserve(total);
     launch_unbrick(pyr_[l].p, brickNB_[l], N, pyrH_[l], pyrW_[l], rows, scratch_.p, st);
     ATDN_HIP(hipStreamSynchronize(st));
     const long n = std::min(capacity, total);
@@ -1020,7 +1011,7 @@ long GmaNet::debug_read(const char* name, float* host, long capacity, hipStream_
   long n = std::min(capacity, b->n);
   if (k == "attn" && !classic_) {   // fragment-major exp(s - max) + row sums -> normalised fp32 rows [maxB][N][ldN]
     const long rows = (long)maxB * N * ldN;
-    if (scratch_.n < rows) { scratch_.release(); scratch_.alloc(rows); }
+    scratch_.reserve(rows);
     ATDN_HIP(hipMemsetAsync(scratch_.p, 0, (size_t)rows * sizeof(float), st));
     launch_attn_decode(attn_.p, rinv_.p, attn_geom(maxB, N, ldN), scratch_.p, st);
     ATDN_HIP(hipStreamSynchronize(st));
@@ -1031,7 +1022,7 @@ long GmaNet::debug_read(const char* name, float* host, long capacity, hipStream_
   const bool is_sf = precision >= 1 && (k == "fmap" || k == "net" || k == "x" || k == "attn" || k == "corrfeat" || k == "qk" || k == "cor1");
   const float* src = b->p;
   if (is_sf) {  // decode the split-f16 tensor into a scratch fp32 copy first
-    if (scratch_.n < b->n) { scratch_.release(); scratch_.alloc(b->n); }
+    scratch_.reserve(b->n);
     launch_from_sf(b->p, scratch_.p, b->n / 32, 32, st);
     src = scratch_.p;
   }

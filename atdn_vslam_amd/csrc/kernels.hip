@@ -547,7 +547,7 @@ void launch_mlp_heads(const float* h2, int B, MlpHead rot, MlpHead tr, float* ro
 
 const float* zero_line() {
   static float* z = nullptr;
-  if (!z) {
+  if (!z) {   // process-lifetime block, never freed on purpose: every handle's kernels read it
     ATDN_HIP(hipMalloc(&z, 256));
     ATDN_HIP(hipMemset(z, 0, 256));
     ATDN_HIP(hipDeviceSynchronize());
@@ -585,7 +585,8 @@ unsigned int* sf_counter_for_current_device(bool create) {
   if (!create) return nullptr;
   unsigned int* p = nullptr;
   // p[0] = the counter, p[1] = the result slot of read-and-reset (allocated once: a hipMalloc / hipFree pair per read would
-  // synchronise the whole device, every lane stream and the ingest stream, at each saturation check — ADVICE r4)
+  // synchronise the whole device, every lane stream and the ingest stream, at each saturation check — ADVICE r4).
+  // Process-lifetime block, never freed on purpose: the device symbols of every translation unit point at it.
   ATDN_HIP(hipMalloc(&p, 2 * sizeof(unsigned int)));
   ATDN_HIP(hipMemset(p, 0, 2 * sizeof(unsigned int)));
   for (auto set : sf_counter_setters()) {   // one per translation unit that includes sf.h

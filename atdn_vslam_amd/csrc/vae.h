@@ -2,9 +2,9 @@
 // relocalisation compares between a query frame and the stored keyframes. Decoder and training stay outside.
 #pragma once
 #include "conv_dispatch.h"
+#include "device_buf.h"
 #include "kernels.h"
 #include "weights.h"
-#include "gma.h"  // DeviceBuf
 #include "vae_plan.h"
 
 namespace atdn {
@@ -12,7 +12,6 @@ namespace atdn {
 class VaeEncoder {
  public:
   VaeEncoder(int H, int W, int max_batch);
-  ~VaeEncoder();
   StateDict& state() { return sd_; }
   void finalize();
   // images NCHW [B,3,H,W] with values 0..255 -> mu NHWC [B][h*w][128] (h, w = out_h(), out_w())

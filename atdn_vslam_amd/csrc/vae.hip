@@ -29,11 +29,6 @@ VaeEncoder::VaeEncoder(int H_, int W_, int max_batch) : H(H_), W(W_), maxB(max_b
   oh_ = plan_.h[kVaeStages - 1]; ow_ = plan_.w[kVaeStages - 1];
 }
 
-VaeEncoder::~VaeEncoder() {
-  for (DeviceBuf* b : {&in4_, &bufA_, &bufB_, &bufS_}) b->release();
-  arena_.release();
-}
-
 VaeEncoder::ConvBN VaeEncoder::pack_convbn(const std::string& p) {
   ConvBN c;
   const HostTensor& w = sd_.get(p + ".conv.weight");

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "conv_mfma.h"
+#include "device_buf.h"
 
 namespace atdn {
 
@@ -69,16 +70,15 @@ class WeightArena {
   }
   float* at(long off) { return host_.data() + off; }
   void upload() {
-    ATDN_HIP(hipMalloc(&dev_, host_.size() * sizeof(float)));
-    ATDN_HIP(hipMemcpy(dev_, host_.data(), host_.size() * sizeof(float), hipMemcpyHostToDevice));
+    dev_.alloc((long)host_.size());
+    ATDN_HIP(hipMemcpy(dev_.p, host_.data(), host_.size() * sizeof(float), hipMemcpyHostToDevice));
   }
-  const float* dev(long off) const { return dev_ + off; }
-  void release() { if (dev_) { (void)hipFree(dev_); dev_ = nullptr; } }
+  const float* dev(long off) const { return dev_.p + off; }
   size_t bytes() const { return host_.size() * sizeof(float); }
 
  private:
   std::vector<float> host_;
-  float* dev_ = nullptr;
+  DeviceBuf dev_;
 };
 
 // Per-output-channel affine folded into a conv: w' = w*scale[n], b' = b*scale[n] + shift[n]

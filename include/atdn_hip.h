@@ -143,6 +143,13 @@ int atdn_range_probe_launch(const float* x, int64_t rows, int64_t cols, int64_t 
 size_t atdn_gma_workspace_bytes(atdn_gma* h);
 void atdn_gma_destroy(atdn_gma* h);
 
+/* Diagnostic: bytes of device memory the library's buffer owners hold at this moment, over every handle and device of the
+ * process (workspaces, weight arenas, on-demand scratch, the per-call scratch of the unit entries while they run). A handle's
+ * create / finalize / calls raise it, its destroy takes it back to the value from before the create: a leak test compares the
+ * two exactly. Not counted: the three process-lifetime blocks the library never frees (a 256-byte line of zeros, the split-f16
+ * saturation counter, the cached resize tables). Thread-safe. */
+int64_t atdn_device_bytes_live(void);
+
 /* ---------------------------------------------------------------------------------------------------
  * CLVO pose head  —  replaces ATDNVO()  (atdn_vslam/odometry/network.py:20-162)
  *   construction: evaluate_odometry.py:124, neural_slam.py:57-59 ; forward: network.py:122-146
