@@ -93,6 +93,13 @@ SIGNATURES = {
                                  C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "atdn_pnp_solve_host": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                                       C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp]),
+    "atdn_pose_graph_workspace_bytes": (C.c_long, [C.c_int, C.c_int, C.c_int]),
+    "atdn_pose_graph_terms": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "atdn_pose_graph_terms_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp]),
+    "atdn_pose_graph_solve": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
+                                        C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "atdn_pose_graph_solve_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
+                                             C.c_double, _vp, _vp, _vp, _vp]),
     "atdn_map_search": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "atdn_map_gather_images_u8": (C.c_int, [_vp, C.c_int, C.c_long, _vp, C.c_int, _vp, _vp]),
     "atdn_corr_lookup": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),

@@ -376,18 +376,19 @@ class KeyframeMap:
             a += b
         return torch.cat(poses).cpu(), torch.cat(counts).cpu()
 
-    def _relocalize_verified(self, q, dist, indices, flow_net, odometry_net, calib=None):
-        """The verify=True half of `relocalize` (called under its device and no_grad): q [Q,3,H,W] fp32 on the device, `dist`
-        the device distances, `indices` [Q,top_k] int64 on the host; `calib` not None: with the geometric leg."""
-        Q, top_k = int(indices.shape[0]), int(indices.shape[1])
-        n = self.hw[0] * self.hw[1]
-        flat = indices.reshape(-1)                                   # pair p = q * top_k + r
-        keyframes = self.images(flat)
-        queries = q.repeat_interleave(top_k, dim=0) if top_k > 1 else q
+    def _evaluate_pairs(self, keyframe_indices, images, flow_net, odometry_net, calib=None):
+        """The evidence for P pairs (keyframe keyframe_indices[p], images[p]) — shared by `_relocalize_verified` and
+        `loop_closure.find_loops`, called under the map's device and no_grad: `flow_net.forward_backward` in chunks of
+        max(1, max_batch // 2) pairs, the consistency mask and count of each chunk (alpha1 = 0.01, alpha2 = 0.5), the pose head's
+        encoder on the forward flows and ONE recurrent step with P independent sequences from the reset state; with `calib`
+        the PnP pose of every pair from the keyframe's depth under the consistency mask. `images` [P,3,H,W] fp32 on the device.
+        Returns host tensors (rot [P,3], tr [P,3], counts [P] int64, geo [P,4,4] or None, geo_counts [P,4] or None)."""
+        P = len(keyframe_indices)
+        keyframes = self.images(keyframe_indices)
         chunk = max(1, int(getattr(flow_net, "max_batch", 1)) // 2)     # 2 * chunk images per flow call
         feats, counts, flows, masks = [], [], [], []
-        for a in range(0, Q * top_k, chunk):
-            fw, bw = flow_net.forward_backward(keyframes[a:a + chunk], queries[a:a + chunk], iters=12)
+        for a in range(0, P, chunk):
+            fw, bw = flow_net.forward_backward(keyframes[a:a + chunk], images[a:a + chunk], iters=12)
             mask, count = transforms._flow_consistency_counts(fw, bw, 0.01, 0.5)
             counts.append(count)
             feats.append(odometry_net.encode(fw))
@@ -396,9 +397,28 @@ class KeyframeMap:
                 masks.append(mask)
         rot, tr, _ = odometry_net.scan(torch.cat(feats, dim=0)[None], state=None, hw=self.hw)
         rot, tr = rot[0].cpu(), tr[0].cpu()
+        geo = geo_counts = None
         if calib is not None:
-            geo, geo_counts = self._geometric(flat.tolist(), flows, masks, rot, tr, calib)
-        counts = torch.cat(counts).cpu().long().view(Q, top_k)
+            geo, geo_counts = self._geometric(list(keyframe_indices), flows, masks, rot, tr, calib)
+        return rot, tr, torch.cat(counts).cpu().long(), geo, geo_counts
+
+    def update_poses(self, poses):
+        """Replace the poses of all keyframes (after a loop closure): [K,4,4], [K,3,4] or [K,12]; the only writer of the
+        map's poses besides `append`. Images, embeddings and depth maps stay: depth lives in the keyframe's own camera."""
+        p = _homogeneous(torch.as_tensor(poses).detach().cpu())
+        if p.shape[0] != self.n:
+            raise ValueError("expected %d poses, got %d" % (self.n, p.shape[0]))
+        self._poses[:self.n] = p
+
+    def _relocalize_verified(self, q, dist, indices, flow_net, odometry_net, calib=None):
+        """The verify=True half of `relocalize` (called under its device and no_grad): q [Q,3,H,W] fp32 on the device, `dist`
+        the device distances, `indices` [Q,top_k] int64 on the host; `calib` not None: with the geometric leg."""
+        Q, top_k = int(indices.shape[0]), int(indices.shape[1])
+        n = self.hw[0] * self.hw[1]
+        flat = indices.reshape(-1)                                   # pair p = q * top_k + r
+        queries = q.repeat_interleave(top_k, dim=0) if top_k > 1 else q
+        rot, tr, counts, geo, geo_counts = self._evaluate_pairs(flat.tolist(), queries, flow_net, odometry_net, calib)
+        counts = counts.view(Q, top_k)
         scores = (counts.double() / float(n)).float()
         chosen = torch.tensor([row.index(max(row)) for row in counts.tolist()], dtype=torch.int64)   # ties: the lower rank
         rows = torch.arange(Q)

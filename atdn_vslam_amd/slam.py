@@ -93,8 +93,14 @@ class NeuralSLAM:
     FLOW_CHECKPOINT = "atdn_vslam/checkpoints/gma-kitti.pth"  # utils/gma_parameters.py
 
     def __init__(self, args, odometry_weights=None, start_mode=None, flow_weights=None, mapping_weights=None,
-                 precision=None, map_options=None, resident_map=False, warm_start=False, calib=None, keyframe_depth="pair"):
+                 precision=None, map_options=None, resident_map=False, warm_start=False, calib=None, keyframe_depth="pair",
+                 loop_closure=False, loop_options=None):
         from .depth import intrinsics
+        if loop_closure and not resident_map:
+            raise ValueError("loop_closure=True needs the keyframe map in device memory: pass resident_map=True")
+        self._loop_closure = bool(loop_closure)
+        self._loop_options = dict(loop_options or {})
+        self.loop_report = None      # the report of the last close_loops()
         if keyframe_depth not in ("pair", "track"):
             raise ValueError('keyframe_depth is "pair" or "track", got %r' % (keyframe_depth,))
         if keyframe_depth == "track" and calib is None:
@@ -147,7 +153,7 @@ class NeuralSLAM:
             for f in glob.glob(os.path.join(self._base, "depth", "*")):
                 os.remove(f)
             # a cold start owns the directory: poses and map weights of an earlier session go too
-            for stale in ("poses.pth", "MappingVAE_weights.pth"):
+            for stale in ("poses.pth", "poses_closed.pth", "MappingVAE_weights.pth"):
                 stale_path = os.path.join(self._base, stale)
                 if os.path.exists(stale_path):
                     os.remove(stale_path)
@@ -185,6 +191,8 @@ class NeuralSLAM:
             self._set_mapping_net(mapping_weights)
             self._embed_keyframes()
             self._mode = "relocalization"
+            if self._loop_closure:
+                self.close_loops(**self._loop_options)
         elif len(self._keyframes) == 0:
             print("There is no explored enviromnent yet!")
         elif self._mode == "mapping" and mapping_weights is not None:
@@ -193,6 +201,25 @@ class NeuralSLAM:
             self._mode = "relocalization"
         else:
             print("Current state is not odometry")
+
+    def close_loops(self, **options):
+        """Close the loops of the keyframe map (relocalisation mode, resident map only): `loop_closure.close_loops` with this
+        object's networks and calibration (`options`: its keyword arguments, `calib` among them). The optimised poses replace
+        the frames' and the map's and are written to `poses_closed.pth` ([K,12]); `poses.pth` stays the raw odometry. Without
+        a verified loop nothing changes and no file is written. Returns the report."""
+        from . import loop_closure
+        if getattr(self, "_map", None) is None:
+            raise RuntimeError("close_loops needs the keyframe map in device memory: construct NeuralSLAM(..., resident_map=True)")
+        if self._mode != "relocalization":
+            raise Exception("SLAM called in invalid state!")
+        options.setdefault("calib", self._calib)
+        report = loop_closure.close_loops(self._map, self._flow_for_batches(), self._odometry_net, **options)
+        self.loop_report = report
+        if report["counts"] is not None:
+            for i, kf in enumerate(self._keyframes):
+                kf.pose = self._map.poses[i].clone()
+            torch.save(self._map.poses[:, :3, :].reshape(-1, 12).clone(), os.path.join(self._base, "poses_closed.pth"))
+        return report
 
     @torch.no_grad()
     def __call__(self, im):
@@ -336,12 +363,16 @@ class NeuralSLAM:
         if self._resident:
             from .keyframe_map import KeyframeMap
             self._map = KeyframeMap.from_directory(self._base, self._device)
+            closed = os.path.join(self._base, "poses_closed.pth")
+            if embed and os.path.exists(closed):                  # a relocalisation start after a loop closure
+                self._map.update_poses(torch.load(closed))
             files = sorted(glob.glob(os.path.join(self._base, "rgb", "*.pth")))
             self._keyframes = [Frame(f, self._map.poses[i].clone()) for i, f in enumerate(files)]
             if embed:
                 self._embed_keyframes()
             return
-        poses = _homogeneous(torch.load(os.path.join(self._base, "poses.pth")))
+        closed = os.path.join(self._base, "poses_closed.pth")
+        poses = _homogeneous(torch.load(closed if embed and os.path.exists(closed) else os.path.join(self._base, "poses.pth")))
         files = sorted(glob.glob(os.path.join(self._base, "rgb", "*")))
         for i, f in enumerate(files):
             code = self._embed(torch.load(f)) if embed else None

@@ -389,6 +389,136 @@ def flow_track_step(flow, acc, alive, pose=None, calib=None, mask=None, depth=No
     return a_out, l_out, d_ret, counts
 
 
+def _graph_rows(x, what):
+    """Poses [n,4,4], [n,3,4] or [n,12], or those with a batch axis in front -> (float32 [B,n,12] on x's device, batched)."""
+    p = torch.as_tensor(x)
+    if p.dim() >= 3 and tuple(p.shape[-2:]) in ((4, 4), (3, 4)):
+        p = p[..., :3, :].reshape(tuple(p.shape[:-2]) + (12,))
+    if p.dim() not in (2, 3) or p.shape[-1] != 12:
+        raise RuntimeError("expected %s [n,4,4], [n,3,4] or [n,12], or batched, got %s" % (what, tuple(torch.as_tensor(x).shape)))
+    batched = p.dim() == 3
+    return (p if batched else p[None]).detach().float().contiguous(), batched
+
+
+def _pose_graph_inputs(poses, edge_index, edge_pose, edge_weight, edge_robust, fixed, robust_scale):
+    """The checked, contiguous inputs of `pose_graph_terms` and `pose_graph_optimize`, with the batch axis added."""
+    p, batched = _graph_rows(poses, "poses")
+    dev = p.device
+    B, N = p.shape[:2]
+    z, zb = _graph_rows(edge_pose, "edge poses")
+    E = z.shape[1]
+
+    def arg(t, shape, dtype, what):
+        if t is None:
+            return None
+        t = torch.as_tensor(t)
+        if t.device != dev:
+            raise RuntimeError("poses on %s but %s on %s" % (dev, what, t.device))
+        if t.dim() == len(shape) - 1:
+            t = t[None]
+        if tuple(t.shape) != shape:
+            raise RuntimeError("expected %s of shape %s, got %s" % (what, shape, tuple(t.shape)))
+        if dtype == torch.uint8 and t.dtype != torch.uint8:
+            t = t != 0
+        return t.detach().to(dtype).contiguous()
+
+    if z.device != dev or z.shape[0] != B or zb != batched:
+        raise RuntimeError("expected edge poses [%s%d,12] on %s" % ("%d," % B if batched else "", E, dev))
+    idx = arg(edge_index, (B, 2, E), torch.int32, "edge_index")
+    w = arg(edge_weight, (B, E, 2), torch.float64, "edge_weight")
+    if idx is None or w is None:
+        raise RuntimeError("edge_index and edge_weight are required")
+    rob = arg(edge_robust, (B, E), torch.uint8, "edge_robust")
+    fix = arg(fixed, (B, N), torch.uint8, "fixed")
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    return batched, dev, (B, N, E), (p, idx, z, w, rob, fix), ptr
+
+
+def pose_graph_terms(poses, edge_index, edge_pose, edge_weight, edge_robust=None, robust_scale=None):
+    """The cost of a pose graph at given poses. `poses` [N,4,4], [N,3,4] or [N,12] (or with a batch axis in front: B graphs of the
+    same N and E, each on its own) are the nodes, world <- camera, as `KeyframeMap.poses` holds them. `edge_index` [2,E] integers:
+    edge e joins node i = edge_index[0,e] and j = edge_index[1,e]; `edge_pose` [E,4,4] (or [E,12]) its measurement of
+    T_i^-1 T_j — what `transform(rot, tr)` of the pair (image i, image j) and `pose_from_depth` return; `edge_weight` [E,2] =
+    (w_rot, w_tr) >= 0, 1/sigma^2 in rad^-2 and m^-2; `edge_robust` [E] marks the edges under the Geman-McClure loss of scale
+    `robust_scale` (in sigmas; None = 1). Returns `(cost, edge_chi2, counts)` on the poses' device: `cost` float64 [B] (or a
+    scalar), `edge_chi2` float64 [B,E] = w_rot |a|^2 + w_tr |te|^2 of every edge (a: the chordal rotation error, te: the
+    translation error; +0.0 for an absent edge) and `counts` int32 [B,2] = (valid edges, absent ones: an index outside [0, N),
+    i == j or a weight that is not >= 0). Device tensors go through libatdn_hip's kernel on the current stream (one launch, no
+    synchronisation), CPU tensors through the library's host form. The rule is float64, fixes the order of every sum and is
+    stated in full in include/atdn_hip.h, atdn_pose_graph_terms; the same bits on every call and on both paths."""
+    batched, dev, (B, N, E), t, ptr = _pose_graph_inputs(poses, edge_index, edge_pose, edge_weight, edge_robust, None, robust_scale)
+    cost = torch.empty((B,), dtype=torch.float64, device=dev)
+    chi2 = torch.empty((B, E), dtype=torch.float64, device=dev)
+    counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    args = tuple(ptr(x) for x in t[:5]) + (B, N, E, 1.0 if robust_scale is None else float(robust_scale), ptr(cost), ptr(chi2),
+                                           ptr(counts))
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            ws = _pose_graph_workspace(B, N, E, dev)
+            _lib.check(L.atdn_pose_graph_terms(*args, ptr(ws), _stream()))
+    else:
+        _lib.check(L.atdn_pose_graph_terms_host(*args))
+    return (cost, chi2, counts) if batched else (cost[0], chi2[0], counts[0])
+
+
+def _pose_graph_workspace(B, N, E, device):
+    n = int(_lib.lib().atdn_pose_graph_workspace_bytes(B, N, E))
+    return torch.empty((max(n, 8) + 7) // 8, dtype=torch.float64, device=device)
+
+
+def pose_graph_optimize(poses, edge_index, edge_pose, edge_weight, edge_robust=None, robust_scale=None, fixed=None, iters=10,
+                        cg_iters=64, cg_tol=1e-8):
+    """The poses that agree best with the edges of a pose graph (loop closure): `iters` Levenberg-Marquardt steps from `poses`,
+    each a conjugate-gradient solve (at most `cg_iters` iterations, to a relative residual `cg_tol`) preconditioned by the
+    block-tridiagonal part of the system, every graph of the batch in its own workgroup, all in one launch. Arguments as for
+    `pose_graph_terms`; `fixed` [N] marks the nodes that are held (default: node 0, the gauge). `robust_scale` may be a sequence,
+    large to small: the graph is solved with each scale in turn, each from the last result — the Geman-McClure loss only works
+    when the drift at a loop is within its scale; far beyond it every robust edge saturates and nothing moves.
+    Returns `(poses, cost, edge_chi2, counts)` on the poses' device: `poses` float32 in the shape of the input (4 x 4 inputs come
+    back 4 x 4 with the last row copied), `cost` float64 [B,2] ([2]) = (the cost at the input — of the last scale —, the cost
+    reached), `edge_chi2` float64 [B,E] at the returned poses, `counts` int32 [B,4] = (valid edges, absent edges, accepted
+    steps, CG iterations; the last two summed over a sequence of scales). A held node, and one without an edge of positive weight,
+    comes back with its input bits; so does every node when no step is accepted. An edge of weight (0, 0) gives the same bits as
+    the list without it. CPU tensors go through the library's host form. The rule is stated in full in include/atdn_hip.h,
+    atdn_pose_graph_solve; the same inputs give the same bits on every call and on both paths."""
+    batched, dev, (B, N, E), t, ptr = _pose_graph_inputs(poses, edge_index, edge_pose, edge_weight, edge_robust, fixed, robust_scale)
+    p, idx, z, w, rob, fix = t
+    if fix is None:
+        fix = torch.zeros((B, N), dtype=torch.uint8, device=dev)
+        fix[:, 0] = 1
+    scales = [1.0] if robust_scale is None else [float(s) for s in (robust_scale if isinstance(robust_scale, (list, tuple))
+                                                                    else [robust_scale])]
+    if not scales:
+        raise RuntimeError("robust_scale is an empty sequence")
+    L = _lib.lib()
+    total = None
+    for scale in scales:
+        rows = torch.empty((B, N, 12), dtype=torch.float32, device=dev)
+        cost = torch.empty((B, 2), dtype=torch.float64, device=dev)
+        chi2 = torch.empty((B, E), dtype=torch.float64, device=dev)
+        counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        args = (ptr(p), ptr(idx), ptr(z), ptr(w), ptr(rob), ptr(fix), B, N, E, scale, int(iters), int(cg_iters), float(cg_tol),
+                ptr(rows), ptr(cost), ptr(chi2), ptr(counts))
+        if dev.type == "cuda":
+            with torch.cuda.device(dev):
+                ws = _pose_graph_workspace(B, N, E, dev)
+                _lib.check(L.atdn_pose_graph_solve(*args, ptr(ws), _stream()))
+        else:
+            _lib.check(L.atdn_pose_graph_solve_host(*args))
+        if total is not None:
+            counts[:, 2:] += total[:, 2:]
+        total = counts
+        p = rows
+    src = torch.as_tensor(poses)
+    if src.shape[-1] == 12:
+        out = rows.view(src.shape)
+    else:
+        out = src.detach().float().clone()
+        out[..., :3, :] = rows.view(tuple(src.shape[:-2]) + (3, 4))
+    return (out, cost, chi2, total) if batched else (out, cost[0], chi2[0], total[0])
+
+
 class InputPadder:
     """Replicate-pads frames to multiples of 8 ('sintel' mode splits the padding on both sides)."""
 

@@ -560,6 +560,113 @@ int atdn_pnp_solve_host(const float* depth, const float* flow, const unsigned ch
                         float* pose_out, double* cost, int* counts);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Pose-graph optimisation (loop closure)  —  the poses of the keyframes are the nodes, a measured relative pose between two of
+ * them is an edge: consecutive keyframes by odometry, revisits by relocalisation and PnP. Levenberg-Marquardt over the graph
+ * with a conjugate-gradient solve preconditioned by the block-tridiagonal part of the system (a keyframe graph is a chain plus
+ * a few loops), batched over graphs, all on the device in ONE launch. atdn_pose_graph_terms is one evaluation,
+ * atdn_pose_graph_solve the solver. The reference has nothing like it.
+ * ------------------------------------------------------------------------------------------------- */
+
+/* Bytes of the workspace of atdn_pose_graph_terms / atdn_pose_graph_solve for B graphs of N nodes and E edges (0 for sizes they
+ * refuse): per graph 190 float64 per node, 122 per edge and (5 E + 3 N + 1) int32 rounded up to 8 bytes. No call reads what an
+ * earlier call left there. */
+long atdn_pose_graph_workspace_bytes(int B, int N, int E);
+
+/* cost[b] = the cost of graph b at poses[b], edge_chi2[b][e] = c_e of every edge, counts[b] = (valid edges, absent edges).
+ *   poses [B,N,12] fp32 DEVICE: the rows of [R|t] of every node, world <- camera. edge_index [B,2,E] int32 DEVICE: the i's of
+ *   the E edges, then their j's. edge_pose [B,E,12] fp32 DEVICE: the rows of the measurement Z_e = [Rz|tz] of T_i^-1 T_j.
+ *   edge_weight [B,E,2] float64 DEVICE = (w_rot, w_tr), 1/sigma^2 in rad^-2 and m^-2, 8-byte aligned. edge_robust [B,E] uint8
+ *   DEVICE or NULL: a non-zero byte puts the edge under the Geman-McClure loss of scale robust_scale (NULL: none).
+ *   cost [B] float64, edge_chi2 [B,E] float64 (both 8-byte aligned), counts [B,2] int32, workspace of
+ *   atdn_pose_graph_workspace_bytes(B, N, E) bytes (8-byte aligned), all DEVICE; no output (the workspace is one) overlaps an
+ *   input or another output. 1 <= B <= 1024, 2 <= N <= 2048, 1 <= E <= 8192, robust_scale finite and > 0. Anything else fails
+ *   before a launch. The B graphs are independent.
+ * The rule: everything in float64, every operation rounded on its own (no fused multiply-add), only + - * / and comparisons, in
+ * exactly this order. dot3(a, b) = (a0*b0 + a1*b1) + a2*b2. Poses and measurements are converted to float64 exactly.
+ * Edge e = (i, j) is ABSENT if i or j is outside [0, N), i == j, or a weight fails 0 <= w <= DBL_MAX: it contributes nothing,
+ * reads no pose and has edge_chi2 = +0.0. An edge that is not absent is valid; a valid edge with w_rot == 0 and w_tr == 0 is
+ * IDLE: it is counted, has edge_chi2 = c_e (+0.0) and takes part in nothing else, so that it gives the same bits as the list
+ * without it. The other valid edges are ACTIVE.
+ * Residual of an edge at (R_i, t_i), (R_j, t_j):
+ *   M_ab = dot3(column a of R_i, column b of R_j);  Re_ab = dot3(column a of Rz, column b of M)          (Re = Rz^T R_i^T R_j)
+ *   d = t_j - t_i;  tm_a = dot3(column a of R_i, d);  u = tm - tz;  te_a = dot3(column a of Rz, u)
+ *   a = (0.5*(Re_21 - Re_12), 0.5*(Re_02 - Re_20), 0.5*(Re_10 - Re_01))       (indices from 0: the chordal rotation error, sin of
+ *     the angle times the axis, no trigonometry; monotone in the angle below 90 degrees, far above any drift a loop closure sees)
+ *   c_e = w_rot*dot3(a, a) + w_tr*dot3(te, te)
+ *   not robust: cost term c_e, omega = 1.  robust, q = robust_scale*robust_scale: s = q + c_e, cost term (q*c_e)/s,
+ *   omega = (q/s)*(q/s)
+ * Cost: node n's share is the sum of the cost terms of the active edges whose i is n, in ascending edge number (+0.0 without
+ * one); the cost is the ordered sum of the shares over the nodes (below). Summing by node rather than by edge number is what
+ * makes an idle edge invisible.
+ * Ordered sum over the nodes n = 0 .. N-1: chunks of 256 consecutive nodes, +0.0 beyond N; in a chunk for stride = 1, 2, .., 128:
+ * v[i] = v[i] + v[i + stride] for every i that is a multiple of 2*stride; the chunk sums are added in chunk order (the tree of
+ * atdn_pnp_terms).
+ * One launch on `stream`: asynchronous, capturable, no host synchronisation, no atomics, no memset. */
+int atdn_pose_graph_terms(const float* poses, const int* edge_index, const float* edge_pose, const double* edge_weight,
+                          const unsigned char* edge_robust, int B, int N, int E, double robust_scale, double* cost,
+                          double* edge_chi2, int* counts, void* workspace, void* stream);
+/* The same function on HOST buffers in plain C++ float64 (csrc/pose_graph_host.h, the functions the kernel calls too): serves
+ * CPU tensors, needs no GPU and no workspace, the same bits. */
+int atdn_pose_graph_terms_host(const float* poses, const int* edge_index, const float* edge_pose, const double* edge_weight,
+                               const unsigned char* edge_robust, int B, int N, int E, double robust_scale, double* cost,
+                               double* edge_chi2, int* counts);
+
+/* poses_out[b] = the poses of graph b after `iters` Levenberg-Marquardt steps (iters + 1 cost evaluations). Arguments as for
+ * atdn_pose_graph_terms, and: fixed [B,N] uint8 DEVICE or NULL (a non-zero byte holds the node; NULL: none is held — the
+ * caller should hold at least one, the gauge), 0 <= iters <= 32, 1 <= cg_iters <= 128, cg_tol finite and > 0, poses_out
+ * [B,N,12] fp32, cost [B,2] float64 = (the cost at poses, the last accepted cost), edge_chi2 [B,E] float64 = c_e at poses_out
+ * (what atdn_pose_graph_terms returns for poses_out), counts [B,4] int32 = (valid edges, absent edges, accepted steps, CG
+ * iterations in total).
+ * A node is FREE if it is not held and has at least one active edge; every other node is left out of the system and its pose
+ * comes back with the input bits. A step moves node n by x_n = (dw, dt): R <- R C(dw), t <- R dt + t (C: the Cayley map below).
+ * Jacobians of (a, te) of an edge with respect to that step (6 x 6, rows (a, te), columns (dw, dt); tr = (Re_00 + Re_11) + Re_22):
+ *   node j: rows 0..2: 0.5*(tr - Re_aa) on the diagonal, -0.5*Re_ba off it, then zeros; rows 3..5: zeros, then Re
+ *   node i: rows 0..2: -0.5*dot3(row a of G, row b of Rz) with G_aa = tr - Re_aa, G_ab = -Re_ab, then zeros;
+ *           rows 3..5: P_ab = dot3(column a of Rz, column b of [tm]x) with [tm]x = ((0, -tm2, tm1), (tm2, 0, -tm0), (-tm1, tm0, 0)),
+ *           then -Rz^T
+ * With w = omega*(w_rot, w_rot, w_rot, w_tr, w_tr, w_tr), an edge's blocks are (X^T W Y)_ab = the sum over k = 0..5, in that
+ * order, of (w_k*X_ka)*Y_kb — the products with the structural zeros formed like any other —: A_ii = Ji^T W Ji and
+ * A_jj = Jj^T W Jj (a <= b computed, the rest mirrored), A_ij = Ji^T W Jj; its gradients g_a = the sum over k of (w_k*J_ka)*r_k
+ * with r = (a, te).
+ * A free node's diagonal block D_n and gradient g_n are the sums of A_ii / g_i (where it is the edge's i) or A_jj / g_j (where it
+ * is the j) over its active edges in ascending edge number. The damped system: A = D_n with (D_n)_aa + lambda*(D_n)_aa on the
+ * diagonal, and for every active edge between two free nodes A_ij at (i, j) and its transpose at (j, i). (A p)_n = the rows of
+ * the damped D_n times p_n (b ascending), then + the edge blocks times the other node's p, edge by edge in ascending edge number
+ * (each a sum over b ascending). U_n, the block (n, n+1) of the preconditioner, exists where n and n+1 are both free: the sum
+ * over the active edges that join them, in ascending edge number, of A_ij (i == n) or its transpose (zeros without such an edge).
+ * Block LDL^T, n ascending over the free nodes: S_n = damped D_n, minus, where n-1 is free, for a >= b the sum over c ascending
+ * of (U_{n-1})_ca*(W_{n-1})_cb; S_n = L diag(d) L^T by the 6 x 6 recurrence of atdn_pnp_solve on its lower triangle; a pivot that
+ * is not > 0 fails the step; where n+1 is free, W_n = S_n^-1 U_n column by column (forward, divide, backward as there).
+ * z = M^-1 r: forwards y_n = r_n - (sum over c ascending of (W_{n-1})_ca*(y_{n-1})_c) where n-1 is free; backwards
+ * z_n = S_n^-1 y_n - (sum over c ascending of (W_n)_ac*(z_{n+1})_c) where n+1 is free. Vectors are +0.0 at nodes that are not free.
+ * Dot products: a node's six products summed in index order, then the ordered sum over the nodes.
+ * PCG for A x = -g: x = 0, r = -g, z = M^-1 r, p = z, rz = r.z, thr = (cg_tol*cg_tol)*rz; no iteration unless rz > 0 (a zero
+ * right-hand side gives a zero step). At most cg_iters times: pAp = p.(A p); stop unless pAp > 0; alpha = rz/pAp;
+ * x = x + alpha*p; r = r - alpha*(A p) (one iteration counted); z = M^-1 r; rz' = r.z; stop unless rz' > thr; beta = rz'/rz;
+ * p = z + beta*p; rz = rz'.
+ * Retraction of a free node (the Cayley map of atdn_pnp_solve): h = 0.5*dw, n2 = (h0*h0 + h1*h1) + h2*h2, f = 2/(1 + n2),
+ *   M_ii = h_i*h_i - n2, M_ij = K_ij + h_i*h_j with K = [h]x, C_ii = 1 + f*M_ii, C_ij = f*M_ij;
+ *   R'_ab = dot3(row a of R, column b of C), t'_a = dot3(row a of R, dt) + t_a.
+ * Outer loop: the first evaluation is at poses and is the accepted point, lambda = 1e-3. Each of the `iters` steps: linearise at
+ * the accepted point (unless the last step was rejected: the linearisation stands), factor, PCG, retract, evaluate the cost
+ * at the trial; accepted iff cost_trial < cost_accepted (a NaN fails); on accept lambda = max(lambda/3, 1e-9), on reject
+ * lambda = min(4*lambda, 1e6) (the decision rule and the constants of atdn_pnp_solve). A failed pivot or a step with some
+ * |x| <= DBL_MAX failing is a rejection without an evaluation.
+ * Output: each value of an accepted free node's pose rounded to fp32 once; with no accepted step every pose holds the input bits.
+ * The Geman-McClure loss works when the drift at a loop is within robust_scale: far beyond it every robust edge saturates
+ * (omega -> 0) and nothing moves — a property of the loss. Solve with a large scale first, then a smaller one.
+ * One launch of one workgroup per graph on `stream`: asynchronous, capturable, no host synchronisation, no atomics, no memset;
+ * every loop bound is an argument. */
+int atdn_pose_graph_solve(const float* poses, const int* edge_index, const float* edge_pose, const double* edge_weight,
+                          const unsigned char* edge_robust, const unsigned char* fixed, int B, int N, int E, double robust_scale,
+                          int iters, int cg_iters, double cg_tol, float* poses_out, double* cost, double* edge_chi2, int* counts,
+                          void* workspace, void* stream);
+int atdn_pose_graph_solve_host(const float* poses, const int* edge_index, const float* edge_pose, const double* edge_weight,
+                               const unsigned char* edge_robust, const unsigned char* fixed, int B, int N, int E,
+                               double robust_scale, int iters, int cg_iters, double cg_tol, float* poses_out, double* cost,
+                               double* edge_chi2, int* counts);
+
+/* ---------------------------------------------------------------------------------------------------
  * Keyframe map  —  replaces the keyframe list of NeuralSLAM's relocalisation (keyframe_map.py)
  *   embeddings: Frame.embedding, one MappingVAE call per keyframe (slam_framework/neural_slam.py:88-103,158-164)
  *   search:     the per-keyframe torch.norm loop, torch.stack and argmin (neural_slam.py:374-383)
