@@ -1,5 +1,5 @@
 // Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip), shared by each device
-// entry point and its host twin in capi.hip.
+// entry point and its host twin in capi.hip, and the overlap rule that the pose solvers (pnp.hip, pose_graph.hip) share.
 #pragma once
 #include <cmath>
 
@@ -14,6 +14,16 @@ inline void check_plane_batch(int B, int H, int W, bool grid_limit = true) {
   ATDN_CHECK(B >= 1 && H >= 1 && W >= 1, "bad batch or image size");
   if (grid_limit) ATDN_CHECK(B <= 65535, "batch too large (B <= 65535)");
   ATDN_CHECK((long)H * W <= (1L << 24), "image too large (H * W <= 2^24)");
+}
+
+// in[k] of in_bytes[k] (null: not given), out[i] of out_bytes[i]: no output may overlap an input or another output
+inline void check_disjoint(const void* const* in, const long* in_bytes, int n_in, const void* const* out, const long* out_bytes,
+                           int n_out) {
+  for (int i = 0; i < n_out; ++i) {
+    for (int k = 0; k < n_in; ++k)
+      if (in[k]) ATDN_CHECK(disjoint(in[k], in_bytes[k], out[i], out_bytes[i]), "an output overlaps an input");
+    for (int j = 0; j < i; ++j) ATDN_CHECK(disjoint(out[j], out_bytes[j], out[i], out_bytes[i]), "two outputs overlap");
+  }
 }
 
 inline void check_pinhole(double fx, double fy, double cx, double cy) {

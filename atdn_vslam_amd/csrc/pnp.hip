@@ -1,7 +1,8 @@
 // Pose from depth and flow on the device: the reprojection terms of a pose (atdn_pnp_terms) and a Levenberg-Marquardt solve over
 // them (atdn_pnp_solve), batched over problems. The rule — float64, every operation rounded on its own — is pnp_pixel,
-// pnp_lm_update, pnp_lm_step and pnp_output of pnp_host.h, which these kernels call, so the kernels and the host form evaluate
-// one function, and the ORDER of every sum is part of the rule (include/atdn_hip.h): the same bits on every call and on both paths.
+// pnp_lm_update, pnp_lm_step and pnp_output of pnp_host.h (over the 6 x 6 algebra of lm6.h), which these kernels call, so the
+// kernels and the host form evaluate one function, and the ORDER of every sum is part of the rule (include/atdn_hip.h): the same
+// bits on every call and on both paths.
 //
 // Two launches per evaluation, nothing else on the stream (no memset, no atomics, no host synchronisation; capturable):
 //   pnp_terms_kernel     (chunks, B) workgroups of pixel_quads.h with off = 0: workgroup c of plane b owns the flat indices
@@ -11,8 +12,8 @@
 //                        workspace (store-and-sum: cdna_hip_programming.md, Guideline 12).
 //   pnp_finalise_kernel  one wave per problem: thread e < 28 adds the chunk sums of term e in chunk order (coalesced: the 28
 //                        terms of a chunk are contiguous), threads 32 .. 34 the integer counts; thread 0 then either writes the
-//                        sums out (atdn_pnp_terms) or takes the Levenberg-Marquardt decision and the next step (a 6 x 6 LDL^T,
-//                        fully unrolled, in registers) on the problem's PnpState in the workspace.
+//                        sums out (atdn_pnp_terms) or takes the Levenberg-Marquardt decision and the next step (the 6 x 6 LDL^T
+//                        of lm6.h, fully unrolled, in registers) on the problem's PnpState in the workspace.
 // The pose of evaluation 0 is read from the caller's float32 pose by both kernels; later ones from the state.
 #include "../../include/atdn_hip.h"
 
@@ -209,11 +210,7 @@ void pnp_check_args(const float* depth, const float* flow, const unsigned char* 
   const long n = (long)H * W;
   const void* in[4] = {depth, flow, mask, pose};
   const long in_bytes[4] = {(long)B * n * 4, (long)B * 2 * n * 4, (long)B * n, (long)B * 48};
-  for (int i = 0; i < n_out; ++i) {
-    for (int k = 0; k < 4; ++k)
-      if (in[k]) ATDN_CHECK(disjoint(in[k], in_bytes[k], out[i], out_bytes[i]), "an output overlaps an input");
-    for (int j = 0; j < i; ++j) ATDN_CHECK(disjoint(out[j], out_bytes[j], out[i], out_bytes[i]), "two outputs overlap");
-  }
+  check_disjoint(in, in_bytes, 4, out, out_bytes, n_out);
 }
 
 }  // namespace atdn

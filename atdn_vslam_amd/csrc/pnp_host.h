@@ -1,17 +1,18 @@
 // Pose from depth and flow (robust PnP), the rule in plain C++ float64 (no HIP needed). A depth map of image 1 gives a 3-D point
 // per pixel, the flow image 1 -> image 2 gives that point's pixel in image 2: pnp_pixel is the contribution of one pixel to the
 // Gauss-Newton normal equations of the reprojection error under the Geman-McClure loss, pnp_plane_host the fixed-order sum of
-// a plane (chunks of 1024 pixels), pnp_lm_update / pnp_lm_step one Levenberg-Marquardt decision and step, pnp_terms_host /
-// pnp_solve_host the host forms behind atdn_pnp_terms_host / atdn_pnp_solve_host (capi.hip), which serve CPU tensors. The
-// kernels of pnp.hip call the same functions, so the two cannot drift apart; the independent statement the tests compare both
-// with is tests/pnp_ref.py (NumPy). The rule is stated in full in include/atdn_hip.h, atdn_pnp_terms and atdn_pnp_solve; only
-// + - * / and comparisons, every operation rounded on its own (fp contraction off).
+// a plane (chunks of 1024 pixels), pnp_lm_update / pnp_lm_step one Levenberg-Marquardt decision and step (the 6 x 6 algebra, the
+// Cayley matrix and the damping constants are those of lm6.h, shared with the pose graph; the composition from the left is
+// PnP's own), pnp_terms_host / pnp_solve_host the host forms behind atdn_pnp_terms_host / atdn_pnp_solve_host (capi.hip), which
+// serve CPU tensors. The kernels of pnp.hip call the same functions, so the two cannot drift apart; the independent statement
+// the tests compare both with is tests/pnp_ref.py (NumPy). The rule is stated in full in include/atdn_hip.h, atdn_pnp_terms and
+// atdn_pnp_solve; only + - * / and comparisons, every operation rounded on its own (fp contraction off).
 #pragma once
 #include <cfloat>
 #include <cmath>
 #include <vector>
 
-#include "pixel_rule.h"
+#include "lm6.h"
 
 namespace atdn {
 
@@ -61,10 +62,7 @@ ATDN_HD inline void pnp_internal_pose(const float* pose12, double p[12]) {
   }
   for (int i = 0; i < 3; ++i) {
     for (int j = 0; j < 3; ++j) p[3 * i + j] = r[j][i];
-    const double a = r[0][i] * t[0], b = r[1][i] * t[1], c = r[2][i] * t[2];
-    const double ab = a + b;
-    const double s = ab + c;
-    p[9 + i] = -s;
+    p[9 + i] = -dot3(r[0][i], t[0], r[1][i], t[1], r[2][i], t[2]);
   }
 }
 
@@ -73,10 +71,7 @@ ATDN_HD inline void pnp_public_pose(const double p[12], float* pose12) {
 #pragma clang fp contract(off)
   for (int i = 0; i < 3; ++i) {
     for (int j = 0; j < 3; ++j) pose12[4 * i + j] = (float)p[3 * j + i];
-    const double a = p[i] * p[9], b = p[3 + i] * p[10], c = p[6 + i] * p[11];
-    const double ab = a + b;
-    const double s = ab + c;
-    pose12[4 * i + 3] = (float)(-s);
+    pose12[4 * i + 3] = (float)(-dot3(p[i], p[9], p[3 + i], p[10], p[6 + i], p[11]));
   }
 }
 
@@ -97,12 +92,7 @@ ATDN_HD inline int pnp_pixel(float zf, float u, float v, bool keep, const double
   const double X1 = zx / c.fx, Y1 = zy / c.fy;
   double Xc[3];
 #pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const double a = P[3 * i] * X1, b = P[3 * i + 1] * Y1, d = P[3 * i + 2] * z;
-    const double ab = a + b;
-    const double abd = ab + d;
-    Xc[i] = abd + P[9 + i];
-  }
+  for (int i = 0; i < 3; ++i) Xc[i] = dot3(P[3 * i], X1, P[3 * i + 1], Y1, P[3 * i + 2], z) + P[9 + i];
   const double X = Xc[0], Y = Xc[1], Z = Xc[2];
   if (!(Z >= c.min_z)) {
     t[27] = c.rho_behind;
@@ -155,109 +145,34 @@ ATDN_HD inline void pnp_lm_update(PnpState& s, const double* sums, const int* co
   if (k == 0) {
     s.lambda = 1e-3;
     s.accepted = 0;
-  } else if (accept) {
-    const double l = s.lambda / 3.0;
-    s.lambda = l > 1e-9 ? l : 1e-9;
-    s.accepted += 1;
   } else {
-    const double l = 4.0 * s.lambda;
-    s.lambda = l < 1e6 ? l : 1e6;
+    s.lambda = lm_lambda(s.lambda, accept);
+    if (accept) s.accepted += 1;
   }
 }
 
 // The damped step from the accepted point: s.trial = retract(s.acc, delta), or s.acc again where the factorisation fails.
 ATDN_HD inline void pnp_lm_step(PnpState& s) {
 #pragma clang fp contract(off)
-  double A[6][6], L[6][6], D[6], dl[6];
+  double A[36], F[21], b[6], dl[6], E[9];
   int n = 0;
   for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j) {
-      A[i][j] = s.sums[n];
-      A[j][i] = s.sums[n];
-      ++n;
-    }
+    for (int j = i; j < 6; ++j) A[6 * i + j] = A[6 * j + i] = s.sums[n++];
   for (int i = 0; i < 6; ++i) {
-    const double l = s.lambda * A[i][i];
-    A[i][i] = A[i][i] + l;
+    const double l = s.lambda * A[7 * i];
+    A[7 * i] = A[7 * i] + l;
+    b[i] = -s.sums[21 + i];
   }
-  // no early exit: after a failed pivot the remaining values are garbage that is computed and never used
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double dj = A[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) {
-      const double ld = L[j][k] * D[k];
-      const double lld = L[j][k] * ld;
-      dj = dj - lld;
-    }
-    ok = ok && dj > 0.0;
-    D[j] = dj;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double l = A[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) {
-        const double ld = L[j][k] * D[k];
-        const double lld = L[i][k] * ld;
-        l = l - lld;
-      }
-      L[i][j] = l / dj;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double y = -s.sums[21 + i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) {
-      const double ly = L[i][k] * dl[k];
-      y = y - ly;
-    }
-    dl[i] = y;
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) dl[i] = dl[i] / D[i];
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double y = dl[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; ++k) {
-      const double ly = L[k][i] * dl[k];
-      y = y - ly;
-    }
-    dl[i] = y;
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) ok = ok && dl[i] >= -DBL_MAX && dl[i] <= DBL_MAX;
-  if (!ok) {
+  const bool ok = ldl6_factor(A, F);
+  ldl6_solve(F, b, dl);
+  if (!(ok && finite6(dl))) {
     for (int i = 0; i < 12; ++i) s.trial[i] = s.acc[i];
     return;
   }
-  const double h[3] = {0.5 * dl[0], 0.5 * dl[1], 0.5 * dl[2]};
-  const double h00 = h[0] * h[0], h11 = h[1] * h[1], h22 = h[2] * h[2];
-  const double h01 = h00 + h11;
-  const double n2 = h01 + h22;
-  const double den = 1.0 + n2;
-  const double f = 2.0 / den;
-  const double K[3][3] = {{0.0, -h[2], h[1]}, {h[2], 0.0, -h[0]}, {-h[1], h[0], 0.0}};
-  double E[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      const double hh = h[i] * h[j];
-      const double m = i == j ? hh - n2 : K[i][j] + hh;
-      const double fm = f * m;
-      E[i][j] = i == j ? 1.0 + fm : fm;
-    }
+  cayley3(dl, E);
   for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) {
-      const double a = E[i][0] * s.acc[j], b = E[i][1] * s.acc[3 + j], c = E[i][2] * s.acc[6 + j];
-      const double ab = a + b;
-      s.trial[3 * i + j] = ab + c;
-    }
-    const double a = E[i][0] * s.acc[9], b = E[i][1] * s.acc[10], c = E[i][2] * s.acc[11];
-    const double ab = a + b;
-    const double abc = ab + c;
-    s.trial[9 + i] = abc + dl[3 + i];
+    for (int j = 0; j < 3; ++j) s.trial[3 * i + j] = dot3(E[3 * i], s.acc[j], E[3 * i + 1], s.acc[3 + j], E[3 * i + 2], s.acc[6 + j]);
+    s.trial[9 + i] = dot3(E[3 * i], s.acc[9], E[3 * i + 1], s.acc[10], E[3 * i + 2], s.acc[11]) + dl[3 + i];
   }
 }
 

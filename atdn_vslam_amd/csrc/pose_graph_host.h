@@ -3,16 +3,19 @@
 // Levenberg-Marquardt over the graph with a conjugate-gradient solve preconditioned by the block-tridiagonal part of the system.
 // pg_edge_residual / pg_edge_blocks are one edge's residual and its contribution to the normal equations, pg_node_gather a
 // node's sums over its incident edges, pg_factor_node / pg_sweep_*_all / pg_node_pivot_solve the block LDL^T of the
-// preconditioner and its sweeps, pg_apply_node one block row of A p, pg_retract_node the Cayley retraction, pg_tree_sum the fixed-order sum over nodes.
-// pose_graph_run_host is the host form behind atdn_pose_graph_terms_host / atdn_pose_graph_solve_host (capi.hip); the kernel of
-// pose_graph.hip calls the same per-edge and per-node functions phase by phase, so the two cannot drift apart; the independent
-// statement the tests compare both with is tests/pose_graph_ref.py (NumPy and plain Python floats). The rule is stated in full in
-// include/atdn_hip.h, atdn_pose_graph_solve; only + - * / and comparisons, every operation rounded on its own.
+// preconditioner and its sweeps, pg_apply_node one block row of A p, pg_retract_node the retraction from the right, pg_tree_sum
+// the fixed-order sum over nodes; the 6 x 6 factorisation, the Cayley matrix and the damping constants are those of lm6.h, shared
+// with PnP. pg_solve is the solver itself, written once: every phase from the classification of the edges to the last output,
+// over an executor that says how a phase reaches all edges or nodes. pose_graph_run_host runs it with plain loops (PgHostExec)
+// behind atdn_pose_graph_terms_host / atdn_pose_graph_solve_host, the kernel of pose_graph.hip with a workgroup, so the two
+// cannot drift apart; the independent statement the tests compare both with is tests/pose_graph_ref.py (NumPy and plain Python
+// floats). The rule is stated in full in include/atdn_hip.h, atdn_pose_graph_solve; only + - * / and comparisons, every
+// operation rounded on its own.
 #pragma once
 #include <cfloat>
 #include <vector>
 
-#include "pixel_rule.h"
+#include "lm6.h"
 
 namespace atdn {
 
@@ -79,19 +82,12 @@ ATDN_HD inline PgView pg_carve(void* base, int N, int E) {
   return v;
 }
 
-ATDN_HD inline double pg_dot3(double a0, double b0, double a1, double b1, double a2, double b2) {
-#pragma clang fp contract(off)
-  const double x = a0 * b0, y = a1 * b1, z = a2 * b2;
-  const double xy = x + y;
-  return xy + z;
-}
-
 // out = A^T B (3 x 3, row-major)
 ATDN_HD inline void pg_atb(const double* A, const double* B, double* out) {
 #pragma unroll
   for (int a = 0; a < 3; ++a)
 #pragma unroll
-    for (int b = 0; b < 3; ++b) out[3 * a + b] = pg_dot3(A[a], B[b], A[3 + a], B[3 + b], A[6 + a], B[6 + b]);
+    for (int b = 0; b < 3; ++b) out[3 * a + b] = dot3(A[a], B[b], A[3 + a], B[3 + b], A[6 + a], B[6 + b]);
 }
 
 // public pose (12 float32, rows of [R|t]) -> internal (R row-major, t)
@@ -143,16 +139,16 @@ ATDN_HD inline void pg_edge_residual(const double* Xi, const double* Xj, const f
   pg_atb(o.Rz, M, o.Re);
   const double d0 = Xj[9] - Xi[9], d1 = Xj[10] - Xi[10], d2 = Xj[11] - Xi[11];
 #pragma unroll
-  for (int a = 0; a < 3; ++a) o.tm[a] = pg_dot3(Xi[a], d0, Xi[3 + a], d1, Xi[6 + a], d2);
+  for (int a = 0; a < 3; ++a) o.tm[a] = dot3(Xi[a], d0, Xi[3 + a], d1, Xi[6 + a], d2);
   const double u0 = o.tm[0] - tz[0], u1 = o.tm[1] - tz[1], u2 = o.tm[2] - tz[2];
 #pragma unroll
-  for (int a = 0; a < 3; ++a) o.r[3 + a] = pg_dot3(o.Rz[a], u0, o.Rz[3 + a], u1, o.Rz[6 + a], u2);
+  for (int a = 0; a < 3; ++a) o.r[3 + a] = dot3(o.Rz[a], u0, o.Rz[3 + a], u1, o.Rz[6 + a], u2);
   const double s0 = o.Re[7] - o.Re[5], s1 = o.Re[2] - o.Re[6], s2 = o.Re[3] - o.Re[1];
   o.r[0] = 0.5 * s0;
   o.r[1] = 0.5 * s1;
   o.r[2] = 0.5 * s2;
-  const double aa = pg_dot3(o.r[0], o.r[0], o.r[1], o.r[1], o.r[2], o.r[2]);
-  const double tt = pg_dot3(o.r[3], o.r[3], o.r[4], o.r[4], o.r[5], o.r[5]);
+  const double aa = dot3(o.r[0], o.r[0], o.r[1], o.r[1], o.r[2], o.r[2]);
+  const double tt = dot3(o.r[3], o.r[3], o.r[4], o.r[4], o.r[5], o.r[5]);
   const double ca = wr * aa, ct = wt * tt;
   o.c = ca + ct;
   if (robust) {
@@ -214,7 +210,7 @@ ATDN_HD inline void pg_edge_blocks(const PgRes& o, double wr, double wt, double*
   for (int a = 0; a < 3; ++a)
 #pragma unroll
     for (int b = 0; b < 3; ++b) {
-      const double gr = pg_dot3(G[3 * a], Rz[3 * b], G[3 * a + 1], Rz[3 * b + 1], G[3 * a + 2], Rz[3 * b + 2]);
+      const double gr = dot3(G[3 * a], Rz[3 * b], G[3 * a + 1], Rz[3 * b + 1], G[3 * a + 2], Rz[3 * b + 2]);
       Ji[6 * a + b] = -0.5 * gr;
       Ji[6 * (3 + a) + b] = Pm[3 * a + b];
       Ji[6 * (3 + a) + 3 + b] = -Rz[3 * b + a];
@@ -338,36 +334,6 @@ ATDN_HD inline void pg_node_gather(const PgView& V, int N, int n) {
   for (int k = 0; k < 6; ++k) V.g[6 * (size_t)n + k] = g[k];
 }
 
-// x = S^-1 b for the factor F = (L rows 1..5: 15 values, pivots: 6), as in pnp_lm_step
-ATDN_HD inline void pg_ldl_solve(const double* F, const double* b, double* x) {
-#pragma clang fp contract(off)
-  double y[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double v = b[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) {
-      const double ly = F[i * (i - 1) / 2 + k] * y[k];
-      v = v - ly;
-    }
-    y[i] = v;
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) y[i] = y[i] / F[15 + i];
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double v = y[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; ++k) {
-      const double ly = F[k * (k - 1) / 2 + i] * y[k];
-      v = v - ly;
-    }
-    y[i] = v;
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) x[i] = y[i];
-}
-
 // Step n of the block LDL^T of the damped block-tridiagonal part. Returns false on a non-positive pivot.
 ATDN_HD inline bool pg_factor_node(const PgView& V, int N, int n, double lambda) {
 #pragma clang fp contract(off)
@@ -396,38 +362,8 @@ ATDN_HD inline bool pg_factor_node(const PgView& V, int N, int n, double lambda)
         A[6 * a + b] = A[6 * a + b] - s;
       }
   }
-  double L[6][6], Dg[6];
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double dj = A[7 * j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) {
-      const double ld = L[j][k] * Dg[k];
-      const double lld = L[j][k] * ld;
-      dj = dj - lld;
-    }
-    ok = ok && dj > 0.0;
-    Dg[j] = dj;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double l = A[6 * i + j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) {
-        const double ld = L[j][k] * Dg[k];
-        const double lld = L[i][k] * ld;
-        l = l - lld;
-      }
-      L[i][j] = l / dj;
-    }
-  }
   double* F = V.F + 21 * (size_t)n;
-#pragma unroll
-  for (int i = 1; i < 6; ++i)
-#pragma unroll
-    for (int k = 0; k < i; ++k) F[i * (i - 1) / 2 + k] = L[i][k];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) F[15 + i] = Dg[i];
+  const bool ok = ldl6_factor(A, F);
   if (ok && n + 1 < N && V.free_[n + 1]) {
     const double* U = V.U + 36 * (size_t)n;
     double* W = V.W + 36 * (size_t)n;
@@ -436,7 +372,7 @@ ATDN_HD inline bool pg_factor_node(const PgView& V, int N, int n, double lambda)
       double col[6], x[6];
 #pragma unroll
       for (int a = 0; a < 6; ++a) col[a] = U[6 * a + b];
-      pg_ldl_solve(F, col, x);
+      ldl6_solve(F, col, x);
 #pragma unroll
       for (int a = 0; a < 6; ++a) W[6 * a + b] = x[a];
     }
@@ -501,7 +437,7 @@ ATDN_HD inline void pg_node_pivot_solve(const PgView& V, int n) {
   double y[6], v[6];
 #pragma unroll
   for (int a = 0; a < 6; ++a) y[a] = V.z[6 * (size_t)n + a];
-  pg_ldl_solve(V.F + 21 * (size_t)n, y, v);
+  ldl6_solve(V.F + 21 * (size_t)n, y, v);
 #pragma unroll
   for (int a = 0; a < 6; ++a) V.z[6 * (size_t)n + a] = v[a];
 }
@@ -552,12 +488,6 @@ ATDN_HD inline void pg_sweep_backward_all(const PgView& V, int N) {
     for (int a = 0; a < 6; ++a) zp[a] = v[a];
     linked = true;
   }
-}
-
-inline void pg_sweeps_host(const PgView& V, int N) {
-  pg_sweep_forward_all(V, N);
-  for (int n = 0; n < N; ++n) pg_node_pivot_solve(V, n);
-  pg_sweep_backward_all(V, N);
 }
 
 // Ap_n = (D_n + lambda diag D_n) p_n + the off-diagonal blocks of n's edges to free nodes times their p, in edge order
@@ -618,8 +548,8 @@ ATDN_HD inline double pg_dot6(const double* a, const double* b, int n) {
   return s;
 }
 
-// trial_n = acc_n . [C(dw) | dt] with the step x_n = (dw, dt) (the Cayley map of pnp_lm_step); a node that is not free is
-// copied. Returns whether the step is finite.
+// trial_n = acc_n . [C(dw) | dt] with the step x_n = (dw, dt) and its Cayley matrix C; a node that is not free is copied.
+// Returns whether the step is finite.
 ATDN_HD inline bool pg_retract_node(const PgView& V, int n) {
 #pragma clang fp contract(off)
   const double* A = V.acc + 12 * (size_t)n;
@@ -629,49 +559,18 @@ ATDN_HD inline bool pg_retract_node(const PgView& V, int n) {
     for (int k = 0; k < 12; ++k) T[k] = A[k];
     return true;
   }
-  double dl[6];
-  bool ok = true;
+  double dl[6], Em[9];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    dl[k] = V.x[6 * (size_t)n + k];
-    ok = ok && dl[k] >= -DBL_MAX && dl[k] <= DBL_MAX;
-  }
-  const double h[3] = {0.5 * dl[0], 0.5 * dl[1], 0.5 * dl[2]};
-  const double h00 = h[0] * h[0], h11 = h[1] * h[1], h22 = h[2] * h[2];
-  const double h01 = h00 + h11;
-  const double n2 = h01 + h22;
-  const double den = 1.0 + n2;
-  const double f = 2.0 / den;
-  const double K[9] = {0.0, -h[2], h[1], h[2], 0.0, -h[0], -h[1], h[0], 0.0};
-  double Em[9];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const double hh = h[i] * h[j];
-      const double m = i == j ? hh - n2 : K[3 * i + j] + hh;
-      const double fm = f * m;
-      Em[3 * i + j] = i == j ? 1.0 + fm : fm;
-    }
+  for (int k = 0; k < 6; ++k) dl[k] = V.x[6 * (size_t)n + k];
+  cayley3(dl, Em);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
 #pragma unroll
-    for (int b = 0; b < 3; ++b) T[3 * a + b] = pg_dot3(A[3 * a], Em[b], A[3 * a + 1], Em[3 + b], A[3 * a + 2], Em[6 + b]);
-    const double rt = pg_dot3(A[3 * a], dl[3], A[3 * a + 1], dl[4], A[3 * a + 2], dl[5]);
+    for (int b = 0; b < 3; ++b) T[3 * a + b] = dot3(A[3 * a], Em[b], A[3 * a + 1], Em[3 + b], A[3 * a + 2], Em[6 + b]);
+    const double rt = dot3(A[3 * a], dl[3], A[3 * a + 1], dl[4], A[3 * a + 2], dl[5]);
     T[9 + a] = rt + A[9 + a];
   }
-  return ok;
-}
-
-// The Levenberg-Marquardt damping after a decision (the constants of pnp_lm_update).
-ATDN_HD inline double pg_lambda(double lambda, bool accept) {
-#pragma clang fp contract(off)
-  if (accept) {
-    const double l = lambda / 3.0;
-    return l > 1e-9 ? l : 1e-9;
-  }
-  const double l = 4.0 * lambda;
-  return l < 1e6 ? l : 1e6;
+  return finite6(dl);
 }
 
 // The fixed-order sum of v[0..n): chunks of 256 values (+0.0 beyond n), in a chunk the binary tree of strides 1 .. 128
@@ -689,121 +588,185 @@ inline double pg_tree_sum(const double* v, int n) {
   return total;
 }
 
-inline double pg_dot_host(const PgView& V, const double* a, const double* b, int N, std::vector<double>& tmp) {
-  for (int n = 0; n < N; ++n) tmp[n] = pg_dot6(a, b, n);
-  return pg_tree_sum(tmp.data(), N);
-}
-
-inline double pg_cost_host(const PgProblem& P, const PgView& V, const double* X) {
-  for (int e = 0; e < P.E; ++e) pg_edge_phase(P, V, X, e, false);
-  for (int n = 0; n < P.N; ++n) pg_node_cost(V, n);
-  return pg_tree_sum(V.costn, P.N);
-}
-
-// One graph: iters < 0 is one evaluation (atdn_pose_graph_terms: cost[0] only, counts[0..1] only). The phases and their
-// order are those of pose_graph_kernel.
-inline void pose_graph_run_host(const PgProblem& P, int iters, int cg_iters, double cg_tol, float* poses_out, double* cost,
-                                double* edge_chi2, int* counts) {
+// The solver, written once. It reaches all edges or nodes only through the executor x:
+//   x.each(n, f)    f(i) for every i < n; what it wrote is visible to all afterwards
+//   x.serial(f)     f() once, after everything before it; its result is known to all
+//   x.sum(n, f)     the fixed-order sum (pg_tree_sum) of f(i), i < n, the same value for all
+//   x.count(n, f)   how many i < n have f(i)
+//   x.all(n, f)     whether all i < n have f(i); every f(i) is evaluated
+// Where "all" are the threads of a workgroup, every one of them runs this function: its control flow depends only on its
+// arguments and on what the primitives return, so all take the same path, and no primitive stands inside an f.
+// iters < 0 is one evaluation (atdn_pose_graph_terms: cost[0] and counts[0..1] only, poses_out unused).
+template <class X>
+ATDN_HD inline void pg_solve(const PgProblem& P, const PgView& V, int iters, int cg_iters, double tol2, float* poses_out,
+                             double* cost, double* edge_chi2, int* counts, X& x) {
 #pragma clang fp contract(off)
   const int N = P.N, E = P.E;
-  std::vector<double> mem(pg_graph_bytes(N, E) / 8), tmp(N);
-  const PgView V = pg_carve(mem.data(), N, E);
-  int valid = 0;
-  for (int e = 0; e < E; ++e) {
-    V.kind[e] = pg_edge_kind(P, e, &V.ei[e], &V.ej[e]);
-    valid += V.kind[e] != PG_ABSENT;
-  }
-  for (int n = 0; n < N; ++n) V.deg[n] = pg_node_incidence(V, E, n, false);
-  V.off[0] = 0;
-  for (int n = 0; n < N; ++n) V.off[n + 1] = V.off[n] + V.deg[n];
-  for (int n = 0; n < N; ++n) {
+  const int valid = x.count(E, [&](int e) {
+    const int kind = pg_edge_kind(P, e, &V.ei[e], &V.ej[e]);
+    V.kind[e] = kind;
+    return kind != PG_ABSENT;
+  });
+  x.each(N, [&](int n) { V.deg[n] = pg_node_incidence(V, E, n, false); });
+  x.serial([&] {
+    V.off[0] = 0;
+    for (int n = 0; n < N; ++n) V.off[n + 1] = V.off[n] + V.deg[n];
+    return true;
+  });
+  x.each(N, [&](int n) {
     pg_node_incidence(V, E, n, true);
     V.free_[n] = V.deg[n] > 0 && !(P.fixed && P.fixed[n] != 0);
     pg_internal_pose(P.poses + 12 * (size_t)n, V.acc + 12 * (size_t)n);
-  }
-  double cost_acc = pg_cost_host(P, V, V.acc);
+  });
+  const auto cost_at = [&](const double* poses) {
+    x.each(E, [&](int e) { pg_edge_phase(P, V, poses, e, false); });
+    return x.sum(N, [&](int n) {
+      pg_node_cost(V, n);
+      return V.costn[n];
+    });
+  };
+  const auto dot = [&](const double* a, const double* b) { return x.sum(N, [&](int n) { return pg_dot6(a, b, n); }); };
+  const auto precondition = [&] {   // z = M^-1 r
+    x.serial([&] {
+      pg_sweep_forward_all(V, N);
+      return true;
+    });
+    x.each(N, [&](int n) { pg_node_pivot_solve(V, n); });
+    x.serial([&] {
+      pg_sweep_backward_all(V, N);
+      return true;
+    });
+  };
+  double cost_acc = cost_at(V.acc);
   const double cost0 = cost_acc;
   double lambda = 1e-3;
   int accepted = 0, cg_total = 0;
   bool fresh = false;
-  const double tol2 = cg_tol * cg_tol;
   for (int k = 0; k < iters; ++k) {
     if (!fresh) {
-      for (int e = 0; e < E; ++e) pg_edge_phase(P, V, V.acc, e, true);
-      for (int n = 0; n < N; ++n) pg_node_gather(V, N, n);
+      x.each(E, [&](int e) { pg_edge_phase(P, V, V.acc, e, true); });
+      x.each(N, [&](int n) { pg_node_gather(V, N, n); });
       fresh = true;
     }
-    bool ok = true;
-    for (int n = 0; n < N && ok; ++n) ok = pg_factor_node(V, N, n, lambda);
-    if (ok) {
+    bool ok = x.serial([&] {
       for (int n = 0; n < N; ++n)
-        for (int a = 0; a < 6; ++a) {
-          const size_t i = 6 * (size_t)n + a;
+        if (!pg_factor_node(V, N, n, lambda)) return false;
+      return true;
+    });
+    if (ok) {
+      x.each(N, [&](int n) {
+        for (size_t i = 6 * (size_t)n; i < 6 * (size_t)n + 6; ++i) {
           V.x[i] = 0.0;
           V.r[i] = V.free_[n] ? -V.g[i] : 0.0;
           V.z[i] = 0.0;
           V.Ap[i] = 0.0;
         }
-      pg_sweeps_host(V, N);
-      for (size_t i = 0; i < 6 * (size_t)N; ++i) V.p[i] = V.z[i];
-      double rz = pg_dot_host(V, V.r, V.z, N, tmp);
+      });
+      precondition();
+      x.each(N, [&](int n) {
+        for (size_t i = 6 * (size_t)n; i < 6 * (size_t)n + 6; ++i) V.p[i] = V.z[i];
+      });
+      double rz = dot(V.r, V.z);
       const double thr = tol2 * rz;
       if (rz > 0.0) {
         for (int it = 0; it < cg_iters; ++it) {
-          for (int n = 0; n < N; ++n) pg_apply_node(V, n, lambda);
-          const double pAp = pg_dot_host(V, V.p, V.Ap, N, tmp);
+          x.each(N, [&](int n) { pg_apply_node(V, n, lambda); });
+          const double pAp = dot(V.p, V.Ap);
           if (!(pAp > 0.0)) break;
           const double alpha = rz / pAp;
-          for (size_t i = 0; i < 6 * (size_t)N; ++i) {
-            const double ap = alpha * V.p[i], aAp = alpha * V.Ap[i];
-            V.x[i] = V.x[i] + ap;
-            V.r[i] = V.r[i] - aAp;
-          }
+          x.each(N, [&](int n) {
+#pragma clang fp contract(off)
+            for (size_t i = 6 * (size_t)n; i < 6 * (size_t)n + 6; ++i) {
+              const double ap = alpha * V.p[i], aAp = alpha * V.Ap[i];
+              V.x[i] = V.x[i] + ap;
+              V.r[i] = V.r[i] - aAp;
+            }
+          });
           ++cg_total;
-          pg_sweeps_host(V, N);
-          const double rz_new = pg_dot_host(V, V.r, V.z, N, tmp);
+          precondition();
+          const double rz_new = dot(V.r, V.z);
           if (!(rz_new > thr)) break;
           const double beta = rz_new / rz;
-          for (size_t i = 0; i < 6 * (size_t)N; ++i) {
-            const double bp = beta * V.p[i];
-            V.p[i] = V.z[i] + bp;
-          }
+          x.each(N, [&](int n) {
+#pragma clang fp contract(off)
+            for (size_t i = 6 * (size_t)n; i < 6 * (size_t)n + 6; ++i) {
+              const double bp = beta * V.p[i];
+              V.p[i] = V.z[i] + bp;
+            }
+          });
           rz = rz_new;
         }
       }
-      for (int n = 0; n < N; ++n) ok = pg_retract_node(V, n) && ok;
+      ok = x.all(N, [&](int n) { return pg_retract_node(V, n); });
     }
     bool accept = false;
     if (ok) {
-      const double c = pg_cost_host(P, V, V.trial);
+      const double c = cost_at(V.trial);
       accept = c < cost_acc;
       if (accept) {
-        for (size_t i = 0; i < 12 * (size_t)N; ++i) V.acc[i] = V.trial[i];
+        x.each(N, [&](int n) {
+          for (size_t i = 12 * (size_t)n; i < 12 * (size_t)n + 12; ++i) V.acc[i] = V.trial[i];
+        });
         cost_acc = c;
         accepted += 1;
         fresh = false;
       }
     }
-    lambda = pg_lambda(lambda, accept);
+    lambda = lm_lambda(lambda, accept);
   }
-  cost[0] = cost0;
-  counts[0] = valid;
-  counts[1] = E - valid;
   const float* final_poses = P.poses;
   if (iters >= 0) {
-    for (int n = 0; n < N; ++n) {
+    x.each(N, [&](int n) {
       float* o = poses_out + 12 * (size_t)n;
       if (accepted > 0 && V.free_[n])
         pg_public_pose(V.acc + 12 * (size_t)n, o);
       else
         for (int k = 0; k < 12; ++k) o[k] = P.poses[12 * (size_t)n + k];
-    }
-    cost[1] = cost_acc;
-    counts[2] = accepted;
-    counts[3] = cg_total;
+    });
     final_poses = poses_out;
   }
-  for (int e = 0; e < E; ++e) edge_chi2[e] = pg_edge_chi2(P, V, final_poses, e);
+  x.each(E, [&](int e) { edge_chi2[e] = pg_edge_chi2(P, V, final_poses, e); });
+  x.serial([&] {
+    cost[0] = cost0;
+    counts[0] = valid;
+    counts[1] = E - valid;
+    if (iters >= 0) {
+      cost[1] = cost_acc;
+      counts[2] = accepted;
+      counts[3] = cg_total;
+    }
+    return true;
+  });
+}
+
+// The executor of the host form: plain loops.
+struct PgHostExec {
+  std::vector<double> tmp;   // [N]: the terms of a sum
+  template <class F> void each(int n, F f) { for (int i = 0; i < n; ++i) f(i); }
+  template <class F> bool serial(F f) { return f(); }
+  template <class F> double sum(int n, F f) {
+    for (int i = 0; i < n; ++i) tmp[i] = f(i);
+    return pg_tree_sum(tmp.data(), n);
+  }
+  template <class F> int count(int n, F f) {
+    int c = 0;
+    for (int i = 0; i < n; ++i) c += f(i) ? 1 : 0;
+    return c;
+  }
+  template <class F> bool all(int n, F f) {
+    bool ok = true;
+    for (int i = 0; i < n; ++i) ok = f(i) && ok;
+    return ok;
+  }
+};
+
+// One graph on the host, its working arrays in a std::vector.
+inline void pose_graph_run_host(const PgProblem& P, int iters, int cg_iters, double cg_tol, float* poses_out, double* cost,
+                                double* edge_chi2, int* counts) {
+#pragma clang fp contract(off)
+  std::vector<double> mem(pg_graph_bytes(P.N, P.E) / 8);
+  PgHostExec x{std::vector<double>(P.N)};
+  pg_solve(P, pg_carve(mem.data(), P.N, P.E), iters, cg_iters, cg_tol * cg_tol, poses_out, cost, edge_chi2, counts, x);
 }
 
 }  // namespace atdn

@@ -4,7 +4,10 @@ the rule's. The edge phase is NumPy, vectorised over the edges (element-wise ope
 its sweeps and the conjugate gradient are loops over plain Python floats (IEEE float64, never fused). Seeded scenes, and
 `check_case`, which asserts on this helper ALONE before anything is compared with it: every comparison the rule takes (accept or
 reject, pivots, the CG stops) has a relative margin >= MIN_MARGIN, at least one step is accepted, and a case that claims a
-rejected step, an early CG stop or a CG cap really takes that branch."""
+rejected step, an early CG stop or a CG cap really takes that branch. `check_driver_case` does the same for the two scenes
+that accept no step: a factorisation that fails on an exactly zero pivot (`stalled`) and a right-hand side that is exactly zero
+(`optimum`). The third such branch of the solver, the curvature stop of the CG (p.Ap <= 0, `info["cg_curvature"]`), is claimed
+by NO case: the system is positive semi-definite by construction and no scene was found that takes the stop with a margin."""
 import functools
 
 import numpy as np
@@ -583,6 +586,28 @@ SINGLE_CASES = {"pair": _pair, "ring5": _ring5, "robust33": _robust33, "ring65":
                 "rejected": _rejected}
 
 
+def _stalled():
+    """`pair` with the rotation weight zero: the free node's block is diag(0, wt Re^T Re), whose first pivot is an exact 0.0
+    (products with an exact zero), so the factorisation fails on every step and the input comes back."""
+    s = ring_scene(2, [], 1, drift=(2e-2, 2e-1))
+    s["weight"][:, 0] = 0.0
+    return s, dict(iters=3)
+
+
+def _optimum():
+    """N = 4 at the optimum: rotations I, translations (k, 0, 2k), the four edges of the ring with measurements T_i^-1 T_j —
+    small integers, exact in float32 — so every residual and every gradient is exactly zero."""
+    N, pairs = 4, [(0, 1), (1, 2), (2, 3), (3, 0)]
+    T = np.stack([_T(np.eye(3), [k, 0.0, 2.0 * k]) for k in range(N)])
+    meas = np.stack([np.linalg.inv(T[i]) @ T[j] for i, j in pairs])
+    s = dict(poses=rows(T), index=np.ascontiguousarray(np.array(pairs, dtype=np.int32).T), meas=rows(meas),
+             weight=np.array([[1e6, 1e4]] * len(pairs)), robust=np.zeros(len(pairs), np.uint8), truth=T, E=len(pairs), N=N)
+    return s, dict(iters=2)
+
+
+DRIVER_CASES = {"stalled": _stalled, "optimum": _optimum}
+
+
 def batch_scene():
     """B = 3 graphs of N = 26 nodes and E = 48 edges in one call, every irregularity the rule names: graph 0 a ring with a
     zero-weight edge, a duplicate edge, a backward edge (i > j) and the three kinds of absent edge (an index -1, an index N,
@@ -641,6 +666,26 @@ def check_case(name):
     for claim in claims:
         assert ref["info"][claim] >= 1, (name, claim, ref["info"])
     return dict(scene=scene, args=args, options=opt, solve=ref, terms=t)
+
+
+@functools.lru_cache(maxsize=None)
+def check_driver_case(name):
+    """`stalled` and `optimum` with their reference solutions, in the form of `check_case`. Neither accepts a step, and the
+    helper reports margin 0.0 for a pivot that is exactly zero, so `stalled` is not held to MIN_MARGIN: what is asserted, on
+    this helper alone, is the branch itself — every step fails, or every step has a zero right-hand side and is rejected because
+    0 < 0 is false — and that the input poses come back bit for bit."""
+    scene, opt = DRIVER_CASES[name]()
+    args = _graph_args(scene)
+    ref = solve(*args, fixed=_node0(scene["N"]), **opt)
+    info, iters, E = ref["info"], opt["iters"], scene["E"]
+    assert ref["counts"].tolist() == [E, 0, 0, 0] and np.array_equal(ref["poses"].view(np.uint32), scene["poses"].view(np.uint32))
+    assert ref["cost"][0] == ref["cost"][1], (name, ref["cost"])
+    if name == "stalled":
+        assert info["failed"] == iters and info["rejected"] == 0 and ref["cost"][0] > 0.0, (name, info)
+    else:
+        assert info["zero_rhs"] == iters and info["rejected"] == iters and info["failed"] == 0, (name, info)
+        assert ref["cost"].tolist() == [0.0, 0.0] and ref["margin"] >= MIN_MARGIN, (name, ref["cost"], ref["margin"])
+    return dict(scene=scene, args=args, options=opt, solve=ref, terms=terms(*args))
 
 
 # The float32 round-off of the public poses and measurements: the mean position error (m) that this helper's converged solution

@@ -70,6 +70,20 @@ def test_kernel_equals_the_helper_and_the_host_form(name):
     assert counts.cpu().tolist() == c["terms"][2].tolist()
 
 
+@pytest.mark.parametrize("name", list(R.DRIVER_CASES))
+def test_kernel_equals_the_helper_and_the_host_form_where_no_step_is_accepted(name):
+    """stalled: an exactly zero pivot, the factorisation fails on every step; optimum: an exactly zero right-hand side, the CG
+    does not start and the step that changes nothing is rejected. One launch each; the input comes back."""
+    c = R.check_driver_case(name)
+    got = _optimize(_dev, c["args"], **c["options"])
+    _equal_solution(got, c["solve"], name)
+    _equal_solution(_optimize(_cpu, c["args"], **c["options"]), c["solve"], name)
+    assert _same_bits(got[0], c["scene"]["poses"])
+    cost, chi2, counts = transforms.pose_graph_terms(*[_dev(a) for a in c["args"]])
+    assert _same_bits(cost.cpu().numpy(), np.float64(c["terms"][0])) and _same_bits(chi2.cpu().numpy(), c["terms"][1])
+    assert counts.cpu().tolist() == c["terms"][2].tolist()
+
+
 def test_three_different_graphs_in_one_call():
     """B = 3: a zero-weight edge, an isolated node, two held nodes, a duplicate edge, a backward edge, a hub of degree 22, a
     missing chain link, a long-range edge, and absent edges (-1, N, i == j), which read nothing out of range."""

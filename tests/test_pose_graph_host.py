@@ -61,6 +61,19 @@ def test_host_form_equals_the_helper(name):
     assert _same_bits(again[1].numpy(), got[2])
 
 
+@pytest.mark.parametrize("name", list(R.DRIVER_CASES))
+def test_host_form_equals_the_helper_where_no_step_is_accepted(name):
+    """stalled: an exactly zero pivot, the factorisation fails on every step; optimum: an exactly zero right-hand side, the CG
+    does not start and the step that changes nothing is rejected. The input comes back."""
+    c = R.check_driver_case(name)
+    got = _optimize(c["args"], **c["options"])
+    _equal_solution(got, c["solve"], name)
+    assert _same_bits(got[0], c["scene"]["poses"])
+    cost, chi2, counts = transforms.pose_graph_terms(*[_t(a) for a in c["args"]])
+    assert _same_bits(cost.numpy(), np.float64(c["terms"][0])) and _same_bits(chi2.numpy(), c["terms"][1])
+    assert counts.tolist() == c["terms"][2].tolist() and _same_bits(chi2.numpy(), got[2])
+
+
 def test_pair_ends_at_the_measurement():
     c = R.check_case("pair")
     s = c["scene"]
