@@ -93,6 +93,15 @@ SIGNATURES = {
                                  C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "atdn_pnp_solve_host": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                                       C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp]),
+    "atdn_epipolar_workspace_bytes": (C.c_long, [C.c_int, C.c_int, C.c_int]),
+    "atdn_epipolar_terms": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                      C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
+    "atdn_epipolar_terms_host": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                           C.c_double, C.c_double, _vp, _vp]),
+    "atdn_epipolar_solve": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                      C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "atdn_epipolar_solve_host": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                           C.c_double, C.c_double, C.c_int, _vp, _vp, _vp]),
     "atdn_pose_graph_workspace_bytes": (C.c_long, [C.c_int, C.c_int, C.c_int]),
     "atdn_pose_graph_terms": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "atdn_pose_graph_terms_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp]),

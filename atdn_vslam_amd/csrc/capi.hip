@@ -12,6 +12,7 @@
 #include "frontend.h"
 #include "conv_sf.h"
 #include "epilogues_sf.h"
+#include "epipolar_host.h"
 #include "flow_args.h"
 #include "flow_consistency_host.h"
 #include "flow_track_host.h"
@@ -450,6 +451,30 @@ int atdn_pnp_solve_host(const float* depth, const float* flow, const unsigned ch
   ATDN_CHECK(iters >= 0 && iters <= 64, "iters must be in [0, 64]");
   pnp_solve_host(depth, flow, mask, pose_init, B, H, W, pnp_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, H, W), iters,
                  pose_out, cost, counts);
+  ATDN_API_END
+}
+
+// ------------------------------------------------------------------ pose from flow alone (host twins of epipolar.hip)
+int atdn_epipolar_terms_host(const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W, double fx,
+                             double fy, double cx, double cy, double scale_px, double inlier_px, double* sums, int* counts) {
+  ATDN_API_BEGIN
+  const void* out[2] = {sums, counts};
+  const long out_bytes[2] = {(long)B * PLANE_TERMS * 8, (long)B * 12};
+  epipolar_check_args(flow, mask, pose, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, false, out, out_bytes, 2);
+  epipolar_terms_host(flow, mask, pose, B, H, W, epipolar_params(fx, fy, cx, cy, scale_px, inlier_px), sums, counts);
+  ATDN_API_END
+}
+
+int atdn_epipolar_solve_host(const float* flow, const unsigned char* mask, const float* pose_init, int B, int H, int W, double fx,
+                             double fy, double cx, double cy, double scale_px, double inlier_px, int iters, float* pose_out,
+                             double* cost, int* counts) {
+  ATDN_API_BEGIN
+  const void* out[3] = {pose_out, cost, counts};
+  const long out_bytes[3] = {(long)B * 48, (long)B * 8, (long)B * 16};
+  epipolar_check_args(flow, mask, pose_init, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, false, out, out_bytes, 3);
+  ATDN_CHECK(iters >= 0 && iters <= 64, "iters must be in [0, 64]");
+  epipolar_solve_host(flow, mask, pose_init, B, H, W, epipolar_params(fx, fy, cx, cy, scale_px, inlier_px), iters, pose_out, cost,
+                      counts);
   ATDN_API_END
 }
 

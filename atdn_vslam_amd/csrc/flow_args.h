@@ -1,4 +1,4 @@
-// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip), shared by each device
+// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip, epipolar.hip), shared by each device
 // entry point and its host twin in capi.hip, and the overlap rule that the pose solvers (pnp.hip, pose_graph.hip) share.
 #pragma once
 #include <cmath>
@@ -31,6 +31,17 @@ inline void check_pinhole(double fx, double fy, double cx, double cy) {
   ATDN_CHECK(std::isfinite(cx) && std::isfinite(cy), "cx and cy must be finite");
 }
 
+// What the argument rules of the dense pose solvers (pnp.hip, epipolar.hip) share: no null output, the plane batch, the pinhole,
+// the two pixel scales of the robust loss.
+inline void check_plane_solver(int B, int H, int W, bool grid_limit, double fx, double fy, double cx, double cy, double scale_px,
+                               double inlier_px, const void* const* out, int n_out) {
+  for (int i = 0; i < n_out; ++i) ATDN_CHECK(out[i], "null argument");
+  check_plane_batch(B, H, W, grid_limit);
+  check_pinhole(fx, fy, cx, cy);
+  ATDN_CHECK(std::isfinite(scale_px) && scale_px > 0.0, "scale_px must be finite and > 0");
+  ATDN_CHECK(std::isfinite(inlier_px) && inlier_px > 0.0, "inlier_px must be finite and > 0");
+}
+
 inline void check_two_view_camera(const TwoViewCamera& cam) {
   check_pinhole(cam.fx, cam.fy, cam.cx, cam.cy);
   ATDN_CHECK(std::isfinite(cam.max_epipolar) && cam.max_epipolar >= 0.0, "max_epipolar must be finite and >= 0");
@@ -49,5 +60,8 @@ void flow_track_check_args(const float* flow, const unsigned char* mask, const f
 void pnp_check_args(const float* depth, const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W,
                     double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, bool grid_limit,
                     const void* const* out, const long* out_bytes, int n_out);
+void epipolar_check_args(const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W, double fx, double fy,
+                         double cx, double cy, double scale_px, double inlier_px, bool grid_limit, const void* const* out,
+                         const long* out_bytes, int n_out);
 
 }  // namespace atdn

@@ -1,0 +1,99 @@
+// The device side of plane_lm.h, shared by the two dense pose solvers (pnp.hip, epipolar.hip): the workspace of a solve, the
+// fixed binary tree that takes the 28 sums of a workgroup's threads to its slot of the workspace, and the order-fixed sum of the
+// slots of a plane. The terms kernels run (chunks, B) workgroups of pixel_quads.h with off = 0 — workgroup c of plane b owns the
+// flat indices 1024 c .. 1024 c + 1023, a thread four consecutive ones —; the finalise kernels one wave per problem. No memset
+// and no atomics: every workgroup writes its own slot (store-and-sum: cdna_hip_programming.md, Guideline 12).
+#pragma once
+#include "pixel_quads.h"
+#include "plane_lm.h"
+
+namespace atdn {
+
+static_assert(PLANE_CHUNK == 4 * PQ_THREADS && PLANE_CHUNK_THREADS == PQ_THREADS, "a chunk is one workgroup of pixel_quads.h");
+static_assert(sizeof(PlaneLmState) % 8 == 0, "the chunk sums follow the states in the workspace");
+
+constexpr int PLANE_FIN_THREADS = 64;
+
+struct PlaneWorkspace {
+  PlaneLmState* state;   // [B]
+  double* sums;          // [B, chunks, 28]
+  int* counts;           // [B, chunks, 4] (three used)
+};
+
+inline long plane_chunks(int H, int W) { return cdivl((long)H * W, PLANE_CHUNK); }
+
+inline size_t plane_workspace_size(int B, int H, int W) {
+  const size_t chunks = (size_t)plane_chunks(H, W);
+  return (size_t)B * (sizeof(PlaneLmState) + chunks * (PLANE_TERMS * sizeof(double) + 4 * sizeof(int)));
+}
+
+inline PlaneWorkspace plane_carve(void* workspace, int B, int H, int W) {
+  const size_t chunks = (size_t)plane_chunks(H, W);
+  PlaneWorkspace ws;
+  ws.state = (PlaneLmState*)workspace;
+  ws.sums = (double*)(ws.state + B);
+  ws.counts = (int*)(ws.sums + (size_t)B * chunks * PLANE_TERMS);
+  return ws;
+}
+
+// acc: the thread's 28 sums; cnt: the WAVE's three counts, in every lane. Every thread of workgroup (blockIdx.x, b) calls it, once.
+__device__ __forceinline__ void plane_chunk_reduce(double acc[PLANE_TERMS], const int cnt[3], int b, double* __restrict__ csums,
+                                                   int* __restrict__ ccounts) {
+#pragma clang fp contract(off)
+  __shared__ double part[PQ_WAVES][PLANE_TERMS];
+  __shared__ int ipart[PQ_WAVES][3];
+  // strides 1 .. 32 inside the wave: lane i (a multiple of 2 * stride) takes v[i] + v[i + stride]; the other lanes hold values
+  // that nobody reads
+#pragma unroll
+  for (int e = 0; e < PLANE_TERMS; ++e) {
+#pragma unroll
+    for (int stride = 1; stride < 64; stride *= 2) acc[e] = acc[e] + __shfl_down(acc[e], stride, 64);
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int e = 0; e < PLANE_TERMS; ++e) part[wave][e] = acc[e];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) ipart[wave][j] = cnt[j];
+  }
+  __syncthreads();
+  const long slot = (long)b * gridDim.x + blockIdx.x;
+  if (threadIdx.x < PLANE_TERMS) {
+    const int e = threadIdx.x;
+    const double lo = part[0][e] + part[1][e], hi = part[2][e] + part[3][e];     // strides 64 and 128
+    csums[slot * PLANE_TERMS + e] = lo + hi;
+  } else if (threadIdx.x >= 32 && threadIdx.x < 35) {
+    const int j = threadIdx.x - 32;
+    ccounts[slot * 4 + j] = (ipart[0][j] + ipart[1][j]) + (ipart[2][j] + ipart[3][j]);
+  }
+}
+
+// One wave per problem b: thread e < 28 adds the chunk sums of term e in chunk order (coalesced: the 28 terms of a chunk are
+// contiguous), threads 32 .. 34 the integer counts; after the barrier inside, S and Cn (in LDS) hold the plane's.
+__device__ __forceinline__ void plane_ordered_sum(const double* __restrict__ csums, const int* __restrict__ ccounts, int chunks,
+                                                  int b, double* S, int* Cn) {
+#pragma clang fp contract(off)
+  const int t = threadIdx.x;
+  if (t < PLANE_TERMS) {
+    const double* p = csums + (long)b * chunks * PLANE_TERMS + t;
+    double s = p[0];
+    int ch = 1;
+    for (; ch + 8 <= chunks; ch += 8) {                        // eight loads in flight, the adds in chunk order
+      double v[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v[i] = p[(long)(ch + i) * PLANE_TERMS];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) s = s + v[i];
+    }
+    for (; ch < chunks; ++ch) s = s + p[(long)ch * PLANE_TERMS];
+    S[t] = s;
+  } else if (t >= 32 && t < 35) {
+    const int* p = ccounts + (long)b * chunks * 4 + (t - 32);
+    int s = 0;
+    for (int ch = 0; ch < chunks; ++ch) s += p[(long)ch * 4];
+    Cn[t - 32] = s;
+  }
+  __syncthreads();
+}
+
+}  // namespace atdn

@@ -1,6 +1,6 @@
 // Pose from depth and flow on the device: the reprojection terms of a pose (atdn_pnp_terms) and a Levenberg-Marquardt solve over
 // them (atdn_pnp_solve), batched over problems. The rule — float64, every operation rounded on its own — is pnp_pixel,
-// pnp_lm_update, pnp_lm_step and pnp_output of pnp_host.h (over the 6 x 6 algebra of lm6.h), which these kernels call, so the
+// plane_lm_update (plane_lm.h), pnp_lm_step and pnp_output of pnp_host.h (over the 6 x 6 algebra of lm6.h), which these kernels call, so the
 // kernels and the host form evaluate one function, and the ORDER of every sum is part of the rule (include/atdn_hip.h): the same
 // bits on every call and on both paths.
 //
@@ -15,43 +15,17 @@
 //                        sums out (atdn_pnp_terms) or takes the Levenberg-Marquardt decision and the next step (the 6 x 6 LDL^T
 //                        of lm6.h, fully unrolled, in registers) on the problem's PnpState in the workspace.
 // The pose of evaluation 0 is read from the caller's float32 pose by both kernels; later ones from the state.
+// The tree, the ordered sum and the workspace are written once, in plane_sum.h, for this file and epipolar.hip.
 #include "../../include/atdn_hip.h"
 
 #include <cmath>
 #include <cstdint>
 
 #include "flow_args.h"
-#include "pixel_quads.h"
+#include "plane_sum.h"
 #include "pnp_host.h"
 
 namespace atdn {
-
-static_assert(PNP_CHUNK == 4 * PQ_THREADS && PNP_CHUNK_THREADS == PQ_THREADS, "a chunk is one workgroup of pixel_quads.h");
-static_assert(sizeof(PnpState) % 8 == 0, "the chunk sums follow the states in the workspace");
-
-constexpr int PNP_FIN_THREADS = 64;
-
-struct PnpWorkspace {
-  PnpState* state;   // [B]
-  double* sums;      // [B, chunks, 28]
-  int* counts;       // [B, chunks, 4] (three used)
-};
-
-inline long pnp_chunks(int H, int W) { return cdivl((long)H * W, PNP_CHUNK); }
-
-inline size_t pnp_workspace_size(int B, int H, int W) {
-  const size_t chunks = (size_t)pnp_chunks(H, W);
-  return (size_t)B * (sizeof(PnpState) + chunks * (PNP_TERMS * sizeof(double) + 4 * sizeof(int)));
-}
-
-inline PnpWorkspace pnp_carve(void* workspace, int B, int H, int W) {
-  const size_t chunks = (size_t)pnp_chunks(H, W);
-  PnpWorkspace ws;
-  ws.state = (PnpState*)workspace;
-  ws.sums = (double*)(ws.state + B);
-  ws.counts = (int*)(ws.sums + (size_t)B * chunks * PNP_TERMS);
-  return ws;
-}
 
 // pose32 != nullptr: the public float32 poses [B,12]; otherwise the trial pose of the problem's state
 template <bool MASKED>
@@ -61,8 +35,6 @@ __global__ __launch_bounds__(PQ_THREADS) void pnp_terms_kernel(const float* __re
                                                                const PnpState* __restrict__ state, int H, int W, PnpParams cam,
                                                                double* __restrict__ csums, int* __restrict__ ccounts) {
 #pragma clang fp contract(off)
-  __shared__ double part[PQ_WAVES][PNP_TERMS];
-  __shared__ int ipart[PQ_WAVES][3];
   const int n = H * W;
   const int b = blockIdx.y;
   const float* fu = flow + (long)b * 2 * n;
@@ -110,34 +82,11 @@ __global__ __launch_bounds__(PQ_THREADS) void pnp_terms_kernel(const float* __re
 #pragma unroll
     for (int j = 0; j < 3; ++j) cnt[j] += __popcll(__ballot(flags & (1 << j)));   // the wave's count, in every lane
   }
-  // strides 1 .. 32 inside the wave: lane i (a multiple of 2 * stride) takes v[i] + v[i + stride]; the other lanes hold values
-  // that nobody reads
-#pragma unroll
-  for (int e = 0; e < PNP_TERMS; ++e) {
-#pragma unroll
-    for (int stride = 1; stride < 64; stride *= 2) acc[e] = acc[e] + __shfl_down(acc[e], stride, 64);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int e = 0; e < PNP_TERMS; ++e) part[wave][e] = acc[e];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) ipart[wave][j] = cnt[j];
-  }
-  __syncthreads();
-  const long slot = (long)b * gridDim.x + blockIdx.x;
-  if (threadIdx.x < PNP_TERMS) {
-    const int e = threadIdx.x;
-    const double lo = part[0][e] + part[1][e], hi = part[2][e] + part[3][e];     // strides 64 and 128
-    csums[slot * PNP_TERMS + e] = lo + hi;
-  } else if (threadIdx.x >= 32 && threadIdx.x < 35) {
-    const int j = threadIdx.x - 32;
-    ccounts[slot * 4 + j] = (ipart[0][j] + ipart[1][j]) + (ipart[2][j] + ipart[3][j]);
-  }
+  plane_chunk_reduce(acc, cnt, b, csums, ccounts);
 }
 
 // k < 0: atdn_pnp_terms (the plane sums go to sums_out / counts_out). k >= 0: evaluation k of a solve of `iters` steps.
-__global__ __launch_bounds__(PNP_FIN_THREADS) void pnp_finalise_kernel(const double* __restrict__ csums,
+__global__ __launch_bounds__(PLANE_FIN_THREADS) void pnp_finalise_kernel(const double* __restrict__ csums,
                                                                         const int* __restrict__ ccounts, int chunks, int k, int iters,
                                                                         PnpState* __restrict__ state,
                                                                         const float* __restrict__ pose_init,
@@ -148,26 +97,7 @@ __global__ __launch_bounds__(PNP_FIN_THREADS) void pnp_finalise_kernel(const dou
   __shared__ int Cn[3];
   const int b = blockIdx.x;
   const int t = threadIdx.x;
-  if (t < PNP_TERMS) {
-    const double* p = csums + (long)b * chunks * PNP_TERMS + t;
-    double s = p[0];
-    int ch = 1;
-    for (; ch + 8 <= chunks; ch += 8) {                        // eight loads in flight, the adds in chunk order
-      double v[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = p[(long)(ch + i) * PNP_TERMS];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s = s + v[i];
-    }
-    for (; ch < chunks; ++ch) s = s + p[(long)ch * PNP_TERMS];
-    S[t] = s;
-  } else if (t >= 32 && t < 35) {
-    const int* p = ccounts + (long)b * chunks * 4 + (t - 32);
-    int s = 0;
-    for (int ch = 0; ch < chunks; ++ch) s += p[(long)ch * 4];
-    Cn[t - 32] = s;
-  }
-  __syncthreads();
+  plane_ordered_sum(csums, ccounts, chunks, b, S, Cn);
   if (k < 0) {
     if (t < PNP_TERMS) sums_out[(long)b * PNP_TERMS + t] = S[t];
     if (t < 3) counts_out[3 * b + t] = Cn[t];
@@ -176,7 +106,7 @@ __global__ __launch_bounds__(PNP_FIN_THREADS) void pnp_finalise_kernel(const dou
   if (t != 0) return;
   PnpState& s = state[b];
   if (k == 0) pnp_internal_pose(pose_init + 12 * b, s.trial);
-  pnp_lm_update(s, S, Cn, k);
+  plane_lm_update(s, S, Cn, k);
   if (k < iters)
     pnp_lm_step(s);
   else
@@ -184,8 +114,8 @@ __global__ __launch_bounds__(PNP_FIN_THREADS) void pnp_finalise_kernel(const dou
 }
 
 static void pnp_launch_terms(const float* depth, const float* flow, const unsigned char* mask, const float* pose32,
-                             const PnpWorkspace& ws, int B, int H, int W, const PnpParams& cam, hipStream_t stream) {
-  const dim3 grid((unsigned)pnp_chunks(H, W), (unsigned)B);
+                             const PlaneWorkspace& ws, int B, int H, int W, const PnpParams& cam, hipStream_t stream) {
+  const dim3 grid((unsigned)plane_chunks(H, W), (unsigned)B);
   if (mask)
     hipLaunchKernelGGL(pnp_terms_kernel<true>, grid, dim3(PQ_THREADS), 0, stream, depth, flow, mask, pose32, ws.state, H, W, cam,
                        ws.sums, ws.counts);
@@ -201,11 +131,7 @@ void pnp_check_args(const float* depth, const float* flow, const unsigned char* 
                     double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, bool grid_limit,
                     const void* const* out, const long* out_bytes, int n_out) {
   ATDN_CHECK(depth && flow && pose, "null argument");
-  for (int i = 0; i < n_out; ++i) ATDN_CHECK(out[i], "null argument");
-  check_plane_batch(B, H, W, grid_limit);
-  check_pinhole(fx, fy, cx, cy);
-  ATDN_CHECK(std::isfinite(scale_px) && scale_px > 0.0, "scale_px must be finite and > 0");
-  ATDN_CHECK(std::isfinite(inlier_px) && inlier_px > 0.0, "inlier_px must be finite and > 0");
+  check_plane_solver(B, H, W, grid_limit, fx, fy, cx, cy, scale_px, inlier_px, out, n_out);
   ATDN_CHECK(std::isfinite(min_z) && min_z > 0.0, "min_z must be finite and > 0");
   const long n = (long)H * W;
   const void* in[4] = {depth, flow, mask, pose};
@@ -219,7 +145,7 @@ using namespace atdn;
 
 long atdn_pnp_workspace_bytes(int B, int H, int W) {
   if (B < 1 || H < 1 || W < 1 || (long)H * W > (1L << 24)) return 0;
-  return (long)pnp_workspace_size(B, H, W);
+  return (long)plane_workspace_size(B, H, W);
 }
 
 int atdn_pnp_terms(const float* depth, const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W,
@@ -228,14 +154,14 @@ int atdn_pnp_terms(const float* depth, const float* flow, const unsigned char* m
   ATDN_API_BEGIN
   check_plane_batch(B, H, W);
   const void* out[3] = {sums, counts, workspace};
-  const long out_bytes[3] = {(long)B * PNP_TERMS * 8, (long)B * 12, (long)pnp_workspace_size(B, H, W)};
+  const long out_bytes[3] = {(long)B * PNP_TERMS * 8, (long)B * 12, (long)plane_workspace_size(B, H, W)};
   pnp_check_args(depth, flow, mask, pose, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z, true, out, out_bytes, 3);
   ATDN_CHECK(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)sums & 7) == 0, "workspace and sums must be 8-byte aligned");
   const PnpParams cam = pnp_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, H, W);
-  const PnpWorkspace ws = pnp_carve(workspace, B, H, W);
+  const PlaneWorkspace ws = plane_carve(workspace, B, H, W);
   pnp_launch_terms(depth, flow, mask, pose, ws, B, H, W, cam, (hipStream_t)stream);
-  hipLaunchKernelGGL(pnp_finalise_kernel, dim3((unsigned)B), dim3(PNP_FIN_THREADS), 0, (hipStream_t)stream, ws.sums, ws.counts,
-                     (int)pnp_chunks(H, W), -1, 0, ws.state, pose, sums, counts, (float*)nullptr, (double*)nullptr);
+  hipLaunchKernelGGL(pnp_finalise_kernel, dim3((unsigned)B), dim3(PLANE_FIN_THREADS), 0, (hipStream_t)stream, ws.sums, ws.counts,
+                     (int)plane_chunks(H, W), -1, 0, ws.state, pose, sums, counts, (float*)nullptr, (double*)nullptr);
   ATDN_HIP(hipGetLastError());
   ATDN_API_END
 }
@@ -246,16 +172,16 @@ int atdn_pnp_solve(const float* depth, const float* flow, const unsigned char* m
   ATDN_API_BEGIN
   check_plane_batch(B, H, W);
   const void* out[4] = {pose_out, cost, counts, workspace};
-  const long out_bytes[4] = {(long)B * 48, (long)B * 8, (long)B * 16, (long)pnp_workspace_size(B, H, W)};
+  const long out_bytes[4] = {(long)B * 48, (long)B * 8, (long)B * 16, (long)plane_workspace_size(B, H, W)};
   pnp_check_args(depth, flow, mask, pose_init, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z, true, out, out_bytes, 4);
   ATDN_CHECK(iters >= 0 && iters <= 64, "iters must be in [0, 64]");
   ATDN_CHECK(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)cost & 7) == 0, "workspace and cost must be 8-byte aligned");
   const PnpParams cam = pnp_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, H, W);
-  const PnpWorkspace ws = pnp_carve(workspace, B, H, W);
+  const PlaneWorkspace ws = plane_carve(workspace, B, H, W);
   for (int k = 0; k <= iters; ++k) {
     pnp_launch_terms(depth, flow, mask, k == 0 ? pose_init : nullptr, ws, B, H, W, cam, (hipStream_t)stream);
-    hipLaunchKernelGGL(pnp_finalise_kernel, dim3((unsigned)B), dim3(PNP_FIN_THREADS), 0, (hipStream_t)stream, ws.sums, ws.counts,
-                       (int)pnp_chunks(H, W), k, iters, ws.state, pose_init, (double*)nullptr, counts, pose_out, cost);
+    hipLaunchKernelGGL(pnp_finalise_kernel, dim3((unsigned)B), dim3(PLANE_FIN_THREADS), 0, (hipStream_t)stream, ws.sums, ws.counts,
+                       (int)plane_chunks(H, W), k, iters, ws.state, pose_init, (double*)nullptr, counts, pose_out, cost);
     ATDN_HIP(hipGetLastError());
   }
   ATDN_API_END

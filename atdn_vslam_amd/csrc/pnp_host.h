@@ -1,8 +1,8 @@
 // Pose from depth and flow (robust PnP), the rule in plain C++ float64 (no HIP needed). A depth map of image 1 gives a 3-D point
 // per pixel, the flow image 1 -> image 2 gives that point's pixel in image 2: pnp_pixel is the contribution of one pixel to the
 // Gauss-Newton normal equations of the reprojection error under the Geman-McClure loss, pnp_plane_host the fixed-order sum of
-// a plane (chunks of 1024 pixels), pnp_lm_update / pnp_lm_step one Levenberg-Marquardt decision and step (the 6 x 6 algebra, the
-// Cayley matrix and the damping constants are those of lm6.h, shared with the pose graph; the composition from the left is
+// a plane, pnp_lm_step one Levenberg-Marquardt step (the 28 terms, the chunks, the state and the decision are those of
+// plane_lm.h, shared with epipolar_host.h; the 6 x 6 algebra, the Cayley matrix and the damping constants are those of lm6.h, shared with the pose graph; the composition from the left is
 // PnP's own), pnp_terms_host / pnp_solve_host the host forms behind atdn_pnp_terms_host / atdn_pnp_solve_host (capi.hip), which
 // serve CPU tensors. The kernels of pnp.hip call the same functions, so the two cannot drift apart; the independent statement
 // the tests compare both with is tests/pnp_ref.py (NumPy). The rule is stated in full in include/atdn_hip.h, atdn_pnp_terms and
@@ -10,15 +10,15 @@
 #pragma once
 #include <cfloat>
 #include <cmath>
-#include <vector>
 
-#include "lm6.h"
+#include "plane_lm.h"
 
 namespace atdn {
 
-constexpr int PNP_TERMS = 28;          // 21 upper-triangle Hessian entries (row-major), 6 gradient entries, the cost
-constexpr int PNP_CHUNK = 1024;        // flat indices per chunk: 256 threads x 4
-constexpr int PNP_CHUNK_THREADS = 256;
+// the 28 terms, the chunks of the plane sum, the state and the decision are those of plane_lm.h, shared with epipolar_host.h
+constexpr int PNP_TERMS = PLANE_TERMS;
+constexpr int PNP_CHUNK = PLANE_CHUNK;
+constexpr int PNP_CHUNK_THREADS = PLANE_CHUNK_THREADS;
 enum { PNP_CAND = 1, PNP_USED = 2, PNP_INLIER = 4 };
 
 struct PnpParams {
@@ -43,14 +43,7 @@ inline PnpParams pnp_params(double fx, double fy, double cx, double cy, double s
 }
 
 // The solver's state of one problem. Poses are INTERNAL: p[0..8] = Rc (row-major), p[9..11] = tc, X2 = Rc X1 + tc.
-struct PnpState {
-  double acc[12];            // the accepted pose
-  double trial[12];          // the pose of the next (or the current) evaluation
-  double sums[PNP_TERMS];    // H, g and cost at the accepted pose
-  double lambda;
-  int counts[3];             // (candidates, used, inliers) at the accepted pose
-  int accepted;              // number of accepted steps
-};
+using PnpState = PlaneLmState;
 
 // public pose (12 float32, rows of [R|t], X1 = R X2 + t) -> internal pose
 ATDN_HD inline void pnp_internal_pose(const float* pose12, double p[12]) {
@@ -133,24 +126,6 @@ ATDN_HD inline int pnp_pixel(float zf, float u, float v, bool keep, const double
   return PNP_CAND | PNP_USED | (e2 <= c.thr ? PNP_INLIER : 0);
 }
 
-// After evaluation k (k = 0: the initial pose) with the plane sums `sums` and counts `counts` at s.trial: accept or reject.
-ATDN_HD inline void pnp_lm_update(PnpState& s, const double* sums, const int* counts, int k) {
-#pragma clang fp contract(off)
-  const bool accept = k == 0 || sums[27] < s.sums[27];
-  if (accept) {
-    for (int i = 0; i < 12; ++i) s.acc[i] = s.trial[i];
-    for (int i = 0; i < PNP_TERMS; ++i) s.sums[i] = sums[i];
-    for (int i = 0; i < 3; ++i) s.counts[i] = counts[i];
-  }
-  if (k == 0) {
-    s.lambda = 1e-3;
-    s.accepted = 0;
-  } else {
-    s.lambda = lm_lambda(s.lambda, accept);
-    if (accept) s.accepted += 1;
-  }
-}
-
 // The damped step from the accepted point: s.trial = retract(s.acc, delta), or s.acc again where the factorisation fails.
 ATDN_HD inline void pnp_lm_step(PnpState& s) {
 #pragma clang fp contract(off)
@@ -188,40 +163,13 @@ ATDN_HD inline void pnp_output(const PnpState& s, const float* pose_in, float* p
   counts4[3] = s.accepted;
 }
 
-// The sums of one plane at the internal pose P: chunks of 1024 flat indices; inside a chunk, thread j owns the indices
-// 4j .. 4j + 3 and sums them as ((t0 + t1) + t2) + t3, the 256 thread values go through the binary tree of strides 1 .. 128
-// (v[i] += v[i + stride] for i a multiple of 2 * stride); the chunk sums are added in chunk order.
+// The sums of one plane at the internal pose P, in the order of plane_sum_host (plane_lm.h).
 inline void pnp_plane_host(const float* depth, const float* fu, const float* fv, const unsigned char* mask, const double* P,
                            const PnpParams& c, int H, int W, double sums[PNP_TERMS], int counts[3]) {
-#pragma clang fp contract(off)
-  const long n = (long)H * W;
-  const long chunks = (n + PNP_CHUNK - 1) / PNP_CHUNK;
-  std::vector<double> v((size_t)PNP_CHUNK_THREADS * PNP_TERMS);
-  double t[PNP_TERMS];
-  counts[0] = counts[1] = counts[2] = 0;
-  for (long ch = 0; ch < chunks; ++ch) {
-    for (int j = 0; j < PNP_CHUNK_THREADS; ++j) {
-      double* a = &v[(size_t)j * PNP_TERMS];
-      for (int k = 0; k < 4; ++k) {
-        const long i = ch * PNP_CHUNK + 4 * j + k;
-        int flags = 0;
-        if (i < n) {
-          const int y = (int)(i / W), x = (int)(i - (long)y * W);
-          flags = pnp_pixel(depth[i], fu[i], fv[i], mask ? mask[i] != 0 : true, P, c, H, W, x, y, t);
-        } else {
-          for (int e = 0; e < PNP_TERMS; ++e) t[e] = 0.0;
-        }
-        for (int e = 0; e < PNP_TERMS; ++e) a[e] = k == 0 ? t[e] : a[e] + t[e];
-        counts[0] += (flags & PNP_CAND) ? 1 : 0;
-        counts[1] += (flags & PNP_USED) ? 1 : 0;
-        counts[2] += (flags & PNP_INLIER) ? 1 : 0;
-      }
-    }
-    for (int stride = 1; stride < PNP_CHUNK_THREADS; stride *= 2)
-      for (int i = 0; i < PNP_CHUNK_THREADS; i += 2 * stride)
-        for (int e = 0; e < PNP_TERMS; ++e) v[(size_t)i * PNP_TERMS + e] = v[(size_t)i * PNP_TERMS + e] + v[(size_t)(i + stride) * PNP_TERMS + e];
-    for (int e = 0; e < PNP_TERMS; ++e) sums[e] = ch == 0 ? v[e] : sums[e] + v[e];
-  }
+  plane_sum_host((long)H * W, [&](long i, double* t) {
+    const int y = (int)(i / W), x = (int)(i - (long)y * W);
+    return pnp_pixel(depth[i], fu[i], fv[i], mask ? mask[i] != 0 : true, P, c, H, W, x, y, t);
+  }, sums, counts);
 }
 
 // depth [B,H,W], flow [B,2,H,W], mask [B,H,W] uint8 or null, pose [B,12] -> sums [B,28], counts [B,3]
@@ -248,7 +196,7 @@ inline void pnp_solve_host(const float* depth, const float* flow, const unsigned
       int cnt[3];
       pnp_plane_host(depth + b * n, flow + 2 * b * n, flow + (2 * b + 1) * n, mask ? mask + b * n : nullptr, s.trial, c, H, W,
                      sums, cnt);
-      pnp_lm_update(s, sums, cnt, k);
+      plane_lm_update(s, sums, cnt, k);
       if (k < iters) pnp_lm_step(s);
     }
     pnp_output(s, pose_init + 12L * b, pose_out + 12L * b, cost + b, counts + 4L * b);

@@ -1,7 +1,8 @@
 // Two-view geometry of a flow and a relative pose, the rule in plain C++ float64 (no HIP needed): two_view_pixel is the rule for
 // one pixel, two_view_depth_host the host form behind atdn_flow_two_view_depth_host (capi.hip), which serves CPU tensors. The
 // kernel of two_view.hip evaluates the same function, so the two cannot drift apart; the independent statement the tests compare
-// both with is tests/two_view_ref.py (NumPy).
+// both with is tests/two_view_ref.py (NumPy). The epipolar part of the pixel rule (x2 .. epi2) is two_view_epipolar, which
+// epipolar_host.h (pose from flow alone) calls too.
 //
 // Given the calibration (fx, fy, cx, cy; no skew), the flow of pixel (x, y) of image 1 names its correspondence (x2, y2) in image 2,
 // and the relative pose [R|t] (X1 = R X2 + t, what `transform(rot, tr)` of the pose head returns) names the epipolar line of (x, y)
@@ -57,19 +58,24 @@ ATDN_HD inline TwoViewPose two_view_load_pose(const float* pose12) {
 
 enum { TV_INSIDE = 1, TV_INLIER = 2, TV_VALID = 4 };
 
-// u, v: the flow at (x, y). Returns the depth (0 = none) and sets `flags` to the TV_* bits of the pixel.
-ATDN_HD inline float two_view_pixel(float u, float v, const TwoViewPose& P, const TwoViewCamera& c, int H, int W, int x, int y,
-                                    int* flags) {
+// The epipolar part of the rule for one pixel — x2 .. epi2 above, in that order —, written once for two_view_pixel and for
+// epipolar_pixel (epipolar_host.h: pose from flow alone), so that the two cannot drift apart.
+struct TwoViewEpi {
+  double x2, y2, a0, a1, b[3], n0, n1, n2, res, l0, l1, ll, epi2;
+};
+
+// Returns `inside`; e is set only when inside.
+ATDN_HD inline bool two_view_epipolar(float u, float v, const TwoViewPose& P, double fx, double fy, double cx, double cy, int H,
+                                      int W, int x, int y, TwoViewEpi& e) {
 #pragma clang fp contract(off)
-  *flags = 0;
   const double xd = (double)x, yd = (double)y;
   const double x2 = xd + (double)u, y2 = yd + (double)v;
   const bool inside = x2 >= 0.0 && x2 <= (double)(W - 1) && y2 >= 0.0 && y2 <= (double)(H - 1);
-  if (!inside) return 0.0f;
-  const double dx = xd - c.cx, dy = yd - c.cy;
-  const double a0 = dx / c.fx, a1 = dy / c.fy;
-  const double ex = x2 - c.cx, ey = y2 - c.cy;
-  const double q0 = ex / c.fx, q1 = ey / c.fy;
+  if (!inside) return false;
+  const double dx = xd - cx, dy = yd - cy;
+  const double a0 = dx / fx, a1 = dy / fy;
+  const double ex = x2 - cx, ey = y2 - cy;
+  const double q0 = ex / fx, q1 = ey / fy;
   double b[3];
   for (int i = 0; i < 3; ++i) {
     const double s0 = P.r[i][0] * q0, s1 = P.r[i][1] * q1;
@@ -88,10 +94,27 @@ ATDN_HD inline float two_view_pixel(float u, float v, const TwoViewPose& P, cons
     const double s = s0 + s1;
     m[j] = s + s2;
   }
-  const double l0 = m[0] / c.fx, l1 = m[1] / c.fy;
+  const double l0 = m[0] / fx, l1 = m[1] / fy;
   const double rr = res * res, l00 = l0 * l0, l11 = l1 * l1;
   const double ll = l00 + l11;
-  const double epi2 = rr / ll;
+  e.x2 = x2; e.y2 = y2; e.a0 = a0; e.a1 = a1;
+  e.b[0] = b[0]; e.b[1] = b[1]; e.b[2] = b[2];
+  e.n0 = n0; e.n1 = n1; e.n2 = n2;
+  e.res = res; e.l0 = l0; e.l1 = l1; e.ll = ll;
+  e.epi2 = rr / ll;
+  return true;
+}
+
+// u, v: the flow at (x, y). Returns the depth (0 = none) and sets `flags` to the TV_* bits of the pixel.
+ATDN_HD inline float two_view_pixel(float u, float v, const TwoViewPose& P, const TwoViewCamera& c, int H, int W, int x, int y,
+                                    int* flags) {
+#pragma clang fp contract(off)
+  *flags = 0;
+  TwoViewEpi e;
+  if (!two_view_epipolar(u, v, P, c.fx, c.fy, c.cx, c.cy, H, W, x, y, e)) return 0.0f;
+  const double a0 = e.a0, a1 = e.a1, epi2 = e.epi2;
+  const double b[3] = {e.b[0], e.b[1], e.b[2]};
+  const double t0 = P.t[0], t1 = P.t[1], t2 = P.t[2];
   const double thr = c.max_epipolar * c.max_epipolar;
   const bool inlier = epi2 <= thr;
   const double a00 = a0 * a0, a11 = a1 * a1, b00 = b[0] * b[0], b11 = b[1] * b[1], b22 = b[2] * b[2];

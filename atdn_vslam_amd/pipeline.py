@@ -211,7 +211,7 @@ class OdometryPipeline:
 class VisualOdometry:
     """Frame-at-a-time odometry with the reference's call pattern: `pose = vo(frame)`."""
 
-    def __init__(self, gma_state, clvo_state, device="cuda:0", iters=12, warm_start=False, calib=None):
+    def __init__(self, gma_state, clvo_state, device="cuda:0", iters=12, warm_start=False, calib=None, refine_pose=False):
         """`warm_start=True`: every pair after the first of an unbroken run of calls starts its refinement from the previous
         pair's flow, forward-interpolated on the device (RAFTGMA.forward_consecutive); meant to be combined with a smaller
         `iters`, which is the caller's choice. `reset()` makes the next pair run cold again.
@@ -219,8 +219,17 @@ class VisualOdometry:
         calibration there). Every pair then also leaves `last_depth` [1,1,376,1232] and `last_counts` [1,3] on the device
         (transforms.two_view_depth of that pair's flow and the pose just predicted: the depth of the pair's FIRST frame), one
         small copy and one launch more per frame and no further synchronisation; `epipolar_score()` reads the score. Without it
-        the calls and the poses are what they were."""
+        the calls and the poses are what they were.
+        `refine_pose=True` (needs `calib`): every pair's predicted pose is refined on the pair's own flow before anything uses it
+        (transforms.pose_from_flow with its defaults, on the device: the rotation and the direction of t; |t| stays the head's).
+        `last_depth` and `last_counts` are then those of the refined pose, the returned trajectory composes the refined step
+        (float32 pose @ step), and `last_refine_counts` [1,4] = (candidates, used, inliers, accepted steps) stays on the device.
+        The refined pose returns to the host through the same pinned buffer: one more wait per frame, for the 34 launches of
+        the solve. With False (the default) every call and every bit is what it was."""
         from .depth import intrinsics
+        if refine_pose and calib is None:
+            raise ValueError("refine_pose=True needs the calibration: pass calib=")
+        self.refine_pose = bool(refine_pose)
         self.warm_start = bool(warm_start)
         self.calib = None if calib is None else intrinsics(calib)
         # the pose goes back to the device through pinned memory: the copy is asynchronous, and the buffer is free again by
@@ -238,6 +247,7 @@ class VisualOdometry:
         self._prev = None
         self.last_depth = None
         self.last_counts = None
+        self.last_refine_counts = None
         self.current_pose = torch.eye(4, dtype=torch.float32)
         self.pipe.head.reset_lstm()
         self.pipe.flow_net.break_chain()   # a new sequence: no features or flow carried over
@@ -254,11 +264,20 @@ class VisualOdometry:
             _, flow = self.pipe.flow_net.forward_consecutive(self._prev, im, iters=self.pipe.iters, warm_start=self.warm_start)
             rot, tr = self.pipe.head(flow)
             rt = torch.cat([rot.reshape(-1), tr.reshape(-1)]).cpu()   # one trip to the host for both vectors
-            self.current_pose = transforms.accumulate(self.current_pose, rt[:3], rt[3:])
+            if not self.refine_pose:
+                self.current_pose = transforms.accumulate(self.current_pose, rt[:3], rt[3:])
             if self.calib is not None:
                 self._pose_host.copy_(transforms.transform(rt[:3], rt[3:])[:3].reshape(12))
                 pose = self._pose_host.to(self.device, non_blocking=True)[None]
+                if self.refine_pose:
+                    pose, _, self.last_refine_counts = transforms.pose_from_flow(flow, pose, self.calib)
                 self.last_depth, self.last_counts = transforms.two_view_depth(flow, pose, self.calib)
+                if self.refine_pose:
+                    # (the copy into the buffer is ordered after the copy out of it: same stream; it waits for the solve)
+                    self._pose_host.copy_(pose[0, :3].reshape(12))
+                    step = torch.eye(4, dtype=torch.float32)
+                    step[:3] = self._pose_host.view(3, 4)
+                    self.current_pose = self.current_pose @ step
         self._prev = im
         return self.current_pose
 

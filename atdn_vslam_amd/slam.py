@@ -88,14 +88,23 @@ class NeuralSLAM:
     that registers the next keyframe, so each pixel's depth is triangulated over the longest baseline its track survives. The file
     has the same name, shape and dtype; it is written when the next keyframe is registered, or by `end_odometry()` for the last
     keyframe if any pair followed it. Poses and `rgb/` files do not depend on the choice.
+    `refine_pose=True` (needs `calib`): in odometry mode every pair's predicted pose is refined on the pair's own flow
+    (transforms.pose_from_flow with its defaults, on the device: the rotation and the direction of t; |t| stays the head's) before
+    anything uses it: the "pair" keyframe depth, the poses fed to the flow track, the keyframe policy and the running pose
+    (float32 pose @ refined step) all see the refined pose; `last_refine_counts` [1,4] = (candidates, used, inliers, accepted
+    steps) of the last pair stays on the device. With False (the default) nothing changes anywhere.
     """
 
     FLOW_CHECKPOINT = "atdn_vslam/checkpoints/gma-kitti.pth"  # utils/gma_parameters.py
 
     def __init__(self, args, odometry_weights=None, start_mode=None, flow_weights=None, mapping_weights=None,
                  precision=None, map_options=None, resident_map=False, warm_start=False, calib=None, keyframe_depth="pair",
-                 loop_closure=False, loop_options=None):
+                 loop_closure=False, loop_options=None, refine_pose=False):
         from .depth import intrinsics
+        if refine_pose and calib is None:
+            raise ValueError("refine_pose=True needs the calibration: pass calib=")
+        self._refine_pose = bool(refine_pose)
+        self.last_refine_counts = None
         if loop_closure and not resident_map:
             raise ValueError("loop_closure=True needs the keyframe map in device memory: pass resident_map=True")
         self._loop_closure = bool(loop_closure)
@@ -235,7 +244,12 @@ class NeuralSLAM:
                 pred_rot, pred_tr = self._odometry_net(flow)
                 rot, tr = pred_rot.squeeze().cpu(), pred_tr.squeeze().cpu()
                 pred_mat = transforms.transform(rot, tr)
-                self._current_pose = transforms.accumulate(self._current_pose, rot, tr)  # float32 pose @ pred_mat
+                if self._refine_pose:
+                    refined, _, self.last_refine_counts = transforms.pose_from_flow(flow, pred_mat[None].to(self._device), self._calib)
+                    pred_mat = refined[0].cpu()
+                    self._current_pose = self._current_pose @ pred_mat
+                else:
+                    self._current_pose = transforms.accumulate(self._current_pose, rot, tr)  # float32 pose @ pred_mat
                 if self._track_index is not None:
                     self._track.extend(flow, pred_mat)
                 if self._depth_pending is not None:

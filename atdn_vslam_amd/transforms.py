@@ -298,6 +298,88 @@ def pose_from_depth(depth, flow, pose_init, calib, mask=None, iters=16, scale_px
     return (pose[0], cost[0], counts[0]) if single else (pose, cost, counts)
 
 
+def _epipolar_inputs(flow, pose, calib, mask, scale_px, inlier_px):
+    """The checked, contiguous inputs of `epipolar_terms` and `pose_from_flow`, with the batch axis added to 3-d forms."""
+    from .depth import intrinsics
+    if flow.dim() not in (3, 4) or flow.shape[-3] != 2:
+        raise RuntimeError("expected a flow [2,H,W] or [B,2,H,W], got %s" % (tuple(flow.shape),))
+    single = flow.dim() == 3
+    f = (flow[None] if single else flow).detach().float().contiguous()
+    B, _, H, W = f.shape
+    p = _pose_rows(pose, B, f.device)
+    m = None
+    if mask is not None:
+        m = _byte_plane(torch.as_tensor(mask), "a mask", B, H, W)
+        if m.device != f.device:
+            raise RuntimeError("flow on %s but mask on %s" % (f.device, m.device))
+    ptr = (C.c_void_p(f.data_ptr()), C.c_void_p(m.data_ptr()) if m is not None else None, C.c_void_p(p.data_ptr()), B, H, W) + \
+        tuple(intrinsics(calib)) + (float(scale_px), float(inlier_px))
+    return single, (f, m, p), ptr, B, H, W
+
+
+def _epipolar_workspace(B, H, W, device):
+    n = int(_lib.lib().atdn_epipolar_workspace_bytes(B, H, W))
+    return torch.empty((max(n, 8) + 7) // 8, dtype=torch.float64, device=device)
+
+
+def epipolar_terms(flow, pose, calib, mask=None, scale_px=2.0, inlier_px=1.0):
+    """How well a pose explains a flow, without any depth. `flow` [B,2,H,W] (or [2,H,W]) is the flow from image 1 to image 2,
+    `pose`, `calib` and `mask` as for `two_view_depth` (X1 = R X2 + t). Every pixel whose flow lands inside image 2 is a candidate;
+    its signed pixel distance from the epipolar line the pose gives it is the residual. Returns `(sums, counts)` on the flow's
+    device: `sums` float64 [B,28] ([28]) = the 21 upper-triangle entries of the Gauss-Newton Hessian, the 6 gradient entries —
+    over a rotation step and a ROTATION of the translation: its length is not observable and never changes — and the cost under
+    the Geman-McClure loss of scale `scale_px`; `counts` int32 [B,3] ([3]) = (candidates, those with a line, those within
+    `inlier_px` pixels of it). `counts[:, 2] / counts[:, 0]` is the share of inliers: these are not the counts of `two_view_depth`,
+    so `epipolar_score` is not for them. Device tensors go through libatdn_hip's kernels on the current stream and the results
+    stay on the device (no synchronisation); CPU tensors go through the library's host form. The rule is float64, fixes the order
+    of every sum and is stated in full in include/atdn_hip.h, atdn_epipolar_terms; the same inputs give the same bits on every
+    call and on both paths."""
+    single, keep, ptr, B, H, W = _epipolar_inputs(flow, pose, calib, mask, scale_px, inlier_px)
+    dev = keep[0].device
+    sums = torch.empty((B, 28), dtype=torch.float64, device=dev)
+    counts = torch.empty((B, 3), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    out = (C.c_void_p(sums.data_ptr()), C.c_void_p(counts.data_ptr()))
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            ws = _epipolar_workspace(B, H, W, dev)
+            _lib.check(L.atdn_epipolar_terms(*ptr, *out, C.c_void_p(ws.data_ptr()), _stream()))
+    else:
+        _lib.check(L.atdn_epipolar_terms_host(*ptr, *out))
+    return (sums[0], counts[0]) if single else (sums, counts)
+
+
+def pose_from_flow(flow, pose_init, calib, mask=None, iters=16, scale_px=2.0, inlier_px=1.0):
+    """The relative pose refined on the flow alone: `iters` Levenberg-Marquardt steps from `pose_init` on the terms of
+    `epipolar_terms`, every problem of the batch on its own, all on the device. Arguments as for `epipolar_terms`. Returns
+    `(pose, cost, counts)` on the flow's device: `pose` float32 [B,4,4] ([4,4] for a 3-d flow) with X1 = R X2 + t — the rotation
+    and the DIRECTION of t are refined, |t| is `pose_init`'s up to float32 rounding —, `cost` float64 [B] and `counts` int32 [B,4]
+    = (candidates, used, inliers, accepted steps) at it; `counts[:, 2] / counts[:, 0]` is the share of inliers. Where no step was
+    accepted — t = 0, an all-zero mask, a NaN in the pose — `pose` holds the bits of `pose_init`. This is a refinement from a pose
+    that is near (the pose head's), not a global solver: the cost is blind to the sign of t and to the twisted pair. Small images
+    with many outliers converge slowly (the rotation/translation valley of a forward motion is flat under a redescending loss):
+    give them more `iters`. 2 * (iters + 1) launches on the current stream and no synchronisation; CPU tensors go through the
+    library's host form. The rule is stated in full in include/atdn_hip.h, atdn_epipolar_solve; the same inputs give the same
+    bits on every call and on both paths."""
+    single, keep, ptr, B, H, W = _epipolar_inputs(flow, pose_init, calib, mask, scale_px, inlier_px)
+    dev = keep[0].device
+    pose = torch.zeros((B, 4, 4), dtype=torch.float32, device=dev)
+    pose[:, 3, 3] = 1.0
+    rows = torch.empty((B, 12), dtype=torch.float32, device=dev)
+    cost = torch.empty((B,), dtype=torch.float64, device=dev)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    out = (int(iters), C.c_void_p(rows.data_ptr()), C.c_void_p(cost.data_ptr()), C.c_void_p(counts.data_ptr()))
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            ws = _epipolar_workspace(B, H, W, dev)
+            _lib.check(L.atdn_epipolar_solve(*ptr, *out, C.c_void_p(ws.data_ptr()), _stream()))
+    else:
+        _lib.check(L.atdn_epipolar_solve_host(*ptr, *out))
+    pose[:, :3, :] = rows.view(B, 3, 4)
+    return (pose[0], cost[0], counts[0]) if single else (pose, cost, counts)
+
+
 def flow_track_step(flow, acc, alive, pose=None, calib=None, mask=None, depth=None, max_epipolar=1.0, min_parallax_deg=0.05,
                     max_depth=80.0, out=None):
     """One step of a flow track: the correspondences of an anchor frame's pixels carried one frame further and, given a pose,

@@ -560,6 +560,85 @@ int atdn_pnp_solve_host(const float* depth, const float* flow, const unsigned ch
                         float* pose_out, double* cost, int* counts);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Pose from flow alone (epipolar refinement)  —  the flow image 1 -> image 2 gives every pixel a correspondence, a relative pose
+ * gives it an epipolar line: the pose that puts the correspondences on their lines, by Levenberg-Marquardt on the signed pixel
+ * distance under the Geman-McClure loss, over the FIVE degrees of freedom two views show — the rotation and the direction of the
+ * translation; the length of t is kept to the last bit of its own rounding —, batched over problems, all on the device.
+ * atdn_epipolar_terms is one evaluation, atdn_epipolar_solve the solver. It needs no depth (atdn_pnp_solve does) and it is a
+ * REFINEMENT from a pose that is already near, e.g. the pose head's: the cost does not see the sign of t nor the twisted pair
+ * (R, t) <-> (rotation by pi about t, t), and nothing here chooses among them or searches globally. The reference has nothing
+ * like it.
+ * ------------------------------------------------------------------------------------------------- */
+
+/* Bytes of the workspace of atdn_epipolar_terms / atdn_epipolar_solve for B planes of H x W (0 for sizes they refuse): as
+ * atdn_pnp_workspace_bytes. No call reads what an earlier call left there. */
+long atdn_epipolar_workspace_bytes(int B, int H, int W);
+
+/* sums[b] = the 28 epipolar terms of pose[b] summed over the plane, counts[b] = (candidates, used, inliers).
+ *   flow [B,2,H,W] fp32 DEVICE, image 1 -> image 2, channel 0 = x. mask [B,H,W] uint8 DEVICE or NULL: pixels whose byte is 0 are
+ *   skipped. pose [B,12] fp32 DEVICE: the rows of [R|t] with X1 = R X2 + t, as for atdn_flow_two_view_depth. sums [B,28] float64
+ *   DEVICE, counts [B,3] int32 DEVICE, workspace: atdn_epipolar_workspace_bytes(B, H, W) bytes DEVICE, 8-byte aligned like sums;
+ *   no output (the workspace is one) overlaps an input or another output. fx, fy finite and > 0; cx, cy finite; scale_px,
+ *   inlier_px (pixels) finite and > 0. B <= 65535, H * W <= 2^24, B, H, W >= 1. Anything else fails before a launch.
+ * The rule: everything in float64, every operation rounded on its own (no fused multiply-add), only + - * / and comparisons — no
+ * square root —, in exactly this order. r_ij, t_i: the pose as float64. c2 = scale_px*scale_px, thr = inlier_px*inlier_px.
+ * Pixel (x, y) with (u, v) = flow:
+ *   x2, y2, inside, a0, a1, q0, q1, b_i, n_i, res, m0, m1, l0, l1, ll = l0*l0 + l1*l1, epi2 = (res*res)/ll
+ *                                                                 exactly as in atdn_flow_two_view_depth (one shared function)
+ *   cand = mask byte != 0 && inside;  used = cand && ll > 0 && epi2 <= DBL_MAX  (a NaN fails);  inlier = used && epi2 <= thr
+ *   s = 1 + epi2/c2, w = 1/(s*s), rho = (0.5*epi2)/s              (Geman-McClure)
+ *   The step (dw, dth) acts as R <- C(dw) R, t <- C(dth) t with C the Cayley matrix below: the translation is rotated, never
+ *   added to. With x*y - z*w meaning two rounded products and their rounded difference:
+ *   Jres = (b x n, t x k) with k = a x b, a2 = 1:
+ *     Jres_0 = b1*n2 - b2*n1, Jres_1 = b2*n0 - b0*n2, Jres_2 = b0*n1 - b1*n0
+ *     k0 = a1*b2 - b1, k1 = b0 - a0*b2, k2 = a0*b1 - a1*b0
+ *     Jres_3 = t1*k2 - t2*k1, Jres_4 = t2*k0 - t0*k2, Jres_5 = t0*k1 - t1*k0
+ *   at = (a0*t0 + a1*t1) + t2;  e0 = l0/fx, e1 = l1/fy
+ *   dm_j (j = 0, 1; the derivative of m_j; r_.j is column j of R):  R^T [n]x  and  R^T [a]x [t]x = (r_.j . t) a^T - at (r_.j)^T:
+ *     dm_j0 = r_1j*n2 - r_2j*n1, dm_j1 = r_2j*n0 - r_0j*n2, dm_j2 = r_0j*n1 - r_1j*n0
+ *     rt_j = (r_0j*t0 + r_1j*t1) + r_2j*t2
+ *     dm_j3 = rt_j*a0 - at*r_0j, dm_j4 = rt_j*a1 - at*r_1j, dm_j5 = rt_j - at*r_2j
+ *   kk = res/(2*ll), ww = w/ll
+ *   dll_i = 2*(e0*dm_0i + e1*dm_1i),  j_i = Jres_i - kk*dll_i    (the derivative of res/sqrt(ll), times sqrt(ll): no root)
+ *   terms 0..20: H_ij = (ww*j_i)*j_j for i <= j, row by row (00, 01, .., 05, 11, .., 55)
+ *   terms 21..26: g_i = (ww*j_i)*res;  term 27: rho
+ *   !used: +0.0 in all 28 terms
+ * Sums and counts: exactly as for atdn_pnp_terms (chunks of 1024 flat indices, four per thread, the binary tree, the chunks in
+ * order; no atomics, no memset). Two launches on `stream`: asynchronous, capturable, no host synchronisation.
+ * counts[2]/counts[0] is the share of the flow's correspondences within inlier_px of their epipolar line; with no mask and
+ * inlier_px = max_epipolar, counts[0] and counts[2] equal counts[0] and counts[1] of atdn_flow_two_view_depth at the same pose. */
+int atdn_epipolar_terms(const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W, double fx, double fy,
+                        double cx, double cy, double scale_px, double inlier_px, double* sums, int* counts, void* workspace,
+                        void* stream);
+/* The same function on HOST buffers in plain C++ float64 (csrc/epipolar_host.h, the functions the kernels call too): serves CPU
+ * tensors, needs no GPU and no workspace, the same bits. */
+int atdn_epipolar_terms_host(const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W, double fx,
+                             double fy, double cx, double cy, double scale_px, double inlier_px, double* sums, int* counts);
+
+/* pose_out[b] = the pose after `iters` Levenberg-Marquardt steps from pose_init[b] on the terms above; cost[b] and
+ * counts[b] = (candidates, used, inliers, accepted steps) at it. Arguments as for atdn_epipolar_terms; pose_init, pose_out
+ * [B,12] fp32 DEVICE, cost [B] float64 DEVICE (8-byte aligned), counts [B,4] int32 DEVICE, 0 <= iters <= 64.
+ * The state, the decision rule and the lambda constants are those of atdn_pnp_solve, on the pose (R, t) in float64; evaluation 0
+ * is at pose_init. Then, unless k = iters, from the accepted terms and the accepted t:
+ *   A = H;  tt = (t0*t0 + t1*t1) + t2*t2;  gamma = ((H_33 + H_44) + H_55)/tt;  A_(3+i)(3+j) = A_(3+i)(3+j) + (gamma*t_i)*t_j
+ *     (the gauge term: dth along t does not move t, the data give that direction no curvature, this gives it the block's mean)
+ *   A_ii = A_ii + lambda*A_ii;  LDL^T, the two triangular solves and the failure rule of atdn_pnp_solve, delta = (dw, dth)
+ *   C(d): h = 0.5*d, n2 = (h0*h0 + h1*h1) + h2*h2, f = 2/(1 + n2), C_ii = 1 + f*(h_i*h_i - n2), C_ij = f*(K_ij + h_i*h_j), K = [h]x
+ *   R'_ij = (C(dw)_i0*r_0j + C(dw)_i1*r_1j) + C(dw)_i2*r_2j,  t'_i = (C(dth)_i0*t0 + C(dth)_i1*t1) + C(dth)_i2*t2
+ * t = 0, a NaN in the pose or a plane without candidates need no special case: no pixel is used, the sums are +0.0, gamma or a
+ * pivot fails, the trial is the accepted pose again and no step is ever accepted.
+ * Output: the accepted R and t, each rounded to fp32 once; when no step was accepted pose_out holds the bits of pose_init.
+ * `iters` steps are iters + 1 evaluations, two launches each; no host synchronisation, capturable. Under a redescending loss
+ * the valley between rotation and translation direction of a forward motion is flat: small images with many outliers converge
+ * linearly and may want more steps than the default of the Python layer. */
+int atdn_epipolar_solve(const float* flow, const unsigned char* mask, const float* pose_init, int B, int H, int W, double fx,
+                        double fy, double cx, double cy, double scale_px, double inlier_px, int iters, float* pose_out, double* cost,
+                        int* counts, void* workspace, void* stream);
+int atdn_epipolar_solve_host(const float* flow, const unsigned char* mask, const float* pose_init, int B, int H, int W, double fx,
+                             double fy, double cx, double cy, double scale_px, double inlier_px, int iters, float* pose_out,
+                             double* cost, int* counts);
+
+/* ---------------------------------------------------------------------------------------------------
  * Pose-graph optimisation (loop closure)  —  the poses of the keyframes are the nodes, a measured relative pose between two of
  * them is an edge: consecutive keyframes by odometry, revisits by relocalisation and PnP. Levenberg-Marquardt over the graph
  * with a conjugate-gradient solve preconditioned by the block-tridiagonal part of the system (a keyframe graph is a chain plus
