@@ -229,6 +229,7 @@ int atdn_clvo_step(atdn_clvo* h, const float* feat, int T, int Bs, float* state,
   h->net.step(feat, T, Bs, state, rot, tr, (hipStream_t)stream);
   ATDN_API_END
 }
+int atdn_clvo_last_scan_path(atdn_clvo* h) { return h ? h->net.last_scan_path() : 0; }
 void atdn_clvo_destroy(atdn_clvo* h) { delete h; }
 
 int atdn_vae_create(atdn_vae** out, int H, int W, int max_batch) {

@@ -20,6 +20,9 @@ class ClvoNet {
   void encode(const float* flow, int B, float* feat, hipStream_t st);
   // feat [T][Bs][512]; state [4][Bs][512] = h1,c1,h2,c2 (in/out); rot,tr [T][Bs][3]
   void step(const float* feat, int T, int Bs, float* state, float* rot, float* tr, hipStream_t st);
+  // route of the last step(): 0 none yet, 1 eager per-step launches, 2 graph replay of them, 3 persistent scan, 4 persistent scan
+  // that gave up and was repeated per step (clvo.hip; what a test needs to know which kernel it compared)
+  int last_scan_path() const { return last_scan_path_; }
 
   int H, W, maxB;
 
@@ -66,6 +69,7 @@ class ClvoNet {
   bool scan_persistent_ = true;
   DeviceBuf scan_xch_, scan_state0_;
   unsigned int* scan_abort_host_ = nullptr;
+  int last_scan_path_ = 0;
 };
 
 }  // namespace atdn

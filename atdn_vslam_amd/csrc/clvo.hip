@@ -203,6 +203,7 @@ void ClvoNet::step(const float* feat, int T, int Bs, float* state, float* rot, f
   const MlpHead Tt{tr_[0].w, tr_[0].b, tr_[1].w, tr_[1].b, tr_[2].w};
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(st, &capturing);
+  bool gave_up = false;
   if (scan_persistent_ && Bs == 1 && T >= kPersistentMinSteps && capturing == hipStreamCaptureStatusNone) {
     // ONE launch for the whole sequence (lstm_scan.hip): reads and writes the caller's state in place, h2 of every step into
     // hseq2_ rows 1..T (where the per-step pipeline leaves them), then both regressors batched over the sequence.
@@ -218,8 +219,10 @@ void ClvoNet::step(const float* feat, int T, int Bs, float* state, float* rot, f
     ATDN_HIP(hipStreamSynchronize(st));
     if (*scan_abort_host_ == 0u) {
       launch_mlp_heads(hseq2_.p + sb, (int)rows, R, Tt, rot, tr, st);
+      last_scan_path_ = 3;
       return;
     }
+    gave_up = true;
     fprintf(stderr, "atdn: the persistent LSTM scan gave up on a bounded spin (its workgroups were not resident together); "
                     "repeating the sequence on the per-step kernel and staying there\n");
     scan_persistent_ = false;
@@ -264,8 +267,10 @@ void ClvoNet::step(const float* feat, int T, int Bs, float* state, float* rot, f
         scan_graphs_[key] = exec;
       }
       ATDN_HIP(hipGraphLaunch(scan_graphs_[key], st));
+      last_scan_path_ = gave_up ? 4 : 2;
     } else {
       launch_scan_steps(T, Bs, st);
+      last_scan_path_ = gave_up ? 4 : 1;
     }
     ATDN_HIP(hipMemcpyAsync(c1, cstate_.p, sb * sizeof(float), hipMemcpyDeviceToDevice, st));
     ATDN_HIP(hipMemcpyAsync(c2, cstate_.p + sb, sb * sizeof(float), hipMemcpyDeviceToDevice, st));

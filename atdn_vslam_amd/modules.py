@@ -551,6 +551,7 @@ class ATDNVO(_NativeModule):
         self.suffix = "_c" + ("d" if use_dropout else "")  # network.py:52-60 (dropout is Identity in eval)
         _build_tree(self, clvo_state_spec())
         self._state = torch.zeros(4, batch_size, 512)
+        self._last_scan_path = 0
 
     # the reference exposes the four state tensors as attributes
     lstm1_h = property(lambda self: self._state[0])
@@ -609,7 +610,14 @@ class ATDNVO(_NativeModule):
             tr = torch.empty((T, Bs, 3), dtype=torch.float32, device=feats.device)
             h = self._handle(hw[0], hw[1], Bs)
             _lib.check(_lib.lib().atdn_clvo_step(h, _ptr(f), T, Bs, _ptr(st), _ptr(rot), _ptr(tr), _stream()))
+            self._last_scan_path = int(_lib.lib().atdn_clvo_last_scan_path(h))   # read now: a later call may rebuild the handle
         return rot, tr, st
+
+    @property
+    def last_scan_path(self):
+        """Route the last `scan` took inside the library: 0 none yet, 1 per-step kernel launched eagerly, 2 per-step kernel
+        replayed from a graph, 3 persistent scan, 4 persistent scan that gave up and was repeated on the per-step kernel."""
+        return self._last_scan_path
 
     @torch.no_grad()
     def forward(self, flows):

@@ -170,6 +170,10 @@ int atdn_clvo_encode(atdn_clvo* h, const float* flow, int B, float* feat, void* 
  *   feat [T,Bs,512]; state [4,Bs,512] = lstm1_h, lstm1_c, lstm2_h, lstm2_c (in/out; zeros == reset_lstm());
  *   rot, tr [T,Bs,3] (Euler yxz radians, translation). */
 int atdn_clvo_step(atdn_clvo* h, const float* feat, int T, int Bs, float* state, float* rot, float* tr, void* stream);
+/* Which route the last atdn_clvo_step of this handle took (host bookkeeping only): 0 no step yet, 1 per-step kernel launched
+ * eagerly, 2 per-step kernel replayed from a captured graph, 3 persistent scan (one launch per sequence), 4 persistent scan that
+ * gave up, the sequence repeated on the per-step kernel. A null handle reports 0. */
+int atdn_clvo_last_scan_path(atdn_clvo* h);
 void atdn_clvo_destroy(atdn_clvo* h);
 
 /* ---------------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@ encoder and the stateful head (the scanned rotation, floor 1e-6); M_ITER and M_E
 relative to its own max|g64|, was 4.2e-4 (that same stem bias, a sum over every pixel that BatchNorm nearly cancels; the fp32
 oracle's own error there is 1.2e-4); no tensor needs the 1e-3 cap. Running `pytest -s` prints every comparison ("PARITY" lines)."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -24,13 +25,15 @@ from atdn_vslam_amd.training import CLVOTrainer
 from oracle import clvo_ref
 from oracle import clvo_train_ref as ref
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from parity_check import CAP, Checker  # noqa: E402,F401
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 M_ITER, FLOOR = 20.0, 1e-5       # one training iteration (observed 5.82)
 M_ENC, FLOOR_ENC = 2.5, 1e-6      # inference encoder and head (observed 0.72)
 TRAJ = 1e-4                       # four iterations end to end, relative to max|x64| (observed 2.5e-5)
-CAP = 1e-3
 
 GEOMS = [(376, 1232), (375, 1232), (370, 1226), (353, 1217)]
 SHAPES = [(2, 1), (3, 2), (5, 3)]
@@ -76,32 +79,6 @@ def oracle(sd):
             cache[key] = (inputs, _oracle_iteration(sd, inputs, torch.float32), _oracle_iteration(sd, inputs, torch.float64))
         return cache[key]
     return get
-
-
-class Checker:
-    """Collects every comparison (for the calibration table) and every violation (reported together at the end)."""
-
-    def __init__(self, case, m, floor=FLOOR):
-        self.case, self.m, self.floor, self.rows, self.bad = case, m, floor, [], []
-
-    def __call__(self, name, hip, x32, x64):
-        hip, x32, x64 = hip.detach().cpu().double().flatten(), x32.detach().double().flatten(), x64.detach().double().flatten()
-        assert hip.shape == x64.shape, (name, hip.shape, x64.shape)
-        assert bool(torch.isfinite(hip).all()), name
-        scale = float(x64.abs().max())
-        e_hip, e32 = float((hip - x64).abs().max()), float((x32 - x64).abs().max())
-        bound = min(self.m * e32 + self.floor * scale, CAP * scale)
-        need = max(0.0, e_hip - self.floor * scale) / e32 if e32 > 0 else (0.0 if e_hip <= self.floor * scale else float("inf"))
-        self.rows.append((name, e_hip / scale if scale else e_hip, e32 / scale if scale else e32, need))
-        if not e_hip <= bound:
-            self.bad.append("%s: max|hip-64| %.3e > bound %.3e (max|64| %.3e, max|32-64| %.3e)" % (name, e_hip, bound, scale, e32))
-
-    def finish(self):
-        for name, rel, rel32, need in self.rows:
-            print("PARITY %s %s rel_hip=%.3e rel_32=%.3e need_m=%.3g" % (self.case, name, rel, rel32, need))
-        worst = max(self.rows, key=lambda r: r[3])
-        print("PARITY-WORST %s %s need_m=%.3g" % (self.case, worst[0], worst[3]))
-        assert not self.bad, "%s:\n  " % self.case + "\n  ".join(self.bad)
 
 
 def _check_iteration(chk, trainer, got, o32, o64):
