@@ -34,7 +34,10 @@ std::vector<ResizeTable> make_table_aa(int in, int out) {
     int xmin = (int)(center - support + 0.5f); if (xmin < 0) xmin = 0;
     int xmax = (int)(center + support + 0.5f); if (xmax > in) xmax = in;
     const int size = xmax - xmin;
-    ATDN_CHECK(size >= 1 && size <= RESIZE_TAPS, "resize ratio outside the supported range (down-scaling by more than 3.5x)");
+    // a window is int(c + s + .5) - int(c - s + .5) <= floor(2s) + 1 taps wide, and exactly 2s at s = 4 (c - s + .5 = 4i + .5):
+    // every ratio up to and including 4 fits RESIZE_TAPS = 8; 129 -> 32 (4.03x) already has a 9-tap pixel
+    ATDN_CHECK(size >= 1 && size <= RESIZE_TAPS,
+               "resize ratio outside the supported range (antialiased down-scaling by more than 4x needs more than 8 taps per pixel)");
     float total = 0.f;
     ResizeTable t{};
     t.start = xmin; t.count = size;

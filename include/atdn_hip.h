@@ -265,7 +265,11 @@ int atdn_pose_accumulate_f32(float* pose16, const float* rot, const float* tr);
 #define ATDN_RESIZE_ANTIALIAS 1
 
 /* src [planes,Hin,Win] (planes = any product of leading dims, e.g. B*3) -> dst [planes,Hout,Wout]; antialiased.
- * Weight tables are cached per (device, geometry, mode); no intermediate buffer: safe on any number of streams. */
+ * Weight tables are cached per (device, geometry, mode); no intermediate buffer: safe on any number of streams.
+ * RATIO LIMIT (ANTIALIAS only): a weight table holds 8 taps per output pixel, which serves every down-scaling ratio up to and
+ * including 4x per axis (at 4x each pixel has exactly 8 taps). A geometry in which some output pixel needs more (129 -> 32
+ * already does) is refused with an error by these calls and by atdn_ingest_create, and dst is left untouched. Up-scaling
+ * and ATDN_RESIZE_BILINEAR (two taps) have no limit. */
 int atdn_resize_frames(const float* src, int planes, int Hin, int Win, int Hout, int Wout, float* dst, void* stream);
 int atdn_resize_frames_mode(const float* src, int planes, int Hin, int Win, int Hout, int Wout, int antialias, float* dst,
                             void* stream);
