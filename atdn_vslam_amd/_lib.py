@@ -85,6 +85,10 @@ SIGNATURES = {
                                        C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp]),
     "atdn_flow_track_step_host": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, C.c_double,
                                             C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp]),
+    "atdn_depth_fuse": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                  C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp, _vp]),
+    "atdn_depth_fuse_host": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                       C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp]),
     "atdn_pnp_workspace_bytes": (C.c_long, [C.c_int, C.c_int, C.c_int]),
     "atdn_pnp_terms": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                                  C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),

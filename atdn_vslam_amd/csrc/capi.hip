@@ -11,6 +11,7 @@
 #include "train_kernels.h"  // launch_clvo_loss_composite
 #include "frontend.h"
 #include "conv_sf.h"
+#include "depth_fusion_host.h"
 #include "epilogues_sf.h"
 #include "epipolar_host.h"
 #include "flow_args.h"
@@ -427,6 +428,18 @@ int atdn_flow_track_step_host(const float* flow, const unsigned char* mask, cons
   const TwoViewCamera cam{fx, fy, cx, cy, max_epipolar, min_sin2, max_depth};
   flow_track_check_args(flow, mask, acc_in, alive_in, B, H, W, acc_out, alive_out, pose, cam, depth, counts);
   flow_track_step_host(flow, mask, acc_in, alive_in, B, H, W, acc_out, alive_out, pose, cam, depth, counts);
+  ATDN_API_END
+}
+
+// ------------------------------------------------------------------ depth fusion (host twin of depth_fusion.hip)
+int atdn_depth_fuse_host(const float* bank, const float* poses, const int* targets, const int* sources, int N, int B, int S, int H,
+                         int W, double fx, double fy, double cx, double cy, double max_reproj, double max_rel_depth, int min_views,
+                         double min_z, int average, float* fused, unsigned char* views, int* counts) {
+  ATDN_API_BEGIN
+  depth_fuse_check_args(bank, poses, targets, sources, N, B, S, H, W, fx, fy, cx, cy, max_reproj, max_rel_depth, min_views, min_z,
+                        fused, views, counts);
+  depth_fuse_host(bank, poses, targets, sources, N, B, S, H, W,
+                  depth_fuse_params(fx, fy, cx, cy, max_reproj, max_rel_depth, min_views, min_z, average), fused, views, counts);
   ATDN_API_END
 }
 

@@ -1,4 +1,4 @@
-// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip, epipolar.hip), shared by each device
+// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip, epipolar.hip, depth_fusion.hip), shared by each device
 // entry point and its host twin in capi.hip, and the overlap rule that the pose solvers (pnp.hip, pose_graph.hip) share.
 #pragma once
 #include <cmath>
@@ -63,5 +63,9 @@ void pnp_check_args(const float* depth, const float* flow, const unsigned char* 
 void epipolar_check_args(const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W, double fx, double fy,
                          double cx, double cy, double scale_px, double inlier_px, bool grid_limit, const void* const* out,
                          const long* out_bytes, int n_out);
+// sources may be null only when S == 0
+void depth_fuse_check_args(const float* bank, const float* poses, const int* targets, const int* sources, int N, int B, int S,
+                           int H, int W, double fx, double fy, double cx, double cy, double max_reproj, double max_rel_depth,
+                           int min_views, double min_z, const float* fused, const unsigned char* views, const int* counts);
 
 }  // namespace atdn

@@ -87,6 +87,18 @@ __device__ __forceinline__ void quad_store(const Quad& q, unsigned char* p, cons
   }
 }
 
+// p[s0 + k] = the low byte of v[k] (0 .. 255)
+__device__ __forceinline__ void quad_store_bytes(const Quad& q, unsigned char* p, const int v[4]) {
+  if (q.full && ((uintptr_t)(p + q.s0) & 3) == 0) {
+    *reinterpret_cast<uint32_t*>(p + q.s0) = ((uint32_t)v[0] & 0xFFu) | (((uint32_t)v[1] & 0xFFu) << 8) |
+                                             (((uint32_t)v[2] & 0xFFu) << 16) | (((uint32_t)v[3] & 0xFFu) << 24);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (q.has(k)) p[q.s0 + k] = (unsigned char)v[k];
+  }
+}
+
 // counts[j] += the number of pixels of the workgroup whose flags have bits[j], j < NC. Integer sums — ballot / popcount per wave
 // (every lane gets the wave's sums; lane 0 hands them to LDS), the waves of the workgroup through LDS, one integer atomic add per
 // workgroup and counter, none for a zero —, so the result does not depend on the order of arrival. Every thread of the workgroup

@@ -191,6 +191,46 @@ class KeyframeMap:
             return torch.zeros((len(ix),) + self.hw, dtype=torch.float32, device=self.device)
         return self.depth_bank.index_select(0, torch.tensor(ix, dtype=torch.int64).to(self.device, non_blocking=True))
 
+    @torch.no_grad()
+    def fuse_depths(self, calib, window=2, sources=None, replace=False, batch=16, **thresholds):
+        """Multi-view consistency filter of the keyframe depths (`transforms.fuse_depths`, where the rule and the `thresholds`
+        max_reproj, max_rel_depth, min_views, min_z, average are described) over the whole map, straight from the depth bank and
+        the poses: no copy of the bank, `batch` targets per launch. The sources of keyframe k are `sources[k]` ([n,S] integers,
+        host; an entry < 0, >= n or == k is an empty slot) or, by default, its neighbours k-window .. k+window without k, with
+        empty slots where the map ends. Returns device tensors `(fused [n,H,W] float32, views [n,H,W] uint8, counts [n,3] int32)`,
+        counts = (pixels with a depth, pixels some source saw, pixels kept). The fusion is Jacobi: every target reads the
+        unfused bank; `replace=True` then puts the fused depths into the bank (relocalisation's PnP leg and a second call
+        see them). `calib` is the calibration of the map's grid. A map without a depth bank raises."""
+        if self.depth_bank is None or self.n == 0:
+            raise RuntimeError("fuse_depths: the map holds no depth (set_depth gives a keyframe its depth map)")
+        n = self.n
+        if sources is None:
+            w = int(window)
+            if w < 0:
+                raise ValueError("window must be >= 0, got %d" % w)
+            offsets = [d for d in range(-w, w + 1) if d != 0]
+            src = np.array([[k + d if 0 <= k + d < n else -1 for d in offsets] for k in range(n)], dtype=np.int32).reshape(n, len(offsets))
+        else:
+            src = np.asarray(sources.cpu() if isinstance(sources, torch.Tensor) else sources, dtype=np.int64)
+            if src.ndim != 2 or src.shape[0] != n:
+                raise ValueError("sources must be [%d,S], got %s" % (n, src.shape))
+            src = np.clip(src, -1, 2 ** 31 - 1).astype(np.int32)
+        batch = max(1, int(batch))
+        bank = self.depth_bank[:n]                                    # a view of the bank's first n planes
+        poses = self._poses[:n, :3, :].reshape(n, 12).to(self.device)
+        fused, views, counts = [], [], []
+        with torch.cuda.device(self.device):
+            for a in range(0, n, batch):
+                b = min(batch, n - a)
+                f, v, c = transforms.fuse_depths(bank, poses, np.arange(a, a + b), src[a:a + b], calib, **thresholds)
+                fused.append(f[:, 0])
+                views.append(v)
+                counts.append(c)
+            fused, views, counts = torch.cat(fused), torch.cat(views), torch.cat(counts)
+            if replace:
+                bank.copy_(fused)                                     # after the last target has read the unfused bank
+        return fused, views, counts
+
     @classmethod
     def from_directory(cls, keyframes_path, device, mapping_net=None):
         """The map of a keyframe directory as the reference and slam.NeuralSLAM write it: `rgb/*.pth` (sorted; uint8

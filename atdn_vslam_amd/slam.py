@@ -93,14 +93,24 @@ class NeuralSLAM:
     anything uses it: the "pair" keyframe depth, the poses fed to the flow track, the keyframe policy and the running pose
     (float32 pose @ refined step) all see the refined pose; `last_refine_counts` [1,4] = (candidates, used, inliers, accepted
     steps) of the last pair stays on the device. With False (the default) nothing changes anywhere.
+    `fuse_depth=True` (needs `calib` and `resident_map`): at the end of `end_odometry()` — after the loop closure when that is on,
+    so with the optimised poses — the keyframe depths are filtered against their neighbours (`fuse_depths`, `fuse_options` its
+    keyword arguments): `depth_fused/%06d.pth`, `depth_views/%06d.pth` and `fusion_counts`; `keyframe_points(i, fused=True)` reads
+    them. With False (the default) no file, directory or return value changes.
     """
 
     FLOW_CHECKPOINT = "atdn_vslam/checkpoints/gma-kitti.pth"  # utils/gma_parameters.py
 
     def __init__(self, args, odometry_weights=None, start_mode=None, flow_weights=None, mapping_weights=None,
                  precision=None, map_options=None, resident_map=False, warm_start=False, calib=None, keyframe_depth="pair",
-                 loop_closure=False, loop_options=None, refine_pose=False):
+                 loop_closure=False, loop_options=None, refine_pose=False, fuse_depth=False, fuse_options=None):
         from .depth import intrinsics
+        if fuse_depth and (calib is None or not resident_map):
+            raise ValueError("fuse_depth=True needs the calibration and the keyframe map in device memory: pass calib= and "
+                             "resident_map=True")
+        self._fuse_depth = bool(fuse_depth)
+        self._fuse_options = dict(fuse_options or {})
+        self.fusion_counts = None    # [K,3] int32 (host) of the last fuse_depths(): pixels with a depth, seen, kept
         if refine_pose and calib is None:
             raise ValueError("refine_pose=True needs the calibration: pass calib=")
         self._refine_pose = bool(refine_pose)
@@ -161,6 +171,11 @@ class NeuralSLAM:
                 os.makedirs(os.path.join(self._base, "depth"), exist_ok=True)
             for f in glob.glob(os.path.join(self._base, "depth", "*")):
                 os.remove(f)
+            if self._fuse_depth:
+                for sub in ("depth_fused", "depth_views"):
+                    os.makedirs(os.path.join(self._base, sub), exist_ok=True)
+                    for f in glob.glob(os.path.join(self._base, sub, "*")):
+                        os.remove(f)
             # a cold start owns the directory: poses and map weights of an earlier session go too
             for stale in ("poses.pth", "poses_closed.pth", "MappingVAE_weights.pth"):
                 stale_path = os.path.join(self._base, stale)
@@ -202,6 +217,8 @@ class NeuralSLAM:
             self._mode = "relocalization"
             if self._loop_closure:
                 self.close_loops(**self._loop_options)
+            if self._fuse_depth:
+                self.fuse_depths(**self._fuse_options)               # after the loop closure: it sees the optimised poses
         elif len(self._keyframes) == 0:
             print("There is no explored enviromnent yet!")
         elif self._mode == "mapping" and mapping_weights is not None:
@@ -229,6 +246,30 @@ class NeuralSLAM:
                 kf.pose = self._map.poses[i].clone()
             torch.save(self._map.poses[:, :3, :].reshape(-1, 12).clone(), os.path.join(self._base, "poses_closed.pth"))
         return report
+
+    @torch.no_grad()
+    def fuse_depths(self, **options):
+        """Fuse the keyframe depths across the map (resident map and `calib` only): `KeyframeMap.fuse_depths` with this object's
+        calibration (`options`: its keyword arguments — window, sources, batch, the thresholds; `replace` too). Writes, for every
+        keyframe, `depth_fused/%06d.pth` (float32 [1,H,W], 0 = no depth or rejected) and `depth_views/%06d.pth` (uint8 [H,W], the
+        number of agreeing neighbours); `depth/` stays the unfused depth. Sets and returns `fusion_counts` [K,3] int32 (host).
+        A map in which no keyframe has a depth writes nothing and returns None."""
+        if getattr(self, "_map", None) is None or self._calib is None:
+            raise RuntimeError("fuse_depths needs the keyframe map in device memory and the calibration: construct "
+                               "NeuralSLAM(..., calib=..., resident_map=True)")
+        if self._map.depth_bank is None:
+            self.fusion_counts = None
+            return None
+        fused, views, counts = self._map.fuse_depths(self._calib, **options)
+        fused, views = fused.cpu(), views.cpu()
+        for sub in ("depth_fused", "depth_views"):
+            os.makedirs(os.path.join(self._base, sub), exist_ok=True)
+        for i, kf in enumerate(self._keyframes):
+            name = os.path.basename(kf.rgb_file_name)
+            torch.save(fused[i:i + 1].clone(), os.path.join(self._base, "depth_fused", name))
+            torch.save(views[i].clone(), os.path.join(self._base, "depth_views", name))
+        self.fusion_counts = counts.cpu()
+        return self.fusion_counts
 
     @torch.no_grad()
     def __call__(self, im):
@@ -310,16 +351,17 @@ class NeuralSLAM:
         return len(self._keyframes)
 
     @torch.no_grad()
-    def keyframe_points(self, index):
+    def keyframe_points(self, index, fused=False):
         """[3,N] float32 on the device: the pixels of keyframe `index` that have a depth, as points of the world frame — its
         depth file back-projected (depth.project_depth) and moved by the keyframe's pose. Needs `calib`; a keyframe without a
-        depth file (no successor yet) raises FileNotFoundError."""
+        depth file (no successor yet) raises FileNotFoundError. `fused=True` reads the fused depth (`depth_fused/`, written by
+        `fuse_depths`) instead: only the pixels that enough neighbouring keyframes agree on."""
         from .depth import project_depth
         if self._calib is None:
             raise RuntimeError("keyframe_points needs the calibration: construct NeuralSLAM(..., calib=...)")
         kf = self._keyframes[index]
         number = os.path.splitext(os.path.basename(kf.rgb_file_name))[0]
-        depth = torch.load(os.path.join(self._base, "depth", number + ".pth")).to(self._device)
+        depth = torch.load(os.path.join(self._base, "depth_fused" if fused else "depth", number + ".pth")).to(self._device)
         points = project_depth(depth, self._calib)
         points = points[:, depth[0] > 0]
         pose = torch.as_tensor(kf.pose, dtype=torch.float32).to(self._device)

@@ -196,6 +196,69 @@ def two_view_depth(flow, pose, calib, mask=None, max_epipolar=1.0, min_parallax_
     return (depth[0], counts[0]) if single else (depth, counts)
 
 
+def _index_tensor(values, what, device):
+    """`values` (an integer tensor on `device`, or a host sequence) as contiguous int32 on `device`; a tensor elsewhere raises.
+    Values outside the int32 range become -1 and int32's largest: outside every bank, as they were."""
+    if isinstance(values, torch.Tensor):
+        if values.device != device:
+            raise RuntimeError("bank on %s but %s on %s" % (device, what, values.device))
+        t = values.detach()
+    else:
+        t = torch.from_numpy(np.asarray(values, dtype=np.int64))
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise RuntimeError("%s must be integers, got %s" % (what, t.dtype))
+    return t.to(device).clamp(min=-1, max=2 ** 31 - 1).to(torch.int32).contiguous()
+
+
+def fuse_depths(bank, poses, targets, sources, calib, max_reproj=1.0, max_rel_depth=0.01, min_views=2, min_z=0.1, average=True):
+    """Multi-view consistency filter of depth maps (the geometric-consistency fusion of multi-view stereo). `bank` [N,H,W] float32
+    holds N depth maps (0 = no depth), `poses` ([N,12], [N,3,4] or [N,4,4]; rows of [R|t], world <- camera, as `poses.pth` and
+    `KeyframeMap.poses` hold them) their cameras, `calib` is (fx, fy, cx, cy) or a calibration matrix without skew. `targets` [B]
+    names the maps to fuse and `sources` [B,S] the maps each is compared with (tensors on the bank's device or host sequences;
+    a source < 0, >= N or equal to its target is an empty slot). Every target pixel with a depth is projected into each source,
+    the source's depth there (bilinear; not across a hole) is projected back, and the source agrees when it returns within
+    `max_reproj` pixels and `max_rel_depth` relative depth, in front of both cameras by `min_z`. Returns `(fused, views, counts)`
+    on the bank's device: `fused` float32 [B,1,H,W], the target's depth where at least `min_views` sources agree (with `average`
+    the mean of it and the agreeing estimates) and 0 elsewhere; `views` uint8 [B,H,W], the number of agreeing sources; `counts`
+    int32 [B,3] = (pixels with a depth, pixels some source saw, pixels kept). All targets read the unfused bank. Device tensors go
+    through libatdn_hip's kernel on the current stream and the results stay on the device (no synchronisation); CPU tensors go
+    through the library's host form. The rule is float64 and stated in full in include/atdn_hip.h, atdn_depth_fuse; the same
+    inputs give the same bits on every call and on both paths."""
+    from .depth import intrinsics
+    if not isinstance(bank, torch.Tensor) or bank.dim() != 3:
+        raise RuntimeError("expected a depth bank [N,H,W], got %s" % (tuple(getattr(bank, "shape", ())),))
+    if bank.dtype != torch.float32 or not bank.is_contiguous():
+        bank = bank.detach().float().contiguous()
+    N, H, W = (int(v) for v in bank.shape)
+    p = torch.as_tensor(poses)
+    if isinstance(poses, torch.Tensor) and poses.device != bank.device:
+        raise RuntimeError("bank on %s but poses on %s" % (bank.device, poses.device))
+    p = _pose_rows(p, N, bank.device)
+    t = _index_tensor(targets, "targets", bank.device).reshape(-1)
+    B = int(t.shape[0])
+    if B < 1:
+        raise RuntimeError("fuse_depths: no target")
+    s = _index_tensor(sources, "sources", bank.device)
+    s = s.reshape(B, 0) if s.numel() == 0 else s
+    if s.dim() != 2 or s.shape[0] != B:
+        raise RuntimeError("expected sources [%d,S], got %s" % (B, tuple(s.shape)))
+    S = int(s.shape[1])
+    fx, fy, cx, cy = intrinsics(calib)
+    fused = torch.empty((B, 1, H, W), dtype=torch.float32, device=bank.device)
+    views = torch.empty((B, H, W), dtype=torch.uint8, device=bank.device)
+    counts = torch.empty((B, 3), dtype=torch.int32, device=bank.device)
+    L = _lib.lib()
+    args = (C.c_void_p(bank.data_ptr()), C.c_void_p(p.data_ptr()), C.c_void_p(t.data_ptr()), C.c_void_p(s.data_ptr()) if S else None,
+            N, B, S, H, W, fx, fy, cx, cy, float(max_reproj), float(max_rel_depth), int(min_views), float(min_z),
+            1 if average else 0, C.c_void_p(fused.data_ptr()), C.c_void_p(views.data_ptr()), C.c_void_p(counts.data_ptr()))
+    if bank.is_cuda:
+        with torch.cuda.device(bank.device):
+            _lib.check(L.atdn_depth_fuse(*args, _stream()))
+    else:
+        _lib.check(L.atdn_depth_fuse_host(*args))
+    return fused, views, counts
+
+
 def epipolar_score(counts):
     """float32 inliers / inside of the `counts` [B,3] (or [3]) of `two_view_depth`, 0 where no correspondence is inside: the
     share of the flow's correspondences that lie within `max_epipolar` pixels of the epipolar line the pose gives them. Exact

@@ -481,6 +481,58 @@ int atdn_flow_track_step_host(const float* flow, const unsigned char* mask, cons
                               double fy, double cx, double cy, double max_epipolar, double min_sin2, double max_depth, float* depth,
                               int* counts);
 
+/* Keyframe depth fusion: the geometric-consistency filter of multi-view stereo (COLMAP / MVSNet fusion) over a bank of depth maps
+ * with poses. For target i = targets[b], every pixel with a depth is projected into the sources sources[b][.], their depth is
+ * read there and projected back; the pixel is kept where at least min_views sources agree, optionally averaged with their
+ * estimates. Gather only (no atomics on the data), deterministic. All targets of a call read the same, unfused bank.
+ *   bank [N,H,W] fp32 DEVICE, 0 = no depth. poses [N,12] fp32 DEVICE: the rows of [R|t], world <- camera (r_ij = poses[k][4*i + j],
+ *   t_i = poses[k][4*i + 3]), as a keyframe map holds them. targets [B] int32 DEVICE, sources [B,S] int32 DEVICE (may be NULL only
+ *   when S == 0). fused [B,1,H,W] fp32, views [B,H,W] uint8, counts [B,3] int32 = (has, seen, kept), all DEVICE. No other pointer
+ *   may be NULL; every output is disjoint from every input and from the other outputs (fusing into the bank in place is an
+ *   "overlap" error). 1 <= N, 1 <= B <= 65535, 0 <= S <= 255, 1 <= min_views <= 255, H * W <= 2^24; fx, fy finite and > 0; cx, cy
+ *   finite; max_reproj (pixels), max_rel_depth and min_z finite and > 0; average 0 or not 0. Anything else fails before a launch.
+ * The rule, everything in float64 and every operation rounded on its own (no fused multiply-add), in exactly this order. The
+ * sources of target i are walked in list order; a slot with j < 0, j >= N or j == i is skipped and reads nothing; a target outside
+ * [0, N) gives all-zero outputs. Per (target i, source j), once, from the float32 rows, every dot product (p0 + p1) + p2:
+ *   R = R_j^T R_i:  R_kl = (rj_0k*ri_0l + rj_1k*ri_1l) + rj_2k*ri_2l
+ *   d_m = ti_m - tj_m,  t_k = (rj_0k*d_0 + rj_1k*d_1) + rj_2k*d_2                               (X_j = R X_i + t)
+ * Pixel (x, y) with z = bank[i][y][x]:
+ *   has = z > 0; not has: fused 0, views 0, counted nowhere
+ *   a0 = (x - cx)/fx, a1 = (y - cy)/fy, X = (z*a0, z*a1, z)
+ * Per source:
+ *   Xs_k = ((R_k0*X0 + R_k1*X1) + R_k2*X2) + t_k
+ *   front = Xs_2 >= min_z                                         not front: the source is not ok and reads nothing
+ *   u = fx*(Xs_0/Xs_2) + cx, v = fy*(Xs_1/Xs_2) + cy
+ *   inside = 0 <= u <= W-1 && 0 <= v <= H-1                       (closed intervals; a NaN fails); not inside: not ok, nothing read
+ *   ds = bank[j] at (u, v), bilinear exactly as the flow of atdn_flow_track_step is read: x0 = floor(u), ax = u - x0, y0 = floor(v),
+ *   ay = v - y0, taps t00, t10, t01, t11 at (x0, y0), (min(x0+1, W-1), y0), (x0, min(y0+1, H-1)), (min(x0+1, W-1), min(y0+1, H-1)),
+ *   all four always read; top = t00*(1-ax) + t10*ax, bot = t01*(1-ax) + t11*ax, ds = top*(1-ay) + bot*ay
+ *   ok = front && inside && all four taps > 0                     (a hole is not interpolated across)
+ *   q0 = (u - cx)/fx, q1 = (v - cy)/fy, Y = (ds*q0 - t0, ds*q1 - t1, ds - t2)
+ *   Yt_k = (R_0k*Y0 + R_1k*Y1) + R_2k*Y2                          (the source's surface point in the target camera)
+ *   back = ok && Yt_2 >= min_z
+ *   xr = fx*(Yt_0/Yt_2) + cx, yr = fy*(Yt_1/Yt_2) + cy
+ *   e2 = (xr - x)*(xr - x) + (yr - y)*(yr - y),  rd = |Yt_2 - z| / z
+ *   consistent = back && e2 <= max_reproj*max_reproj && rd <= max_rel_depth
+ *   consistent: n += 1, zsum += Yt_2                              (n starts at 0, zsum at z)
+ * Result:
+ *   views = n (written for every pixel); kept = has && n >= min_views
+ *   fused = kept ? (float)(average ? zsum/(n + 1) : z) : 0
+ *   counts = (number of has, of seen, of kept), seen = has and ok for at least one source
+ * Only + - * /, floor, |.|, comparisons and one double -> float conversion, all correctly rounded: the device, the host form and any
+ * IEEE float64 restatement agree bit for bit. Any NaN fails every comparison it reaches.
+ * A memset of `counts` and one launch on `stream`: asynchronous, capturable, no host synchronisation, no workspace. The counts
+ * are integer sums (wave ballots, LDS, one integer atomic add per workgroup and counter; no float atomics): the same bits on
+ * every call. */
+int atdn_depth_fuse(const float* bank, const float* poses, const int* targets, const int* sources, int N, int B, int S, int H, int W,
+                    double fx, double fy, double cx, double cy, double max_reproj, double max_rel_depth, int min_views, double min_z,
+                    int average, float* fused, unsigned char* views, int* counts, void* stream);
+/* The same function on HOST buffers in plain C++ float64 (csrc/depth_fusion_host.h, the functions the kernel calls too): serves
+ * CPU tensors, needs no GPU, the same bits and the same argument rules. */
+int atdn_depth_fuse_host(const float* bank, const float* poses, const int* targets, const int* sources, int N, int B, int S, int H,
+                         int W, double fx, double fy, double cx, double cy, double max_reproj, double max_rel_depth, int min_views,
+                         double min_z, int average, float* fused, unsigned char* views, int* counts);
+
 /* ---------------------------------------------------------------------------------------------------
  * Pose from depth and flow (robust PnP)  —  a depth map of image 1 gives a 3-D point per pixel, the flow image 1 -> image 2 gives
  * that point's pixel in image 2: the pose that explains the correspondences, by Levenberg-Marquardt on the reprojection error
