@@ -208,8 +208,8 @@ def parse_args(argv=None):
         h, w = (int(v) for v in a.size.lower().split("x"))
     except ValueError:
         ap.error("--size must look like 376x1232")
-    if h < 64 or w < 64:
-        ap.error("--size: frames must be at least 64x64")
+    if h < 128 or w < 128:
+        ap.error("--size: frames must be at least 128x128 (level 3 of the correlation pyramid needs at least 2x2 cells)")
     a.size = (h, w)
     if a.pairs < 1:
         ap.error("--pairs must be at least 1")

@@ -32,8 +32,10 @@ const char* atdn_last_error(void);
  *   forward:                   whl:GMA/core/network.py:72-129 (called at neural_slam.py:202,395)
  * ------------------------------------------------------------------------------------------------- */
 
-/* H, W: frame size after the caller's resize/pad (multiples of 8; 376x1232 in NeuralSLAM,
- * neural_slam.py:54,198-199). max_batch: largest number of frame pairs per forward.
+/* H, W: frame size after the caller's resize/pad (multiples of 8, each at least 128; 376x1232 in NeuralSLAM,
+ * neural_slam.py:54,198-199). Below 128 level 3 of the correlation pyramid (H/64 x W/64 cells) is one cell high or wide, and
+ * the reference's bilinear_sampler divides by H/64 - 1 = 0 there (utils/utils.py:63-64): its flow is NaN, so there is nothing
+ * to reproduce and atdn_gma_create refuses the size. max_batch: largest number of frame pairs per forward.
  * precision: ATDN_PRECISION_F32 = every GEMM on the exact-fp32 matrix core (v_mfma_f32_32x32x2_f32);
  *            ATDN_PRECISION_SPLIT_F16 = every channel-wide GEMM as three f16 MFMAs on split operands
  *            (x = hi + lo, fp32 accumulate): fp32-grade results at 5.3x the matrix rate (the default);
