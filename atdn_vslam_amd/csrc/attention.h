@@ -12,8 +12,8 @@ namespace atdn {
 //   a block holds two ROW BLOCKS rb = 0, 1 of 16 rows each; lane (n = lane & 15, g = lane >> 4) owns, in row block rb, row
 //   32*strip + 16*rb + n and the eight columns 32*chunk + 4*g + (i & 3) + 16*(i >> 2), i = 0..7 — the B operand of
 //   v_mfma_f32_16x16x32_f16 (round 3; K = 32 = the whole chunk), with the columns of a key group in the accumulator
-//   order of the producing MFMAs (two 16-key blocks), so producer stores and consumer loads need no shuffle; the V^T
-//   operand is brought into the same column order when it is written to LDS.
+//   order of the producing MFMAs (two 16-key blocks), so producer stores and consumer loads need no shuffle; the V
+//   operand gets the same column order from the two transposed LDS reads that fetch it (keys 4g.. and 16 + 4g..).
 // Values are e = exp(s - rowmax~) * 2^AT_SHIFT, NOT normalised: rinv[pair][row] = 1 / sum_k e is applied by the
 // consumer. rowmax~ comes from a cheap first pass (f16 x f16 logits); softmax is shift-invariant, so any shift close to
 // the true maximum gives the same probabilities and keeps e inside the f16 range (largest element of a row ~ 2^10).
@@ -41,9 +41,10 @@ void launch_qk_rowmax(const float* qk, const AttnGeom& g, float* rowmax, hipStre
 // pass 2: P (fragment-major, see above) and rinv[b][m] = 1 / sum_n exp(s_mn - rowmax_m) * 2^-AT_SHIFT scaling included
 void launch_qk_softmax(const float* qk, const AttnGeom& g, const float* rowmax, float* P, float* rinv, bool fast,
                        hipStream_t st);
-// out[b][m][c] = mf[b][m][c] + gamma * rinv[b][m] * sum_k P[b][m][k] * V[b][k][c]          (gma.py:111-115)
-//   vT sf [B][128][ldN] (V transposed, k contiguous, the 32 keys of every chunk in the operand order above: SfVT);
-//   mf / out sf rows with pixel stride ld (floats), per-pair stride sb
+// out[b][m][c] = rinv[b][m] * sum_k P[b][m][k] * mf[b][k][c]: the aggregate of the motion features THEMSELVES. The rest of
+//   gma.py:111-115 — to_v, gamma and the residual — is folded into the ConvGRU weights at handle build (gma.hip).
+//   mf / out sf rows [pixel][128 channels] with pixel stride ld (floats), per-pair stride sb; the kernel reads mf as it is
+//   stored and transposes it with the LDS read. `vT` and `gamma` are unused (kept in the signature): pass null.
 // `part` != nullptr (the low-latency form, round 6): when the launch would leave most CUs idle (B <= 4 at KITTI size) the key axis
 // is cut into attn_v_splits(g) ranges, one block each, with fp32 partial slabs in `part` ([8][B][Npad][128] floats) and a reduce
 // pass; another summation order than the one-block-per-tile form, so only callers that asked for it get it.

@@ -9,7 +9,8 @@
 //       never exist in memory; the separate softmax pass (read 1.68 GB, write 1.68 GB) is gone.
 //   attn_v3_kernel             attention x V (gma.py:102-115) as a two-set ping-pong, described at the kernel. Every wave
 //       streams ITS strip of the attention matrix — one contiguous 0.5-0.7 MB run — straight into MFMA operand registers,
-//       1 KiB per wave load; only V^T (L2-resident, shared by the block) goes through LDS. (The 4-wave kernel it replaced
+//       1 KiB per wave load; only V (the motion features as stored, L2-resident, shared by the block) goes through LDS, and
+//       the LDS read transposes it (ds_read_b64_tr_b16). (The 4-wave kernel it replaced
 //       — every wave interleaving its own memory work with its own MFMAs — and the 4-byte SF4 element format were
 //       deleted in round 3 after their A/B tests; measurements in DESIGN.md 3.6.)
 #include "attention.h"
@@ -36,6 +37,14 @@ __device__ __forceinline__ void st_frag_nt(char* p, f16x8 v) {
   __builtin_nontemporal_store(__builtin_bit_cast(v4f, v), reinterpret_cast<v4f*>(p));
 }
 __device__ __forceinline__ f32x16 mfma(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+// ds_read_b64_tr_b16: a 16-lane group reads a block of 4 rows x 16 f16 columns and gets it column-major — lane 4 q + p of the
+// group supplies the address of row q, columns 4 p .. 4 p + 3; lane i receives column i, row q in element q. Every lane's
+// address must be 8-byte aligned and EXEC all ones (the gather crosses lanes): only call it in uniform control flow.
+typedef __fp16 fp16x4_tr_ __attribute__((__vector_size__(4 * sizeof(__fp16))));
+__device__ __forceinline__ f16x4 ld_tr4(const char* p) {
+  return __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
+                                       (__attribute__((address_space(3))) fp16x4_tr_*)(p)));
+}
 
 // ---- H3 element format (attention.h): hi = f16(e); residual byte in units of 2^(E - 33), E = f16 exponent (>= 1) of the
 // largest hi of the group of eight
@@ -312,9 +321,9 @@ __global__ __launch_bounds__(256, 2) void qk_softmax_kernel(const float* __restr
 // four SIMDs pairwise and alternate roles every phase, separated by a barrier:
 //     phase 2q    : A multiplies chunk q (48 MFMAs, every operand already in registers) and, in the gaps between them,
 //                     decodes the H3 residuals of ITS chunk q + 1
-//                   B does memory work: attention loads two chunks ahead, V^T fragments of chunk q from LDS into registers
+//                   B does memory work: attention loads two chunks ahead, V fragments of chunk q from LDS into registers
 //     phase 2q + 1: B multiplies chunk q and decodes its chunk q + 1
-//                   A does memory work: stages V^T chunk q + 2 into the LDS ring (three images), attention loads, fragments
+//                   A does memory work: stages V chunk q + 2 into the LDS ring (three images), attention loads, fragments
 //                     for chunk q + 1
 // Round 4 put s_memtime stamps around the segments of a phase (tools/diag/attn_stamps.py, profiles/r04_attn_stamps*.txt).
 // Before: a multiply phase took 1280-1350 cycles for 768 cycles of MFMAs, and it was what the barrier waited for. Two causes:
@@ -327,7 +336,7 @@ __global__ __launch_bounds__(256, 2) void qk_softmax_kernel(const float* __restr
 // pairs against 315 for the first ping-pong. Measured in round 4 and not kept (profiles/r04_ab_attention.txt; priority 1 and 2 again in round 5 with the
 // decode in the MFMA gaps, after it had paid in the conv kernels: 6.85 / 6.49 ms per forward for the product against 6.83 / 6.50
 // and 6.57 / 6.65 — inside the run-to-run spread of this stage, profiles/r05_ab_attn_prio.txt): s_setprio(1)
-// around the multiplying set's MFMAs; the V^T staging split over both sets (it only moves work between two memory phases).
+// around the multiplying set's MFMAs; the V^T staging (V was then a transposed tensor of its own) split over both sets (it only moves work between two memory phases).
 #ifdef ATDN_ATTN_STAMP   // diagnostic: s_memtime stamps around the segments of a phase, summed per wave (waves 0 and 4 of every block)
 __device__ unsigned atdn_attn_stamps_dev[1024][2][8];
 #define STAMP(k) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
@@ -339,7 +348,7 @@ __device__ unsigned atdn_attn_stamps_dev[1024][2][8];
 // SPLIT (round 6: the low-latency form for the per-frame callers, B <= 4): the key axis of a (pair, 8 strips) tile is cut into
 // `nsplit` ranges of `qsplit` chunks, one block each — ONE pair is 29 tiles on 256 CUs otherwise (attention x V was 2.4 of the
 // 7.1 ms of a single-pair forward) — and a block stores its raw fp32 sums into its slab of `part` [nsplit][B][Npad][128];
-// attn_reduce_kernel adds the slabs in order and applies the residual. Same kernel body, another summation order: the
+// attn_reduce_kernel adds the slabs in order and normalises the rows. Same kernel body, another summation order: the
 // default path (SPLIT = false) keeps one order for every batch size, which is what makes clip mode bit-identical to pair mode.
 template <bool FAST, bool SPLIT = false>
 __global__ __launch_bounds__(512, 2) void attn_v3_kernel(const float* __restrict__ P, const float* __restrict__ rinv,
@@ -347,13 +356,19 @@ __global__ __launch_bounds__(512, 2) void attn_v3_kernel(const float* __restrict
                                                         const float* __restrict__ gamma, const float* __restrict__ mf,
                                                         float* __restrict__ out, const long sb, const int ld,
                                                         const int qsplit = 0, float* __restrict__ part = nullptr) {
+  // (`vT` and `gamma` are unused since V is read from `mf` as stored: the parameter list is kept, callers pass null)
+  (void)vT; (void)gamma;
   // Round 3: the multiply runs on v_mfma_f32_16x16x32_f16 (K = 32 = one whole chunk of keys per instruction; same FLOP per
-  // cycle, but the chip holds a higher clock under this shape on random operands: §3.10 of DESIGN.md). A = V^T (16 channels
+  // cycle, but the chip holds a higher clock under this shape on random operands: §3.10 of DESIGN.md). A = V^T (the LDS read transposes V; 16 channels
   // per block), B = the attention fragment (16 query rows per block): lane (n = lane & 15, g = lane >> 4) holds row / column
   // n and the eight keys of group g. 8 channel blocks x 2 row blocks x 3 products = 48 MFMAs per chunk, as many matrix-pipe
-  // cycles as the 24 MFMAs of the 32x32x16 form; the V^T image has a 160-byte row pitch (conflict-free for this lane map).
-  constexpr int VROW = 160;
-  constexpr int IMG = 128 * VROW;      // V^T chunk: [128 channels][160 B]
+  // cycles as the 24 MFMAs of the 32x32x16 form.
+  // V is the motion features themselves (`mf`: sf rows [pixel][128 channels], the projection to_v is folded into the ConvGRU
+  // weights, gma.hip), staged as they lie in memory — a chunk = 32 key rows of 512 B — and transposed by the LDS read
+  // (ld_tr4). Row pitch 544 B: the 32-lane half of a transposed read takes 8 consecutive keys x 32 B, and 544 r mod 256 =
+  // 32 r puts them on the 64 banks once each.
+  constexpr int VROW = 544;
+  constexpr int IMG = 32 * VROW;       // V chunk: [32 keys][512 B + 32 B]
   constexpr int BLK = AT_BLK_BYTES;
   constexpr int D = 3;                 // attention chunks resident per wave (ring of register sets; 4 measured 1-2 % slower, twice)
   constexpr int DEC2 = 14;             // MFMA gaps that carry two instructions of the decode (the other 34 carry one: 62 in all)
@@ -387,23 +402,26 @@ __global__ __launch_bounds__(512, 2) void attn_v3_kernel(const float* __restrict
   };
   auto bytes_of = [&](int slot, int rb) __attribute__((always_inline)) { return u32x2{ringb[slot][2 * rb], ringb[slot][2 * rb + 1]}; };
 
-  // V^T staging (set A only: tid < 256): rows lr + 32 i, 16-byte slot ls of the row's 128-byte [32 hi | 32 lo] chunk. The
-  // producer of V^T (epilogues_sf.h: SfVT) already stores the keys of a chunk in operand order — slot g = keys
-  // 4 g + (i & 3) + 16 (i >> 2), the order of the attention fragments — so a slot is copied verbatim: one ds_write_b128
-  // per row, eight lanes = one contiguous 128-byte row, no bank conflicts (the 8-byte piece moves this replaced had
-  // SQ_LDS_BANK_CONFLICT at 17 % of the kernel's LDS cycles).
-  const int lr = (tid & 255) >> 3, ls = tid & 7;
-  const float* vrow = vT + ((long)b * 128 + lr) * g.ldN + 4 * ls + qlo * 32;
+  // V staging (set A only: tid < 256): key rows lr + 8 i, 16-byte slot ls of the key's 512-byte row, copied verbatim: 32
+  // lanes = one contiguous 512-byte run in memory and in LDS. A key past the pair's N (the tail of the last chunk; a chunk
+  // past the range, whose products are never issued) reads key N - 1: its attention entries are zero and sf values are
+  // always finite, and nothing is read behind the last pair's rows.
+  const int lr = (tid & 255) >> 5, ls = tid & 31;
+  const char* vrow = reinterpret_cast<const char*>(mf + (long)b * sb) + 16 * ls;
+  const unsigned vpitch = 4u * (unsigned)ld;
+  const int vkey0 = qlo * 32 + lr;
   constexpr int NSTG = 4;
   v4f breg[2][NSTG];
   auto fetchB = [&](int q, int set) __attribute__((always_inline)) {
+    const int k = vkey0 + min(q, Q - 1) * 32;
 #pragma unroll
-    for (int i = 0; i < NSTG; ++i) breg[set][i] = *reinterpret_cast<const v4f*>(vrow + (long)(32 * i) * g.ldN + min(q, Q - 1) * 32);
+    for (int i = 0; i < NSTG; ++i)
+      breg[set][i] = *reinterpret_cast<const v4f*>(vrow + (unsigned)min(k + 8 * i, g.N - 1) * vpitch);
   };
   const int boff = lr * VROW + 16 * ls;
   auto stashB = [&](int image, int set) __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < NSTG; ++i) *reinterpret_cast<v4f*>(lds + image * IMG + 32 * i * VROW + boff) = breg[set][i];
+    for (int i = 0; i < NSTG; ++i) *reinterpret_cast<v4f*>(lds + image * IMG + 8 * i * VROW + boff) = breg[set][i];
   };
 
   f32x4v acc[8][2];      // [channel block][row block]
@@ -416,13 +434,18 @@ __global__ __launch_bounds__(512, 2) void attn_v3_kernel(const float* __restrict
 
   // operands of the chunk about to be multiplied, all in registers
   f16x8 vh[8], vl[8], ph[2], pl[2];
-  const int foff = n16 * VROW + 16 * g16;
+  // transposed reads: lane (n, g) supplies, for the 4-key x 16-channel block of its 16-lane group, key 4 g + (n >> 2) and
+  // the four channels 4 (n & 3) ..; it receives channel n of keys 4 g .. 4 g + 3 (elements 0-3) and, from the block 16 keys
+  // on, of keys 16 + 4 g .. (elements 4-7): the key order of the attention fragments (attention.h). Channel block cb lies in
+  // the key row's [32 hi | 32 lo] group cb >> 1, at halves 16 (cb & 1) ..; the lo plane 64 B further. Called by every lane
+  // of the block in uniform control flow (EXEC all ones).
+  const int foff = (4 * g16 + (n16 >> 2)) * VROW + 8 * (n16 & 3);
   auto read_frags = [&](int image) __attribute__((always_inline)) {
 #pragma unroll
     for (int cb = 0; cb < 8; ++cb) {
-      const char* vp = lds + image * IMG + foff + 16 * cb * VROW;
-      vh[cb] = ld_frag(vp);
-      if (!FAST) vl[cb] = ld_frag(vp + 64);
+      const char* vp = lds + image * IMG + foff + 128 * (cb >> 1) + 32 * (cb & 1);
+      vh[cb] = __builtin_shufflevector(ld_tr4(vp), ld_tr4(vp + 16 * VROW), 0, 1, 2, 3, 4, 5, 6, 7);
+      if (!FAST) vl[cb] = __builtin_shufflevector(ld_tr4(vp + 64), ld_tr4(vp + 64 + 16 * VROW), 0, 1, 2, 3, 4, 5, 6, 7);
     }
   };
   auto take_chunk = [&](int slot) __attribute__((always_inline)) {   // attention operands of a chunk out of the ring
@@ -478,14 +501,14 @@ __global__ __launch_bounds__(512, 2) void attn_v3_kernel(const float* __restrict
     }
   };
 
-  constexpr int U = (D % 2) ? 2 * D : D;        // unroll: ring slots (D) x V^T register sets (2)
+  constexpr int U = (D % 2) ? 2 * D : D;        // unroll: ring slots (D) x V register sets (2)
 #ifdef ATDN_ATTN_STAMP
   unsigned seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tlast = 0;
 #endif
   const int nq = (Q + U - 1) / U * U;           // surplus chunks multiply nothing (uniform branch), barriers still match
   if (setA) {
-    // prologue: V^T chunks 0, 1 -> images 0, 1; chunks 2, 3 wait in the register sets; attention chunks 0..2
+    // prologue: V chunks 0, 1 -> images 0, 1; chunks 2, 3 wait in the register sets; attention chunks 0..2
     fetchB(0, 0);
     fetchB(1, 1);
 #pragma unroll
@@ -513,7 +536,7 @@ __global__ __launch_bounds__(512, 2) void attn_v3_kernel(const float* __restrict
         STAMP(0);
         __syncthreads();
         STAMP(1);
-        // phase 2q + 1: memory work. V^T chunk q + 2 (requested two iterations ago) -> image (q + 2) % 3, last read in
+        // phase 2q + 1: memory work. V chunk q + 2 (requested two iterations ago) -> image (q + 2) % 3, last read in
         // phase 2q - 2; its register set takes chunk q + 4; the ring slot of chunk q takes chunk q + 3
         stashB(image2, d & 1);
         fetchB(q + 4, d & 1);
@@ -579,21 +602,18 @@ __global__ __launch_bounds__(512, 2) void attn_v3_kernel(const float* __restrict
     }
     return;
   }
-  const float gam = gamma[0];
-  const float* mfb = mf + (long)b * sb;
+  // the aggregate itself, agg = A . mf: the residual, gamma and to_v live in the ConvGRU weights (gma.hip: the weight fold)
   float* ob = out + (long)b * sb;
   bool clamped = false;
 #pragma unroll
   for (int rb = 0; rb < 2; ++rb) {
     const int m = strip * 32 + 16 * rb + n16;
     if (strip_ok && m < g.N) {
-      const float rv = rinv[(long)b * g.Npad + m] * gam;
+      const float rv = rinv[(long)b * g.Npad + m];
 #pragma unroll
       for (int cb = 0; cb < 8; ++cb) {
         const int c = 16 * cb + 4 * g16;
-        const float4 x = sf_load4(mfb, (long)m * ld, c);
-        const float4 o = make_float4(x.x + rv * acc[cb][rb][0], x.y + rv * acc[cb][rb][1], x.z + rv * acc[cb][rb][2],
-                                     x.w + rv * acc[cb][rb][3]);
+        const float4 o = make_float4(rv * acc[cb][rb][0], rv * acc[cb][rb][1], rv * acc[cb][rb][2], rv * acc[cb][rb][3]);
         sf_store4_flag(ob, (long)m * ld, c, o, clamped);
       }
     }
@@ -601,7 +621,7 @@ __global__ __launch_bounds__(512, 2) void attn_v3_kernel(const float* __restrict
   sf_report(clamped);
 }
 
-// the split form's second half: out[b][m][c] = mf + gamma * rinv[m] * (slab 0 + slab 1 + ... in order), stored as sf
+// the split form's second half: out[b][m][c] = rinv[m] * (slab 0 + slab 1 + ... in order), stored as sf
 __global__ __launch_bounds__(256) void attn_reduce_kernel(const float* __restrict__ part, const int nsplit, const AttnGeom g,
                                                           const float* __restrict__ rinv, const float* __restrict__ gamma,
                                                           const float* __restrict__ mf, float* __restrict__ out, const long sb,
@@ -620,10 +640,8 @@ __global__ __launch_bounds__(256) void attn_reduce_kernel(const float* __restric
       const float4 t = *reinterpret_cast<const float4*>(p + k * slab);
       s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
     }
-    const float rv = rinv[(long)b * g.Npad + m] * gamma[0];
-    const float4 x = sf_load4(mf + (long)b * sb, (long)m * ld, c);
-    sf_store4_flag(out + (long)b * sb, (long)m * ld, c, make_float4(x.x + rv * s.x, x.y + rv * s.y, x.z + rv * s.z, x.w + rv * s.w),
-                   clamped);
+    const float rv = rinv[(long)b * g.Npad + m];
+    sf_store4_flag(out + (long)b * sb, (long)m * ld, c, make_float4(rv * s.x, rv * s.y, rv * s.z, rv * s.w), clamped);
   }
   sf_report(clamped);
 }

@@ -102,6 +102,8 @@ struct SfQK {
   }
 };
 
+// (No longer launched by the flow network: attention x V reads the motion features as stored and transposes them with its LDS
+// reads, gma.hip. The instantiations stay compiled.)
 // V^T for attention x V (attention.hip): dst[img][channel m][key n] in sf, with the 32 keys of a chunk stored in the order
 // the consumer's MFMA operand wants them — slot g (16 bytes) = keys 4 g + (i & 3) + 16 (i >> 2), i = 0..7 (attention.h) —
 // so the consumer copies 16-byte slots verbatim into its LDS image (round 3: it used to move 8-byte pieces to permuted

@@ -136,6 +136,7 @@ class GmaNet {
   PackedConv gru_zr_ctx_[2], gru_q_ctx_[2];  // sf mode: context-channel (inp) slices, applied once per pair
   const float* gamma_ = nullptr;
   long gamma_off_ = -1;
+  long to_v_w32_off_ = -1;   // split-f16 / f16 modes: to_v's weight as fp32 [128][128] (debug reads only)
 
   // workspace
   DeviceBuf img4_, enc_[4], scratch_, pcnt_, fin_, fmap_, psum_, pm2_, mean_[3], rstd_[3];   // [2]: the feature network's stem statistics, alive until its first block's residual pass

@@ -260,9 +260,14 @@ void GmaNet::finalize() {
     if (sf) {
       // hx = [h(0:128) | inp(128:256) | motion(256:384) | motion_global(384:512)] (update.py:50,130): the inp slice
       // does not change over the iterations, so its contribution is computed once per pair (run_body_sf)
-      const std::vector<std::pair<int, int>> rest = {{0, 128}, {256, 512}}, ctx = {{128, 256}};
-      gru_zr_[p] = pack_conv_sf_channels(arena_, sd_, {u + "gru.convz" + t, u + "gru.convr" + t}, rest, true);
-      gru_q_[p] = pack_conv_sf_channels(arena_, sd_, {u + "gru.convq" + t}, rest, true);
+      // The iterations convolve [h | motion | agg] with agg = A . motion as attention x V stores it: to_v, gamma and the
+      // residual of the aggregator are folded into the motion and motion_global blocks (weights.h: pack_gru_sf_folded)
+      const std::vector<std::pair<int, int>> ctx = {{128, 256}};
+      const HostTensor& wv = sd_.get(u + "aggregator.to_v.weight");
+      const HostTensor& gam = sd_.get(u + "aggregator.gamma");
+      ATDN_CHECK(gam.data.size() == 1, "aggregator.gamma is one value");
+      gru_zr_[p] = pack_gru_sf_folded(arena_, sd_, {u + "gru.convz" + t, u + "gru.convr" + t}, wv, (double)gam.data[0]);
+      gru_q_[p] = pack_gru_sf_folded(arena_, sd_, {u + "gru.convq" + t}, wv, (double)gam.data[0]);
       gru_zr_ctx_[p] = pack_conv_sf_channels(arena_, sd_, {u + "gru.convz" + t, u + "gru.convr" + t}, ctx, false);
       gru_q_ctx_[p] = pack_conv_sf_channels(arena_, sd_, {u + "gru.convq" + t}, ctx, false);
     } else {
@@ -288,6 +293,8 @@ void GmaNet::finalize() {
   mask0_ = tap({u + "mask.0"});
   mask2_ = tap({u + "mask.2"});
   gamma_off_ = pack_vector(arena_, sd_.get(u + "aggregator.gamma").data);
+  // to_v in fp32 [128][128]: debug_read("x") rebuilds motion_global from the stored aggregate with it
+  if (sf) to_v_w32_off_ = pack_vector(arena_, sd_.get(u + "aggregator.to_v.weight").data);
   arena_.upload();
   resolve_encoder(arena_, fnet_);
   resolve_encoder(arena_, cnet_);
@@ -322,7 +329,9 @@ void GmaNet::finalize() {
   }
   h_[0].alloc(n8 * 128); h_[1].alloc(n8 * 128); x_.alloc(n8 * XLD);
   const AttnGeom ag = attn_geom(B, N, ldN);
-  qk_.alloc(n8 * 256); attn_.alloc(std::max(n8 * ldN, attn_floats(ag))); vT_.alloc((long)B * 128 * ldN);
+  qk_.alloc(n8 * 256); attn_.alloc(std::max(n8 * ldN, attn_floats(ag)));
+  // (V^T exists on the exact-fp32 path only: the split-f16 modes aggregate the motion features as they are stored)
+  if (classic_) vT_.alloc((long)B * 128 * ldN);
   if (sf) { rowmax_.alloc((long)B * ag.Npad); rinv_.alloc((long)B * ag.Npad); }
   // (only where the split can engage: attn_v_splits() is 1 from 8 pairs per launch on at KITTI size)
   if (sf && low_latency_ && attn_v_splits(attn_geom(1, N, ldN)) > 1) attn_part_.alloc(8L * B * ag.Npad * 128);
@@ -339,7 +348,7 @@ void GmaNet::finalize() {
   if (sf) for (int p = 0; p < 2; ++p) { pre_zr_[p].alloc(n8 * 256); pre_q_[p].alloc(n8 * 128); }
   // pad lanes that kernels read but never write must be finite zeros
   ATDN_HIP(hipMemset(corrfeat_.p, 0, corrfeat_.n * sizeof(float)));
-  ATDN_HIP(hipMemset(vT_.p, 0, vT_.n * sizeof(float)));
+  if (vT_.p) ATDN_HIP(hipMemset(vT_.p, 0, vT_.n * sizeof(float)));
   ATDN_HIP(hipMemset(attn_.p, 0, attn_.n * sizeof(float)));
   ATDN_HIP(hipMemset(flow4_.p, 0, flow4_.n * sizeof(float)));
   ATDN_HIP(hipDeviceSynchronize());
@@ -724,14 +733,10 @@ void GmaNet::iteration_sf(int B, hipStream_t st) {
   conv_sf_dispatch(s, convm_.wscale, SfBias<ACT_RELU>{convm_.b, mf, (long)N * XLD, XLD}, st);
   mark(ST_MOTION, st);
 
-  // v^T [128][pixels] directly: the projection matrix is the A operand (128 rows), the motion features are the
-  // K-contiguous "weight" rows, so the sf store runs along pixels (no transposed 2-byte scatter)
-  ConvShape v;
-  v.src0 = to_v_.w; v.ld0 = 128; v.sb0 = 0; v.C0 = 128; v.H = 1; v.W = 128;
-  v.w = mf; v.wb = (long)N * XLD; v.ldw = XLD; v.N = N; v.nimg = B;
-  conv_sf_dispatch(v, to_v_.wscale, SfVT{vT_.p, (long)128 * ldN, ldN}, st);   // keys of a chunk in operand order
-  mark(ST_AGG_VT, st);
-  launch_attn_v(attn_.p, rinv_.p, attn_geom(B, N, ldN), vT_.p, gamma_, mf, x_.p + 256, (long)N * XLD, XLD,
+  // agg = A . motion into x[:, 256:384]: attention x V reads the motion features as the motion encoder has just stored them
+  // (its LDS reads transpose them), so there is no V^T pass; to_v, gamma and the residual of gma.py:111-115 are in the gate
+  // weights (finalize). The agg_vt stage has no mark and reports 0, as convc1 does since it was fused.
+  launch_attn_v(attn_.p, rinv_.p, attn_geom(B, N, ldN), nullptr, nullptr, mf, x_.p + 256, (long)N * XLD, XLD,
                 sf_fast_mode(), st, attn_part_.p);   // (attn_part_ is null unless the handle was built low-latency)
   mark(ST_AGG, st);
 
@@ -740,7 +745,7 @@ void GmaNet::iteration_sf(int B, hipStream_t st) {
     float* hout = h_[p ^ 1].p;
     const int ph = p ? 2 : 0, pw = p ? 0 : 2;
     ConvShape g = conv_shape(gru_zr_[p], hin, 128, (long)N * 128, B, H8, W8, 1, ph, pw);
-    g.C0 = 128; g.src1 = x_.p + 128; g.ld1 = XLD; g.sb1 = (long)N * XLD; g.C1 = 256;  // [h | motion | motion_global]
+    g.C0 = 128; g.src1 = x_.p + 128; g.ld1 = XLD; g.sb1 = (long)N * XLD; g.C1 = 256;  // [h | motion | agg]
     conv_sf_dispatch(g, gru_zr_[p].wscale,
                      SfGruZR{gru_zr_[p].b, hin, z_.p, rh_.p, (long)N * 128, pre_zr_[p].p, (long)N * 256}, st);
     mark(p ? ST_GRU_ZR_V : ST_GRU_ZR, st);
@@ -1012,6 +1017,19 @@ long GmaNet::debug_read(const char* name, float* host, long capacity, hipStream_
   else if (k == "mask") b = &mask_; else if (k == "coords1") b = &coords1_; else if (k == "flow4") b = &flow4_;
   else if (k == "qk") b = &qk_; else if (k == "img4") b = &img4_;
   else if (k == "cor1") b = &cor1_;   // relu(convc1(lookup)) of the last iteration: the fused kernel's product phase
+  if (k == "agg") {
+    // the stored aggregate A . motion itself, [maxB * N][128]: channels 256..383 of the split-f16 GRU input (the exact-fp32
+    // path stores motion_global there and has no such tensor)
+    if (classic_) return -1;
+    scratch_.reserve(x_.n);
+    launch_from_sf(x_.p, scratch_.p, x_.n / 32, 32, st);
+    ATDN_HIP(hipStreamSynchronize(st));
+    const long rows = std::min(capacity / 128, (long)maxB * N);
+    if (rows > 0)
+      ATDN_HIP(hipMemcpy2D(host, 128 * sizeof(float), scratch_.p + 256, XLD * sizeof(float), 128 * sizeof(float), (size_t)rows,
+                           hipMemcpyDeviceToHost));
+    return rows * 128;
+  }
   if (!b) return -1;
   long n = std::min(capacity, b->n);
   if (k == "attn" && !classic_) {   // fragment-major exp(s - max) + row sums -> normalised fp32 rows [maxB][N][ldN]
@@ -1030,6 +1048,11 @@ long GmaNet::debug_read(const char* name, float* host, long capacity, hipStream_
     scratch_.reserve(b->n);
     launch_from_sf(b->p, scratch_.p, b->n / 32, 32, st);
     src = scratch_.p;
+    // x[:, 256:384] holds agg = A . motion (iteration_sf): the tap keeps its meaning, motion_global = motion + gamma * agg . Wv^T,
+    // rebuilt in fp32 on the decoded copy
+    // (the flow channels of the residual: from the coordinates the last lookup used, the update has overwritten x[:, 254:256])
+    if (k == "x")
+      launch_mfg_reconstruct(scratch_.p, (long)maxB * N, XLD, 128, 256, arena_.dev(to_v_w32_off_), gamma_, coords_used_.p, N, W8, 254, st);
   }
   ATDN_HIP(hipStreamSynchronize(st));
   ATDN_HIP(hipMemcpy(host, src, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));

@@ -91,6 +91,13 @@ void launch_mlp_heads(const float* h2, int B, MlpHead rot, MlpHead tr, float* ro
 void launch_to_sf(const float* src, float* dst, long rows, int C, hipStream_t st);
 // sf -> fp32 NHWC
 void launch_from_sf(const float* src, float* dst, long rows, int C, hipStream_t st);
+// debug reads only: the GRU input decoded to fp32 rows [rows][ld] holds the motion features at channels cmf.. and their
+// aggregate agg = A . mf at cagg.. (128 each); overwrites the latter with motion_global = mf + gamma * agg . Wv^T
+// (gma.py:111-115), wv = to_v's weight [128][128] in fp32. The flow channels cflow, cflow + 1 of the motion features are the
+// NEXT iteration's by the time of the read: the residual takes them from coords_used [rows][2] (the coordinates the last
+// lookup sampled at; rows = pairs x N pixels of a W8-wide map), flow = coords_used - grid.
+void launch_mfg_reconstruct(float* x, long rows, int ld, int cmf, int cagg, const float* wv, const float* gamma,
+                            const float* coords_used, int N, int W8, int cflow, hipStream_t st);
 // InstanceNorm apply, out of place: raw fp32 x -> sf y = relu((x-mean)*rstd); optional residual (sf `res`, or raw fp32
 // `res_raw` normalised with rmean/rrstd): y = relu(r + y)
 void launch_in_apply_sf(const float* x, float* y, const float* mean, const float* rstd, const float* res,

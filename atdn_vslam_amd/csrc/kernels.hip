@@ -666,6 +666,39 @@ void launch_from_sf(const float* src, float* dst, long rows, int C, hipStream_t 
   ATDN_HIP(hipGetLastError());
 }
 
+// debug reads only: one block per pixel row of the DECODED fp32 GRU input, thread c = one output channel. The two flow channels of
+// the motion features (cflow, cflow + 1) have been overwritten by the iteration's flow update since the aggregate was formed:
+// for the residual term they are taken from the coordinates the iteration's lookup used, flow = coords - grid, through the
+// same hi + lo rounding as the stored value.
+__global__ __launch_bounds__(128) void mfg_reconstruct_kernel(float* __restrict__ x, int ld, int cmf, int cagg,
+                                                              const float* __restrict__ wv, const float* __restrict__ gamma,
+                                                              const float* __restrict__ coords_used, int N, int W8, int cflow) {
+  __shared__ float a[128];
+  const long pix = blockIdx.x;
+  float* row = x + pix * ld;
+  const int c = threadIdx.x;
+  a[c] = row[cagg + c];
+  __syncthreads();
+  float s = 0.f;
+  for (int k = 0; k < 128; ++k) s = fmaf(wv[c * 128 + k], a[k], s);
+  float m = row[cmf + c];
+  const int n = cmf + c - cflow;
+  if (coords_used && (n == 0 || n == 1)) {
+    const int p = (int)(pix % N);
+    const float f = coords_used[pix * 2 + n] - (n == 0 ? (float)(p % W8) : (float)(p / W8));
+    const _Float16 hi = (_Float16)f;
+    m = (float)hi + (float)(_Float16)(f - (float)hi);
+  }
+  row[cagg + c] = m + gamma[0] * s;
+}
+
+void launch_mfg_reconstruct(float* x, long rows, int ld, int cmf, int cagg, const float* wv, const float* gamma,
+                            const float* coords_used, int N, int W8, int cflow, hipStream_t st) {
+  if (rows <= 0) return;
+  hipLaunchKernelGGL(mfg_reconstruct_kernel, dim3((unsigned)rows), dim3(128), 0, st, x, ld, cmf, cagg, wv, gamma, coords_used, N, W8, cflow);
+  ATDN_HIP(hipGetLastError());
+}
+
 __global__ void in_apply_sf_kernel(const float4* __restrict__ x, float* __restrict__ y, const float* __restrict__ mean,
                                    const float* __restrict__ rstd, const float* __restrict__ res,
                                    const float4* __restrict__ res_raw, const float* __restrict__ rmean,

@@ -1,5 +1,6 @@
 // Host-side checkpoint staging and weight packing for the implicit-GEMM engine.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -251,6 +252,57 @@ inline PackedConv pack_conv_sf_channels(WeightArena& A, const StateDict& sd, con
     tnames.push_back(key);
   }
   return pack_conv_sf(A, tmp, tnames, nullptr, has_bias);
+}
+
+// ConvGRU gate weights of the iterations with the aggregator folded in. The reference convolves hx = [h(0:128) | inp(128:256) |
+// mf(256:384) | mfg(384:512)] (update.py:50,130) with mfg = mf + gamma * A . (mf . Wv^T) (gma.py:111-115: one head, no bias, no
+// project). With agg = A . mf — what attention x V stores — mfg_c = mf_c + gamma * sum_c' Wv[c][c'] agg_c', so for every output
+// o and tap t the same convolution over [h | mf | agg] gives the same sum with
+//     Wm'[o][c][t]  = Wm[o][c][t] + Wg[o][c][t]
+//     Wa'[o][c'][t] = gamma * sum_c Wg[o][c][t] * Wv[c][c']
+// in place of the mf and mfg blocks (zero padding is consistent: mf, agg and mfg are all zero outside the image). Computed in
+// fp64, rounded once to fp32; pack_conv_sf then chooses the layer's power-of-two scale over the FOLDED tensor and splits it.
+// gamma = 0 gives an all-zero agg block. The inp block is packed apart (pack_conv_sf_channels), as before.
+inline PackedConv pack_gru_sf_folded(WeightArena& A, const StateDict& sd, const std::vector<std::string>& names,
+                                     const HostTensor& wv, double gamma) {
+  ATDN_CHECK(wv.shape.size() == 4 && wv.shape[0] == 128 && wv.shape[1] == 128 && wv.shape[2] == 1 && wv.shape[3] == 1,
+             "aggregator.to_v is a 1x1 convolution, 128 -> 128");
+  StateDict tmp;
+  std::vector<std::string> tnames;
+  for (size_t t = 0; t < names.size(); ++t) {
+    const HostTensor& w = sd.get(names[t] + ".weight");
+    ATDN_CHECK(w.shape.size() == 4 && w.shape[1] == 512, "ConvGRU convolutions read 512 channels");
+    const int Co = (int)w.shape[0], T = (int)(w.shape[2] * w.shape[3]);
+    std::vector<float> out((size_t)Co * 384 * T);
+    std::vector<double> acc(128);
+    for (int n = 0; n < Co; ++n) {
+      const float* wn = &w.data[(size_t)n * 512 * T];
+      float* on = &out[(size_t)n * 384 * T];
+      std::memcpy(on, wn, sizeof(float) * 128 * T);   // h
+      for (int c = 0; c < 128; ++c)
+        for (int k = 0; k < T; ++k)
+          on[(128 + c) * T + k] = (float)((double)wn[(256 + c) * T + k] + (double)wn[(384 + c) * T + k]);
+      for (int k = 0; k < T; ++k) {
+        std::fill(acc.begin(), acc.end(), 0.0);
+        for (int c = 0; c < 128; ++c) {
+          const double g = (double)wn[(384 + c) * T + k];
+          const float* v = &wv.data[(size_t)c * 128];
+          for (int c2 = 0; c2 < 128; ++c2) acc[c2] += g * (double)v[c2];
+        }
+        for (int c2 = 0; c2 < 128; ++c2) on[(256 + c2) * T + k] = (float)(gamma * acc[c2]);
+      }
+    }
+    const std::string key = "s" + std::to_string(t);
+    const int64_t shp[4] = {Co, 384, w.shape[2], w.shape[3]};
+    tmp.put(key + ".weight", out.data(), shp, 4);
+    if (sd.has(names[t] + ".bias")) {
+      const HostTensor& b = sd.get(names[t] + ".bias");
+      const int64_t bs[1] = {Co};
+      tmp.put(key + ".bias", b.data.data(), bs, 1);
+    }
+    tnames.push_back(key);
+  }
+  return pack_conv_sf(A, tmp, tnames, nullptr, true);
 }
 
 inline long pack_vector(WeightArena& A, const std::vector<float>& v) {

@@ -101,7 +101,8 @@ long atdn_gma_debug_read(atdn_gma* h, const char* name, float* host, long capaci
  * `stream`. ms_out has ATDN_GMA_STAGES entries: fnet, corr, pool, cnet, attention (row softmax), lookup, motion_encoder
  * (without convc1), aggregate (the attention x V kernel alone), gru_zr (fused z|r convolution, horizontal 1x5 pass),
  * gru_q (horizontal pass), flow_head, mask, gru_ctx (once-per-pair context part of the GRU convolutions; split-f16
- * pipeline only), attn_logits (q,k projection + first QK^T sweep), agg_vt (the v^T projection in front of attention x V),
+ * pipeline only), attn_logits (q,k projection + first QK^T sweep), agg_vt (the v^T projection in front of attention x V; zero since
+ * attention x V reads the motion features as stored and to_v lives in the ConvGRU weights),
  * convc1 (the 1x1 convolution behind the lookup; zero when it is fused into the lookup), gru_zr_v / gru_q_v (the vertical
  * 5x1 passes).
  * Stages that hold launches of ONE kernel (aggregate, gru_zr, gru_zr_v, gru_q, gru_q_v, lookup, corr) divide into
