@@ -89,7 +89,13 @@ SIGNATURES = {
                                   C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp, _vp]),
     "atdn_depth_fuse_host": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                        C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp]),
-    "atdn_pnp_workspace_bytes": (C.c_long, [C.c_int, C.c_int, C.c_int]),
+    "atdn_multiview_depth": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                       C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double,
+                                       C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "atdn_multiview_depth_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                            C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                                            C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp]),
+    "atdn_pnp_workspace_bytes":(C.c_long, [C.c_int, C.c_int, C.c_int]),
     "atdn_pnp_terms": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                                  C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
     "atdn_pnp_terms_host": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,

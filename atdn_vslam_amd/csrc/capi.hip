@@ -17,6 +17,7 @@
 #include "flow_args.h"
 #include "flow_consistency_host.h"
 #include "flow_track_host.h"
+#include "multiview_depth_host.h"
 #include "pnp_host.h"
 #include "two_view_host.h"
 #include "warm_start_host.h"
@@ -440,6 +441,20 @@ int atdn_depth_fuse_host(const float* bank, const float* poses, const int* targe
                         fused, views, counts);
   depth_fuse_host(bank, poses, targets, sources, N, B, S, H, W,
                   depth_fuse_params(fx, fy, cx, cy, max_reproj, max_rel_depth, min_views, min_z, average), fused, views, counts);
+  ATDN_API_END
+}
+
+// ------------------------------------------------------------------ multi-view depth (host twin of multiview_depth.hip)
+int atdn_multiview_depth_host(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
+                              const float* depth_init, int N, int B, int S, int H, int W, double fx, double fy, double cx, double cy,
+                              double scale_px, double inlier_px, double min_z, int min_views, double max_rel_sigma, double max_depth,
+                              int iters, float* depth, float* info, unsigned char* views, int* counts) {
+  ATDN_API_BEGIN
+  multiview_check_args(acc_bank, alive_bank, poses, slots, depth_init, N, B, S, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z,
+                       min_views, max_rel_sigma, max_depth, iters, depth, info, views, counts);
+  multiview_depth_host(acc_bank, alive_bank, poses, slots, depth_init, N, B, S, H, W,
+                       multiview_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, min_views, max_rel_sigma, max_depth, iters, H, W),
+                       depth, info, views, counts);
   ATDN_API_END
 }
 

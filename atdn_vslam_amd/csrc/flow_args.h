@@ -1,4 +1,4 @@
-// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip, epipolar.hip, depth_fusion.hip), shared by each device
+// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip, epipolar.hip, depth_fusion.hip, multiview_depth.hip), shared by each device
 // entry point and its host twin in capi.hip, and the overlap rule that the pose solvers (pnp.hip, pose_graph.hip) share.
 #pragma once
 #include <cmath>
@@ -67,5 +67,10 @@ void epipolar_check_args(const float* flow, const unsigned char* mask, const flo
 void depth_fuse_check_args(const float* bank, const float* poses, const int* targets, const int* sources, int N, int B, int S,
                            int H, int W, double fx, double fy, double cx, double cy, double max_reproj, double max_rel_depth,
                            int min_views, double min_z, const float* fused, const unsigned char* views, const int* counts);
+// depth_init may be null
+void multiview_check_args(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
+                          const float* depth_init, int N, int B, int S, int H, int W, double fx, double fy, double cx, double cy,
+                          double scale_px, double inlier_px, double min_z, int min_views, double max_rel_sigma, double max_depth,
+                          int iters, const float* depth, const float* info, const unsigned char* views, const int* counts);
 
 }  // namespace atdn

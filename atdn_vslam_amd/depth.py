@@ -83,14 +83,28 @@ class FlowTrack:
     inliers, valid); `pose` [B,4,4] float64 on the host, anchor <- latest frame; `steps`, the number of pairs since the anchor.
     `calib` is that of the grid the flows live on (`resize_calib`); `thresholds` are max_epipolar, min_parallax_deg and max_depth
     of `transforms.two_view_depth`. `start()` begins a track at a new anchor, `extend(flow, pred_mat)` carries it over one pair.
-    The pose goes to the device as 12 float32 through pinned memory, asynchronously; no call synchronises with the host."""
+    The pose goes to the device as 12 float32 through pinned memory, asynchronously; no call synchronises with the host.
+    `history=K` (1 <= K <= 16, transforms.multiview_depth's limit) also keeps `acc`, `alive` and the pose row of the last K steps
+    in preallocated device banks [K * B, ...] (`hist_acc`, `hist_alive`, `hist_pose`; ring position r of image b is slot r * B + b):
+    a ring, filled after every step by device copies of `acc` and `alive` on the same stream — the pose row is uploaded straight
+    into its ring slot —, still without a host synchronisation. `multiview()` solves the depth over the stored steps. With
+    `history=0` (the default) nothing is allocated and `extend` does what it always did."""
 
-    def __init__(self, hw, calib, device, batch=1, **thresholds):
+    def __init__(self, hw, calib, device, batch=1, history=0, **thresholds):
         unknown = set(thresholds) - {"max_epipolar", "min_parallax_deg", "max_depth"}
         if unknown:
             raise TypeError("unknown threshold(s): %s" % ", ".join(sorted(unknown)))
         H, W = int(hw[0]), int(hw[1])
         B = int(batch)
+        K = int(history)
+        if not 0 <= K <= 16:
+            raise ValueError("history must be in [0, 16], got %r" % (history,))
+        self.history = K
+        self.hist_acc = self.hist_alive = self.hist_pose = None
+        if K:
+            self.hist_acc = torch.zeros((K * B, 2, H, W), dtype=torch.float32, device=device)
+            self.hist_alive = torch.zeros((K * B, H, W), dtype=torch.uint8, device=device)
+            self.hist_pose = torch.zeros((K * B, 12), dtype=torch.float32, device=device)
         self.calib = intrinsics(calib)
         self.device = torch.device(device)
         self.thresholds = dict(thresholds)
@@ -105,7 +119,7 @@ class FlowTrack:
     def to(self, device):
         """Move the device state, a running track included; the pose and `steps` stay on the host. Returns self."""
         self.device = torch.device(device)
-        for name in ("acc", "alive", "depth", "counts", "_pose_dev"):
+        for name in ("acc", "alive", "depth", "counts", "_pose_dev") + (("hist_acc", "hist_alive", "hist_pose") if self.history else ()):
             setattr(self, name, getattr(self, name).to(self.device))
         return self
 
@@ -131,8 +145,35 @@ class FlowTrack:
         # a pinned buffer of the caching host allocator per step: it is handed out again only after the copy that reads it is done
         rows = torch.empty((B, 12), dtype=torch.float32, pin_memory=self.device.type == "cuda")
         rows.copy_(self.pose[:, :3, :].reshape(B, 12))
-        self._pose_dev.copy_(rows, non_blocking=True)
-        transforms.flow_track_step(flow, self.acc, self.alive, pose=self._pose_dev, calib=self.calib, mask=mask, depth=self.depth,
+        ring = None
+        if self.history:
+            r = self.steps % self.history
+            ring = slice(r * B, (r + 1) * B)
+        pose_dev = self._pose_dev if ring is None else self.hist_pose[ring]
+        pose_dev.copy_(rows, non_blocking=True)
+        transforms.flow_track_step(flow, self.acc, self.alive, pose=pose_dev, calib=self.calib, mask=mask, depth=self.depth,
                                    out=(self.acc, self.alive, self.counts), **self.thresholds)
+        if ring is not None:
+            self.hist_acc[ring].copy_(self.acc)
+            self.hist_alive[ring].copy_(self.alive)
         self.steps += 1
         return self.counts
+
+    def history_slots(self):
+        """[B,S] int64 on the host: the bank slots of the stored steps of every image, oldest first (S = min(steps, history))."""
+        B, K = self.pose.shape[0], self.history
+        S = min(self.steps, K)
+        first = self.steps - S
+        return torch.tensor([[((first + i) % K) * B + b for i in range(S)] for b in range(B)], dtype=torch.int64).reshape(B, S)
+
+    def multiview(self, **options):
+        """`transforms.multiview_depth` over the stored steps in time order (oldest first), started from `depth`: returns
+        `(depth, info, views, counts)`; `options` are its keyword arguments (iters, scale_px, inlier_px, min_z, min_views,
+        max_rel_sigma, max_depth). Needs `history` > 0 and at least one step since `start()`; the track's own state is untouched."""
+        from . import transforms
+        if not self.history:
+            raise RuntimeError("FlowTrack.multiview needs a track created with history > 0")
+        if self.steps < 1:
+            raise RuntimeError("FlowTrack.multiview: no step since start()")
+        return transforms.multiview_depth(self.hist_acc, self.hist_alive, self.hist_pose, self.history_slots().tolist(), self.calib,
+                                          depth_init=self.depth, **options)

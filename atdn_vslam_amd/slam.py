@@ -88,6 +88,11 @@ class NeuralSLAM:
     that registers the next keyframe, so each pixel's depth is triangulated over the longest baseline its track survives. The file
     has the same name, shape and dtype; it is written when the next keyframe is registered, or by `end_odometry()` for the last
     keyframe if any pair followed it. Poses and `rgb/` files do not depend on the choice.
+    "multiview" (needs `calib`) keeps the last 16 steps of that track (FlowTrack(history=16)) and solves every pixel's depth over
+    all of them at once (FlowTrack.multiview, `multiview_options` its keyword arguments), started from the track's depth: the same
+    `depth/%06d.pth`, and beside it `depth_info/%06d.pth` (float32 [1,376,1232], the inverse variance of the relative depth for
+    unit pixel noise) and `depth_mv_views/%06d.pth` (uint8 [376,1232], the views that agree); `multiview_counts` [1,3] =
+    (candidates, solved, valid) of the last keyframe stays on the device. "pair" and "track" change no file, directory or bit.
     `refine_pose=True` (needs `calib`): in odometry mode every pair's predicted pose is refined on the pair's own flow
     (transforms.pose_from_flow with its defaults, on the device: the rotation and the direction of t; |t| stays the head's) before
     anything uses it: the "pair" keyframe depth, the poses fed to the flow track, the keyframe policy and the running pose
@@ -103,7 +108,8 @@ class NeuralSLAM:
 
     def __init__(self, args, odometry_weights=None, start_mode=None, flow_weights=None, mapping_weights=None,
                  precision=None, map_options=None, resident_map=False, warm_start=False, calib=None, keyframe_depth="pair",
-                 loop_closure=False, loop_options=None, refine_pose=False, fuse_depth=False, fuse_options=None):
+                 loop_closure=False, loop_options=None, refine_pose=False, fuse_depth=False, fuse_options=None,
+                 multiview_options=None):
         from .depth import intrinsics
         if fuse_depth and (calib is None or not resident_map):
             raise ValueError("fuse_depth=True needs the calibration and the keyframe map in device memory: pass calib= and "
@@ -120,13 +126,16 @@ class NeuralSLAM:
         self._loop_closure = bool(loop_closure)
         self._loop_options = dict(loop_options or {})
         self.loop_report = None      # the report of the last close_loops()
-        if keyframe_depth not in ("pair", "track"):
-            raise ValueError('keyframe_depth is "pair" or "track", got %r' % (keyframe_depth,))
-        if keyframe_depth == "track" and calib is None:
-            raise ValueError('keyframe_depth="track" needs the calibration: pass calib=')
+        if keyframe_depth not in ("pair", "track", "multiview"):
+            raise ValueError('keyframe_depth is "pair", "track" or "multiview", got %r' % (keyframe_depth,))
+        if keyframe_depth != "pair" and calib is None:
+            raise ValueError('keyframe_depth="%s" needs the calibration: pass calib=' % keyframe_depth)
         self._args = args
         self._calib = None if calib is None else intrinsics(calib)
-        self._track_depth = keyframe_depth == "track"
+        self._track_depth = keyframe_depth in ("track", "multiview")
+        self._multiview = keyframe_depth == "multiview"
+        self._multiview_options = dict(multiview_options or {})
+        self.multiview_counts = None   # [1,3] int32 (device) of the last multi-view keyframe depth: candidates, solved, valid
         self._track = None           # depth.FlowTrack of the latest keyframe (keyframe_depth="track"), created with the first frame
         self._track_index = None     # index of the keyframe the track is anchored at
         self._depth_pending = None   # index of the keyframe that is the first frame of the next pair
@@ -173,6 +182,11 @@ class NeuralSLAM:
                 os.remove(f)
             if self._fuse_depth:
                 for sub in ("depth_fused", "depth_views"):
+                    os.makedirs(os.path.join(self._base, sub), exist_ok=True)
+                    for f in glob.glob(os.path.join(self._base, sub, "*")):
+                        os.remove(f)
+            if self._multiview:
+                for sub in ("depth_info", "depth_mv_views"):
                     os.makedirs(os.path.join(self._base, sub), exist_ok=True)
                     for f in glob.glob(os.path.join(self._base, sub, "*")):
                         os.remove(f)
@@ -373,16 +387,22 @@ class NeuralSLAM:
         """keyframe_depth="track": the flow track of keyframe `index` begins with the next pair."""
         if self._track is None:
             from .depth import FlowTrack
-            self._track = FlowTrack(SLAM_SIZE, self._calib, self._device)
+            self._track = FlowTrack(SLAM_SIZE, self._calib, self._device, history=16 if self._multiview else 0)
         self._track.start()
         self._track_index = index
 
     def _flush_track(self):
         """Write the depth of the keyframe the track is anchored at, if any pair has extended it."""
         if self._track_index is not None and self._track.steps > 0:
-            torch.save(self._track.depth[0].to("cpu"), os.path.join(self._base, "depth", "%06d.pth" % self._track_index))
+            depth = self._track.depth
+            name = "%06d.pth" % self._track_index
+            if self._multiview:
+                depth, info, views, self.multiview_counts = self._track.multiview(**self._multiview_options)
+                torch.save(info[0].to("cpu"), os.path.join(self._base, "depth_info", name))
+                torch.save(views[0].to("cpu"), os.path.join(self._base, "depth_mv_views", name))
+            torch.save(depth[0].to("cpu"), os.path.join(self._base, "depth", name))
             if self._map is not None:
-                self._map.set_depth(self._track_index, self._track.depth[0])
+                self._map.set_depth(self._track_index, depth[0])
         self._track_index = None
 
     def _set_mapping_net(self, weights):

@@ -259,6 +259,66 @@ def fuse_depths(bank, poses, targets, sources, calib, max_reproj=1.0, max_rel_de
     return fused, views, counts
 
 
+def multiview_depth(acc_bank, alive_bank, poses, slots, calib, depth_init=None, iters=4, scale_px=4.0, inlier_px=2.0, min_z=0.1,
+                    min_views=2, max_rel_sigma=0.25, max_depth=80.0):
+    """Depth of an anchor frame from its correspondences in several later frames at once: per pixel the inverse depth that
+    minimises the robust (Geman-McClure, `scale_px`) reprojection error over all listed views, by `iters` Levenberg-Marquardt steps
+    from the closed-form linear solution (or from `depth_init` where that costs less). `acc_bank` [N,2,H,W] float32: slot k is the
+    flow from the anchor to some later frame on the anchor's grid (what `depth.FlowTrack.acc` holds after a step); `alive_bank`
+    [N,H,W] uint8 or bool; `poses` ([N,12], [N,3,4] or [N,4,4]) anchor <- that frame, the convention of `two_view_depth`; `slots`
+    [B,S] (a tensor on the bank's device or a host sequence; [S] for one problem), S <= 16: the views of problem b in list order, a
+    slot < 0 or >= N is empty; `calib` is (fx, fy, cx, cy) or a calibration matrix without skew; `depth_init` [B,1,H,W] float32
+    (0 = none) or None. Returns `(depth, info, views, counts)` on the bank's device: `depth` float32 [B,1,H,W], 0 = none; `info`
+    float32 [B,1,H,W], the inverse variance of the RELATIVE depth for unit pixel noise (sigma_z / z = noise_px / sqrt(info));
+    `views` uint8 [B,H,W], the views whose residual is within `inlier_px`; `counts` int32 [B,3] = (pixels observed in at least
+    `min_views` views, pixels solved, pixels valid: at least `min_views` inliers, sigma_z / z <= `max_rel_sigma` at one pixel of
+    noise, depth <= `max_depth`). A view the point lies behind (closer than `min_z` times its depth) costs as much as a residual of
+    H + W pixels. Device tensors go through libatdn_hip's kernel on the current stream and the results stay on the device (no
+    synchronisation); CPU tensors go through the library's host form. The rule is float64 and stated in full in
+    include/atdn_hip.h, atdn_multiview_depth; the same inputs give the same bits on every call and on both paths."""
+    from .depth import intrinsics
+    if not isinstance(acc_bank, torch.Tensor) or acc_bank.dim() != 4 or acc_bank.shape[1] != 2:
+        raise RuntimeError("expected a flow bank [N,2,H,W], got %s" % (tuple(getattr(acc_bank, "shape", ())),))
+    if acc_bank.dtype != torch.float32 or not acc_bank.is_contiguous():
+        acc_bank = acc_bank.detach().float().contiguous()
+    N, _, H, W = (int(v) for v in acc_bank.shape)
+    device = acc_bank.device
+    if not isinstance(alive_bank, torch.Tensor) or alive_bank.device != device:
+        raise RuntimeError("flow bank on %s but the liveness bank on %s" % (device, getattr(alive_bank, "device", "the host")))
+    alive = _byte_plane(alive_bank, "a liveness bank", N, H, W)
+    if isinstance(poses, torch.Tensor) and poses.device != device:
+        raise RuntimeError("bank on %s but poses on %s" % (device, poses.device))
+    p = _pose_rows(torch.as_tensor(poses), N, device)
+    s = _index_tensor(slots, "slots", device)
+    s = s[None] if s.dim() == 1 else s
+    if s.dim() != 2 or s.shape[0] < 1 or s.shape[1] < 1:
+        raise RuntimeError("expected slots [B,S], got %s" % (tuple(s.shape),))
+    B, S = int(s.shape[0]), int(s.shape[1])
+    z0 = None
+    if depth_init is not None:
+        if not isinstance(depth_init, torch.Tensor) or depth_init.device != device:
+            raise RuntimeError("bank on %s but depth_init on %s" % (device, getattr(depth_init, "device", "the host")))
+        if depth_init.numel() != B * H * W or tuple(depth_init.shape[-2:]) != (H, W):
+            raise RuntimeError("expected depth_init [%d,1,%d,%d], got %s" % (B, H, W, tuple(depth_init.shape)))
+        z0 = depth_init.detach().float().contiguous()
+    fx, fy, cx, cy = intrinsics(calib)
+    depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=device)
+    info = torch.empty((B, 1, H, W), dtype=torch.float32, device=device)
+    views = torch.empty((B, H, W), dtype=torch.uint8, device=device)
+    counts = torch.empty((B, 3), dtype=torch.int32, device=device)
+    L = _lib.lib()
+    args = (C.c_void_p(acc_bank.data_ptr()), C.c_void_p(alive.data_ptr()), C.c_void_p(p.data_ptr()), C.c_void_p(s.data_ptr()),
+            C.c_void_p(z0.data_ptr()) if z0 is not None else None, N, B, S, H, W, fx, fy, cx, cy, float(scale_px), float(inlier_px),
+            float(min_z), int(min_views), float(max_rel_sigma), float(max_depth), int(iters), C.c_void_p(depth.data_ptr()),
+            C.c_void_p(info.data_ptr()), C.c_void_p(views.data_ptr()), C.c_void_p(counts.data_ptr()))
+    if acc_bank.is_cuda:
+        with torch.cuda.device(device):
+            _lib.check(L.atdn_multiview_depth(*args, _stream()))
+    else:
+        _lib.check(L.atdn_multiview_depth_host(*args))
+    return depth, info, views, counts
+
+
 def epipolar_score(counts):
     """float32 inliers / inside of the `counts` [B,3] (or [3]) of `two_view_depth`, 0 where no correspondence is inside: the
     share of the flow's correspondences that lie within `max_epipolar` pixels of the epipolar line the pose gives them. Exact

@@ -536,6 +536,76 @@ int atdn_depth_fuse_host(const float* bank, const float* poses, const int* targe
                          int W, double fx, double fy, double cx, double cy, double max_reproj, double max_rel_depth, int min_views,
                          double min_z, int average, float* fused, unsigned char* views, int* counts);
 
+/* Multi-view keyframe depth: per anchor pixel, the inverse depth that best explains its correspondences in up to
+ * ATDN_MULTIVIEW_MAX_VIEWS later frames with known poses — the depth half of bundle adjustment, the batch form of a depth filter —
+ * by Levenberg-Marquardt on the reprojection error under the Geman-McClure loss, with the information of the result.
+ * atdn_flow_track_step keeps one triangulation per pixel (the last valid one); this uses every correspondence of the interval.
+ *   acc_bank [N,2,H,W] fp32 DEVICE: slot k is the flow from the anchor frame to some later frame on the anchor's grid, channel 0 =
+ *   x (the acc_out of atdn_flow_track_step). alive_bank [N,H,W] uint8 DEVICE, any non-zero byte = alive. poses [N,12] fp32 DEVICE,
+ *   anchor <- that frame in the convention of atdn_flow_two_view_depth (X_anchor = R X + t; r_ij = poses[k][4*i + j], t_i =
+ *   poses[k][4*i + 3]). slots [B,S] int32 DEVICE: the views of problem b, walked in list order; a slot with k < 0 or k >= N is
+ *   skipped and reads nothing. depth_init [B,1,H,W] fp32 DEVICE or NULL: a depth to start from, 0 = none at that pixel.
+ *   depth [B,1,H,W] fp32 (0 = none), info [B,1,H,W] fp32, views [B,H,W] uint8, counts [B,3] int32 = (candidates, solved, valid),
+ *   all DEVICE. 1 <= N, 1 <= B <= 65535, 1 <= S <= ATDN_MULTIVIEW_MAX_VIEWS, 1 <= min_views <= S, 0 <= iters <= 16, H * W <= 2^24;
+ *   fx, fy finite and > 0; cx, cy finite; scale_px, inlier_px (pixels), min_z, max_rel_sigma and max_depth finite and > 0. Only
+ *   depth_init may be NULL; every output is disjoint from every input and from every other output. Anything else fails before a
+ *   launch.
+ * The rule, everything in float64 and every operation rounded on its own (no fused multiply-add), only + - * / and comparisons,
+ * in exactly this order. Constants: c2 = scale_px*scale_px, thr = inlier_px*inlier_px, e = (double)(H + W),
+ * rho_behind = (0.5*(e*e)) / (1 + (e*e)/c2) (those of atdn_pnp_terms), min_rel_info = 1 / (max_rel_sigma*max_rel_sigma).
+ * Per (problem, listed view), once, from the float32 row, the internal pose of atdn_pnp_terms:
+ *   Rc = R^T,  tc_i = -((r_0i*t_0 + r_1i*t_1) + r_2i*t_2)                                       (X = Rc X_anchor + tc)
+ * Pixel (x, y): a0 = (x - cx)/fx, a1 = (y - cy)/fy. Per listed view, in list order:
+ *   (u, v) = acc_bank[k][:, y, x];  x2 = x + u, y2 = y + v
+ *   obs = alive byte != 0 && 0 <= x2 <= W-1 && 0 <= y2 <= H-1     (closed intervals; a NaN fails)
+ *   m_i = (rc_i0*a0 + rc_i1*a1) + rc_i2                           (the pixel's ray in that view; its point is m + rho*tc)
+ *   kx = fx*(tc_0*m_2 - m_0*tc_2),  ky = fy*(tc_1*m_2 - m_1*tc_2)
+ *   xt = x2 - cx,  yt = y2 - cy
+ * Linear start over the obs views, each sum starting at +0.0:
+ *   Ax = fx*tc_0 - xt*tc_2,  Bx = xt*m_2 - fx*m_0;  Ay, By likewise with fy, yt and index 1
+ *   num = num + (Ax*Bx + Ay*By),  den = den + (Ax*Ax + Ay*Ay);  n_obs counts the obs views
+ * cand = n_obs >= min_views; not cand: depth 0, info 0, views 0, counted nowhere.
+ * The evaluation E(rho) over the obs views in list order; g, h, cost start at +0.0 and n_in at 0:
+ *   P_i = m_i + rho*tc_i
+ *   front = P_2 >= min_z*rho                                      not front: cost = cost + rho_behind, nothing else from this view
+ *   iz = 1/P_2,  px = (fx*P_0)*iz,  py = (fy*P_1)*iz
+ *   rx = (px + cx) - x2,  ry = (py + cy) - y2,  e2 = rx*rx + ry*ry
+ *   s = 1 + e2/c2,  w = 1/(s*s),  r = (0.5*e2)/s
+ *   Jx = (kx*iz)*iz,  Jy = (ky*iz)*iz
+ *   g = g + ((w*Jx)*rx + (w*Jy)*ry),  h = h + ((w*Jx)*Jx + (w*Jy)*Jy),  cost = cost + r,  n_in += (e2 <= thr)
+ * Start: rho_lin = num/den, lin_ok = 0 < rho_lin <= DBL_MAX. With depth_init and 0 < z0 <= FLT_MAX at the pixel: rho_0 = 1/z0, and
+ * both E(rho_lin) (if lin_ok) and E(rho_0) are formed; the start is the one of smaller cost, the linear one on a tie or when only
+ * it exists. Neither exists: not solved, depth 0, info 0, views 0.
+ * Steps k = 1 .. iters, lambda = 1e-3 at the start:
+ *   rho' = rho - g/(h + lambda*h)
+ *   accepted iff 0 < rho' <= DBL_MAX && cost(rho') < cost(rho)    (a NaN fails)
+ *   accepted: rho, g, h, cost, n_in are the trial's, lambda = max(lambda/3, 1e-9); rejected: lambda = min(4*lambda, 1e6)
+ *   (the decision rule and the constants of atdn_pnp_solve)
+ * Result:
+ *   z = 1/rho,  ri = (h*rho)*rho                                  (the inverse variance of the RELATIVE depth for unit pixel noise:
+ *                                                                  sigma_z / z = noise_px / sqrt(ri))
+ *   valid = solved && n_in >= min_views && ri >= min_rel_info && z >= FLT_MIN && z <= max_depth
+ *   depth = valid ? (float)z : 0,  info = valid ? (float)min(ri, FLT_MAX) : 0,  views = solved ? n_in : 0
+ *   counts = (number of cand, of solved, of valid)
+ * So: with every tc = 0 (no baseline) den = 0 and no pixel is solved from the linear start. A NaN or an infinity in a view's flow
+ * removes that view at that pixel only. A NaN or an infinity in a pose fails every comparison it reaches: the linear start of
+ * every pixel that observes that view fails, and in an evaluation the view counts as behind. All operations are correctly
+ * rounded: the device, the host form and any IEEE float64 restatement agree bit for bit.
+ * A memset of `counts` and one launch on `stream`: asynchronous, capturable, no host synchronisation, no workspace. The counts
+ * are integer sums (wave ballots, LDS, one integer atomic add per workgroup and counter; no float atomics): the same bits on
+ * every call. */
+#define ATDN_MULTIVIEW_MAX_VIEWS 16
+int atdn_multiview_depth(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
+                         const float* depth_init, int N, int B, int S, int H, int W, double fx, double fy, double cx, double cy,
+                         double scale_px, double inlier_px, double min_z, int min_views, double max_rel_sigma, double max_depth,
+                         int iters, float* depth, float* info, unsigned char* views, int* counts, void* stream);
+/* The same function on HOST buffers in plain C++ float64 (csrc/multiview_depth_host.h, the per-pixel function the kernel calls
+ * too): serves CPU tensors, needs no GPU, the same bits and the same argument rules. */
+int atdn_multiview_depth_host(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
+                              const float* depth_init, int N, int B, int S, int H, int W, double fx, double fy, double cx, double cy,
+                              double scale_px, double inlier_px, double min_z, int min_views, double max_rel_sigma, double max_depth,
+                              int iters, float* depth, float* info, unsigned char* views, int* counts);
+
 /* ---------------------------------------------------------------------------------------------------
  * Pose from depth and flow (robust PnP)  —  a depth map of image 1 gives a 3-D point per pixel, the flow image 1 -> image 2 gives
  * that point's pixel in image 2: the pose that explains the correspondences, by Levenberg-Marquardt on the reprojection error
