@@ -574,9 +574,9 @@ int atdn_corr_lookup_bricks(const float* fmap1, const float* fmap2, int B, int H
       src = plain[l - 1].p;
     }
     fbrick[l].alloc((long)B * bp.NB[l] * 256);
-    launch_brick_rows(src, src_sb, B, pH[l], pW[l], 256, fbrick[l].p, (long)bp.NB[l] * 256, st);
+    launch_brick_rows(src, src_sb, B, pH[l], pW[l], 256, 256, fbrick[l].p, (long)bp.NB[l] * 256, st);
     pyr[l].alloc((long)B * bp.NPB * kBrickPixelBlock * bp.NB[l]);
-    launch_corr_bricks(f1.p, (long)N * 256, fbrick[l].p, (long)bp.NB[l] * 256, B, N, bp.NB[l], 1.0f / sqrtf(256.0f), pyr[l].p, false, st);
+    launch_corr_bricks(f1.p, (long)N * 256, fbrick[l].p, (long)bp.NB[l] * 256, B, N, bp.NB[l], 256, 1.0f / sqrtf(256.0f), pyr[l].p, false, st);
     bp.base[l] = pyr[l].p;
     if (rowmajor[l]) launch_unbrick(pyr[l].p, bp.NB[l], N, pH[l], pW[l], n8, rowmajor[l], st);
   }

@@ -78,7 +78,16 @@ class GmaNet {
   bool par_ = false;       // true only inside capture() of a low-latency handle
   bool par_ok_ = true;     // cleared when a capture with branches failed once: later captures are single chains
   void fork(hipStream_t from, hipStream_t to);   // `to` continues from where `from` stands
-  DeviceBuf fbrick_[4], fplain_[3], coords_used_;   // features in brick order (levels 0-3), plain pooled features (1-3)
+  // target features in brick order (levels 0-3: 160-channel rows, the pre-head features + the constant chunk), plain pooled
+  // pre-head features (levels 1-3: 128 channels)
+  DeviceBuf fbrick_[4], fplain_[3], coords_used_;
+  // split-f16 modes (weights.h: pack_fnet_head_folded): the feature network's pre-head features of every frame, sf
+  // [slot][N][128] (slot b = frame b in the sequence modes, [im1 batch | im2 batch] in pair mode) — the correlation's target
+  // operand and what a continued clip carries over — and the folded head's output for the source frames, sf [pair][N][160]
+  DeviceBuf fpre_, fsrc_;
+  PackedConv fhead_fold_;
+  float corr_mul_ = 1.f;       // 2^k of the folded head: the correlation scale is corr_mul_ / 16
+  long fhead_w32_off_ = -1, fhead_b32_off_ = -1;   // fnet.conv2 as fp32 [256][128] + [256]: debug_read("fmap") rebuilds W f + b
   int brickBW_[4], brickBH_[4], brickNB_[4];
   BrickPyramid brick_pyramid() const;
   DeviceBuf rowmax_, rinv_;
@@ -107,14 +116,15 @@ class GmaNet {
   void iteration(int B, hipStream_t st);
   void run_body_sf(int B, int iters, hipStream_t st);
   // first_img: index of the first image of img4_ to encode (continued sequences skip frame 0 in the feature network)
+  // final_dst: where the last block's residual pass writes the encoder's output (default: one of the scratch maps)
   void run_encoder_sf(const EncoderWeights& E, bool instance, int nimg, hipStream_t st, float** out_buf, int first_img = 0,
-                      DeviceBuf* bufs = nullptr);   // bufs: four scratch maps (default enc_)
+                      DeviceBuf* bufs = nullptr, float* final_dst = nullptr);   // bufs: four scratch maps (default enc_)
   void iteration_sf(int B, hipStream_t st);
   void capture(int B, int iters);
   void launch_body(int B, int iters, hipStream_t st);
   int seq_ = 0;        // 0: pair mode; 1: sequence (B+1 frames, every frame through fnet once); 2: sequence continued
                        //    (frame 0 is the previous call's last frame: its features are reused, fnet sees B frames)
-  int last_frame_ = -1;  // fmap_ slot of the last frame of the previous sequence call
+  int last_frame_ = -1;  // fpre_ slot of the last frame of the previous sequence call
   float* preds_out_ = nullptr;   // forward_predictions only: where iteration `it` writes its upsampled flow (+ it * preds_stride_)
   long preds_stride_ = 0;
   void mask_head_sf(int B, hipStream_t st);
@@ -139,7 +149,7 @@ class GmaNet {
   long to_v_w32_off_ = -1;   // split-f16 / f16 modes: to_v's weight as fp32 [128][128] (debug reads only)
 
   // workspace
-  DeviceBuf img4_, enc_[4], scratch_, pcnt_, fin_, fmap_, psum_, pm2_, mean_[3], rstd_[3];   // [2]: the feature network's stem statistics, alive until its first block's residual pass
+  DeviceBuf img4_, enc_[4], scratch_, pcnt_, fin_, fmap_ /* exact-fp32 path only */, psum_, pm2_, mean_[3], rstd_[3];   // [2]: the feature network's stem statistics, alive until its first block's residual pass
   DeviceBuf pyr_[4], h_[2], x_, qk_, attn_, vT_, corrfeat_, cor1_, corflo_, flo1_, z_, rh_, fh_, mask_;
   DeviceBuf coords1_, flow4_, pre_zr_[2], pre_q_[2];
   int pyrH_[4], pyrW_[4];

@@ -112,8 +112,8 @@ void GmaNet::profile(int B, int iters, int reps, float* ms, hipStream_t st, int 
   ATDN_CHECK(mode == 0 || precision >= 1, "sequence modes are built for the split-f16 pipeline");
   ATDN_CHECK(!probe_, "switch the range probe off before profiling: its launches would be timed with the stages");
   for (int i = 0; i < ST_COUNT; ++i) ms[i] = 0.f;
-  seq_ = mode;   // 0 pair, 1 sequence, 2 continued sequence (fmap_ slot 0 is read as it stands: timing only)
-  last_frame_ = 0;   // fmap_ is overwritten: a continued sequence call must not read it
+  seq_ = mode;   // 0 pair, 1 sequence, 2 continued sequence (feature slot 0 is read as it stands: timing only)
+  last_frame_ = 0;   // the feature slots are overwritten: a continued sequence call must not read them
   for (int r = 0; r < reps; ++r) {
     Timer t;
     timer_ = &t;
@@ -220,6 +220,13 @@ void GmaNet::finalize() {
   };
   fnet_ = pack_encoder(arena_, sd_, "fnet.", false, sf);
   cnet_ = pack_encoder(arena_, sd_, "cnet.", true, sf);
+  if (sf) {
+    // the feature head folded into the correlation (weights.h); these modes never launch fnet_.head itself —
+    // debug_read("fmap") multiplies with the fp32 copy below
+    fhead_fold_ = pack_fnet_head_folded(arena_, sd_, "fnet.conv2", &corr_mul_);
+    fhead_w32_off_ = pack_vector(arena_, sd_.get("fnet.conv2.weight").data);
+    fhead_b32_off_ = pack_vector(arena_, sd_.get("fnet.conv2.bias").data);
+  }
   convc1_ = tap({u + "encoder.convc1"});
   if (sf) pack_fragment_major16(arena_, convc1_);   // the fused lookup kernel loads operand-order weights (16x16x32)
   convc2_ = tap({u + "encoder.convc2"});
@@ -301,7 +308,7 @@ void GmaNet::finalize() {
   for (PackedConv* L : {&convc1_, &convc2_, &convf1_, &convf2_, &convm_, &to_v_, &to_qk_, &gru_zr_[0], &gru_zr_[1],
                         &gru_q_[0], &gru_q_[1], &fh1_, &fh2_, &mask0_, &mask2_})
     resolve(arena_, *L);
-  if (sf) for (PackedConv* L : {&gru_zr_ctx_[0], &gru_zr_ctx_[1], &gru_q_ctx_[0], &gru_q_ctx_[1]}) resolve(arena_, *L);
+  if (sf) for (PackedConv* L : {&gru_zr_ctx_[0], &gru_zr_ctx_[1], &gru_q_ctx_[0], &gru_q_ctx_[1], &fhead_fold_}) resolve(arena_, *L);
   gamma_ = arena_.dev(gamma_off_);
 
   // ---- workspace (sized for maxB pairs; everything stays resident in HBM between calls)
@@ -310,7 +317,9 @@ void GmaNet::finalize() {
   const long n8 = (long)B * N;
   img4_.alloc(2L * B * H * W * 4);
   for (int i = 0; i < (sf ? 4 : 3); ++i) enc_[i].alloc(2L * B * H2 * W2 * 64);
-  fmap_.alloc(2L * B * N * 256);
+  // (split-f16 modes: no 256-channel feature tensor; pre-head features of 2B slots and the folded head's output for B sources)
+  if (sf) { fpre_.alloc(2L * B * N * 128); fsrc_.alloc((long)B * N * 160); }
+  else fmap_.alloc(2L * B * N * 256);
   const long groups = (long)cdiv(H2 * W2, 64) * 4 + 8;
   psum_.alloc(2L * B * groups * 128); pm2_.alloc(2L * B * groups * 128); pcnt_.alloc(2L * B * groups); fin_.alloc(2L * B * 32 * 128 * 4 * 2);
   for (int i = 0; i < 3; ++i) { mean_[i].alloc(2L * B * 128); rstd_[i].alloc(2L * B * 128); }
@@ -323,8 +332,8 @@ void GmaNet::finalize() {
     pyr_[l].alloc(classic_ ? n8 * pyrH_[l] * pyrW_[l] : (long)B * brick_pixel_blocks(N) * kBrickPixelBlock * brickNB_[l]);
   }
   if (sf) {
-    for (int l = 0; l < 4; ++l) fbrick_[l].alloc((long)B * brickNB_[l] * 256);
-    for (int l = 1; l < 4; ++l) fplain_[l - 1].alloc((long)B * pyrH_[l] * pyrW_[l] * 256);
+    for (int l = 0; l < 4; ++l) fbrick_[l].alloc((long)B * brickNB_[l] * 160);
+    for (int l = 1; l < 4; ++l) fplain_[l - 1].alloc((long)B * pyrH_[l] * pyrW_[l] * 128);
     coords_used_.alloc(n8 * 2);
   }
   h_[0].alloc(n8 * 128); h_[1].alloc(n8 * 128); x_.alloc(n8 * XLD);
@@ -353,7 +362,7 @@ void GmaNet::finalize() {
   ATDN_HIP(hipMemset(flow4_.p, 0, flow4_.n * sizeof(float)));
   ATDN_HIP(hipDeviceSynchronize());
   ws_bytes_ = 0;
-  DeviceBuf* all[] = {&img4_, &enc_[0], &enc_[1], &enc_[2], &enc_[3], &fmap_, &psum_, &pm2_, &pyr_[0], &pyr_[1], &pyr_[2],
+  DeviceBuf* all[] = {&img4_, &enc_[0], &enc_[1], &enc_[2], &enc_[3], &fmap_, &fpre_, &fsrc_, &psum_, &pm2_, &pyr_[0], &pyr_[1], &pyr_[2],
                       &pyr_[3], &h_[0], &h_[1], &x_, &qk_, &attn_, &vT_, &corrfeat_, &cor1_, &corflo_, &flo1_, &z_,
                       &rh_, &fh_, &mask_, &coords1_, &flow4_};
   for (auto* b : all) ws_bytes_ += (size_t)b->n * sizeof(float);
@@ -600,7 +609,7 @@ void GmaNet::mask_head(int B, hipStream_t st) {
 // Same op sequence; every TAP-mode GEMM runs on conv_sf_kernel and every tensor that feeds one is stored in the
 // sf format (sf.h). ROW-mode layers (7x7 stems, convf1) stay on the exact-fp32 engine and write sf directly.
 void GmaNet::run_encoder_sf(const EncoderWeights& E, bool instance, int nimg, hipStream_t st, float** out_buf, int first_img,
-                            DeviceBuf* bufs) {
+                            DeviceBuf* bufs, float* final_dst) {
   const float* images = img4_.p + (long)first_img * H * W * 4;
   int h = conv_out(H, 7, 2, 3), w = conv_out(W, 7, 2, 3);
   DeviceBuf* eb = bufs ? bufs : enc_;
@@ -653,6 +662,7 @@ void GmaNet::run_encoder_sf(const EncoderWeights& E, bool instance, int nimg, hi
     const int co = Bk.c1.N;
     const int oh = conv_out(h, 3, stride, 1), ow = conv_out(w, 3, stride, 1);
     const long ohw = (long)oh * ow;
+    if (bi == 5 && final_dst) O = final_dst;   // the last block's output pass writes the caller's buffer: no extra pass
     if (instance && norm_on_load_) {
       // conv1 -> (InstanceNorm + ReLU inside conv2's patch loader) -> conv2: the pass that used to materialise
       // relu(IN(conv1)) between them (4 B read + 4 B written per element) is gone. conv2's statistics land in slot 1
@@ -765,8 +775,8 @@ void GmaNet::iteration_sf(int B, hipStream_t st) {
 
 void GmaNet::run_body_sf(int B, int iters, hipStream_t st) {
   float* f;
-  // feature-network passes: two per pair; one per frame in sequence mode; in a continued sequence frame 0's features
-  // were already moved into fmap_ slot 0 by forward_sequence and only frames 1..B are encoded (img4_ still holds all
+  // feature-network passes: two per pair; one per frame in sequence mode; in a continued sequence frame 0's pre-head
+  // features were already moved into fpre_ slot 0 by forward_sequence and only frames 1..B are encoded (img4_ still holds all
   // B+1 frames: the context network needs frame 0)
   const int nfeat = seq_ == 0 ? 2 * B : seq_ == 1 ? B + 1 : B;
   // low-latency capture (par_): the context chain (context network -> attention -> GRU context terms) is a branch of its own
@@ -776,30 +786,35 @@ void GmaNet::run_body_sf(int B, int iters, hipStream_t st) {
   // (Round 4 measured the encoders depth-first in sub-batches of <= 2-8 frames, so that a conv's output and its consumer's
   // input fit the 256 MiB Infinity Cache together: every extra launch cost 10-12 us and nothing came back from the cache,
   // profiles/r04_ab_encoder_subbatch.txt. All frames of a launch go through a layer together.)
-  run_encoder_sf(fnet_, true, nfeat, st, &f, seq_ == 2 ? 1 : 0);
-  ConvShape s = conv_shape(fnet_.head, f, 128, (long)N * 128, nfeat, H8, W8, 1, 0, 0);
-  float* fdst = fmap_.p + (seq_ == 2 ? (long)N * 256 : 0);
-  conv_sf_dispatch(s, fnet_.head.wscale, SfBias<ACT_NONE>{fnet_.head.b, fdst, (long)N * 256, 256}, st);
+  // layer3's output goes straight into fpre_ (not an enc_ map: the context network reuses those). The head (fnet.conv2) is
+  // folded into the correlation (weights.h: pack_fnet_head_folded): only the B SOURCE frames get one, 128 -> 160 — slots
+  // 0..B-1 in every mode ([im1 batch | ...], or frames 0..B-1 of a clip; a continued clip's slot 0 is the carried row, so its
+  // head sees the same bits the same frame's head would see as a source of any other call).
+  run_encoder_sf(fnet_, true, nfeat, st, &f, seq_ == 2 ? 1 : 0, nullptr, fpre_.p + (seq_ == 2 ? (long)N * 128 : 0));
+  ConvShape s = conv_shape(fhead_fold_, fpre_.p, 128, (long)N * 128, B, H8, W8, 1, 0, 0);
+  conv_sf_dispatch(s, fhead_fold_.wscale, SfBias<ACT_NONE>{fhead_fold_.b, fsrc_.p, (long)N * 160, 160}, st);
   mark(ST_FNET, st);
 
-  // all-pairs correlation (corr.py:55-63) and its pyramid (corr.py:16-30): every level = fmap1 x (target features of that level
-  // in BRICK order)^T, written by corr_bricks_kernel in the brick-major layout the lookup reads; padding cells are zero feature
-  // rows. Levels 1-3: 2x2-pooled features — correlation is linear in the target features, so avg_pool2d of corr.py:28-30
-  // commutes with the dot product. fmap_ slot b is frame b (sequence modes: pair b = frames b, b + 1) or [im1 batch | im2 batch].
-  const float* target = fmap_.p + (long)(seq_ ? 1 : B) * N * 256;
+  // all-pairs correlation (corr.py:55-63) and its pyramid (corr.py:16-30): every level = folded source features x (target
+  // features of that level in BRICK order)^T, written by corr_bricks_kernel in the brick-major layout the lookup reads; the target
+  // rows are the pre-head features + the constant chunk (brick_rows_kernel), padding cells are all-zero rows. Levels 1-3: 2x2-pooled
+  // features — correlation is linear in the target features, so avg_pool2d of corr.py:28-30 commutes with the dot product (and
+  // the average of the constant 1 is 1: the chunk is appended after pooling). fpre_ slot b is frame b (sequence modes: pair b =
+  // frames b, b + 1) or [im1 batch | im2 batch].
+  const float* target = fpre_.p + (long)(seq_ ? 1 : B) * N * 128;
   for (int l = 0; l < 4; ++l) {
     const float* plain = target;
-    long plain_sb = (long)N * 256;
+    long plain_sb = (long)N * 128;
     if (l > 0) {
       const float* prev = l == 1 ? target : fplain_[l - 2].p;
-      const long prev_sb = l == 1 ? (long)N * 256 : (long)pyrH_[l - 1] * pyrW_[l - 1] * 256;
-      plain_sb = (long)pyrH_[l] * pyrW_[l] * 256;
-      launch_pool_features_sf(prev, B, pyrH_[l - 1], pyrW_[l - 1], 256, prev_sb, fplain_[l - 1].p, plain_sb, st);
+      const long prev_sb = l == 1 ? (long)N * 128 : (long)pyrH_[l - 1] * pyrW_[l - 1] * 128;
+      plain_sb = (long)pyrH_[l] * pyrW_[l] * 128;
+      launch_pool_features_sf(prev, B, pyrH_[l - 1], pyrW_[l - 1], 128, prev_sb, fplain_[l - 1].p, plain_sb, st);
       plain = fplain_[l - 1].p;
     }
-    launch_brick_rows(plain, plain_sb, B, pyrH_[l], pyrW_[l], 256, fbrick_[l].p, (long)brickNB_[l] * 256, st);
-    launch_corr_bricks(fmap_.p, (long)N * 256, fbrick_[l].p, (long)brickNB_[l] * 256, B, N, brickNB_[l], 1.0f / sqrtf(256.0f), pyr_[l].p,
-                       sf_fast_mode(), st);
+    launch_brick_rows(plain, plain_sb, B, pyrH_[l], pyrW_[l], 128, 160, fbrick_[l].p, (long)brickNB_[l] * 160, st);
+    launch_corr_bricks(fsrc_.p, (long)N * 160, fbrick_[l].p, (long)brickNB_[l] * 160, B, N, brickNB_[l], 160,
+                       corr_mul_ / sqrtf(256.0f), pyr_[l].p, sf_fast_mode(), st);
     if (l == 0) mark(ST_CORR, st);
   }
   mark(ST_POOL, st);
@@ -896,10 +911,11 @@ void GmaNet::forward_sequence(const float* frames, int B, int iters, const float
   ATDN_CHECK(frames && flow_low && flow_up, "null tensor");
   const long frame = 3L * H * W;
   if (continued) {
-    // frame 0 is the last frame of the previous sequence call on this handle: its features move to slot 0 and the
-    // feature network only sees frames 1..B (every frame of a long sequence passes through it exactly once)
+    // frame 0 is the last frame of the previous sequence call on this handle: its pre-head features move to slot 0 and the
+    // feature network only sees frames 1..B (every frame of a long sequence passes through it exactly once); as this clip's
+    // first source it gets its folded head with the others (run_body_sf)
     ATDN_CHECK(last_frame_ >= 1, "continued sequence call without a previous sequence call on this handle");
-    ATDN_HIP(hipMemcpyAsync(fmap_.p, fmap_.p + (long)last_frame_ * N * 256, (size_t)N * 256 * sizeof(float),
+    ATDN_HIP(hipMemcpyAsync(fpre_.p, fpre_.p + (long)last_frame_ * N * 128, (size_t)N * 128 * sizeof(float),
                             hipMemcpyDeviceToDevice, st));
     seq_ = 2;
   } else {
@@ -932,7 +948,7 @@ void GmaNet::forward(const float* im1, const float* im2, int B, int iters, const
   ATDN_CHECK(iters >= 1 && iters <= 64, "iters out of range");
   ATDN_CHECK(im1 && im2 && flow_low && flow_up, "null tensor");
   seq_ = 0;
-  last_frame_ = 0;   // pair mode overwrites fmap_: a later continued sequence call fails loudly instead of reading it
+  last_frame_ = 0;   // pair mode overwrites the feature slots: a later continued sequence call fails loudly instead of reading it
   if (probe_) probe_begin(st);
   launch_prep_images(im1, im2, B, H, W, img4_.p, st, B);
   if (precision >= 1) launch_init_coords_sf(flow_init, B, H8, W8, coords1_.p, flow4_.p, x_.p, XLD, 254, st);
@@ -1017,6 +1033,18 @@ long GmaNet::debug_read(const char* name, float* host, long capacity, hipStream_
   else if (k == "mask") b = &mask_; else if (k == "coords1") b = &coords1_; else if (k == "flow4") b = &flow4_;
   else if (k == "qk") b = &qk_; else if (k == "img4") b = &img4_;
   else if (k == "cor1") b = &cor1_;   // relu(convc1(lookup)) of the last iteration: the fused kernel's product phase
+  if (k == "fmap" && !classic_) {
+    // the split-f16 modes never form W f + b (the head is folded into the correlation): the tap keeps its meaning, rebuilt in
+    // fp32 from the decoded pre-head features, [2 * maxB slots][N][256] in fpre_'s slot order
+    const long rows = 2L * maxB * N;
+    scratch_.reserve(rows * (128 + 256));
+    launch_from_sf(fpre_.p, scratch_.p, rows, 128, st);
+    launch_linear_rows(scratch_.p, rows, 128, arena_.dev(fhead_w32_off_), arena_.dev(fhead_b32_off_), 256, scratch_.p + rows * 128, st);
+    ATDN_HIP(hipStreamSynchronize(st));
+    const long n = std::min(capacity, rows * 256);
+    ATDN_HIP(hipMemcpy(host, scratch_.p + rows * 128, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return n;
+  }
   if (k == "agg") {
     // the stored aggregate A . motion itself, [maxB * N][128]: channels 256..383 of the split-f16 GRU input (the exact-fp32
     // path stores motion_global there and has no such tensor)

@@ -127,13 +127,19 @@ struct BrickPyramid {
   int NPB;   // pixel blocks per pair: 2 * ceil(N / 128)
 };
 inline int brick_pixel_blocks(int N) { return 2 * ((N + 127) / 128); }
-// feature rows [img][H*W][C] -> brick order [img][BH*BW*32][C] (zero rows for padding cells); sb / db per-image strides
-void launch_brick_rows(const float* src, long sb, int nimg, int H, int W, int C, float* dst, long db, hipStream_t st);
+// feature rows [img][H*W][C] -> brick order [img][BH*BW*32][Cd] (zero rows for padding cells); sb / db per-image strides.
+// Cd == C: a plain copy. Cd == C + 32: every row of a cell INSIDE the map gets one more sf chunk that holds the constant 1
+// in its first channel and zeros in the other 31 (the target side of the folded feature head, corr_bricks.hip); rows of
+// padding cells stay all zero.
+void launch_brick_rows(const float* src, long sb, int nimg, int H, int W, int C, int Cd, float* dst, long db, hipStream_t st);
 // one pyramid level in the layout above: out[...] = scale * <f1[pair][p], f2b[pair][n']> for brick n' / 32, cell n' % 32
-// (corr_bricks.hip); f1 sf [B][N][256] (per-pair stride sb1 floats), f2b sf [B][NB][256] in brick order (zero rows for padding
-// cells), out fp32 with brick_pixel_blocks(N) * 64 * NB floats per pair (rows N .. 64 * NPB - 1 of a pair are scratch)
-void launch_corr_bricks(const float* f1, long sb1, const float* f2b, long sb2, int B, int N, int NB, float scale, float* out,
-                        bool fast, hipStream_t st);
+// (corr_bricks.hip); f1 sf [B][N][K] (per-pair stride sb1 floats), f2b sf [B][NB][K] in brick order (zero rows for padding
+// cells), K = 256 or 160; out fp32 with brick_pixel_blocks(N) * 64 * NB floats per pair (rows N .. 64 * NPB - 1 of a pair
+// are scratch)
+void launch_corr_bricks(const float* f1, long sb1, const float* f2b, long sb2, int B, int N, int NB, int K, float scale,
+                        float* out, bool fast, hipStream_t st);
+// debug reads only: fp32 1x1 convolution out[r][o] = b[o] + sum_c w[o][c] * in[r][c], Cin <= 256, one block per row
+void launch_linear_rows(const float* in, long rows, int Cin, const float* w, const float* b, int Cout, float* out, hipStream_t st);
 // bricked level (pairs of N source pixels) -> row-major [npix][H*W] (debug reads)
 void launch_unbrick(const float* src, long NB, int N, int H, int W, long npix, float* dst, hipStream_t st);
 // cor1 = relu(convc1(lookup(coords1))) (corr.py:32-53 + update.py:76-78): out sf [npix][256]; wfrag = convc1 weights in

@@ -699,6 +699,27 @@ void launch_mfg_reconstruct(float* x, long rows, int ld, int cmf, int cagg, cons
   ATDN_HIP(hipGetLastError());
 }
 
+// debug reads only: fp32 1x1 convolution, one block per row, thread o = one output channel (fma in channel order)
+__global__ __launch_bounds__(256) void linear_rows_kernel(const float* __restrict__ in, int Cin, const float* __restrict__ w,
+                                                          const float* __restrict__ b, int Cout, float* __restrict__ out) {
+  __shared__ float a[256];
+  const long r = blockIdx.x;
+  for (int c = threadIdx.x; c < Cin; c += blockDim.x) a[c] = in[r * Cin + c];
+  __syncthreads();
+  for (int o = threadIdx.x; o < Cout; o += blockDim.x) {
+    float s = b ? b[o] : 0.f;
+    for (int k = 0; k < Cin; ++k) s = fmaf(w[(long)o * Cin + k], a[k], s);
+    out[r * Cout + o] = s;
+  }
+}
+
+void launch_linear_rows(const float* in, long rows, int Cin, const float* w, const float* b, int Cout, float* out, hipStream_t st) {
+  ATDN_CHECK(Cin >= 1 && Cin <= 256 && Cout >= 1, "linear_rows: bad geometry");
+  if (rows <= 0) return;
+  hipLaunchKernelGGL(linear_rows_kernel, dim3((unsigned)rows), dim3(256), 0, st, in, Cin, w, b, Cout, out);
+  ATDN_HIP(hipGetLastError());
+}
+
 __global__ void in_apply_sf_kernel(const float4* __restrict__ x, float* __restrict__ y, const float* __restrict__ mean,
                                    const float* __restrict__ rstd, const float* __restrict__ res,
                                    const float4* __restrict__ res_raw, const float* __restrict__ rmean,

@@ -372,21 +372,27 @@ __global__ __launch_bounds__(NWAVE * 64, TP == 32 ? 4 : 1) void lookup_conv_kern
 
 // feature rows in brick order: dst[img][n'][C] = src[img][y * W + x][C] for the cell (y, x) that brick position n'
 // addresses, zero rows for the padding cells. One thread = 16 bytes (the sf chunk layout is copied verbatim).
-__global__ void brick_rows_kernel(const float* __restrict__ src, long sb, int H, int W, int BW, int C,
+// Cd > C: the destination row has one more sf chunk than the source, the constant channel of the folded feature head
+// (corr_bricks.hip): [1.0, 0 x 31] in the hi plane (its first half is the first two bytes of the chunk), lo plane zero, for
+// cells inside the map; padding cells keep an all-zero row, so a sample outside the map is still exactly zero.
+__global__ void brick_rows_kernel(const float* __restrict__ src, long sb, int H, int W, int BW, int C, int Cd,
                                   float* __restrict__ dst, long db, long total4) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total4) return;
-  const int c4 = C / 4;
+  const int c4 = Cd / 4;
   const int part = (int)(i % c4);
   const long row = i / c4;
-  const long per_img = db / C;
+  const long per_img = db / Cd;
   const long img = row / per_img;
   const int n = (int)(row - img * per_img);
   const int brick = n >> 5, within = n & 31;
   const int y = (brick / BW) * 4 + (within >> 3), x = (brick % BW) * 8 + (within & 7);
   v4f v = {0.f, 0.f, 0.f, 0.f};
-  if (y < H && x < W) v = *reinterpret_cast<const v4f*>(src + img * sb + ((long)y * W + x) * C + part * 4);
-  *reinterpret_cast<v4f*>(dst + img * db + (long)n * C + part * 4) = v;
+  if (y < H && x < W) {
+    if (part * 4 < C) v = *reinterpret_cast<const v4f*>(src + img * sb + ((long)y * W + x) * C + part * 4);
+    else if (part * 4 == C) v[0] = __int_as_float(0x3C00);   // f16 1.0 in the low half of the first dword
+  }
+  *reinterpret_cast<v4f*>(dst + img * db + (long)n * Cd + part * 4) = v;
 }
 
 // bricked level -> row-major [pixels][H * W] (debug reads)
@@ -405,11 +411,11 @@ __global__ void unbrick_kernel(const float* __restrict__ src, long NB, int N, in
 
 }  // namespace
 
-void launch_brick_rows(const float* src, long sb, int nimg, int H, int W, int C, float* dst, long db, hipStream_t st) {
-  ATDN_CHECK(C % 4 == 0 && db % C == 0, "brick_rows: bad geometry");
+void launch_brick_rows(const float* src, long sb, int nimg, int H, int W, int C, int Cd, float* dst, long db, hipStream_t st) {
+  ATDN_CHECK(C % 4 == 0 && (Cd == C || (Cd == C + 32 && C % 32 == 0)) && db % Cd == 0, "brick_rows: bad geometry");
   const int BW = (W + 7) / 8;
-  const long total4 = (long)nimg * (db / C) * (C / 4);
-  hipLaunchKernelGGL(brick_rows_kernel, dim3((unsigned)cdivl(total4, 256)), dim3(256), 0, st, src, sb, H, W, BW, C, dst, db, total4);
+  const long total4 = (long)nimg * (db / Cd) * (Cd / 4);
+  hipLaunchKernelGGL(brick_rows_kernel, dim3((unsigned)cdivl(total4, 256)), dim3(256), 0, st, src, sb, H, W, BW, C, Cd, dst, db, total4);
   ATDN_HIP(hipGetLastError());
 }
 

@@ -305,6 +305,60 @@ inline PackedConv pack_gru_sf_folded(WeightArena& A, const StateDict& sd, const 
   return pack_conv_sf(A, tmp, tnames, nullptr, true);
 }
 
+// The feature network's head (fnet.conv2: 1x1, 128 -> 256, bias, nothing behind it) folded into the correlation. Its output is
+// used only as corr[p, q] = <a1[p], a2[q]> / 16 with a = W f + b, f = layer3's output (128 channels), and
+//     <a1, a2> = f1^T (W^T W) f2 + (W^T b) . f1 + (W^T b) . f2 + b . b = <g1, f2> + c1,
+//     g1 = M f1 + u,  c1 = u . f1 + b . b,  M = W^T W,  u = W^T b,
+// so only SOURCE frames need a head, 128 -> 129 outputs, and the target operand is f2 itself with one constant channel that
+// holds 1 (brick_rows_kernel appends it): K = 129, padded to 160, instead of 256. Packed as a 1x1 layer 128 -> 160:
+//     rows 0..127 = 2^-k M with bias 2^-k u;  row 128 = 2^-k u^T with bias 2^-k b . b;  rows 129..159 zero (stored as exact zeros).
+// M, u and b . b are formed in fp64 and rounded once. k is the binary exponent of the largest row sum of |M|: max_f |M f| <=
+// (row sum) max |f|, so 2^-k g has the magnitude of f whatever the checkpoint's scale of W (a conv2 scaled by s scales M by
+// s^2 and moves k by 2 log2 s); the correlation kernel multiplies by 2^k / 16 instead of 1 / 16 (*corr_mul = 2^k, exact).
+inline PackedConv pack_fnet_head_folded(WeightArena& A, const StateDict& sd, const std::string& name, float* corr_mul) {
+  const HostTensor& w = sd.get(name + ".weight");
+  ATDN_CHECK(w.shape.size() == 4 && w.shape[0] == 256 && w.shape[1] == 128 && w.shape[2] == 1 && w.shape[3] == 1,
+             "the feature head is a 1x1 convolution, 128 -> 256");
+  std::vector<double> b(256, 0.0);
+  if (sd.has(name + ".bias")) {
+    const HostTensor& bt = sd.get(name + ".bias");
+    ATDN_CHECK(bt.data.size() == 256, "feature head bias");
+    for (int o = 0; o < 256; ++o) b[o] = (double)bt.data[o];
+  }
+  std::vector<double> M(128 * 128, 0.0), u(128, 0.0);
+  double bb = 0.0;
+  for (int o = 0; o < 256; ++o) {
+    const float* wo = &w.data[(size_t)o * 128];
+    bb += b[o] * b[o];
+    for (int i = 0; i < 128; ++i) {
+      const double wi = (double)wo[i];
+      u[i] += wi * b[o];
+      for (int j = 0; j < 128; ++j) M[i * 128 + j] += wi * (double)wo[j];
+    }
+  }
+  double rs = 0.0;
+  for (int i = 0; i < 128; ++i) {
+    double s = 0.0;
+    for (int j = 0; j < 128; ++j) s += std::fabs(M[i * 128 + j]);
+    rs = std::max(rs, s);
+  }
+  int k = 0;
+  if (rs > 0.0) (void)std::frexp(rs, &k);   // rs = m * 2^k, m in [0.5, 1)
+  std::vector<float> wf(160 * 128, 0.f), bf(160, 0.f);
+  for (int i = 0; i < 128; ++i) {
+    for (int j = 0; j < 128; ++j) wf[i * 128 + j] = (float)std::ldexp(M[i * 128 + j], -k);
+    bf[i] = (float)std::ldexp(u[i], -k);
+    wf[128 * 128 + i] = (float)std::ldexp(u[i], -k);
+  }
+  bf[128] = (float)std::ldexp(bb, -k);
+  StateDict tmp;
+  const int64_t shp[4] = {160, 128, 1, 1}, bs[1] = {160};
+  tmp.put("s0.weight", wf.data(), shp, 4);
+  tmp.put("s0.bias", bf.data(), bs, 1);
+  *corr_mul = std::ldexp(1.0f, k);
+  return pack_conv_sf(A, tmp, {"s0"}, nullptr, true);
+}
+
 inline long pack_vector(WeightArena& A, const std::vector<float>& v) {
   const long off = A.alloc((long)v.size());
   std::memcpy(A.at(off), v.data(), v.size() * sizeof(float));
