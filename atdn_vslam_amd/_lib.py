@@ -95,6 +95,14 @@ SIGNATURES = {
     "atdn_multiview_depth_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                             C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
                                             C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp]),
+    "atdn_bundle_workspace_bytes": (C.c_long, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "atdn_bundle_terms": (C.c_int, [_vp] * 6 + [C.c_int] * 5 + [C.c_double] * 4 + [C.c_int] + [C.c_double] * 3 + [C.c_int] + [_vp] * 4),
+    "atdn_bundle_terms_host": (C.c_int, [_vp] * 6 + [C.c_int] * 5 + [C.c_double] * 4 + [C.c_int] + [C.c_double] * 3 + [C.c_int] +
+                               [_vp] * 2),
+    "atdn_bundle_adjust": (C.c_int, [_vp] * 6 + [C.c_int] * 5 + [C.c_double] * 4 + [C.c_int] * 2 + [C.c_double] * 3 + [C.c_int] +
+                           [_vp] * 6),
+    "atdn_bundle_adjust_host": (C.c_int, [_vp] * 6 + [C.c_int] * 5 + [C.c_double] * 4 + [C.c_int] * 2 + [C.c_double] * 3 + [C.c_int] +
+                                [_vp] * 4),
     "atdn_pnp_workspace_bytes":(C.c_long, [C.c_int, C.c_int, C.c_int]),
     "atdn_pnp_terms": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                                  C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),

@@ -17,6 +17,7 @@
 #include "flow_args.h"
 #include "flow_consistency_host.h"
 #include "flow_track_host.h"
+#include "bundle_host.h"
 #include "multiview_depth_host.h"
 #include "pnp_host.h"
 #include "two_view_host.h"
@@ -441,6 +442,41 @@ int atdn_depth_fuse_host(const float* bank, const float* poses, const int* targe
                         fused, views, counts);
   depth_fuse_host(bank, poses, targets, sources, N, B, S, H, W,
                   depth_fuse_params(fx, fy, cx, cy, max_reproj, max_rel_depth, min_views, min_z, average), fused, views, counts);
+  ATDN_API_END
+}
+
+// ------------------------------------------------------------------ bundle adjustment (host twins of bundle.hip)
+int atdn_bundle_terms_host(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
+                           const float* depth, const unsigned char* mask, int N, int B, int S, int H, int W, double fx, double fy,
+                           double cx, double cy, int stride, double scale_px, double inlier_px, double min_z, int min_views,
+                           double* sums, int* counts) {
+  ATDN_API_BEGIN
+  ATDN_CHECK(S >= 1 && S <= BA_MAX_VIEWS && stride >= 1, "S must be in [1, ATDN_MULTIVIEW_MAX_VIEWS] and stride >= 1");
+  check_plane_batch(B, H, W, false);
+  const void* out[2] = {sums, counts};
+  const long out_bytes[2] = {(long)B * ba_sums(S) * 8, (long)B * 12};
+  bundle_check_args(acc_bank, alive_bank, poses, slots, depth, mask, N, B, S, H, W, fx, fy, cx, cy, stride, 0, scale_px, inlier_px,
+                    min_z, min_views, false, out, out_bytes, 2);
+  bundle_terms_host(acc_bank, alive_bank, poses, slots, depth, mask, N, B, S, H, W,
+                    bundle_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, min_views, 0, stride, H, W), sums, counts);
+  ATDN_API_END
+}
+
+int atdn_bundle_adjust_host(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
+                            const float* depth_init, const unsigned char* mask, int N, int B, int S, int H, int W, double fx,
+                            double fy, double cx, double cy, int stride, int iters, double scale_px, double inlier_px, double min_z,
+                            int min_views, float* poses_out, float* depth, double* cost, int* counts) {
+  ATDN_API_BEGIN
+  ATDN_CHECK(S >= 1 && S <= BA_MAX_VIEWS && stride >= 1, "S must be in [1, ATDN_MULTIVIEW_MAX_VIEWS] and stride >= 1");
+  check_plane_batch(B, H, W, false);
+  const long n = (long)H * W;
+  const void* out[4] = {poses_out, depth, cost, counts};
+  const long out_bytes[4] = {(long)B * S * 48, (long)B * n * 4, (long)B * 16, (long)B * 16};
+  bundle_check_args(acc_bank, alive_bank, poses, slots, depth_init, mask, N, B, S, H, W, fx, fy, cx, cy, stride, iters, scale_px,
+                    inlier_px, min_z, min_views, false, out, out_bytes, 4);
+  bundle_adjust_host(acc_bank, alive_bank, poses, slots, depth_init, mask, N, B, S, H, W,
+                     bundle_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, min_views, iters, stride, H, W), poses_out, depth,
+                     cost, counts);
   ATDN_API_END
 }
 

@@ -1,4 +1,4 @@
-// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip, epipolar.hip, depth_fusion.hip, multiview_depth.hip), shared by each device
+// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip, epipolar.hip, depth_fusion.hip, multiview_depth.hip, bundle.hip), shared by each device
 // entry point and its host twin in capi.hip, and the overlap rule that the pose solvers (pnp.hip, pose_graph.hip) share.
 #pragma once
 #include <cmath>
@@ -72,5 +72,11 @@ void multiview_check_args(const float* acc_bank, const unsigned char* alive_bank
                           const float* depth_init, int N, int B, int S, int H, int W, double fx, double fy, double cx, double cy,
                           double scale_px, double inlier_px, double min_z, int min_views, double max_rel_sigma, double max_depth,
                           int iters, const float* depth, const float* info, const unsigned char* views, const int* counts);
+
+// mask may be null; out[i] of out_bytes[i], i < n_out: the outputs (a workspace among them)
+void bundle_check_args(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
+                       const float* depth_init, const unsigned char* mask, int N, int B, int S, int H, int W, double fx, double fy,
+                       double cx, double cy, int stride, int iters, double scale_px, double inlier_px, double min_z, int min_views,
+                       bool grid_limit, const void* const* out, const long* out_bytes, int n_out);
 
 }  // namespace atdn

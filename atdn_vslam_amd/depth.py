@@ -87,7 +87,8 @@ class FlowTrack:
     `history=K` (1 <= K <= 16, transforms.multiview_depth's limit) also keeps `acc`, `alive` and the pose row of the last K steps
     in preallocated device banks [K * B, ...] (`hist_acc`, `hist_alive`, `hist_pose`; ring position r of image b is slot r * B + b):
     a ring, filled after every step by device copies of `acc` and `alive` on the same stream — the pose row is uploaded straight
-    into its ring slot —, still without a host synchronisation. `multiview()` solves the depth over the stored steps. With
+    into its ring slot —, still without a host synchronisation. `multiview()` solves the depth over the stored steps, `bundle()`
+    first refines their poses jointly with the depth (transforms.bundle_adjust). With
     `history=0` (the default) nothing is allocated and `extend` does what it always did."""
 
     def __init__(self, hw, calib, device, batch=1, history=0, **thresholds):
@@ -177,3 +178,25 @@ class FlowTrack:
             raise RuntimeError("FlowTrack.multiview: no step since start()")
         return transforms.multiview_depth(self.hist_acc, self.hist_alive, self.hist_pose, self.history_slots().tolist(), self.calib,
                                           depth_init=self.depth, **options)
+
+    def bundle(self, multiview_options=None, **options):
+        """Windowed bundle adjustment of the stored steps, then the multi-view depth against the refined poses:
+        `transforms.bundle_adjust` over `history_slots()` started from `depth` (`options` are its keyword arguments: stride, iters,
+        scale_px, inlier_px, min_z, min_views, mask), the refined rows scattered into a COPY of `hist_pose` on the device, and
+        `transforms.multiview_depth` (`multiview_options`) with that copy. Returns `(poses, depth, info, views, mv_counts, cost,
+        ba_counts)`: `poses` [B,S,12] the refined poses anchor <- step, oldest first; `depth`, `info`, `views`, `mv_counts` as
+        `multiview()` returns them; `cost` [B,2] and `ba_counts` [B,4] of the adjustment. Needs `history` > 0 and at least one
+        step since `start()`; the track's own state, its banks included, is untouched."""
+        from . import transforms
+        if not self.history:
+            raise RuntimeError("FlowTrack.bundle needs a track created with history > 0")
+        if self.steps < 1:
+            raise RuntimeError("FlowTrack.bundle: no step since start()")
+        slots = self.history_slots()
+        poses, _, cost, ba_counts = transforms.bundle_adjust(self.hist_acc, self.hist_alive, self.hist_pose, slots.tolist(),
+                                                             self.calib, self.depth, **options)
+        refined = self.hist_pose.clone()
+        refined.index_copy_(0, slots.reshape(-1).to(self.device), poses.reshape(-1, 12))
+        depth, info, views, mv_counts = transforms.multiview_depth(self.hist_acc, self.hist_alive, refined, slots.tolist(), self.calib,
+                                                                   depth_init=self.depth, **(multiview_options or {}))
+        return poses, depth, info, views, mv_counts, cost, ba_counts

@@ -93,6 +93,14 @@ class NeuralSLAM:
     `depth/%06d.pth`, and beside it `depth_info/%06d.pth` (float32 [1,376,1232], the inverse variance of the relative depth for
     unit pixel noise) and `depth_mv_views/%06d.pth` (uint8 [376,1232], the views that agree); `multiview_counts` [1,3] =
     (candidates, solved, valid) of the last keyframe stays on the device. "pair" and "track" change no file, directory or bit.
+    "bundle" (needs `calib`) is "multiview" behind a windowed bundle adjustment: FlowTrack.bundle first refines the poses of the
+    stored steps jointly with the anchor's depth (transforms.bundle_adjust, `bundle_options` its keyword arguments) and solves the
+    multi-view depth against the refined poses. It writes what "multiview" writes and `bundle/%06d.pth`, a dict of `poses`
+    (float32 [S,12], anchor <- step, oldest first), `cost` (float64 [2]) and `counts` (int32 [4]); `bundle_cost` [1,2] and
+    `bundle_counts` [1,4] of the last keyframe stay on the device. `bundle_pose=True`: when the interval had at most 16 steps —
+    the window's last step is then the new keyframe's frame — the new keyframe's pose and the running pose become (anchor pose @
+    refined last pose), formed in float64 and stored as float32; otherwise, and with False (the default), the trajectory is that of
+    "multiview", bit for bit.
     `refine_pose=True` (needs `calib`): in odometry mode every pair's predicted pose is refined on the pair's own flow
     (transforms.pose_from_flow with its defaults, on the device: the rotation and the direction of t; |t| stays the head's) before
     anything uses it: the "pair" keyframe depth, the poses fed to the flow track, the keyframe policy and the running pose
@@ -109,7 +117,7 @@ class NeuralSLAM:
     def __init__(self, args, odometry_weights=None, start_mode=None, flow_weights=None, mapping_weights=None,
                  precision=None, map_options=None, resident_map=False, warm_start=False, calib=None, keyframe_depth="pair",
                  loop_closure=False, loop_options=None, refine_pose=False, fuse_depth=False, fuse_options=None,
-                 multiview_options=None):
+                 multiview_options=None, bundle_options=None, bundle_pose=False):
         from .depth import intrinsics
         if fuse_depth and (calib is None or not resident_map):
             raise ValueError("fuse_depth=True needs the calibration and the keyframe map in device memory: pass calib= and "
@@ -126,14 +134,18 @@ class NeuralSLAM:
         self._loop_closure = bool(loop_closure)
         self._loop_options = dict(loop_options or {})
         self.loop_report = None      # the report of the last close_loops()
-        if keyframe_depth not in ("pair", "track", "multiview"):
-            raise ValueError('keyframe_depth is "pair", "track" or "multiview", got %r' % (keyframe_depth,))
+        if keyframe_depth not in ("pair", "track", "multiview", "bundle"):
+            raise ValueError('keyframe_depth is "pair", "track" or "multiview", or "bundle", got %r' % (keyframe_depth,))
         if keyframe_depth != "pair" and calib is None:
             raise ValueError('keyframe_depth="%s" needs the calibration: pass calib=' % keyframe_depth)
         self._args = args
         self._calib = None if calib is None else intrinsics(calib)
-        self._track_depth = keyframe_depth in ("track", "multiview")
-        self._multiview = keyframe_depth == "multiview"
+        self._track_depth = keyframe_depth in ("track", "multiview", "bundle")
+        self._multiview = keyframe_depth in ("multiview", "bundle")
+        self._bundle = keyframe_depth == "bundle"
+        self._bundle_options = dict(bundle_options or {})
+        self._bundle_pose = bool(bundle_pose) and self._bundle
+        self.bundle_cost = self.bundle_counts = None   # [1,2] float64, [1,4] int32 (device) of the last keyframe's adjustment
         self._multiview_options = dict(multiview_options or {})
         self.multiview_counts = None   # [1,3] int32 (device) of the last multi-view keyframe depth: candidates, solved, valid
         self._track = None           # depth.FlowTrack of the latest keyframe (keyframe_depth="track"), created with the first frame
@@ -186,7 +198,7 @@ class NeuralSLAM:
                     for f in glob.glob(os.path.join(self._base, sub, "*")):
                         os.remove(f)
             if self._multiview:
-                for sub in ("depth_info", "depth_mv_views"):
+                for sub in ("depth_info", "depth_mv_views") + (("bundle",) if self._bundle else ()):
                     os.makedirs(os.path.join(self._base, sub), exist_ok=True)
                     for f in glob.glob(os.path.join(self._base, sub, "*")):
                         os.remove(f)
@@ -319,7 +331,7 @@ class NeuralSLAM:
                     self._store_keyframe(im2, name)
                     self._keyframes.append(Frame(name, self._current_pose))
                     if self._track_depth:
-                        self._flush_track()
+                        self._flush_track(new_keyframe=True)
                         self._start_track(len(self._keyframes) - 1)
                     elif self._calib is not None:
                         self._depth_pending = len(self._keyframes) - 1
@@ -391,13 +403,30 @@ class NeuralSLAM:
         self._track.start()
         self._track_index = index
 
-    def _flush_track(self):
-        """Write the depth of the keyframe the track is anchored at, if any pair has extended it."""
+    def _flush_track(self, new_keyframe=False):
+        """Write the depth of the keyframe the track is anchored at, if any pair has extended it. `new_keyframe`: the last
+        step of the track is the frame of the keyframe just registered (the last of the list)."""
         if self._track_index is not None and self._track.steps > 0:
             depth = self._track.depth
             name = "%06d.pth" % self._track_index
-            if self._multiview:
+            if self._bundle:
+                poses, depth, info, views, self.multiview_counts, self.bundle_cost, self.bundle_counts = self._track.bundle(
+                    multiview_options=self._multiview_options, **self._bundle_options)
+                poses = poses[0].to("cpu")
+                torch.save(dict(poses=poses, cost=self.bundle_cost[0].to("cpu"), counts=self.bundle_counts[0].to("cpu")),
+                           os.path.join(self._base, "bundle", name))
+                if self._bundle_pose and new_keyframe and self._track.steps <= self._track.history:
+                    last = torch.eye(4, dtype=torch.float64)
+                    last[:3, :] = poses[-1].reshape(3, 4).double()
+                    anchor = torch.as_tensor(self._keyframes[self._track_index].pose).double()
+                    pose = (anchor @ last).float()
+                    self._keyframes[-1].pose = pose
+                    self._current_pose = pose
+                    if self._map is not None:
+                        self._map.poses[len(self._keyframes) - 1] = pose
+            elif self._multiview:
                 depth, info, views, self.multiview_counts = self._track.multiview(**self._multiview_options)
+            if self._multiview:
                 torch.save(info[0].to("cpu"), os.path.join(self._base, "depth_info", name))
                 torch.save(views[0].to("cpu"), os.path.join(self._base, "depth_mv_views", name))
             torch.save(depth[0].to("cpu"), os.path.join(self._base, "depth", name))

@@ -319,6 +319,113 @@ def multiview_depth(acc_bank, alive_bank, poses, slots, calib, depth_init=None, 
     return depth, info, views, counts
 
 
+def bundle_sums(S):
+    """The number of float64 sums `bundle_terms` returns per problem of S listed views: with n = 6 S, the n (n + 1) / 2 entries of
+    T0, the n of v0, 27 per view (H_s, g_s) and the cost (include/atdn_hip.h, atdn_bundle_adjust)."""
+    n = 6 * int(S)
+    return n * (n + 1) // 2 + n + 27 * int(S) + 1
+
+
+def _bundle_inputs(acc_bank, alive_bank, poses, slots, calib, depth_init, mask, stride, min_views):
+    from .depth import intrinsics
+    if not isinstance(acc_bank, torch.Tensor) or acc_bank.dim() != 4 or acc_bank.shape[1] != 2:
+        raise RuntimeError("expected a flow bank [N,2,H,W], got %s" % (tuple(getattr(acc_bank, "shape", ())),))
+    if acc_bank.dtype != torch.float32 or not acc_bank.is_contiguous():
+        acc_bank = acc_bank.detach().float().contiguous()
+    N, _, H, W = (int(v) for v in acc_bank.shape)
+    device = acc_bank.device
+    if not isinstance(alive_bank, torch.Tensor) or alive_bank.device != device:
+        raise RuntimeError("flow bank on %s but the liveness bank on %s" % (device, getattr(alive_bank, "device", "the host")))
+    alive = _byte_plane(alive_bank, "a liveness bank", N, H, W)
+    if isinstance(poses, torch.Tensor) and poses.device != device:
+        raise RuntimeError("bank on %s but poses on %s" % (device, poses.device))
+    p = _pose_rows(torch.as_tensor(poses), N, device)
+    s = _index_tensor(slots, "slots", device)
+    s = s[None] if s.dim() == 1 else s
+    if s.dim() != 2 or s.shape[0] < 1 or s.shape[1] < 1:
+        raise RuntimeError("expected slots [B,S], got %s" % (tuple(s.shape),))
+    B, S = int(s.shape[0]), int(s.shape[1])
+    if not isinstance(depth_init, torch.Tensor):
+        raise RuntimeError("bundle adjustment needs an initial depth [B,1,H,W] (a tensor on the bank's device)")
+    if depth_init.device != device:
+        raise RuntimeError("bank on %s but depth_init on %s" % (device, depth_init.device))
+    if depth_init.numel() != B * H * W or tuple(depth_init.shape[-2:]) != (H, W):
+        raise RuntimeError("expected depth_init [%d,1,%d,%d], got %s" % (B, H, W, tuple(depth_init.shape)))
+    z0 = depth_init.detach().float().contiguous()
+    m = None
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.device != device:
+            raise RuntimeError("bank on %s but mask on %s" % (device, getattr(mask, "device", "the host")))
+        m = _byte_plane(mask, "a mask", B, H, W)
+    if int(stride) < 1:
+        raise RuntimeError("stride must be >= 1, got %r" % (stride,))
+    fx, fy, cx, cy = intrinsics(calib)
+    ptrs = (C.c_void_p(acc_bank.data_ptr()), C.c_void_p(alive.data_ptr()), C.c_void_p(p.data_ptr()), C.c_void_p(s.data_ptr()),
+            C.c_void_p(z0.data_ptr()), C.c_void_p(m.data_ptr()) if m is not None else None, N, B, S, H, W, fx, fy, cx, cy, int(stride))
+    return ptrs, (acc_bank, alive, p, s, z0, m), device, B, S, H, W
+
+
+def _bundle_workspace(L, device, B, S, H, W, stride):
+    nbytes = int(L.atdn_bundle_workspace_bytes(B, S, H, W, int(stride)))
+    if nbytes <= 0:
+        raise RuntimeError("bundle adjustment: batch, view count or image size out of range")
+    return torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=device)
+
+
+def bundle_terms(acc_bank, alive_bank, poses, slots, calib, depth, mask=None, stride=2, scale_px=4.0, inlier_px=2.0, min_z=0.1,
+                 min_views=2):
+    """One evaluation of the windowed bundle adjustment at the given poses and depth: the sums of the reduced normal equations
+    and the cost, for scoring a window without solving it. Arguments as for `bundle_adjust`. Returns `(sums, counts)` on the
+    bank's device: `sums` float64 [B, bundle_sums(S)] in the layout of include/atdn_hip.h (T0, v0, per view H_s and g_s, and last
+    the cost), `counts` int32 [B,3] = (candidates, observations in front of their camera, those within `inlier_px`)."""
+    ptrs, keep, device, B, S, H, W = _bundle_inputs(acc_bank, alive_bank, poses, slots, calib, depth, mask, stride, min_views)
+    sums = torch.empty((B, bundle_sums(S)), dtype=torch.float64, device=device)
+    counts = torch.empty((B, 3), dtype=torch.int32, device=device)
+    L = _lib.lib()
+    args = ptrs + (float(scale_px), float(inlier_px), float(min_z), int(min_views), C.c_void_p(sums.data_ptr()),
+                   C.c_void_p(counts.data_ptr()))
+    if device.type == "cuda":
+        with torch.cuda.device(device):
+            ws = _bundle_workspace(L, device, B, S, H, W, stride)
+            _lib.check(L.atdn_bundle_terms(*args, C.c_void_p(ws.data_ptr()), _stream()))
+    else:
+        _lib.check(L.atdn_bundle_terms_host(*args))
+    return sums, counts
+
+
+def bundle_adjust(acc_bank, alive_bank, poses, slots, calib, depth_init, mask=None, stride=2, iters=8, scale_px=4.0, inlier_px=2.0,
+                  min_z=0.1, min_views=2):
+    """Windowed dense bundle adjustment of an anchor frame's flow bank: the poses of the listed views and the inverse depths of
+    the anchor's pixels, refined jointly by `iters` Levenberg-Marquardt steps on the robust (Geman-McClure, `scale_px`)
+    reprojection error of every correspondence, the depths eliminated by the Schur complement. `acc_bank`, `alive_bank`, `poses`,
+    `slots` and `calib` as for `multiview_depth` (the anchor's own pose is the frame of reference and is not refined); `depth_init`
+    [B,1,H,W] float32 is mandatory; `mask` [B,H,W] (uint8 or bool) removes the pixels where it is 0. A pixel is a candidate when it
+    lies on the grid of `stride`, the mask allows it, it has an initial depth and at least `min_views` listed views observe it.
+    Scale is unobservable: the largest coordinate of the last listed view's translation (in that camera's frame) is held at its
+    initial value. Returns `(poses, depth, cost, counts)` on the bank's device: `poses` float32 [B,S,12] in the convention of the
+    input (an empty slot is all zeros; the inputs' rows if no step was accepted), `depth` float32 [B,1,H,W], the refined depth at
+    the candidates and 0 elsewhere, `cost` float64 [B,2] = (initial, final), `counts` int32 [B,4] = (candidates, observations in
+    front of their camera at the final state, those within `inlier_px`, accepted steps). Device tensors go through libatdn_hip's
+    kernels on the current stream (2 (iters + 1) launches, no synchronisation); CPU tensors go through the library's host form.
+    The rule is float64 and stated in full in include/atdn_hip.h, atdn_bundle_adjust; the same inputs give the same bits on every
+    call and on both paths."""
+    ptrs, keep, device, B, S, H, W = _bundle_inputs(acc_bank, alive_bank, poses, slots, calib, depth_init, mask, stride, min_views)
+    poses_out = torch.empty((B, S, 12), dtype=torch.float32, device=device)
+    depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=device)
+    cost = torch.empty((B, 2), dtype=torch.float64, device=device)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=device)
+    L = _lib.lib()
+    args = ptrs + (int(iters), float(scale_px), float(inlier_px), float(min_z), int(min_views), C.c_void_p(poses_out.data_ptr()),
+                   C.c_void_p(depth.data_ptr()), C.c_void_p(cost.data_ptr()), C.c_void_p(counts.data_ptr()))
+    if device.type == "cuda":
+        with torch.cuda.device(device):
+            ws = _bundle_workspace(L, device, B, S, H, W, stride)
+            _lib.check(L.atdn_bundle_adjust(*args, C.c_void_p(ws.data_ptr()), _stream()))
+    else:
+        _lib.check(L.atdn_bundle_adjust_host(*args))
+    return poses_out, depth, cost, counts
+
+
 def epipolar_score(counts):
     """float32 inliers / inside of the `counts` [B,3] (or [3]) of `two_view_depth`, 0 where no correspondence is inside: the
     share of the flow's correspondences that lie within `max_epipolar` pixels of the epipolar line the pose gives them. Exact

@@ -606,6 +606,79 @@ int atdn_multiview_depth_host(const float* acc_bank, const unsigned char* alive_
                               double scale_px, double inlier_px, double min_z, int min_views, double max_rel_sigma, double max_depth,
                               int iters, float* depth, float* info, unsigned char* views, int* counts);
 
+/* Windowed dense bundle adjustment over the same banks: the joint Levenberg-Marquardt refinement of the poses of the listed views
+ * and of the inverse depths of the anchor's candidate pixels, the depths eliminated by the Schur complement. The anchor's own pose
+ * is the frame of reference and is not refined; there are no priors. atdn_bundle_terms is one evaluation (all sums of the reduced
+ * normal equations at the given poses and depth, for scoring), atdn_bundle_adjust the solver.
+ *   acc_bank, alive_bank, poses, slots: as for atdn_multiview_depth. depth_init [B,1,H,W] fp32 DEVICE, mandatory. mask [B,H,W]
+ *   uint8 DEVICE or NULL (non-zero = allowed). stride >= 1, 0 <= iters <= 16, the other limits those of atdn_multiview_depth.
+ *   poses_out [B,S,12] fp32 (the public convention; an empty slot is all zeros), depth [B,1,H,W] fp32 (the refined depth at the
+ *   candidates, 0 elsewhere, fully written), cost [B,2] fp64 (initial, final), counts [B,4] int32 = (candidates; observations in
+ *   front of their camera at the final state; those within inlier_px; accepted steps); sums [B, NS] fp64 and counts [B,3] for
+ *   atdn_bundle_terms. workspace: atdn_bundle_workspace_bytes(B, S, H, W, stride) bytes DEVICE, 8-byte aligned, an output like the
+ *   others; nothing in it is read before this call has written it. Only mask may be NULL; anything else fails before a launch.
+ * The rule, everything in float64 and every operation rounded on its own, only + - * / and comparisons, in exactly this order.
+ * Constants c2, thr, rho_behind and the internal pose (Rc, tc) of a listed view: those of atdn_multiview_depth.
+ * Positions: Hs = ceil(H/stride), Ws = ceil(W/stride); position q = ys*Ws + xs is pixel (x, y) = (xs*stride, ys*stride).
+ * Candidates, fixed for the whole solve: the mask allows the pixel, 0 < depth_init <= FLT_MAX, and obs (atdn_multiview_depth) holds
+ * in at least min_views listed views. rho = 1/depth_init at the start. a0 = (x - cx)/fx, a1 = (y - cy)/fy.
+ * One obs view of a candidate at (Rc, tc, rho):
+ *   m_i = (rc_i0*a0 + rc_i1*a1) + rc_i2,  P_i = m_i + rho*tc_i
+ *   front = P_2 >= min_z*rho                   not front: the view costs rho_behind and every term below is +0.0
+ *   iz = 1/P_2,  px = (fx*P_0)*iz,  py = (fy*P_1)*iz,  rx = (px + cx) - x2,  ry = (py + cy) - y2,  e2 = rx*rx + ry*ry
+ *   s = 1 + e2/c2,  w = 1/(s*s),  cost = (0.5*e2)/s
+ *   ax = fx*iz, ay = fy*iz, bx = -(px*iz), by = -(py*iz)                      (A = [[ax, 0, bx], [0, ay, by]])
+ *   Jx = (bx*m_1, ax*m_2 - bx*m_0, -(ax*m_1), rho*ax, 0, rho*bx)               (-A [m]x and rho A)
+ *   Jy = (by*m_1 - ay*m_2, -(by*m_0), ay*m_0, 0, rho*ay, rho*by)
+ *   jrx = ax*tc_0 + bx*tc_2,  jry = ay*tc_1 + by*tc_2                         (A tc)
+ *   H_ij = (w*Jx_i)*Jx_j + (w*Jy_i)*Jy_j (i <= j),  g_i = (w*Jx_i)*rx + (w*Jy_i)*ry,  E_i = (w*Jx_i)*jrx + (w*Jy_i)*jry
+ *   c_s = (w*jrx)*jrx + (w*jry)*jry,  b_s = (w*jrx)*rx + (w*jry)*ry;  inlier = e2 <= thr
+ * Per candidate c, b and cost are the sums of c_s, b_s and the views' costs over its obs views in list order, from +0.0; E is the
+ * concatenation of the E of the views (+0.0 for the others), n = 6 S values; ic = 1/c, bc = b*ic.
+ * Sums over candidates, NS = n(n+1)/2 + n + 27 S + 1 values in this layout: T0 (upper triangle row by row), entry (i, j) takes
+ * (E_i*ic)*E_j; v0, entry i takes E_i*bc; per view the 21 H_ij row by row and the 6 g_i; the cost. A candidate whose c is not > 0
+ * gives its cost only. Order: the positions are cut into chunks of 512 consecutive q; every sum of a chunk starts at +0.0 and
+ * takes the chunk's candidates in ascending q; the chunk sums are added in chunk order from +0.0. atdn_bundle_terms returns these
+ * sums and counts = (candidates, front observations, inliers).
+ * Gauge (scale is unobservable): g = the last non-empty listed view, j = the index of its largest |tc_j| at the start, the lowest
+ * on a tie; unknown 6 g + 3 + j is held, and so are the six unknowns of every empty slot. If that |tc_j| is 0 (or no view is
+ * listed) no step is taken: the outputs are the inputs and no step is accepted.
+ * Step from the accepted sums with damping lambda, opl = 1 + lambda; H and g are zero between different views:
+ *   S_ij = H_ij - T0_ij/opl (i < j),  S_ii = (H_ii + lambda*H_ii) - T0_ii/opl,  rhs_i = -(g_i - v0_i/opl)
+ *   a held unknown: its row and column +0.0, its diagonal 1, its rhs +0.0
+ *   S = L D L^T without pivoting, column j = 0 .. n-1: d_j = S_jj - sum_k L_jk*(L_jk*d_k) and, for i > j,
+ *   L_ij = (S_ij - sum_k L_ik*(L_jk*d_k)) / d_j, each sum subtracted term by term in ascending k < j; forward, diagonal and backward
+ *   solve as in atdn_pnp_solve with 6 replaced by n. A pivot not > 0 or a step that is not finite: no step, the trial is the
+ *   accepted state again (and is rejected, its cost being no smaller).
+ *   trial poses: Rc' = C(dw) Rc, tc' = tc + dt per non-empty view (C: the Cayley matrix of atdn_pnp_solve; tc is NOT rotated)
+ *   trial depth per candidate, from c, b, E at the ACCEPTED state: e = sum over its obs views in list order, from +0.0, of
+ *   ((((E_0*d_0 + E_1*d_1) + E_2*d_2) + E_3*d_3) + E_4*d_4) + E_5*d_5 with that view's six step entries;
+ *   rho' = rho - (b + e)/(c*opl); rho' not in (0, DBL_MAX] or c not > 0: rho' = rho.
+ * Decision and lambda: those of atdn_pnp_solve — evaluation 0 is accepted with lambda = 1e-3, a later one iff its cost is smaller;
+ * T0 and v0 do not depend on lambda, so a rejected step needs no new sums. After `iters` steps: poses_out = the inputs' rows if
+ * no step was accepted, otherwise the accepted poses in the public convention rounded to float32; depth = (float)(1/rho).
+ * 2 (iters + 1) launches on `stream`: asynchronous, capturable, no host synchronisation, no atomics, no memset: the same bits on
+ * every call. */
+long atdn_bundle_workspace_bytes(int B, int S, int H, int W, int stride);   /* 0: arguments out of range */
+int atdn_bundle_terms(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
+                      const float* depth, const unsigned char* mask, int N, int B, int S, int H, int W, double fx, double fy,
+                      double cx, double cy, int stride, double scale_px, double inlier_px, double min_z, int min_views, double* sums,
+                      int* counts, void* workspace, void* stream);
+int atdn_bundle_adjust(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
+                       const float* depth_init, const unsigned char* mask, int N, int B, int S, int H, int W, double fx, double fy,
+                       double cx, double cy, int stride, int iters, double scale_px, double inlier_px, double min_z, int min_views,
+                       float* poses_out, float* depth, double* cost, int* counts, void* workspace, void* stream);
+/* The same functions on HOST buffers in plain C++ float64 (csrc/bundle_host.h, whose functions the kernels call too): serve CPU
+ * tensors, need no GPU and no workspace, the same bits and the same argument rules. */
+int atdn_bundle_terms_host(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
+                           const float* depth, const unsigned char* mask, int N, int B, int S, int H, int W, double fx, double fy,
+                           double cx, double cy, int stride, double scale_px, double inlier_px, double min_z, int min_views,
+                           double* sums, int* counts);
+int atdn_bundle_adjust_host(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
+                            const float* depth_init, const unsigned char* mask, int N, int B, int S, int H, int W, double fx,
+                            double fy, double cx, double cy, int stride, int iters, double scale_px, double inlier_px, double min_z,
+                            int min_views, float* poses_out, float* depth, double* cost, int* counts);
+
 /* ---------------------------------------------------------------------------------------------------
  * Pose from depth and flow (robust PnP)  —  a depth map of image 1 gives a 3-D point per pixel, the flow image 1 -> image 2 gives
  * that point's pixel in image 2: the pose that explains the correspondences, by Levenberg-Marquardt on the reprojection error
