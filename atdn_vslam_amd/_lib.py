@@ -121,6 +121,13 @@ SIGNATURES = {
                                       C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "atdn_epipolar_solve_host": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                                            C.c_double, C.c_double, C.c_int, _vp, _vp, _vp]),
+    "atdn_ground_workspace_bytes": (C.c_long, [C.c_int, C.c_int, C.c_int]),
+    "atdn_ground_terms": (C.c_int, [_vp] * 3 + [C.c_int] * 5 + [C.c_double] * 8 + [_vp] * 4),
+    "atdn_ground_terms_host": (C.c_int, [_vp] * 3 + [C.c_int] * 5 + [C.c_double] * 8 + [_vp] * 2),
+    "atdn_ground_solve": (C.c_int, [_vp] * 3 + [C.c_int] * 5 + [C.c_double] * 11 + [C.c_int] * 2 + [_vp] * 5),
+    "atdn_ground_solve_host": (C.c_int, [_vp] * 3 + [C.c_int] * 5 + [C.c_double] * 11 + [C.c_int] * 2 + [_vp] * 3),
+    "atdn_ground_classify": (C.c_int, [_vp] * 3 + [C.c_int] * 5 + [C.c_double] * 7 + [_vp] * 3),
+    "atdn_ground_classify_host": (C.c_int, [_vp] * 3 + [C.c_int] * 5 + [C.c_double] * 7 + [_vp] * 2),
     "atdn_pose_graph_workspace_bytes": (C.c_long, [C.c_int, C.c_int, C.c_int]),
     "atdn_pose_graph_terms": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "atdn_pose_graph_terms_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp]),

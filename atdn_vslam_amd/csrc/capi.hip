@@ -18,6 +18,7 @@
 #include "flow_consistency_host.h"
 #include "flow_track_host.h"
 #include "bundle_host.h"
+#include "ground_host.h"
 #include "multiview_depth_host.h"
 #include "pnp_host.h"
 #include "two_view_host.h"
@@ -516,6 +517,51 @@ int atdn_pnp_solve_host(const float* depth, const float* flow, const unsigned ch
   ATDN_CHECK(iters >= 0 && iters <= 64, "iters must be in [0, 64]");
   pnp_solve_host(depth, flow, mask, pose_init, B, H, W, pnp_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, H, W), iters,
                  pose_out, cost, counts);
+  ATDN_API_END
+}
+
+// ------------------------------------------------------------------ ground plane of a depth map (host twins of ground.hip)
+int atdn_ground_terms_host(const float* depth, const unsigned char* mask, const double* q, int B, int H, int W, int y0, int y1,
+                           double fx, double fy, double cx, double cy, double scale_rel, double inlier_rel, double min_z,
+                           double max_depth, double* sums, int* counts) {
+  ATDN_API_BEGIN
+  const void* out[2] = {sums, counts};
+  const long out_bytes[2] = {(long)B * GROUND_TERMS * 8, (long)B * 12};
+  ground_check_args(depth, mask, q, false, B, H, W, y0, y1, fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth, false, out,
+                    out_bytes, 2);
+  ground_terms_host(depth, mask, q, B, H, W, y1,
+                    ground_params(fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth, 0.0, 1.0, 0.0, 1, y0, W), sums, counts);
+  ATDN_API_END
+}
+
+int atdn_ground_solve_host(const float* depth, const unsigned char* mask, const double* q_init, int B, int H, int W, int y0, int y1,
+                           double fx, double fy, double cx, double cy, double nx, double ny, double nz, double scale_rel,
+                           double inlier_rel, double min_z, double max_depth, int min_votes, int iters, double* q, double* sums,
+                           int* counts) {
+  ATDN_API_BEGIN
+  const void* out[3] = {q, sums, counts};
+  const long out_bytes[3] = {(long)B * 24, (long)B * GROUND_TERMS * 8, (long)B * 24};
+  ground_check_args(depth, mask, q_init, true, B, H, W, y0, y1, fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth, false, out,
+                    out_bytes, 3);
+  ground_check_solve(nx, ny, nz, min_votes, iters);
+  ground_solve_host(depth, mask, q_init, B, H, W, y1,
+                    ground_params(fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth, nx, ny, nz, min_votes, y0, W), iters, q,
+                    sums, counts);
+  ATDN_API_END
+}
+
+int atdn_ground_classify_host(const float* depth, const unsigned char* mask, const double* q, int B, int H, int W, int y0, int y1,
+                              double fx, double fy, double cx, double cy, double inlier_rel, double min_z, double max_depth,
+                              float* residual, unsigned char* on_ground) {
+  ATDN_API_BEGIN
+  const long n = (long)H * W;
+  const void* out[2] = {residual, on_ground};
+  const long out_bytes[2] = {(long)B * n * 4, (long)B * n};
+  ground_check_args(depth, mask, q, false, B, H, W, y0, y1, fx, fy, cx, cy, 1.0, inlier_rel, min_z, max_depth, false, out, out_bytes,
+                    2);
+  ground_classify_host(depth, mask, q, B, H, W, y1,
+                       ground_params(fx, fy, cx, cy, 1.0, inlier_rel, min_z, max_depth, 0.0, 1.0, 0.0, 1, y0, W), residual,
+                       on_ground);
   ATDN_API_END
 }
 

@@ -1,4 +1,4 @@
-// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip, epipolar.hip, depth_fusion.hip, multiview_depth.hip, bundle.hip), shared by each device
+// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip, epipolar.hip, depth_fusion.hip, multiview_depth.hip, bundle.hip, ground.hip), shared by each device
 // entry point and its host twin in capi.hip, and the overlap rule that the pose solvers (pnp.hip, pose_graph.hip) share.
 #pragma once
 #include <cmath>
@@ -63,6 +63,11 @@ void pnp_check_args(const float* depth, const float* flow, const unsigned char* 
 void epipolar_check_args(const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W, double fx, double fy,
                          double cx, double cy, double scale_px, double inlier_px, bool grid_limit, const void* const* out,
                          const long* out_bytes, int n_out);
+// the ground plane (ground.hip): mask may be null, q only where q_optional; out as for pnp_check_args
+void ground_check_args(const float* depth, const unsigned char* mask, const double* q, bool q_optional, int B, int H, int W, int y0,
+                       int y1, double fx, double fy, double cx, double cy, double scale_rel, double inlier_rel, double min_z,
+                       double max_depth, bool grid_limit, const void* const* out, const long* out_bytes, int n_out);
+void ground_check_solve(double nx, double ny, double nz, int min_votes, int iters);
 // sources may be null only when S == 0
 void depth_fuse_check_args(const float* bank, const float* poses, const int* targets, const int* sources, int N, int B, int S,
                            int H, int W, double fx, double fy, double cx, double cy, double max_reproj, double max_rel_depth,

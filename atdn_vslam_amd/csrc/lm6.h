@@ -8,6 +8,7 @@
 //                each sum subtracted term by term in ascending k
 //   cayley3      the rotation (I - K)^-1 (I + K) of the step w, K = [w / 2]x: with h = w / 2, n2 = (h0^2 + h1^2) + h2^2 and
 //                f = 2 / (1 + n2): C_ii = 1 + f (h_i^2 - n2), C_ij = f (K_ij + h_i h_j); orthogonal for every w, no trigonometry
+//   ldl3_factor / ldl3_solve   the same two recurrences for a 3 x 3 system (the ground plane's step, ground_host.h)
 //   lm_lambda    the damping after a decision: / 3 and not below 1e-9 on acceptance, * 4 and not above 1e6 on rejection
 // On which side a solver multiplies the Cayley matrix onto its pose is the solver's own business (PnP: from the left, the pose
 // graph: from the right). The bits of kernel, host form and NumPy restatement agree because this order is written once, here.
@@ -92,6 +93,79 @@ ATDN_HD inline void ldl6_solve(const double* F, const double* b, double* x) {
   }
 #pragma unroll
   for (int i = 0; i < 6; ++i) x[i] = y[i];
+}
+
+// The same factorisation and solve for a 3 x 3 system (the ground plane's step, ground_host.h): the recurrences of ldl6_factor /
+// ldl6_solve with 6 replaced by 3. A: flat row-major, diagonal and lower triangle read. F: L rows 1 .. 2 (3 values, row i at
+// i (i - 1) / 2), then the 3 pivots.
+ATDN_HD inline bool ldl3_factor(const double* A, double* F) {
+#pragma clang fp contract(off)
+  double L[3][3], D[3];
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    double dj = A[4 * j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) {
+      const double ld = L[j][k] * D[k];
+      const double lld = L[j][k] * ld;
+      dj = dj - lld;
+    }
+    ok = ok && dj > 0.0;
+    D[j] = dj;
+#pragma unroll
+    for (int i = j + 1; i < 3; ++i) {
+      double l = A[3 * i + j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) {
+        const double ld = L[j][k] * D[k];
+        const double lld = L[i][k] * ld;
+        l = l - lld;
+      }
+      L[i][j] = l / dj;
+    }
+  }
+  F[0] = L[1][0]; F[1] = L[2][0]; F[2] = L[2][1];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) F[3 + i] = D[i];
+  return ok;
+}
+
+// x = A^-1 b for the factor F (ldl3_factor) of A; x may be b.
+ATDN_HD inline void ldl3_solve(const double* F, const double* b, double* x) {
+#pragma clang fp contract(off)
+  double y[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    double v = b[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) {
+      const double ly = F[i * (i - 1) / 2 + k] * y[k];
+      v = v - ly;
+    }
+    y[i] = v;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) y[i] = y[i] / F[3 + i];
+#pragma unroll
+  for (int i = 2; i >= 0; --i) {
+    double v = y[i];
+#pragma unroll
+    for (int k = i + 1; k < 3; ++k) {
+      const double ly = F[k * (k - 1) / 2 + i] * y[k];
+      v = v - ly;
+    }
+    y[i] = v;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) x[i] = y[i];
+}
+
+ATDN_HD inline bool finite3(const double* v) {
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) ok = ok && v[k] >= -DBL_MAX && v[k] <= DBL_MAX;
+  return ok;
 }
 
 // C (3 x 3, row-major) = the Cayley matrix of the rotation step w[0..2]

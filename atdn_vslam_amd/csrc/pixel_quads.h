@@ -33,14 +33,17 @@ struct Quad {
   __device__ __forceinline__ bool has(int k) const { return s0 + k >= lo && s0 + k < hi; }
 };
 
-__device__ __forceinline__ Quad quad_of(int n, int off) {
+// the quad of this thread in workgroup `block` of the plane (a kernel whose workgroups walk several: ground.hip's vote)
+__device__ __forceinline__ Quad quad_at(int n, int off, unsigned block) {
   Quad q;
-  q.s0 = 4 * (int)(blockIdx.x * PQ_THREADS + threadIdx.x) - off;
+  q.s0 = 4 * (int)(block * PQ_THREADS + threadIdx.x) - off;
   q.lo = q.s0 > 0 ? q.s0 : 0;
   q.hi = q.s0 + 4 < n ? q.s0 + 4 : n;
   q.full = q.hi - q.lo == 4;
   return q;
 }
+
+__device__ __forceinline__ Quad quad_of(int n, int off) { return quad_at(n, off, blockIdx.x); }
 
 // v = p[s0 .. s0 + 3]; outside [lo, hi) zeros, and nothing is read there
 __device__ __forceinline__ void quad_load(const Quad& q, const float* p, float v[4]) {

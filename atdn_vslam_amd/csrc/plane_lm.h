@@ -10,6 +10,8 @@
 //   decision     evaluation 0 always becomes the accepted point, with lambda = 1e-3; evaluation k >= 1 is accepted iff its cost is
 //                below the accepted one (a NaN fails); lambda by lm_lambda of lm6.h.
 // The kernels (plane_sum.h) walk the same tree, so kernel, host form and NumPy restatement give the same bits.
+// The plane sum takes the number of terms as a template parameter (28 unless given): the ground plane (ground_host.h) sums its 10
+// terms over the same chunks, 4-sums, tree and chunk order.
 #pragma once
 #include <vector>
 
@@ -49,26 +51,28 @@ ATDN_HD inline void plane_lm_update(PlaneLmState& s, const double* sums, const i
   }
 }
 
-// The sums of one plane of n flat indices: pixel(i, t) writes the 28 terms of index i < n and returns its flag bits.
-template <class Pixel>
-inline void plane_sum_host(long n, Pixel pixel, double sums[PLANE_TERMS], int counts[3]) {
+// The sums of one plane of n flat indices: pixel(i, t) writes the TERMS terms of index i < n and returns its flag bits. TERMS is
+// 28 for the two pose solvers and 10 for the ground plane (ground_host.h): the chunks, the 4-sum, the tree and the chunk order
+// do not depend on it.
+template <int TERMS = PLANE_TERMS, class Pixel>
+inline void plane_sum_host(long n, Pixel pixel, double* sums, int counts[3]) {
 #pragma clang fp contract(off)
   const long chunks = (n + PLANE_CHUNK - 1) / PLANE_CHUNK;
-  std::vector<double> v((size_t)PLANE_CHUNK_THREADS * PLANE_TERMS);
-  double t[PLANE_TERMS];
+  std::vector<double> v((size_t)PLANE_CHUNK_THREADS * TERMS);
+  double t[TERMS];
   counts[0] = counts[1] = counts[2] = 0;
   for (long ch = 0; ch < chunks; ++ch) {
     for (int j = 0; j < PLANE_CHUNK_THREADS; ++j) {
-      double* a = &v[(size_t)j * PLANE_TERMS];
+      double* a = &v[(size_t)j * TERMS];
       for (int k = 0; k < 4; ++k) {
         const long i = ch * PLANE_CHUNK + 4 * j + k;
         int flags = 0;
         if (i < n) {
           flags = pixel(i, t);
         } else {
-          for (int e = 0; e < PLANE_TERMS; ++e) t[e] = 0.0;
+          for (int e = 0; e < TERMS; ++e) t[e] = 0.0;
         }
-        for (int e = 0; e < PLANE_TERMS; ++e) a[e] = k == 0 ? t[e] : a[e] + t[e];
+        for (int e = 0; e < TERMS; ++e) a[e] = k == 0 ? t[e] : a[e] + t[e];
         counts[0] += (flags & 1) ? 1 : 0;
         counts[1] += (flags & 2) ? 1 : 0;
         counts[2] += (flags & 4) ? 1 : 0;
@@ -76,9 +80,9 @@ inline void plane_sum_host(long n, Pixel pixel, double sums[PLANE_TERMS], int co
     }
     for (int stride = 1; stride < PLANE_CHUNK_THREADS; stride *= 2)
       for (int i = 0; i < PLANE_CHUNK_THREADS; i += 2 * stride)
-        for (int e = 0; e < PLANE_TERMS; ++e)
-          v[(size_t)i * PLANE_TERMS + e] = v[(size_t)i * PLANE_TERMS + e] + v[(size_t)(i + stride) * PLANE_TERMS + e];
-    for (int e = 0; e < PLANE_TERMS; ++e) sums[e] = ch == 0 ? v[e] : sums[e] + v[e];
+        for (int e = 0; e < TERMS; ++e)
+          v[(size_t)i * TERMS + e] = v[(size_t)i * TERMS + e] + v[(size_t)(i + stride) * TERMS + e];
+    for (int e = 0; e < TERMS; ++e) sums[e] = ch == 0 ? v[e] : sums[e] + v[e];
   }
 }
 

@@ -3,6 +3,8 @@
 // slots of a plane. The terms kernels run (chunks, B) workgroups of pixel_quads.h with off = 0 — workgroup c of plane b owns the
 // flat indices 1024 c .. 1024 c + 1023, a thread four consecutive ones —; the finalise kernels one wave per problem. No memset
 // and no atomics: every workgroup writes its own slot (store-and-sum: cdna_hip_programming.md, Guideline 12).
+// The tree and the ordered sum take the number of terms as a template parameter (28 unless given): ground.hip walks the same
+// tree over its 10 terms, with a workspace of its own.
 #pragma once
 #include "pixel_quads.h"
 #include "plane_lm.h"
@@ -36,56 +38,60 @@ inline PlaneWorkspace plane_carve(void* workspace, int B, int H, int W) {
   return ws;
 }
 
-// acc: the thread's 28 sums; cnt: the WAVE's three counts, in every lane. Every thread of workgroup (blockIdx.x, b) calls it, once.
-__device__ __forceinline__ void plane_chunk_reduce(double acc[PLANE_TERMS], const int cnt[3], int b, double* __restrict__ csums,
+// acc: the thread's TERMS sums (28 for the pose solvers, 10 for the ground plane: the tree does not depend on it); cnt: the WAVE's
+// three counts, in every lane. Every thread of workgroup (blockIdx.x, b) calls it, once.
+template <int TERMS = PLANE_TERMS>
+__device__ __forceinline__ void plane_chunk_reduce(double* acc, const int cnt[3], int b, double* __restrict__ csums,
                                                    int* __restrict__ ccounts) {
 #pragma clang fp contract(off)
-  __shared__ double part[PQ_WAVES][PLANE_TERMS];
+  static_assert(TERMS <= 32, "threads 32 .. 34 carry the counts");
+  __shared__ double part[PQ_WAVES][TERMS];
   __shared__ int ipart[PQ_WAVES][3];
   // strides 1 .. 32 inside the wave: lane i (a multiple of 2 * stride) takes v[i] + v[i + stride]; the other lanes hold values
   // that nobody reads
 #pragma unroll
-  for (int e = 0; e < PLANE_TERMS; ++e) {
+  for (int e = 0; e < TERMS; ++e) {
 #pragma unroll
     for (int stride = 1; stride < 64; stride *= 2) acc[e] = acc[e] + __shfl_down(acc[e], stride, 64);
   }
   const int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
-    for (int e = 0; e < PLANE_TERMS; ++e) part[wave][e] = acc[e];
+    for (int e = 0; e < TERMS; ++e) part[wave][e] = acc[e];
 #pragma unroll
     for (int j = 0; j < 3; ++j) ipart[wave][j] = cnt[j];
   }
   __syncthreads();
   const long slot = (long)b * gridDim.x + blockIdx.x;
-  if (threadIdx.x < PLANE_TERMS) {
+  if (threadIdx.x < TERMS) {
     const int e = threadIdx.x;
     const double lo = part[0][e] + part[1][e], hi = part[2][e] + part[3][e];     // strides 64 and 128
-    csums[slot * PLANE_TERMS + e] = lo + hi;
+    csums[slot * TERMS + e] = lo + hi;
   } else if (threadIdx.x >= 32 && threadIdx.x < 35) {
     const int j = threadIdx.x - 32;
     ccounts[slot * 4 + j] = (ipart[0][j] + ipart[1][j]) + (ipart[2][j] + ipart[3][j]);
   }
 }
 
-// One wave per problem b: thread e < 28 adds the chunk sums of term e in chunk order (coalesced: the 28 terms of a chunk are
+// One wave per problem b: thread e < TERMS adds the chunk sums of term e in chunk order (coalesced: the terms of a chunk are
 // contiguous), threads 32 .. 34 the integer counts; after the barrier inside, S and Cn (in LDS) hold the plane's.
+template <int TERMS = PLANE_TERMS>
 __device__ __forceinline__ void plane_ordered_sum(const double* __restrict__ csums, const int* __restrict__ ccounts, int chunks,
                                                   int b, double* S, int* Cn) {
 #pragma clang fp contract(off)
   const int t = threadIdx.x;
-  if (t < PLANE_TERMS) {
-    const double* p = csums + (long)b * chunks * PLANE_TERMS + t;
+  if (t < TERMS) {
+    const double* p = csums + (long)b * chunks * TERMS + t;
     double s = p[0];
     int ch = 1;
     for (; ch + 8 <= chunks; ch += 8) {                        // eight loads in flight, the adds in chunk order
       double v[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = p[(long)(ch + i) * PLANE_TERMS];
+      for (int i = 0; i < 8; ++i) v[i] = p[(long)(ch + i) * TERMS];
 #pragma unroll
       for (int i = 0; i < 8; ++i) s = s + v[i];
     }
-    for (; ch < chunks; ++ch) s = s + p[(long)ch * PLANE_TERMS];
+    for (; ch < chunks; ++ch) s = s + p[(long)ch * TERMS];
     S[t] = s;
   } else if (t >= 32 && t < 35) {
     const int* p = ccounts + (long)b * chunks * 4 + (t - 32);

@@ -8,6 +8,8 @@
 * `relative_motions`, `reverse_backward_run`, `motion_std`, `kalman_fuse`, `fuse_forward_backward` are the
   forward/backward trajectory fusion of eval/kalman.py (45-88, 91-128): per-axis inverse-variance weighting of the
   relative motions of a forward and a time-reversed run, re-integrated with rel2abs. All float64 on the host.
+* `rescale_intervals` multiplies the translation of every keyframe-to-keyframe motion by that interval's metric-scale
+  correction (NeuralSLAM(..., ground=True, camera_height=...): `poses_scaled.pth`) and chains the poses again.
 """
 import numpy as np
 
@@ -92,6 +94,27 @@ def relative_motions(poses):
         rot.append(_euler_yxz(d[:3, :3]))
         tr.append(d[:3, 3])
     return np.array(rot).reshape(-1, 3), np.array(tr).reshape(-1, 3)
+
+
+def rescale_intervals(poses, scales):
+    """Keyframe poses [K,3|4,4] (or rows [K,12]) with the translation of every relative motion keyframe i -> i+1 multiplied by
+    `scales[i]` (K - 1 values: the metric-scale corrections of the intervals, e.g. camera_height / fitted height of keyframe i's
+    depth), re-chained from the first pose. Returns float64 [K,4,4]. The relative motion is inverse(P_i) @ P_i+1 = [R_i^T R_i+1 |
+    R_i^T (t_i+1 - t_i)]; scaling its translation and chaining again leaves every rotation as it was and gives
+    t'_i+1 = t'_i + s_i (t_i+1 - t_i), written here as t'_k = t_k + sum_{i<k} (s_i - 1) (t_i+1 - t_i): scale 1 everywhere adds
+    exact zeros and returns the input's bits."""
+    p = _hom(poses).copy()
+    s = np.asarray(scales, dtype=np.float64).reshape(-1)
+    if len(s) != max(len(p) - 1, 0):
+        raise ValueError("expected %d scales for %d poses, got %d" % (max(len(p) - 1, 0), len(p), len(s)))
+    if not np.all(np.isfinite(s) & (s > 0)):
+        raise ValueError("scales must be finite and > 0")
+    t = p[:, :3, 3].copy()
+    shift = np.zeros(3)
+    for i in range(len(s)):
+        shift = shift + (s[i] - 1.0) * (t[i + 1] - t[i])
+        p[i + 1, :3, 3] = np.where(shift != 0.0, t[i + 1] + shift, t[i + 1])
+    return p
 
 
 def reverse_backward_run(poses):

@@ -110,6 +110,17 @@ class NeuralSLAM:
     so with the optimised poses — the keyframe depths are filtered against their neighbours (`fuse_depths`, `fuse_options` its
     keyword arguments): `depth_fused/%06d.pth`, `depth_views/%06d.pth` and `fusion_counts`; `keyframe_points(i, fused=True)` reads
     them. With False (the default) no file, directory or return value changes.
+    `ground=True` (needs `calib`): every keyframe depth — the one `keyframe_depth` selects, while it is still on the device — is
+    fitted with the road's plane (transforms.ground_plane; `ground_options` its keyword arguments, plus `min_inlier_share` and
+    `max_tilt_deg` of transforms.ground_accept). `ground/%06d.pth` holds a dict of `q`, `normal`, `height`, `sums`, `counts`
+    (host tensors), `accepted` (bool: ground_accept) and `scale` (float: `camera_height` / height when accepted and a
+    `camera_height`, in the units the trajectory should have, is given; 1.0 otherwise). The depth of a keyframe is triangulated
+    against the poses of its own interval, so `scale` is the correction of exactly that interval's translations. With a
+    `camera_height` and keyframe_depth "track", "multiview" or "bundle", `end_odometry()` also writes `poses_scaled.pth` [K,12]
+    float32 = evaluation.rescale_intervals(poses.pth, the scales of keyframes 0 .. K-2). With "pair" the depth carries the scale
+    of the keyframe's first pair only, not of the interval, and `poses_scaled.pth` is not written. Nothing is fed back: the
+    running pose, `poses.pth`, `poses_closed.pth`, the loop closure, the depth fusion and every other file are what they are
+    without it. With False (the default) no file, directory, attribute or bit changes.
     """
 
     FLOW_CHECKPOINT = "atdn_vslam/checkpoints/gma-kitti.pth"  # utils/gma_parameters.py
@@ -117,8 +128,20 @@ class NeuralSLAM:
     def __init__(self, args, odometry_weights=None, start_mode=None, flow_weights=None, mapping_weights=None,
                  precision=None, map_options=None, resident_map=False, warm_start=False, calib=None, keyframe_depth="pair",
                  loop_closure=False, loop_options=None, refine_pose=False, fuse_depth=False, fuse_options=None,
-                 multiview_options=None, bundle_options=None, bundle_pose=False):
+                 multiview_options=None, bundle_options=None, bundle_pose=False, ground=False, ground_options=None,
+                 camera_height=None):
         from .depth import intrinsics
+        if ground:
+            if calib is None:
+                raise ValueError("ground=True needs the calibration: pass calib=")
+            if camera_height is not None and not (math.isfinite(float(camera_height)) and float(camera_height) > 0.0):
+                raise ValueError("camera_height must be finite and > 0, got %r" % (camera_height,))
+            self._ground_options = dict(ground_options or {})
+            self._ground_accept = {k: self._ground_options.pop(k) for k in ("min_inlier_share", "max_tilt_deg")
+                                   if k in self._ground_options}
+            self._camera_height = None if camera_height is None else float(camera_height)
+            self._ground_scales = {}     # keyframe index -> scale of its interval
+        self._ground = bool(ground)
         if fuse_depth and (calib is None or not resident_map):
             raise ValueError("fuse_depth=True needs the calibration and the keyframe map in device memory: pass calib= and "
                              "resident_map=True")
@@ -202,6 +225,10 @@ class NeuralSLAM:
                     os.makedirs(os.path.join(self._base, sub), exist_ok=True)
                     for f in glob.glob(os.path.join(self._base, sub, "*")):
                         os.remove(f)
+            if self._ground:
+                os.makedirs(os.path.join(self._base, "ground"), exist_ok=True)
+                for f in glob.glob(os.path.join(self._base, "ground", "*")) + glob.glob(os.path.join(self._base, "poses_scaled.pth")):
+                    os.remove(f)
             # a cold start owns the directory: poses and map weights of an earlier session go too
             for stale in ("poses.pth", "poses_closed.pth", "MappingVAE_weights.pth"):
                 stale_path = os.path.join(self._base, stale)
@@ -227,6 +254,11 @@ class NeuralSLAM:
             self._flush_track()
             poses = torch.stack([kf.pose.flatten()[:12] for kf in self._keyframes], dim=0)
             torch.save(poses, os.path.join(self._base, "poses.pth"))
+            if self._ground and self._camera_height is not None and self._track_depth:
+                from .evaluation import rescale_intervals
+                scales = [self._ground_scales.get(i, 1.0) for i in range(len(self._keyframes) - 1)]
+                scaled = torch.from_numpy(rescale_intervals(poses.numpy(), scales)[:, :3, :].reshape(-1, 12)).float()
+                torch.save(scaled, os.path.join(self._base, "poses_scaled.pth"))
             self._mode = "mapping"
             default = os.path.join(self._base, "MappingVAE_weights.pth")
             if mapping_weights is None:
@@ -323,6 +355,8 @@ class NeuralSLAM:
                     # the previous frame is a keyframe: this pair's flow starts at its pixels, so the depth is the keyframe's
                     depth, _ = transforms.two_view_depth(flow, pred_mat[None].to(self._device), self._calib)
                     torch.save(depth[0].to("cpu"), os.path.join(self._base, "depth", "%06d.pth" % self._depth_pending))
+                    if self._ground:
+                        self._fit_ground(self._depth_pending, depth)
                     if self._map is not None:
                         self._map.set_depth(self._depth_pending, depth[0])
                     self._depth_pending = None
@@ -430,9 +464,23 @@ class NeuralSLAM:
                 torch.save(info[0].to("cpu"), os.path.join(self._base, "depth_info", name))
                 torch.save(views[0].to("cpu"), os.path.join(self._base, "depth_mv_views", name))
             torch.save(depth[0].to("cpu"), os.path.join(self._base, "depth", name))
+            if self._ground:
+                self._fit_ground(self._track_index, depth)
             if self._map is not None:
                 self._map.set_depth(self._track_index, depth[0])
         self._track_index = None
+
+    def _fit_ground(self, index, depth):
+        """ground=True: the road's plane of keyframe `index` from its depth [1,1,H,W] on the device -> ground/%06d.pth."""
+        opts = self._ground_options
+        q, sums, counts = transforms.ground_plane(depth, self._calib, **opts)
+        q, sums, counts = q[0].to("cpu"), sums[0].to("cpu"), counts[0].to("cpu")
+        normal, height = transforms.ground_height(q)
+        accepted = bool(transforms.ground_accept(q, counts, opts.get("normal_prior", (0.0, 1.0, 0.0)), **self._ground_accept))
+        scale = self._camera_height / float(height) if accepted and self._camera_height is not None else 1.0
+        self._ground_scales[index] = scale
+        torch.save(dict(q=q, normal=normal, height=height, sums=sums, counts=counts, accepted=accepted, scale=scale),
+                   os.path.join(self._base, "ground", "%06d.pth" % index))
 
     def _set_mapping_net(self, weights):
         self._mapping_net = MappingVAE()

@@ -610,6 +610,181 @@ def pose_from_flow(flow, pose_init, calib, mask=None, iters=16, scale_px=2.0, in
     return (pose[0], cost[0], counts[0]) if single else (pose, cost, counts)
 
 
+# The defaults of the ground-plane fit ("Ground plane"): choices, not measurements.
+GROUND_DEFAULTS = dict(scale_rel=0.05, inlier_rel=0.05, min_z=0.1, max_depth=80.0, min_votes=64)
+
+
+def ground_rows(calib, H):
+    """The default row band of the ground-plane functions: the rows below the principal point, `(floor(cy) + 1, H)` — a level
+    camera sees the road only there. (A principal point below the image leaves no row: the library refuses the band.)"""
+    from .depth import intrinsics
+    cy = intrinsics(calib)[3]
+    return max(int(math.floor(cy)) + 1, 0), H
+
+
+def _ground_inputs(depth, calib, mask, rows, q=None):
+    """The checked, contiguous inputs of the ground-plane functions, with the batch axis added to an [H,W] depth: (single, kept
+    tensors, leading ctypes arguments up to cy, B, H, W, (y0, y1))."""
+    from .depth import intrinsics
+    d = torch.as_tensor(depth)
+    if d.dim() not in (2, 3, 4) or (d.dim() == 4 and d.shape[1] != 1):
+        raise RuntimeError("expected a depth [H,W], [B,H,W] or [B,1,H,W], got %s" % (tuple(d.shape),))
+    single = d.dim() == 2
+    H, W = (int(v) for v in d.shape[-2:])
+    B = 1 if single else int(d.shape[0])
+    d = d.detach().float().contiguous()
+    m = None
+    if mask is not None:
+        m = _byte_plane(torch.as_tensor(mask), "a mask", B, H, W)
+        if m.device != d.device:
+            raise RuntimeError("depth on %s but mask on %s" % (d.device, m.device))
+    qq = None
+    if q is not None:
+        qq = torch.as_tensor(q)
+        if qq.numel() != 3 * B or qq.shape[-1] != 3:
+            raise RuntimeError("expected q of %d x 3 values, got %s" % (B, tuple(qq.shape)))
+        if qq.device != d.device:
+            raise RuntimeError("depth on %s but q on %s" % (d.device, qq.device))
+        qq = qq.detach().to(torch.float64).contiguous()
+    y0, y1 = ground_rows(calib, H) if rows is None else (int(rows[0]), int(rows[1]))
+    ptr = (C.c_void_p(d.data_ptr()), C.c_void_p(m.data_ptr()) if m is not None else None,
+           C.c_void_p(qq.data_ptr()) if qq is not None else None, B, H, W, y0, y1) + tuple(intrinsics(calib))
+    return single, (d, m, qq), ptr, B, H, W, (y0, y1)
+
+
+def _ground_workspace(B, H, W, device):
+    n = int(_lib.lib().atdn_ground_workspace_bytes(B, H, W))
+    return torch.empty((max(n, 8) + 7) // 8, dtype=torch.float64, device=device)
+
+
+def ground_terms(depth, q, calib, mask=None, rows=None, scale_rel=GROUND_DEFAULTS["scale_rel"],
+                 inlier_rel=GROUND_DEFAULTS["inlier_rel"], min_z=GROUND_DEFAULTS["min_z"], max_depth=GROUND_DEFAULTS["max_depth"]):
+    """How well a plane explains the lower part of a depth map. `depth` [B,H,W] ([B,1,H,W] or [H,W]) as a keyframe depth map holds
+    it, `q` [B,3] ([3]) float64 = normal / height of the plane n . X = height in the camera frame (y down: a level camera 1.65 m
+    over the road has q = (0, 1/1.65, 0)), `calib` and `mask` as for `two_view_depth`, `rows` = (y0, y1) the band of image rows
+    to look at (None: `ground_rows`, the rows below the principal point). A pixel of the band that the mask keeps is a candidate;
+    it is used if its depth is finite and in [min_z, max_depth]. Its residual is the RELATIVE depth error e = z (q . ray) - 1.
+    Returns `(sums, counts)` on the depth's device: `sums` float64 [B,10] ([10]) = the 6 upper-triangle entries of the 3 x 3
+    Gauss-Newton Hessian, the 3 gradient entries and the cost of e under the Geman-McClure loss of scale `scale_rel`; `counts`
+    int32 [B,3] ([3]) = (candidates, used, those with |e| <= inlier_rel). Device tensors go through libatdn_hip's kernels on the
+    current stream (no synchronisation); CPU tensors go through the library's host form. The rule is float64, fixes the order of
+    every sum and is stated in full in include/atdn_hip.h, atdn_ground_terms; the same bits on every call and on both paths."""
+    if q is None:
+        raise RuntimeError("ground_terms needs q")
+    single, keep, ptr, B, H, W, _ = _ground_inputs(depth, calib, mask, rows, q)
+    dev = keep[0].device
+    sums = torch.empty((B, 10), dtype=torch.float64, device=dev)
+    counts = torch.empty((B, 3), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    args = ptr + (float(scale_rel), float(inlier_rel), float(min_z), float(max_depth), C.c_void_p(sums.data_ptr()),
+                  C.c_void_p(counts.data_ptr()))
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            ws = _ground_workspace(B, H, W, dev)
+            _lib.check(L.atdn_ground_terms(*args, C.c_void_p(ws.data_ptr()), _stream()))
+    else:
+        _lib.check(L.atdn_ground_terms_host(*args))
+    return (sums[0], counts[0]) if single else (sums, counts)
+
+
+def ground_plane(depth, calib, normal_prior=(0.0, 1.0, 0.0), q_init=None, mask=None, rows=None, iters=8,
+                 scale_rel=GROUND_DEFAULTS["scale_rel"], inlier_rel=GROUND_DEFAULTS["inlier_rel"], min_z=GROUND_DEFAULTS["min_z"],
+                 max_depth=GROUND_DEFAULTS["max_depth"], min_votes=GROUND_DEFAULTS["min_votes"]):
+    """The ground plane of a depth map: a start from a vote, then `iters` Levenberg-Marquardt steps on the terms of `ground_terms`,
+    every problem of the batch on its own, all on the device. Arguments as for `ground_terms`. The vote: nothing lies below the
+    road, so under `normal_prior` (the road's normal in the camera frame, y down; any length) the ground pixels share one height
+    and everything else spreads over smaller ones; the mode of a histogram of these heights (320 bins of 1.6 .. 3.1 % over
+    [1/16, 64), smoothed over three bins) starts the solve, and a mode of fewer than `min_votes` pixels means there is no plane. A
+    robust fit alone, started from least squares, settles between the road and what stands on it; from the mode it does not.
+    `q_init` [B,3] float64 replaces the vote. Returns `(q, sums, counts)` on the depth's device: `q` float64 [B,3] = normal /
+    height (`ground_height` splits it), `sums` float64 [B,10] the terms at it, `counts` int32 [B,6] = (candidates, used, inliers,
+    accepted steps, votes of the mode, mode bin; the bin is -1 with `q_init`). No plane: q = 0, sums = 0 and all counts 0.
+    2 + 2 * (iters + 1) launches on the current stream and no synchronisation; CPU tensors go through the library's host form.
+    The rule is stated in full in include/atdn_hip.h, atdn_ground_solve; the same bits on every call and on both paths."""
+    single, keep, ptr, B, H, W, _ = _ground_inputs(depth, calib, mask, rows, q_init)
+    dev = keep[0].device
+    n0 = [float(v) for v in torch.as_tensor(normal_prior, dtype=torch.float64).reshape(-1).tolist()]
+    if len(n0) != 3:
+        raise RuntimeError("expected a prior normal of 3 values, got %d" % len(n0))
+    q = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    sums = torch.empty((B, 10), dtype=torch.float64, device=dev)
+    counts = torch.empty((B, 6), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    args = ptr + tuple(n0) + (float(scale_rel), float(inlier_rel), float(min_z), float(max_depth), int(min_votes), int(iters),
+                              C.c_void_p(q.data_ptr()), C.c_void_p(sums.data_ptr()), C.c_void_p(counts.data_ptr()))
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            ws = _ground_workspace(B, H, W, dev)
+            _lib.check(L.atdn_ground_solve(*args, C.c_void_p(ws.data_ptr()), _stream()))
+    else:
+        _lib.check(L.atdn_ground_solve_host(*args))
+    return (q[0], sums[0], counts[0]) if single else (q, sums, counts)
+
+
+def ground_classify(depth, q, calib, mask=None, rows=None, inlier_rel=GROUND_DEFAULTS["inlier_rel"],
+                    min_z=GROUND_DEFAULTS["min_z"], max_depth=GROUND_DEFAULTS["max_depth"]):
+    """The road map of a depth map under the plane `q`: `(residual, on_ground)` on the depth's device, `residual` float32
+    [B,1,H,W] ([1,H,W] for an [H,W] depth) = e of `ground_terms` at every used pixel of the band, 0 elsewhere — the pixel stands
+    -height * e above the road —, `on_ground` uint8 [B,H,W] ([H,W]) = 1 where |e| <= inlier_rel. Both are zero outside the band.
+    One launch on the current stream; CPU tensors go through the library's host form (include/atdn_hip.h, atdn_ground_classify)."""
+    if q is None:
+        raise RuntimeError("ground_classify needs q")
+    single, keep, ptr, B, H, W, _ = _ground_inputs(depth, calib, mask, rows, q)
+    dev = keep[0].device
+    residual = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+    on_ground = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    L = _lib.lib()
+    args = ptr + (float(inlier_rel), float(min_z), float(max_depth), C.c_void_p(residual.data_ptr()),
+                  C.c_void_p(on_ground.data_ptr()))
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            _lib.check(L.atdn_ground_classify(*args, _stream()))
+    else:
+        _lib.check(L.atdn_ground_classify_host(*args))
+    return (residual[0], on_ground[0]) if single else (residual, on_ground)
+
+
+def ground_height(q):
+    """`(normal, height)` of `q` [B,3] (or [3]) = normal / height: normal = q / |q| float64 [B,3], height = 1 / |q| float64 [B]; both
+    0 where q = 0 (no plane). Stays on q's device."""
+    q = torch.as_tensor(q).to(torch.float64)
+    norm = torch.sqrt((q * q).sum(-1))
+    some = norm > 0
+    safe = torch.where(some, norm, torch.ones_like(norm))
+    return torch.where(some[..., None], q / safe[..., None], torch.zeros_like(q)), torch.where(some, 1.0 / safe, torch.zeros_like(norm))
+
+
+def ground_sigma(q, sums):
+    """The relative standard deviation of the fitted height per unit of relative depth noise: with H the 3 x 3 Hessian of `sums`
+    [B,10] (or [10]) at `q`, height = 1 / |q| moves by -height (q . dq) / |q|^2, so sigma = sqrt(u^T H^-1 u) with u = q / |q|^2.
+    A depth whose relative noise is s gives the height to s * sigma (relative). float64 [B]; inf where q = 0 or H is singular."""
+    q = torch.as_tensor(q).to(torch.float64)
+    S = torch.as_tensor(sums).to(torch.float64)
+    a, b, c, d, e, f = (S[..., i] for i in range(6))                     # H = [[a, b, c], [b, d, e], [c, e, f]]
+    co = torch.stack([d * f - e * e, c * e - b * f, b * e - c * d, a * f - c * c, b * c - a * e, a * d - b * b], -1)   # adj(H), upper
+    det = a * co[..., 0] + b * co[..., 1] + c * co[..., 2]
+    n2 = (q * q).sum(-1)
+    ok = (det > 0) & (n2 > 0)
+    u = q / torch.where(ok, n2, torch.ones_like(n2))[..., None]
+    quad = (co[..., 0] * u[..., 0] ** 2 + co[..., 3] * u[..., 1] ** 2 + co[..., 5] * u[..., 2] ** 2 +
+            2.0 * (co[..., 1] * u[..., 0] * u[..., 1] + co[..., 2] * u[..., 0] * u[..., 2] + co[..., 4] * u[..., 1] * u[..., 2]))
+    var = quad / torch.where(ok, det, torch.ones_like(det))
+    return torch.where(ok & (var >= 0), torch.sqrt(var.clamp(min=0.0)), torch.full_like(var, float("inf")))
+
+
+def ground_accept(q, counts, normal_prior=(0.0, 1.0, 0.0), min_inlier_share=0.2, max_tilt_deg=10.0):
+    """Whether a fitted plane is believed (bool [B], or a scalar tensor for one plane): there is one, the share of inliers among
+    the used pixels (`counts` of `ground_plane`) is at least `min_inlier_share`, and its normal is within `max_tilt_deg` degrees
+    of `normal_prior`. float64 on q's device."""
+    normal, _ = ground_height(q)
+    c = torch.as_tensor(counts)
+    n0 = torch.as_tensor(normal_prior, dtype=torch.float64, device=normal.device).reshape(3)
+    cos = (normal * (n0 / torch.sqrt((n0 * n0).sum()))).sum(-1)
+    used, inliers = c[..., 1].double(), c[..., 2].double()
+    share = torch.where(used > 0, inliers / used.clamp(min=1.0), torch.zeros_like(used))
+    return (used > 0) & (share >= float(min_inlier_share)) & (cos >= math.cos(math.radians(float(max_tilt_deg))))
+
+
 def flow_track_step(flow, acc, alive, pose=None, calib=None, mask=None, depth=None, max_epipolar=1.0, min_parallax_deg=0.05,
                     max_depth=80.0, out=None):
     """One step of a flow track: the correspondences of an anchor frame's pixels carried one frame further and, given a pose,

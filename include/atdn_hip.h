@@ -845,6 +845,91 @@ int atdn_epipolar_solve_host(const float* flow, const unsigned char* mask, const
                              double* cost, int* counts);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Ground plane of a depth map (camera height and metric scale)  —  a camera of known height over a road sees a plane n . X = h.
+ * With q = n / h, the ray a = ((x - cx)/fx, (y - cy)/fy, 1) and the depth z of a pixel, e = z*(q . a) - 1 is the RELATIVE depth
+ * residual: linear in q, dimensionless, meaningful when the scale of the depth is wrong. The fitted height of a depth whose
+ * scale is off by s is s * h_true: camera_height / h is the correction. n . X = h*(1 + e): a pixel stands -h*e above the road.
+ * atdn_ground_terms is one evaluation, atdn_ground_solve a start vote and a Levenberg-Marquardt solve, atdn_ground_classify the
+ * per-pixel map. No square root and no transcendental anywhere: the outputs are q and sums; normal = q / |q| and h = 1 / |q| are
+ * formed by the caller. The reference has nothing like it.
+ * ------------------------------------------------------------------------------------------------- */
+
+/* Bytes of the workspace of atdn_ground_terms / atdn_ground_solve for B planes of H x W, whatever the rows (0 for sizes they
+ * refuse): one solver state per problem; per chunk of 1024 pixels 10 float64 sums and four int32; per vote workgroup (at most 32
+ * a plane) 320 int32. No call reads what an earlier call left there. */
+long atdn_ground_workspace_bytes(int B, int H, int W);
+
+/* sums[b] = the 10 terms of q[b] summed over the rows [y0, y1) of plane b, counts[b] = (candidates, used, inliers).
+ *   depth [B,H,W] fp32 DEVICE. mask [B,H,W] uint8 DEVICE or NULL: pixels whose byte is 0 are skipped. q [B,3] float64 DEVICE.
+ *   sums [B,10] float64 DEVICE, counts [B,3] int32 DEVICE, workspace: atdn_ground_workspace_bytes(B, H, W) bytes DEVICE; q, sums
+ *   and workspace 8-byte aligned; no output (the workspace is one) overlaps an input or another output. 0 <= y0 < y1 <= H.
+ *   fx, fy finite and > 0; cx, cy finite; scale_rel, inlier_rel (relative depth), min_z and max_depth finite and > 0.
+ *   B <= 65535, H * W <= 2^24, B, H, W >= 1. Anything else fails before a launch.
+ * The rule: everything in float64, every operation rounded on its own (no fused multiply-add), only + - * /, comparisons and
+ * integer operations, in exactly this order. Constants: c2 = scale_rel*scale_rel, thr = inlier_rel*inlier_rel.
+ * Pixel (x, y) of a row y0 <= y < y1, z = (double)depth:
+ *   cand = mask byte != 0;  used = cand && min_z <= z <= max_depth           (a NaN or an infinity fails)
+ *   ax = (x - cx)/fx, ay = (y - cy)/fy
+ *   e = z*((q0*ax + q1*ay) + q2*1) - 1,  e2 = e*e
+ *   s = 1 + e2/c2, w = 1/(s*s), rho = (0.5*e2)/s                             (Geman-McClure)
+ *   inlier = used && e2 <= thr
+ *   J = (z*ax, z*ay, z)                                                      (the derivative of e with respect to q)
+ *   terms 0..5: H_ij = (w*J_i)*J_j for i <= j, row by row (00, 01, 02, 11, 12, 22); terms 6..8: g_i = (w*J_i)*e; term 9: rho
+ *   !used: +0.0 in all 10 terms
+ * Sums: the band is the plane of the (y1 - y0)*W flat indices i = (y - y0)*W + x, summed exactly as a plane of atdn_pnp_terms
+ * (chunks of 1024 flat indices, four per thread, the binary tree over 256 threads, the chunks in order) over 10 terms instead of
+ * 28. The three counts are integer sums. Two launches on `stream`: asynchronous, capturable, no host synchronisation. */
+int atdn_ground_terms(const float* depth, const unsigned char* mask, const double* q, int B, int H, int W, int y0, int y1, double fx,
+                      double fy, double cx, double cy, double scale_rel, double inlier_rel, double min_z, double max_depth,
+                      double* sums, int* counts, void* workspace, void* stream);
+/* The same function on HOST buffers in plain C++ float64 (csrc/ground_host.h, the functions the kernels call too): serves CPU
+ * tensors, needs no GPU and no workspace, the same bits. */
+int atdn_ground_terms_host(const float* depth, const unsigned char* mask, const double* q, int B, int H, int W, int y0, int y1,
+                           double fx, double fy, double cx, double cy, double scale_rel, double inlier_rel, double min_z,
+                           double max_depth, double* sums, int* counts);
+
+/* q[b] = the plane after the start vote (or from q_init[b]) and `iters` Levenberg-Marquardt steps on the terms above; sums[b] the
+ * 10 terms and counts[b] = (candidates, used, inliers, accepted steps, votes of the mode, mode bin) at it. Arguments as for
+ * atdn_ground_terms; q_init [B,3] float64 DEVICE or NULL (the vote); (nx, ny, nz) the prior normal, finite and not zero (any
+ * length); min_votes >= 1; 0 <= iters <= 64; q [B,3] float64, sums [B,10] float64, counts [B,6] int32 DEVICE.
+ * Start vote (q_init NULL): nothing lies below the road, so under the prior normal the ground pixels share one height and
+ * everything else spreads over smaller ones. For every used pixel
+ *   hgt = z*((nx*ax + ny*ay) + nz*1);  k = (int64)(bits(hgt) >> 47) - 1019*32;  the pixel votes for bin k iff 0 <= k < 320
+ *   (the exponent and the top 5 mantissa bits of the float64: 2^-4 <= hgt < 2^6 in 320 bins of 1.6 .. 3.1 % relative width)
+ *   smoothed_k = c_{k-1} + c_k + c_{k+1} (c_-1 = c_320 = 0); the mode is the k of the largest smoothed_k — among equal ones that
+ *   of the largest c_k (a single populated bin k has smoothed_{k-1} = smoothed_k = smoothed_{k+1}: the mode is k), among those
+ *   the lowest k —, votes = smoothed_k
+ *   votes < min_votes: there is no plane — q = 0, sums = +0.0 and all six counts 0
+ *   otherwise the start is q = (nx, ny, nz) / centre, each component one division, centre = the float64 of the bits
+ *   ((k + 1019*32) << 47) | (1 << 46)
+ * With q_init the start is q_init, votes = 0 and bin = -1.
+ * Decision and lambda: those of atdn_pnp_solve — evaluation 0 is accepted with lambda = 1e-3, a later one iff its cost (term 9)
+ * is smaller (a NaN fails); lambda = max(lambda/3, 1e-9) on accept, min(4*lambda, 1e6) on reject. Then, unless k = iters:
+ *   A = H of the accepted terms with A_ii = H_ii + lambda*H_ii; LDL^T without pivoting and the two triangular solves of
+ *   atdn_pnp_solve with 6 replaced by 3, right-hand side -g; some d_j > 0 fails, or some |delta_i| <= DBL_MAX fails: the trial
+ *   is the accepted q again; otherwise trial_i = q_i + delta_i.
+ * Two launches for the vote and two per evaluation (the terms; one wave per problem for the order-fixed sum, the decision and
+ * the step); the histogram is counted in LDS per workgroup and the workgroups' histograms are added by the second launch:
+ * integer sums, no global atomics, no memset, no host synchronisation, capturable. */
+int atdn_ground_solve(const float* depth, const unsigned char* mask, const double* q_init, int B, int H, int W, int y0, int y1,
+                      double fx, double fy, double cx, double cy, double nx, double ny, double nz, double scale_rel,
+                      double inlier_rel, double min_z, double max_depth, int min_votes, int iters, double* q, double* sums,
+                      int* counts, void* workspace, void* stream);
+int atdn_ground_solve_host(const float* depth, const unsigned char* mask, const double* q_init, int B, int H, int W, int y0, int y1,
+                           double fx, double fy, double cx, double cy, double nx, double ny, double nz, double scale_rel,
+                           double inlier_rel, double min_z, double max_depth, int min_votes, int iters, double* q, double* sums,
+                           int* counts);
+
+/* residual [B,H,W] fp32 = e of every used pixel of the rows [y0, y1) at q[b], rounded to fp32 once (+0.0 elsewhere), on_ground
+ * [B,H,W] uint8 = 1 where e2 <= inlier_rel*inlier_rel there, 0 elsewhere. Arguments as for atdn_ground_terms. One launch. */
+int atdn_ground_classify(const float* depth, const unsigned char* mask, const double* q, int B, int H, int W, int y0, int y1,
+                         double fx, double fy, double cx, double cy, double inlier_rel, double min_z, double max_depth,
+                         float* residual, unsigned char* on_ground, void* stream);
+int atdn_ground_classify_host(const float* depth, const unsigned char* mask, const double* q, int B, int H, int W, int y0, int y1,
+                              double fx, double fy, double cx, double cy, double inlier_rel, double min_z, double max_depth,
+                              float* residual, unsigned char* on_ground);
+
+/* ---------------------------------------------------------------------------------------------------
  * Pose-graph optimisation (loop closure)  —  the poses of the keyframes are the nodes, a measured relative pose between two of
  * them is an edge: consecutive keyframes by odometry, revisits by relocalisation and PnP. Levenberg-Marquardt over the graph
  * with a conjugate-gradient solve preconditioned by the block-tridiagonal part of the system (a keyframe graph is a chain plus
