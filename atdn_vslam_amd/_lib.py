@@ -135,6 +135,17 @@ SIGNATURES = {
                                         C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "atdn_pose_graph_solve_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
                                              C.c_double, _vp, _vp, _vp, _vp]),
+    "atdn_voxel_table_bytes": (C.c_long, [C.c_long]),
+    "atdn_voxel_clear": (C.c_int, [_vp, C.c_long, _vp]),
+    "atdn_voxel_clear_host": (C.c_int, [_vp, C.c_long]),
+    "atdn_voxel_integrate": (C.c_int, [_vp] * 5 + [C.c_int] * 4 + [C.c_double] * 4 + [C.c_int] + [C.c_double] * 6 + [C.c_int, _vp,
+                                                                                                                 C.c_long, _vp, _vp]),
+    "atdn_voxel_integrate_host": (C.c_int, [_vp] * 5 + [C.c_int] * 4 + [C.c_double] * 4 + [C.c_int] + [C.c_double] * 6 +
+                                  [C.c_int, _vp, C.c_long, _vp]),
+    "atdn_voxel_rehash": (C.c_int, [_vp, C.c_long, _vp, C.c_long, _vp]),
+    "atdn_voxel_rehash_host": (C.c_int, [_vp, C.c_long, _vp, C.c_long]),
+    "atdn_voxel_extract": (C.c_int, [_vp, C.c_long, C.c_int] + [C.c_double] * 4 + [C.c_long] + [_vp] * 6),
+    "atdn_voxel_extract_host": (C.c_int, [_vp, C.c_long, C.c_int] + [C.c_double] * 4 + [C.c_long] + [_vp] * 5),
     "atdn_map_search": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "atdn_map_gather_images_u8": (C.c_int, [_vp, C.c_int, C.c_long, _vp, C.c_int, _vp, _vp]),
     "atdn_corr_lookup": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),

@@ -22,6 +22,7 @@
 #include "multiview_depth_host.h"
 #include "pnp_host.h"
 #include "two_view_host.h"
+#include "voxel_map_host.h"
 #include "warm_start_host.h"
 
 namespace atdn {
@@ -443,6 +444,40 @@ int atdn_depth_fuse_host(const float* bank, const float* poses, const int* targe
                         fused, views, counts);
   depth_fuse_host(bank, poses, targets, sources, N, B, S, H, W,
                   depth_fuse_params(fx, fy, cx, cy, max_reproj, max_rel_depth, min_views, min_z, average), fused, views, counts);
+  ATDN_API_END
+}
+
+// ------------------------------------------------------------------ voxel map (host twins of voxel_map.hip)
+int atdn_voxel_clear_host(void* table, long capacity) {
+  ATDN_API_BEGIN
+  voxel_check_table(table, capacity);
+  voxel_clear_host((uint64_t*)table, capacity);
+  ATDN_API_END
+}
+int atdn_voxel_integrate_host(const float* depth, const float* poses, const uint8_t* images, const uint8_t* mask, const int* indices,
+                              int N, int K, int H, int W, double fx, double fy, double cx, double cy, int stride, double voxel,
+                              double ox, double oy, double oz, double min_z, double max_z, int retry, void* table, long capacity,
+                              uint8_t* pending) {
+  ATDN_API_BEGIN
+  voxel_check_integrate(depth, poses, images, mask, indices, N, K, H, W, fx, fy, cx, cy, stride, voxel, ox, oy, oz, min_z, max_z,
+                        table, capacity, pending);
+  voxel_integrate_host(depth, poses, images, mask, indices, N, K, H, W,
+                       voxel_params(fx, fy, cx, cy, stride, voxel, ox, oy, oz, min_z, max_z), retry != 0, (uint64_t*)table, capacity,
+                       pending);
+  ATDN_API_END
+}
+int atdn_voxel_rehash_host(const void* src, long src_capacity, void* dst, long dst_capacity) {
+  ATDN_API_BEGIN
+  voxel_check_rehash(src, src_capacity, dst, dst_capacity);
+  voxel_rehash_host((const uint64_t*)src, src_capacity, (uint64_t*)dst, dst_capacity);
+  ATDN_API_END
+}
+int atdn_voxel_extract_host(void* table, long capacity, int min_count, double voxel, double ox, double oy, double oz,
+                            long max_out, float* points, uint8_t* colors, int* counts, int64_t* keys, int64_t* found) {
+  ATDN_API_BEGIN
+  voxel_check_extract(table, capacity, min_count, voxel, ox, oy, oz, max_out, points, colors, counts, keys, found);
+  voxel_extract_host((const uint64_t*)table, capacity, min_count, voxel_params(1.0, 1.0, 0.0, 0.0, 1, voxel, ox, oy, oz, 0.0, 0.0),
+                     max_out, points, colors, counts, keys, found);
   ATDN_API_END
 }
 

@@ -1,7 +1,8 @@
-// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip, epipolar.hip, depth_fusion.hip, multiview_depth.hip, bundle.hip, ground.hip), shared by each device
+// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip, epipolar.hip, depth_fusion.hip, multiview_depth.hip, bundle.hip, ground.hip, voxel_map.hip), shared by each device
 // entry point and its host twin in capi.hip, and the overlap rule that the pose solvers (pnp.hip, pose_graph.hip) share.
 #pragma once
 #include <cmath>
+#include <cstdint>
 
 #include "common.h"
 #include "two_view_host.h"
@@ -83,5 +84,16 @@ void bundle_check_args(const float* acc_bank, const unsigned char* alive_bank, c
                        const float* depth_init, const unsigned char* mask, int N, int B, int S, int H, int W, double fx, double fy,
                        double cx, double cy, int stride, int iters, double scale_px, double inlier_px, double min_z, int min_views,
                        bool grid_limit, const void* const* out, const long* out_bytes, int n_out);
+
+// the voxel map (voxel_map.hip): images, mask, indices and pending may be null
+void voxel_check_table(const void* table, long capacity);
+void voxel_check_integrate(const float* depth, const float* poses, const unsigned char* images, const unsigned char* mask,
+                           const int* indices, int N, int K, int H, int W, double fx, double fy, double cx, double cy, int stride,
+                           double voxel, double ox, double oy, double oz, double min_z, double max_z, const void* table,
+                           long capacity, const unsigned char* pending);
+void voxel_check_rehash(const void* src, long src_capacity, const void* dst, long dst_capacity);
+void voxel_check_extract(const void* table, long capacity, int min_count, double voxel, double ox, double oy, double oz, long max_out,
+                         const float* points, const unsigned char* colors, const int* counts, const int64_t* keys,
+                         const int64_t* found);
 
 }  // namespace atdn

@@ -231,6 +231,32 @@ class KeyframeMap:
                 bank.copy_(fused)                                     # after the last target has read the unfused bank
         return fused, views, counts
 
+    @torch.no_grad()
+    def voxel_map(self, calib, fused=None, batch=8, stride=1, **options):
+        """The map as one coloured point cloud (`voxel_map.VoxelMap`; `options`: voxel, origin, min_z, max_z, capacity): the
+        depth bank, the poses and the image bank integrated straight out of device memory, `batch` keyframes per launch through
+        an index list (no gather copy), every `stride`-th pixel. `fused` ([n,H,W] float32 on the map's device, what
+        `fuse_depths` returns) replaces the depth bank. A keyframe without a depth holds zeros and adds nothing. `calib` is the
+        calibration of the map's grid. Returns the VoxelMap; a map without a depth bank raises."""
+        from .voxel_map import VoxelMap
+        n = self.n
+        if fused is None:
+            if self.depth_bank is None or n == 0:
+                raise RuntimeError("voxel_map: the map holds no depth (set_depth gives a keyframe its depth map)")
+            depth = self.depth_bank[:n]
+        else:
+            depth = torch.as_tensor(fused)
+            if tuple(depth.shape) != (n,) + self.hw or depth.device != self.device:
+                raise ValueError("fused must be [%d,%d,%d] on %s, got %s on %s" %
+                                 ((n,) + self.hw + (self.device, tuple(depth.shape), depth.device)))
+        vm = VoxelMap(self.device, **options)
+        poses = self._poses[:n, :3, :].reshape(n, 12).to(self.device)
+        batch = max(1, int(batch))
+        with torch.cuda.device(self.device):
+            for a in range(0, n, batch):
+                vm.integrate(depth, poses, calib, images=self.image_bank[:n], indices=np.arange(a, min(a + batch, n)), stride=stride)
+        return vm
+
     @classmethod
     def from_directory(cls, keyframes_path, device, mapping_net=None):
         """The map of a keyframe directory as the reference and slam.NeuralSLAM write it: `rgb/*.pth` (sorted; uint8

@@ -121,6 +121,11 @@ class NeuralSLAM:
     of the keyframe's first pair only, not of the interval, and `poses_scaled.pth` is not written. Nothing is fed back: the
     running pose, `poses.pth`, `poses_closed.pth`, the loop closure, the depth fusion and every other file are what they are
     without it. With False (the default) no file, directory, attribute or bit changes.
+    `voxel_map=True` (needs `calib` and `resident_map`): at the end of `end_odometry()` — after the loop closure and the depth
+    fusion when those are on, so with the optimised poses and the fused depths — every keyframe's depth and colours are
+    accumulated into one voxel-hashed point cloud (`build_voxel_map`, `voxel_options` its keyword arguments): `map.ply` and the
+    `voxel_map` attribute. A cold start with the option removes a `map.ply` of an earlier session. With False (the default)
+    nothing anywhere changes.
     """
 
     FLOW_CHECKPOINT = "atdn_vslam/checkpoints/gma-kitti.pth"  # utils/gma_parameters.py
@@ -129,8 +134,15 @@ class NeuralSLAM:
                  precision=None, map_options=None, resident_map=False, warm_start=False, calib=None, keyframe_depth="pair",
                  loop_closure=False, loop_options=None, refine_pose=False, fuse_depth=False, fuse_options=None,
                  multiview_options=None, bundle_options=None, bundle_pose=False, ground=False, ground_options=None,
-                 camera_height=None):
+                 camera_height=None, voxel_map=False, voxel_options=None):
         from .depth import intrinsics
+        if voxel_map and (calib is None or not resident_map):
+            raise ValueError("voxel_map=True needs the calibration and the keyframe map in device memory: pass calib= and "
+                             "resident_map=True")
+        self._voxel_map = bool(voxel_map)
+        self._voxel_options = dict(voxel_options or {})
+        self.voxel_map = None        # voxel_map.VoxelMap of the last build_voxel_map()
+        self._fused_device = None    # the fused depths of the last fuse_depths() (device), kept for the voxel map only
         if ground:
             if calib is None:
                 raise ValueError("ground=True needs the calibration: pass calib=")
@@ -220,6 +232,8 @@ class NeuralSLAM:
                     os.makedirs(os.path.join(self._base, sub), exist_ok=True)
                     for f in glob.glob(os.path.join(self._base, sub, "*")):
                         os.remove(f)
+            if self._voxel_map and os.path.exists(os.path.join(self._base, "map.ply")):
+                os.remove(os.path.join(self._base, "map.ply"))
             if self._multiview:
                 for sub in ("depth_info", "depth_mv_views") + (("bundle",) if self._bundle else ()):
                     os.makedirs(os.path.join(self._base, sub), exist_ok=True)
@@ -277,6 +291,8 @@ class NeuralSLAM:
                 self.close_loops(**self._loop_options)
             if self._fuse_depth:
                 self.fuse_depths(**self._fuse_options)               # after the loop closure: it sees the optimised poses
+            if self._voxel_map:
+                self.build_voxel_map(**self._voxel_options)          # after both: the optimised poses, the fused depths
         elif len(self._keyframes) == 0:
             print("There is no explored enviromnent yet!")
         elif self._mode == "mapping" and mapping_weights is not None:
@@ -319,6 +335,8 @@ class NeuralSLAM:
             self.fusion_counts = None
             return None
         fused, views, counts = self._map.fuse_depths(self._calib, **options)
+        if self._voxel_map:
+            self._fused_device = fused
         fused, views = fused.cpu(), views.cpu()
         for sub in ("depth_fused", "depth_views"):
             os.makedirs(os.path.join(self._base, sub), exist_ok=True)
@@ -328,6 +346,30 @@ class NeuralSLAM:
             torch.save(views[i].clone(), os.path.join(self._base, "depth_views", name))
         self.fusion_counts = counts.cpu()
         return self.fusion_counts
+
+    @torch.no_grad()
+    def build_voxel_map(self, min_count=1, **options):
+        """The map as one coloured point cloud (relocalisation mode, resident map and `calib` only): `KeyframeMap.voxel_map` with
+        this object's calibration (`options`: its keyword arguments — voxel, origin, min_z, max_z, capacity, stride, batch) over
+        the keyframes' poses as they are now (the optimised ones after a loop closure) and their depths — the fused depths of
+        the last `fuse_depths()` of this object when `fuse_depth=True`, the depth bank otherwise. Writes
+        `<keyframes_path>/map.ply` (binary little-endian: x y z float, red green blue uchar, count int; the voxels with at least
+        `min_count` points in ascending key order), keeps the VoxelMap as `self.voxel_map` and returns it. A map in which no
+        keyframe has a depth writes nothing and returns None."""
+        if getattr(self, "_map", None) is None or self._calib is None:
+            raise RuntimeError("build_voxel_map needs the keyframe map in device memory and the calibration: construct "
+                               "NeuralSLAM(..., calib=..., resident_map=True)")
+        if self._mode != "relocalization":
+            raise Exception("SLAM called in invalid state!")
+        if self._map.depth_bank is None:
+            self.voxel_map = None
+            return None
+        fused = self._fused_device if self._fuse_depth else None
+        if fused is not None and int(fused.shape[0]) != len(self._map):
+            fused = None
+        self.voxel_map = self._map.voxel_map(self._calib, fused=fused, **options)
+        self.voxel_map.save_ply(os.path.join(self._base, "map.ply"), min_count=min_count)
+        return self.voxel_map
 
     @torch.no_grad()
     def __call__(self, im):

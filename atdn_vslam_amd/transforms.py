@@ -1006,6 +1006,21 @@ def pose_graph_optimize(poses, edge_index, edge_pose, edge_weight, edge_robust=N
     return (out, cost, chi2, total) if batched else (out, cost[0], chi2[0], total[0])
 
 
+def voxel_map(depth, poses, calib, images=None, mask=None, indices=None, stride=1, min_count=1, **options):
+    """Depth maps and their cameras as ONE voxel-hashed point cloud, in one call: `voxel_map.VoxelMap(depth.device, **options)`
+    (voxel, origin, min_z, max_z, capacity), its `integrate(depth, poses, calib, images, mask, indices, stride)` and its
+    `extract(min_count)`, where the arguments are described. Returns `(points [M,3] float32, colors [M,3] uint8 or None, counts
+    [M] int32, keys [M] int64)` on the depth's device, in ascending key order. Device tensors go through libatdn_hip's kernels,
+    CPU tensors through the library's host form; the rule is integer and float64 and stated in full in include/atdn_hip.h: the
+    same inputs give the same bits on every call and on both paths."""
+    from .voxel_map import VoxelMap
+    if not isinstance(depth, torch.Tensor):
+        raise RuntimeError("expected a depth bank [N,H,W], got %s" % (type(depth).__name__,))
+    m = VoxelMap(depth.device, **options)
+    m.integrate(depth, poses, calib, images=images, mask=mask, indices=indices, stride=stride)
+    return m.extract(min_count)
+
+
 class InputPadder:
     """Replicate-pads frames to multiples of 8 ('sintel' mode splits the padding on both sides)."""
 

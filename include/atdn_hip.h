@@ -1037,6 +1037,86 @@ int atdn_pose_graph_solve_host(const float* poses, const int* edge_index, const 
                                double* edge_chi2, int* counts);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Voxel map  —  every keyframe's depth (and colour) accumulated into ONE voxel-hashed point cloud: the scatter primitive of the
+ * library. A pixel's point falls into a cubic voxel; per voxel the table keeps the number of points, the sum of their sub-voxel
+ * positions and of their colour bytes, all as exact integers. Integer sums commute: every bit of the result is independent of
+ * thread order, launch geometry and of how the keyframes are split over calls. The reference has nothing like it.
+ *
+ * The rule. Integer arithmetic or float64 with every operation rounded on its own (no fused multiply-add); only + - * /,
+ * comparisons and the two conversions named below.
+ *   depth [N,H,W] fp32; poses [N,12] fp32, rows of [R|t], world <- camera; (fx, fy, cx, cy) float64; images [N,3,H,W] uint8 or
+ *   NULL (channels 0, 1, 2 are red, green, blue as stored); mask [K,H,W] uint8 or NULL (a zero byte excludes the pixel);
+ *   stride >= 1: only pixels with x % stride == 0 && y % stride == 0 take part; voxel > 0, origin o, min_z, max_z.
+ * Per pixel (k, y, x) that takes part:
+ *   z = (double)depth; the pixel is a CANDIDATE iff min_z <= z && z <= max_z (a NaN fails)
+ *   xn = ((double)x - cx)/fx, yn = ((double)y - cy)/fy, c = (xn*z, yn*z, z)
+ *   p_a = dot3(row a of R, c) + t_a, dot3 = (r_a0*c_0 + r_a1*c_1) + r_a2*c_2;  g_a = (p_a - o_a)/voxel
+ *   the candidate is OUTSIDE unless -2^20 <= g_a && g_a < 2^20 for all three axes (a NaN or an infinity from a pose lands
+ *   here): counted, not inserted
+ *   k_a = floor(g_a): truncated to an integer, minus 1 if the integer converted back exceeds g_a
+ *   f_a = g_a - (double)k_a, q_a = (integer)(f_a*65536), truncated: 0 .. 65535, and 65536 for the negative g_a so small that
+ *   g_a + 1 rounds to 1
+ *   key = ((k_x + 2^20) << 42) | ((k_y + 2^20) << 21) | (k_z + 2^20)
+ * Per voxel, exact integers: n = the number of inserted points, S_a = the sum of q_a, C_c = the sum of colour byte c (with images).
+ * Extraction with min_count >= 1: the voxels with n >= min_count, and of each
+ *   points_a = (float)(o_a + ((double)k_a + ((double)S_a/(double)n + 0.5)/65536)*voxel)
+ *   colors_c = (C_c + n/2)/n in integer division;  counts = n;  keys = key
+ * Counters (int64): candidates, inserted, outside, dropped, voxels; always candidates == inserted + outside + dropped.
+ *
+ * The table: atdn_voxel_table_bytes(capacity) = 64 + 64*capacity bytes, 8-byte aligned, capacity a power of two in [2, 2^31],
+ * little-endian 64-bit words. Words 0..7: the header — candidates, inserted, outside, dropped, voxels, two scratch words of the device extraction (0 between
+ * calls), one reserved (0). Words
+ * 8 + 8 s .. 8 + 8 s + 7: slot s — key (all ones = empty), n, S_x, S_y, S_z, C_red, C_green, C_blue. While the table holds fewer
+ * than 2^31 points S < 2^47 and C < 2^39: no sum can overflow. Open addressing with linear probing from
+ * home(key) = (((key * 0x9E3779B97F4A7C15 mod 2^64) >> 32) * capacity) >> 32 (the top log2(capacity) bits of the product: every
+ * bit of the key reaches them), over at most min(capacity, 1024) slots; a point that
+ * finds neither its key nor an empty slot there is counted as DROPPED. Which slot a key lives in depends on the order of
+ * arrival; the set of keys and every sum do not. On the device insertion is a 64-bit compare-and-swap on the key word and the
+ * sums are 64-bit integer atomic adds whose results nobody reads; no thread waits for another, there is no lock and no retry,
+ * every loop bound is an argument or a constant. DEVICE entry points take device memory and are launches on `stream`
+ * (asynchronous, capturable, no host synchronisation); the _host twins take host memory, run on the calling thread and give the
+ * same bits.
+ * ------------------------------------------------------------------------------------------------- */
+
+/* Bytes of a table of `capacity` slots (0 for a capacity the entry points refuse). */
+long atdn_voxel_table_bytes(long capacity);
+
+/* An empty table: every key all ones, every sum and counter 0. One launch. */
+int atdn_voxel_clear(void* table, long capacity, void* stream);
+int atdn_voxel_clear_host(void* table, long capacity);
+
+/* Adds the pixels of K keyframes to the table. depth, poses, images are banks of N keyframes; list position j < K reads keyframe
+ * indices[j] (int32 [K], DEVICE; an index outside [0, N) contributes nothing; repeats are integrated again), or keyframe j when
+ * indices is NULL (then K <= N). mask and pending are [K,H,W] by list position. pending (or NULL) is written in full: 1 at
+ * exactly the pixels this call dropped, 0 elsewhere — grow the table (atdn_voxel_rehash) and call again with mask = pending and
+ * retry = 1: a retry call counts no candidates, and every point it inserts moves from `dropped` to `inserted`, so a grown table
+ * ends with the bits of one that was large from the start. No output may overlap an input or another output. One launch. */
+int atdn_voxel_integrate(const float* depth, const float* poses, const uint8_t* images, const uint8_t* mask, const int* indices, int N,
+                         int K, int H, int W, double fx, double fy, double cx, double cy, int stride, double voxel, double ox,
+                         double oy, double oz, double min_z, double max_z, int retry, void* table, long capacity, uint8_t* pending,
+                         void* stream);
+int atdn_voxel_integrate_host(const float* depth, const float* poses, const uint8_t* images, const uint8_t* mask, const int* indices,
+                              int N, int K, int H, int W, double fx, double fy, double cx, double cy, int stride, double voxel,
+                              double ox, double oy, double oz, double min_z, double max_z, int retry, void* table, long capacity,
+                              uint8_t* pending);
+
+/* Re-inserts every occupied slot of src into dst (dst_capacity >= src_capacity, the tables disjoint), sums included, and adds
+ * src's candidates, inserted, outside and dropped to dst's: into a cleared dst, the table as if it had been that large from the
+ * start. An entry that finds no slot (dst was not empty) moves its n from inserted to dropped. One launch. */
+int atdn_voxel_rehash(const void* src, long src_capacity, void* dst, long dst_capacity, void* stream);
+int atdn_voxel_rehash_host(const void* src, long src_capacity, void* dst, long dst_capacity);
+
+/* The voxels with n >= min_count, compacted: points [max_out,3] fp32, colors [max_out,3] uint8 (or NULL), counts [max_out]
+ * int32, keys [max_out] int64, found [1] int64 = the number of qualifying voxels, which may exceed max_out: nothing is written
+ * past max_out entries. The device writes in table order (which entries are kept when found > max_out is then arbitrary); the
+ * host form writes in ascending key order. voxel and origin are those of the integration. One launch, no memset: the device
+ * form counts in the header's two scratch words and leaves them 0, so two extractions of ONE table must not run concurrently. */
+int atdn_voxel_extract(void* table, long capacity, int min_count, double voxel, double ox, double oy, double oz, long max_out,
+                       float* points, uint8_t* colors, int* counts, int64_t* keys, int64_t* found, void* stream);
+int atdn_voxel_extract_host(void* table, long capacity, int min_count, double voxel, double ox, double oy, double oz,
+                            long max_out, float* points, uint8_t* colors, int* counts, int64_t* keys, int64_t* found);
+
+/* ---------------------------------------------------------------------------------------------------
  * Keyframe map  —  replaces the keyframe list of NeuralSLAM's relocalisation (keyframe_map.py)
  *   embeddings: Frame.embedding, one MappingVAE call per keyframe (slam_framework/neural_slam.py:88-103,158-164)
  *   search:     the per-keyframe torch.norm loop, torch.stack and argmin (neural_slam.py:374-383)
