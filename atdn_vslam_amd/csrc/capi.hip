@@ -658,9 +658,20 @@ int atdn_corr_pyramid(const float* fmap1, const float* fmap2, int B, int H8, int
 int atdn_corr_lookup_bricks(const float* fmap1, const float* fmap2, int B, int H8, int W8, int C, const float* coords,
                             float* pyr0, float* pyr1, float* pyr2, float* pyr3, float* samples,
                             const float* convc1_weight_host, const float* convc1_bias_host, float* cor1, void* stream) {
+  return atdn_corr_lookup_bricks_mode(fmap1, fmap2, B, H8, W8, C, coords, pyr0, pyr1, pyr2, pyr3, samples, convc1_weight_host,
+                                      convc1_bias_host, cor1, 0, stream);
+}
+// fast = 1: the plain-f16 builds (precision mode 2) of the correlation and the fused lookup + convc1 kernels. C = 256 runs
+// corr_bricks_kernel, C = 160 corr_bricks_kernel_k160 on 160 plain channels (the network feeds that kernel its folded head; here
+// the five chunks are caller features like any other); the volume is scaled by 1 / sqrt(C).
+int atdn_corr_lookup_bricks_mode(const float* fmap1, const float* fmap2, int B, int H8, int W8, int C, const float* coords,
+                                 float* pyr0, float* pyr1, float* pyr2, float* pyr3, float* samples,
+                                 const float* convc1_weight_host, const float* convc1_bias_host, float* cor1, int fast,
+                                 void* stream) {
   ATDN_API_BEGIN
   ATDN_CHECK(fmap1 && fmap2 && B >= 1 && H8 >= 1 && W8 >= 1, "bad argument");
-  ATDN_CHECK(C == 256, "the correlation kernel keeps a source strip's whole K = 256 in registers: C must be 256");
+  ATDN_CHECK(C == 256 || C == 160, "the correlation kernels keep a source strip's whole K in registers: C must be 256 or 160");
+  ATDN_CHECK(fast == 0 || fast == 1, "fast must be 0 (split-f16) or 1 (plain f16)");
   ATDN_CHECK((H8 >> 3) >= 2 && (W8 >> 3) >= 2, "map too small for four pyramid levels");
   ATDN_CHECK(!(samples || cor1) || coords, "a lookup needs coordinates");
   ATDN_CHECK(!cor1 || (convc1_weight_host && convc1_bias_host), "cor1 needs convc1's weight [256][324] and bias [256]");
@@ -672,28 +683,28 @@ int atdn_corr_lookup_bricks(const float* fmap1, const float* fmap2, int B, int H
   WeightArena A;
   DeviceBuf f1, f2, plain[3], fbrick[4], pyr[4], scratch, outsf, csf;
   sf_counter_attach();
-  f1.alloc(n8 * 256); f2.alloc(n8 * 256);
-  launch_to_sf(fmap1, f1.p, n8, 256, st);
-  launch_to_sf(fmap2, f2.p, n8, 256, st);
+  f1.alloc(n8 * C); f2.alloc(n8 * C);
+  launch_to_sf(fmap1, f1.p, n8, C, st);
+  launch_to_sf(fmap2, f2.p, n8, C, st);
   float* rowmajor[4] = {pyr0, pyr1, pyr2, pyr3};
   int pH[4], pW[4];
   for (int l = 0; l < 4; ++l) {   // the same sequence as GmaNet::run_body_sf
     pH[l] = H8 >> l; pW[l] = W8 >> l;
     bp.H[l] = pH[l]; bp.W[l] = pW[l]; bp.BW[l] = cdiv(pW[l], 8); bp.BH[l] = cdiv(pH[l], 4); bp.NB[l] = bp.BW[l] * bp.BH[l] * 32;
     const float* src = f2.p;
-    long src_sb = (long)N * 256;
+    long src_sb = (long)N * C;
     if (l > 0) {
       const float* prev = l == 1 ? f2.p : plain[l - 2].p;
-      const long prev_sb = l == 1 ? (long)N * 256 : (long)pH[l - 1] * pW[l - 1] * 256;
-      src_sb = (long)pH[l] * pW[l] * 256;
+      const long prev_sb = l == 1 ? (long)N * C : (long)pH[l - 1] * pW[l - 1] * C;
+      src_sb = (long)pH[l] * pW[l] * C;
       plain[l - 1].alloc((long)B * src_sb);
-      launch_pool_features_sf(prev, B, pH[l - 1], pW[l - 1], 256, prev_sb, plain[l - 1].p, src_sb, st);
+      launch_pool_features_sf(prev, B, pH[l - 1], pW[l - 1], C, prev_sb, plain[l - 1].p, src_sb, st);
       src = plain[l - 1].p;
     }
-    fbrick[l].alloc((long)B * bp.NB[l] * 256);
-    launch_brick_rows(src, src_sb, B, pH[l], pW[l], 256, 256, fbrick[l].p, (long)bp.NB[l] * 256, st);
+    fbrick[l].alloc((long)B * bp.NB[l] * C);
+    launch_brick_rows(src, src_sb, B, pH[l], pW[l], C, C, fbrick[l].p, (long)bp.NB[l] * C, st);
     pyr[l].alloc((long)B * bp.NPB * kBrickPixelBlock * bp.NB[l]);
-    launch_corr_bricks(f1.p, (long)N * 256, fbrick[l].p, (long)bp.NB[l] * 256, B, N, bp.NB[l], 256, 1.0f / sqrtf(256.0f), pyr[l].p, false, st);
+    launch_corr_bricks(f1.p, (long)N * C, fbrick[l].p, (long)bp.NB[l] * C, B, N, bp.NB[l], C, 1.0f / sqrtf((float)C), pyr[l].p, fast != 0, st);
     bp.base[l] = pyr[l].p;
     if (rowmajor[l]) launch_unbrick(pyr[l].p, bp.NB[l], N, pH[l], pW[l], n8, rowmajor[l], st);
   }
@@ -715,7 +726,7 @@ int atdn_corr_lookup_bricks(const float* fmap1, const float* fmap2, int B, int H
     A.upload();
     resolve(A, L);
     csf.alloc(n8 * 256);
-    launch_lookup_conv(bp, coords, n8, nullptr, L.wf16, L.wscale, L.b, csf.p, false, st);
+    launch_lookup_conv(bp, coords, n8, nullptr, L.wf16, L.wscale, L.b, csf.p, fast != 0, st);
     launch_from_sf(csf.p, cor1, n8, 256, st);
     ATDN_HIP(hipStreamSynchronize(st));
   }
@@ -803,8 +814,11 @@ int atdn_conv2d_nhwc_sf_epi(const float* src, int nimg, int H, int W, int Cin, c
                             float* dst, void* stream) {
   ATDN_API_BEGIN
   ATDN_CHECK(src && weight_host && dst && nimg >= 1 && Cin % 32 == 0, "bad argument (Cin must be a multiple of 32)");
-  ATDN_CHECK(sf_store >= 0 && sf_store <= 7 && (sf_store & 6) != 6, "sf_store: bit 0 names the epilogue, bit 1 or bit 2 the tile form");
+  ATDN_CHECK(sf_store >= 0 && sf_store <= 15 && (sf_store & 6) != 6,
+             "sf_store: bit 0 names the epilogue, bit 1 or bit 2 the tile form, bit 3 the plain-f16 (FAST) kernels");
   const int tile_form = (sf_store & 2) ? 1 : (sf_store & 4) ? 2 : 0;   // 1x5 / 5x1: rectangular 8 x 16 x 128 tiles / run tiles
+  // bit 3: the dispatch below runs as it does inside a precision-mode-2 forward; the flag is back at its old value on return
+  FastGuard fast_scope((sf_store & 8) != 0);
   sf_store &= 1;
   ATDN_CHECK(!sf_store || Cout % 32 == 0, "the split-f16 store needs Cout % 32 == 0");
   StateDict sd;

@@ -268,6 +268,16 @@ inline void launch_conv_sf(const ConvShape& s, float wscale, const Epi& ep, hipS
 // hi x hi MFMA of every product while this is set (GmaNet sets it around its forward).
 bool& sf_fast_mode();
 
+// Sets the flag for a scope and puts the previous value back (also when the scope is left by an exception): GmaNet's forward in
+// precision mode 2, and the unit-test entry atdn_conv2d_nhwc_sf_epi when its caller asks for the FAST builds.
+struct FastGuard {
+  bool prev;
+  explicit FastGuard(bool on) : prev(sf_fast_mode()) { sf_fast_mode() = on; }
+  ~FastGuard() { sf_fast_mode() = prev; }
+  FastGuard(const FastGuard&) = delete;
+  FastGuard& operator=(const FastGuard&) = delete;
+};
+
 // The run-time flag as the kernels' FAST template argument: f(std::true_type{}) or f(std::false_type{}), so that a launch ladder
 // is written once for both arithmetic modes.
 template <class F>

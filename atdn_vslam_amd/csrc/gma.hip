@@ -36,12 +36,7 @@ extern template void conv_sf_dispatch_pair<SfBias<ACT_RELU>>(const ConvShape&, f
 
 namespace {
 
-// precision mode 2: the sf convolutions of this thread issue only the hi x hi MFMA while the guard lives (conv_sf.h)
-struct FastGuard {
-  bool prev;
-  explicit FastGuard(bool on) : prev(sf_fast_mode()) { sf_fast_mode() = on; }
-  ~FastGuard() { sf_fast_mode() = prev; }
-};
+// (precision mode 2: the sf convolutions of this thread issue only the hi x hi MFMA while a FastGuard lives, conv_sf.h)
 
 constexpr int XLD = 384;       // GRU input x = [inp | motion(126) flow(2) | motion_global]  (update.py:130)
 constexpr int CORR_LD = 352;   // 4*81 lookup channels padded to a multiple of 32

@@ -1158,7 +1158,9 @@ int atdn_corr_pyramid(const float* fmap1, const float* fmap2, int B, int H8, int
  * bench.py times: corr_bricks_kernel for all four levels (corr.py:16-30,55-63; levels 1-3 from 2x2-pooled target features,
  * avg_pool2d commutes with the dot product), the brick-major pyramid, and lookup_conv_kernel (corr.py:32-53 +
  * utils/utils.py:59-73 bilinear_sampler; fused with convc1 of update.py:76-78). fmap1, fmap2 fp32 channels-last
- * [B][H8*W8][256] (C must be 256); coords [B*H8*W8][2] (x, y) or NULL when no lookup is wanted. Every output is optional
+ * [B][H8*W8][C], C = 256 (corr_bricks_kernel) or 160 (corr_bricks_kernel_k160, the chunk count the network's folded feature head
+ * runs; here all 160 channels are caller features), volume = <f1, f2> / sqrt(C); coords [B*H8*W8][2] (x, y) or NULL when no
+ * lookup is wanted. Every output is optional
  * (NULL skips it): pyr0..pyr3 = the levels un-bricked to the reference's row-major [B*H8*W8][H_l*W_l]; samples
  * [B*H8*W8][324], channel l*81 + i*9 + j (the FUSED = false instantiation of the sampling code); cor1 [B*H8*W8][256] =
  * relu(convc1(samples)) from the fused instantiation, with convc1's HOST weight [256][324] (torch layout [256,324,1,1])
@@ -1166,6 +1168,13 @@ int atdn_corr_pyramid(const float* fmap1, const float* fmap2, int B, int H8, int
 int atdn_corr_lookup_bricks(const float* fmap1, const float* fmap2, int B, int H8, int W8, int C, const float* coords,
                             float* pyr0, float* pyr1, float* pyr2, float* pyr3, float* samples,
                             const float* convc1_weight_host, const float* convc1_bias_host, float* cor1, void* stream);
+/* ... with the arithmetic named: fast = 0 is the call above (three f16 MFMAs per product), fast = 1 the plain-f16 builds of
+ * the same kernels (precision "f16": the hi x hi product alone) — corr_bricks_kernel<true> / corr_bricks_kernel_k160<true> and
+ * lookup_conv_kernel<true, true>. `samples` comes from the sampling-only instantiation in either mode. */
+int atdn_corr_lookup_bricks_mode(const float* fmap1, const float* fmap2, int B, int H8, int W8, int C, const float* coords,
+                                 float* pyr0, float* pyr1, float* pyr2, float* pyr3, float* samples,
+                                 const float* convc1_weight_host, const float* convc1_bias_host, float* cor1, int fast,
+                                 void* stream);
 
 /* Generic NHWC convolution through the implicit-GEMM MFMA engine: src [nimg][H][W][Cin] (Cin % 32 == 0 or
  * Cin in {4,16}), HOST weight in torch layout [Cout][Cin][KH][KW] (+ HOST bias or NULL), dst
@@ -1184,7 +1193,10 @@ int atdn_conv2d_nhwc_sf(const float* src, int nimg, int H, int W, int Cin, const
  * Tests of the 1x5 / 5x1 halo-patch kernels add one of two bits, which change the tiling and never the result: bit 1 (values 2, 3:
  * the epilogue of 0, 1) runs them on the rectangular 8 x 16-pixel x 128-channel tiles, bit 2 (values 4, 5) on the 128-pixel run
  * tiles where the shape allows them (run length >= 43), both whatever the grid size; without them the product's dispatch rules
- * choose, which take small grids to smaller tiles. Other kernel shapes ignore the bits. */
+ * choose, which take small grids to smaller tiles. Other kernel shapes ignore the bits.
+ * Bit 3 (value 8, combined with any of the above: 8..13) runs the dispatch as a precision-"f16" forward does: the FAST builds of
+ * the same kernels, which issue the hi x hi MFMA alone, i.e. wscale * sum f16(x) * f16(w / wscale) + bias in fp32. The setting
+ * lasts for this call only. Valid values: 0..15 with (sf_store & 6) != 6. */
 int atdn_conv2d_nhwc_sf_epi(const float* src, int nimg, int H, int W, int Cin, const float* weight_host,
                             const float* bias_host, int Cout, int KH, int KW, int stride, int padH, int padW, int sf_store,
                             float* dst, void* stream);
