@@ -208,18 +208,21 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvGeom g, const 
       if constexpr (Epi::kStats) {
         // per-column (sum, M2) of this 32-row group for instance norm, combined across the two lane halves
         const float bias = nok ? biasj[j] : 0.f;
+        // (the sum in fp64, rounded once: a running fp32 sum of a flat frame's DC level rounds alike in every group, and the
+        // channel mean ends up several ulp off under an rstd of up to 316; stem_sf.hip)
         float v[16];
-        float sum = 0.f;
+        double dsum = 0.0;
         int cnt = 0;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int m = mbase + (e & 3) + 8 * (e >> 2) + 4 * h;
           v[e] = acc[i][j][e] + bias;
-          if (m < HoWo) { sum += v[e]; ++cnt; }
+          if (m < HoWo) { dsum += (double)v[e]; ++cnt; }
         }
-        sum += __shfl_xor(sum, 32);
+        dsum += __shfl_xor(dsum, 32);
         cnt += __shfl_xor(cnt, 32);
-        const float mean = sum / (float)(cnt > 0 ? cnt : 1);
+        const float sum = (float)dsum;
+        const float mean = (float)(dsum / (double)(cnt > 0 ? cnt : 1));
         float m2 = 0.f;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {

@@ -230,15 +230,19 @@ __global__ __launch_bounds__(256, MODE == 1 ? 4 : 3) void stem_sf_kernel(const S
       if constexpr (MODE == 3) {
         // statistics of the row tile's 32 pixels from the slab: lane = channel, the pixels in order (the grouping and the order
         // follow from the layer's geometry alone: a clip, a continued clip and single pairs produce the same bits)
+        // The sum runs in fp64 and is rounded once: on a flat frame the 32 values are one DC level, a running fp32 sum k * v
+        // rounds at every step the SAME way in every group of the image, and the channel mean ends up several ulp off — which the
+        // first norm's rstd (up to 1 / sqrt(eps) = 316 on such frames) multiplies (tests/test_gpu_flow_content.py).
         float v[32];
-        float sum = 0.f;
+        double dsum = 0.0;
         int cnt = 0;
 #pragma unroll
         for (int px = 0; px < 32; ++px) {
           v[px] = *reinterpret_cast<const float*>(slab + px * SLAB_PITCH + lane * 4);
-          if (oy < a.Ho && tx0 + px < a.Wo) { sum += v[px]; ++cnt; }
+          if (oy < a.Ho && tx0 + px < a.Wo) { dsum += (double)v[px]; ++cnt; }
         }
-        const float mean = sum / (float)(cnt > 0 ? cnt : 1);
+        const float sum = (float)dsum;
+        const float mean = (float)(dsum / (double)(cnt > 0 ? cnt : 1));
         float m2 = 0.f;
 #pragma unroll
         for (int px = 0; px < 32; ++px)
