@@ -193,6 +193,44 @@ def check(rc):
         raise RuntimeError("libatdn_hip: " + lib().atdn_last_error().decode("utf-8", "replace"))
 
 
+def ptr(t):
+    """A tensor's data as a `void*` argument of the library; None stays None (a null pointer)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream():
+    """The current stream of the current device, as the library's `void* stream` argument."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def call(name, device, *args, workspace=None):
+    """Entry point `name` for tensors on `device`. A CUDA device: `name(*args, [workspace,] stream)` under that device, on its
+    current stream. Otherwise the host twin `name + "_host"` with `args` alone (the convention of every such pair in SIGNATURES:
+    the host form takes the device form's arguments without the workspace and the stream)."""
+    import torch
+    if device.type == "cuda":
+        with torch.cuda.device(device):
+            if workspace is not None:
+                args += (ptr(workspace),)
+            check(getattr(lib(), name)(*args, stream()))
+    else:
+        check(getattr(lib(), name + "_host")(*args))
+
+
+def workspace(symbol, device, *dims, message=None):
+    """The workspace a device entry point asks for through its `*_workspace_bytes` function `symbol(*dims)`: a float64 tensor
+    (8-byte aligned) of at least 8 bytes on `device`; None on the host, whose forms take none. A size <= 0 (dimensions out of
+    range) raises `message` where one is given, and otherwise leaves the refusal to the entry point."""
+    import torch
+    if device.type != "cuda":
+        return None
+    n = int(getattr(lib(), symbol)(*dims))
+    if n <= 0 and message:
+        raise RuntimeError(message)
+    return torch.empty((max(n, 8) + 7) // 8, dtype=torch.float64, device=device)
+
+
 def load_state(load_fn, handle, state):
     """Feed a {key: tensor/ndarray} state dict to atdn_*_load (float entries only)."""
     import numpy as np

@@ -442,25 +442,63 @@ __global__ __launch_bounds__(BA_FIN_THREADS) void ba_finalise_kernel(const doubl
   }
 }
 
-// Argument rules shared by the device entry points below and the host ones (capi.hip). out[i] of out_bytes[i]: the outputs
-// (a workspace among them), none of which may be null or overlap an input or another output.
-void bundle_check_args(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
-                       const float* depth_init, const unsigned char* mask, int N, int B, int S, int H, int W, double fx, double fy,
-                       double cx, double cy, int stride, int iters, double scale_px, double inlier_px, double min_z, int min_views,
-                       bool grid_limit, const void* const* out, const long* out_bytes, int n_out) {
-  ATDN_CHECK(acc_bank && alive_bank && poses && slots, "null argument");
-  ATDN_CHECK(depth_init, "depth_init is mandatory");
-  check_plane_solver(B, H, W, grid_limit, fx, fy, cx, cy, scale_px, inlier_px, out, n_out);
-  ATDN_CHECK(N >= 1, "the bank is empty (N >= 1)");
-  ATDN_CHECK(S >= 1 && S <= BA_MAX_VIEWS, "S must be in [1, ATDN_MULTIVIEW_MAX_VIEWS]");
-  ATDN_CHECK(min_views >= 1 && min_views <= S, "min_views must be in [1, S]");
-  ATDN_CHECK(stride >= 1, "stride must be >= 1");
-  ATDN_CHECK(iters >= 0 && iters <= 16, "iters must be in [0, 16]");
-  ATDN_CHECK(std::isfinite(min_z) && min_z > 0.0, "min_z must be finite and > 0");
-  const long n = (long)H * W;
-  const void* in[6] = {acc_bank, alive_bank, poses, slots, depth_init, mask};
-  const long in_bytes[6] = {(long)N * 2 * n * 4, (long)N * n, (long)N * 48, (long)B * S * 4, (long)B * n * 4, (long)B * n};
+struct BundleCall {
+  const float* acc_bank;
+  const unsigned char* alive_bank;
+  const float* poses;
+  const int* slots;
+  const float* depth_init;
+  const unsigned char* mask;   // may be null
+  int N, B, S, H, W;
+  double fx, fy, cx, cy;
+  int stride, iters;
+  double scale_px, inlier_px, min_z;
+  int min_views;
+};
+
+// What the sizes of the outputs rest on, checked before they are formed. The device form (`device`) limits B to gridDim.y.
+static void bundle_check_sizes(const BundleCall& c, bool device) {
+  ATDN_CHECK(c.S >= 1 && c.S <= BA_MAX_VIEWS && c.stride >= 1, "S must be in [1, ATDN_MULTIVIEW_MAX_VIEWS] and stride >= 1");
+  check_plane_batch(c.B, c.H, c.W, device);
+}
+
+// Argument rules of an entry pair, after bundle_check_sizes. out[i] of out_bytes[i]: the outputs (the device form's workspace
+// among them), none of which may be null or overlap an input or another output. Returns the parameters of the call.
+static BundleParams bundle_check_args(const BundleCall& c, bool device, const void* const* out, const long* out_bytes, int n_out) {
+  ATDN_CHECK(c.acc_bank && c.alive_bank && c.poses && c.slots, "null argument");
+  ATDN_CHECK(c.depth_init, "depth_init is mandatory");
+  check_plane_solver(c.B, c.H, c.W, device, c.fx, c.fy, c.cx, c.cy, c.scale_px, c.inlier_px, out, n_out);
+  ATDN_CHECK(c.N >= 1, "the bank is empty (N >= 1)");
+  ATDN_CHECK(c.S >= 1 && c.S <= BA_MAX_VIEWS, "S must be in [1, ATDN_MULTIVIEW_MAX_VIEWS]");
+  ATDN_CHECK(c.min_views >= 1 && c.min_views <= c.S, "min_views must be in [1, S]");
+  ATDN_CHECK(c.stride >= 1, "stride must be >= 1");
+  ATDN_CHECK(c.iters >= 0 && c.iters <= 16, "iters must be in [0, 16]");
+  ATDN_CHECK(std::isfinite(c.min_z) && c.min_z > 0.0, "min_z must be finite and > 0");
+  const long n = (long)c.H * c.W;
+  const void* in[6] = {c.acc_bank, c.alive_bank, c.poses, c.slots, c.depth_init, c.mask};
+  const long in_bytes[6] = {(long)c.N * 2 * n * 4, (long)c.N * n, (long)c.N * 48, (long)c.B * c.S * 4, (long)c.B * n * 4,
+                            (long)c.B * n};
   check_disjoint(in, in_bytes, 6, out, out_bytes, n_out);
+  return bundle_params(c.fx, c.fy, c.cx, c.cy, c.scale_px, c.inlier_px, c.min_z, c.min_views, c.iters, c.stride, c.H, c.W);
+}
+
+// Both forms of atdn_bundle_terms (iters of the call: 0)
+static BundleParams bundle_terms_args(const BundleCall& c, double* sums, int* counts, bool device, void* workspace) {
+  bundle_check_sizes(c, device);
+  const void* out[3] = {sums, counts, workspace};
+  const long out_bytes[3] = {(long)c.B * ba_sums(c.S) * 8, (long)c.B * 12,
+                             (long)ba_workspace_size(c.B, c.S, c.H, c.W, c.stride)};
+  return bundle_check_args(c, device, out, out_bytes, device ? 3 : 2);
+}
+
+// Both forms of atdn_bundle_adjust
+static BundleParams bundle_adjust_args(const BundleCall& c, float* poses_out, float* depth, double* cost, int* counts, bool device,
+                                       void* workspace) {
+  bundle_check_sizes(c, device);
+  const void* out[5] = {poses_out, depth, cost, counts, workspace};
+  const long out_bytes[5] = {(long)c.B * c.S * 48, (long)c.B * c.H * c.W * 4, (long)c.B * 16, (long)c.B * 16,
+                             (long)ba_workspace_size(c.B, c.S, c.H, c.W, c.stride)};
+  return bundle_check_args(c, device, out, out_bytes, device ? 5 : 4);
 }
 
 static void ba_launch_terms(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
@@ -486,14 +524,10 @@ int atdn_bundle_terms(const float* acc_bank, const unsigned char* alive_bank, co
                       double cx, double cy, int stride, double scale_px, double inlier_px, double min_z, int min_views, double* sums,
                       int* counts, void* workspace, void* stream) {
   ATDN_API_BEGIN
-  ATDN_CHECK(S >= 1 && S <= BA_MAX_VIEWS && stride >= 1, "S must be in [1, ATDN_MULTIVIEW_MAX_VIEWS] and stride >= 1");
-  check_plane_batch(B, H, W);
-  const void* out[3] = {sums, counts, workspace};
-  const long out_bytes[3] = {(long)B * ba_sums(S) * 8, (long)B * 12, (long)ba_workspace_size(B, S, H, W, stride)};
-  bundle_check_args(acc_bank, alive_bank, poses, slots, depth, mask, N, B, S, H, W, fx, fy, cx, cy, stride, 0, scale_px, inlier_px,
-                    min_z, min_views, true, out, out_bytes, 3);
+  const BundleCall a{acc_bank, alive_bank, poses, slots, depth, mask, N, B, S, H, W, fx, fy, cx, cy, stride, 0,
+                     scale_px, inlier_px, min_z, min_views};
+  const BundleParams c = bundle_terms_args(a, sums, counts, true, workspace);
   ATDN_CHECK(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)sums & 7) == 0, "workspace and sums must be 8-byte aligned");
-  const BundleParams c = bundle_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, min_views, 0, stride, H, W);
   const BaWorkspace ws = ba_carve(workspace, B, S, H, W, stride);
   ba_launch_terms(acc_bank, alive_bank, poses, slots, depth, mask, N, B, S, H, W, c, 0, ws, (hipStream_t)stream);
   hipLaunchKernelGGL(ba_finalise_kernel, dim3((unsigned)B), dim3(BA_FIN_THREADS), 0, (hipStream_t)stream, ws.csums, ws.ccounts,
@@ -503,21 +537,27 @@ int atdn_bundle_terms(const float* acc_bank, const unsigned char* alive_bank, co
   ATDN_API_END
 }
 
+int atdn_bundle_terms_host(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
+                           const float* depth, const unsigned char* mask, int N, int B, int S, int H, int W, double fx, double fy,
+                           double cx, double cy, int stride, double scale_px, double inlier_px, double min_z, int min_views,
+                           double* sums, int* counts) {
+  ATDN_API_BEGIN
+  const BundleCall a{acc_bank, alive_bank, poses, slots, depth, mask, N, B, S, H, W, fx, fy, cx, cy, stride, 0,
+                     scale_px, inlier_px, min_z, min_views};
+  const BundleParams c = bundle_terms_args(a, sums, counts, false, nullptr);
+  bundle_terms_host(acc_bank, alive_bank, poses, slots, depth, mask, N, B, S, H, W, c, sums, counts);
+  ATDN_API_END
+}
+
 int atdn_bundle_adjust(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
                        const float* depth_init, const unsigned char* mask, int N, int B, int S, int H, int W, double fx, double fy,
                        double cx, double cy, int stride, int iters, double scale_px, double inlier_px, double min_z, int min_views,
                        float* poses_out, float* depth, double* cost, int* counts, void* workspace, void* stream) {
   ATDN_API_BEGIN
-  ATDN_CHECK(S >= 1 && S <= BA_MAX_VIEWS && stride >= 1, "S must be in [1, ATDN_MULTIVIEW_MAX_VIEWS] and stride >= 1");
-  check_plane_batch(B, H, W);
-  const long n = (long)H * W;
-  const void* out[5] = {poses_out, depth, cost, counts, workspace};
-  const long out_bytes[5] = {(long)B * S * 48, (long)B * n * 4, (long)B * 16, (long)B * 16,
-                             (long)ba_workspace_size(B, S, H, W, stride)};
-  bundle_check_args(acc_bank, alive_bank, poses, slots, depth_init, mask, N, B, S, H, W, fx, fy, cx, cy, stride, iters, scale_px,
-                    inlier_px, min_z, min_views, true, out, out_bytes, 5);
+  const BundleCall a{acc_bank, alive_bank, poses, slots, depth_init, mask, N, B, S, H, W, fx, fy, cx, cy, stride, iters,
+                     scale_px, inlier_px, min_z, min_views};
+  const BundleParams c = bundle_adjust_args(a, poses_out, depth, cost, counts, true, workspace);
   ATDN_CHECK(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)cost & 7) == 0, "workspace and cost must be 8-byte aligned");
-  const BundleParams c = bundle_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, min_views, iters, stride, H, W);
   const BaWorkspace ws = ba_carve(workspace, B, S, H, W, stride);
   for (int k = 0; k <= iters; ++k) {
     ba_launch_terms(acc_bank, alive_bank, poses, slots, depth_init, mask, N, B, S, H, W, c, k, ws, (hipStream_t)stream);
@@ -526,5 +566,17 @@ int atdn_bundle_adjust(const float* acc_bank, const unsigned char* alive_bank, c
                        poses, slots, (double*)nullptr, counts, poses_out, depth, cost);
     ATDN_HIP(hipGetLastError());
   }
+  ATDN_API_END
+}
+
+int atdn_bundle_adjust_host(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
+                            const float* depth_init, const unsigned char* mask, int N, int B, int S, int H, int W, double fx,
+                            double fy, double cx, double cy, int stride, int iters, double scale_px, double inlier_px, double min_z,
+                            int min_views, float* poses_out, float* depth, double* cost, int* counts) {
+  ATDN_API_BEGIN
+  const BundleCall a{acc_bank, alive_bank, poses, slots, depth_init, mask, N, B, S, H, W, fx, fy, cx, cy, stride, iters,
+                     scale_px, inlier_px, min_z, min_views};
+  const BundleParams c = bundle_adjust_args(a, poses_out, depth, cost, counts, false, nullptr);
+  bundle_adjust_host(acc_bank, alive_bank, poses, slots, depth_init, mask, N, B, S, H, W, c, poses_out, depth, cost, counts);
   ATDN_API_END
 }

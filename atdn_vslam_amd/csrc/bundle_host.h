@@ -3,7 +3,7 @@
 // complement (the other half of multiview_depth_host.h, and the coupling of the two). The rule in plain C++ float64 (no HIP
 // needed): ba_view is what one view of one candidate contributes, ba_backsub the depth step of a candidate, ba_decide /
 // ba_system_entry / ldln_* / ba_retract_view the step on the reduced 6S x 6S system, bundle_terms_host / bundle_adjust_host the
-// host forms behind atdn_bundle_terms_host / atdn_bundle_adjust_host (capi.hip), which serve CPU tensors. The kernels of
+// host forms behind atdn_bundle_terms_host / atdn_bundle_adjust_host (bundle.hip), which serve CPU tensors. The kernels of
 // bundle.hip call the same functions, so the two cannot drift apart; the independent statement the tests compare both with is
 // tests/bundle_ref.py (NumPy). The rule is stated in full in include/atdn_hip.h, atdn_bundle_adjust; only + - * / and
 // comparisons, every operation rounded on its own (fp contraction off). The robust loss, the cost of a point behind a camera and

@@ -11,19 +11,7 @@
 #include "train_kernels.h"  // launch_clvo_loss_composite
 #include "frontend.h"
 #include "conv_sf.h"
-#include "depth_fusion_host.h"
 #include "epilogues_sf.h"
-#include "epipolar_host.h"
-#include "flow_args.h"
-#include "flow_consistency_host.h"
-#include "flow_track_host.h"
-#include "bundle_host.h"
-#include "ground_host.h"
-#include "multiview_depth_host.h"
-#include "pnp_host.h"
-#include "two_view_host.h"
-#include "voxel_map_host.h"
-#include "warm_start_host.h"
 
 namespace atdn {
 extern template TileChoice conv_dispatch<MODE_TAP, EpiBias<ACT_NONE>>(const ConvShape&, EpiBias<ACT_NONE>, hipStream_t);
@@ -389,238 +377,6 @@ int atdn_pose_accumulate_f32(float* pose16, const float* rot, const float* tr) {
   make_transform(rot, tr, m);
   matmul4(pose16, m, o);
   for (int i = 0; i < 16; ++i) pose16[i] = o[i];
-  ATDN_API_END
-}
-
-// ------------------------------------------------------------------ warm start (host twin of warm_start.hip)
-int atdn_flow_forward_interpolate_host(const float* flow_low, int B, int h, int w, float* out) {
-  ATDN_API_BEGIN
-  ATDN_CHECK(flow_low && out, "null argument");
-  ATDN_CHECK(B >= 1 && h >= 1 && w >= 1 && (long)h * w <= (1L << 24), "bad batch or grid size");
-  const long bytes = (long)B * 2 * h * w * 4;
-  ATDN_CHECK(disjoint(flow_low, bytes, out, bytes), "input and output overlap");
-  forward_interpolate_host(flow_low, B, h, w, out);
-  ATDN_API_END
-}
-
-// ------------------------------------------------------------------ flow consistency (host twin of flow_consistency.hip)
-int atdn_flow_consistency_host(const float* flow_fw, const float* flow_bw, int B, int H, int W, double alpha1, double alpha2,
-                               unsigned char* mask, int* count) {
-  ATDN_API_BEGIN
-  flow_consistency_check_args(flow_fw, flow_bw, B, H, W, alpha1, alpha2, mask, count);
-  flow_consistency_host(flow_fw, flow_bw, B, H, W, alpha1, alpha2, mask, count);
-  ATDN_API_END
-}
-
-// ------------------------------------------------------------------ two-view depth (host twin of two_view.hip)
-int atdn_flow_two_view_depth_host(const float* flow, const float* pose, const unsigned char* mask, int B, int H, int W, double fx,
-                                  double fy, double cx, double cy, double max_epipolar, double min_sin2, double max_depth,
-                                  float* depth, int* counts) {
-  ATDN_API_BEGIN
-  const TwoViewCamera cam{fx, fy, cx, cy, max_epipolar, min_sin2, max_depth};
-  two_view_check_args(flow, pose, mask, B, H, W, cam, depth, counts);
-  two_view_depth_host(flow, pose, mask, B, H, W, cam, depth, counts);
-  ATDN_API_END
-}
-
-// ------------------------------------------------------------------ flow track (host twin of flow_track.hip)
-int atdn_flow_track_step_host(const float* flow, const unsigned char* mask, const float* acc_in, const unsigned char* alive_in,
-                              int B, int H, int W, float* acc_out, unsigned char* alive_out, const float* pose, double fx,
-                              double fy, double cx, double cy, double max_epipolar, double min_sin2, double max_depth, float* depth,
-                              int* counts) {
-  ATDN_API_BEGIN
-  const TwoViewCamera cam{fx, fy, cx, cy, max_epipolar, min_sin2, max_depth};
-  flow_track_check_args(flow, mask, acc_in, alive_in, B, H, W, acc_out, alive_out, pose, cam, depth, counts);
-  flow_track_step_host(flow, mask, acc_in, alive_in, B, H, W, acc_out, alive_out, pose, cam, depth, counts);
-  ATDN_API_END
-}
-
-// ------------------------------------------------------------------ depth fusion (host twin of depth_fusion.hip)
-int atdn_depth_fuse_host(const float* bank, const float* poses, const int* targets, const int* sources, int N, int B, int S, int H,
-                         int W, double fx, double fy, double cx, double cy, double max_reproj, double max_rel_depth, int min_views,
-                         double min_z, int average, float* fused, unsigned char* views, int* counts) {
-  ATDN_API_BEGIN
-  depth_fuse_check_args(bank, poses, targets, sources, N, B, S, H, W, fx, fy, cx, cy, max_reproj, max_rel_depth, min_views, min_z,
-                        fused, views, counts);
-  depth_fuse_host(bank, poses, targets, sources, N, B, S, H, W,
-                  depth_fuse_params(fx, fy, cx, cy, max_reproj, max_rel_depth, min_views, min_z, average), fused, views, counts);
-  ATDN_API_END
-}
-
-// ------------------------------------------------------------------ voxel map (host twins of voxel_map.hip)
-int atdn_voxel_clear_host(void* table, long capacity) {
-  ATDN_API_BEGIN
-  voxel_check_table(table, capacity);
-  voxel_clear_host((uint64_t*)table, capacity);
-  ATDN_API_END
-}
-int atdn_voxel_integrate_host(const float* depth, const float* poses, const uint8_t* images, const uint8_t* mask, const int* indices,
-                              int N, int K, int H, int W, double fx, double fy, double cx, double cy, int stride, double voxel,
-                              double ox, double oy, double oz, double min_z, double max_z, int retry, void* table, long capacity,
-                              uint8_t* pending) {
-  ATDN_API_BEGIN
-  voxel_check_integrate(depth, poses, images, mask, indices, N, K, H, W, fx, fy, cx, cy, stride, voxel, ox, oy, oz, min_z, max_z,
-                        table, capacity, pending);
-  voxel_integrate_host(depth, poses, images, mask, indices, N, K, H, W,
-                       voxel_params(fx, fy, cx, cy, stride, voxel, ox, oy, oz, min_z, max_z), retry != 0, (uint64_t*)table, capacity,
-                       pending);
-  ATDN_API_END
-}
-int atdn_voxel_rehash_host(const void* src, long src_capacity, void* dst, long dst_capacity) {
-  ATDN_API_BEGIN
-  voxel_check_rehash(src, src_capacity, dst, dst_capacity);
-  voxel_rehash_host((const uint64_t*)src, src_capacity, (uint64_t*)dst, dst_capacity);
-  ATDN_API_END
-}
-int atdn_voxel_extract_host(void* table, long capacity, int min_count, double voxel, double ox, double oy, double oz,
-                            long max_out, float* points, uint8_t* colors, int* counts, int64_t* keys, int64_t* found) {
-  ATDN_API_BEGIN
-  voxel_check_extract(table, capacity, min_count, voxel, ox, oy, oz, max_out, points, colors, counts, keys, found);
-  voxel_extract_host((const uint64_t*)table, capacity, min_count, voxel_params(1.0, 1.0, 0.0, 0.0, 1, voxel, ox, oy, oz, 0.0, 0.0),
-                     max_out, points, colors, counts, keys, found);
-  ATDN_API_END
-}
-
-// ------------------------------------------------------------------ bundle adjustment (host twins of bundle.hip)
-int atdn_bundle_terms_host(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
-                           const float* depth, const unsigned char* mask, int N, int B, int S, int H, int W, double fx, double fy,
-                           double cx, double cy, int stride, double scale_px, double inlier_px, double min_z, int min_views,
-                           double* sums, int* counts) {
-  ATDN_API_BEGIN
-  ATDN_CHECK(S >= 1 && S <= BA_MAX_VIEWS && stride >= 1, "S must be in [1, ATDN_MULTIVIEW_MAX_VIEWS] and stride >= 1");
-  check_plane_batch(B, H, W, false);
-  const void* out[2] = {sums, counts};
-  const long out_bytes[2] = {(long)B * ba_sums(S) * 8, (long)B * 12};
-  bundle_check_args(acc_bank, alive_bank, poses, slots, depth, mask, N, B, S, H, W, fx, fy, cx, cy, stride, 0, scale_px, inlier_px,
-                    min_z, min_views, false, out, out_bytes, 2);
-  bundle_terms_host(acc_bank, alive_bank, poses, slots, depth, mask, N, B, S, H, W,
-                    bundle_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, min_views, 0, stride, H, W), sums, counts);
-  ATDN_API_END
-}
-
-int atdn_bundle_adjust_host(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
-                            const float* depth_init, const unsigned char* mask, int N, int B, int S, int H, int W, double fx,
-                            double fy, double cx, double cy, int stride, int iters, double scale_px, double inlier_px, double min_z,
-                            int min_views, float* poses_out, float* depth, double* cost, int* counts) {
-  ATDN_API_BEGIN
-  ATDN_CHECK(S >= 1 && S <= BA_MAX_VIEWS && stride >= 1, "S must be in [1, ATDN_MULTIVIEW_MAX_VIEWS] and stride >= 1");
-  check_plane_batch(B, H, W, false);
-  const long n = (long)H * W;
-  const void* out[4] = {poses_out, depth, cost, counts};
-  const long out_bytes[4] = {(long)B * S * 48, (long)B * n * 4, (long)B * 16, (long)B * 16};
-  bundle_check_args(acc_bank, alive_bank, poses, slots, depth_init, mask, N, B, S, H, W, fx, fy, cx, cy, stride, iters, scale_px,
-                    inlier_px, min_z, min_views, false, out, out_bytes, 4);
-  bundle_adjust_host(acc_bank, alive_bank, poses, slots, depth_init, mask, N, B, S, H, W,
-                     bundle_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, min_views, iters, stride, H, W), poses_out, depth,
-                     cost, counts);
-  ATDN_API_END
-}
-
-// ------------------------------------------------------------------ multi-view depth (host twin of multiview_depth.hip)
-int atdn_multiview_depth_host(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
-                              const float* depth_init, int N, int B, int S, int H, int W, double fx, double fy, double cx, double cy,
-                              double scale_px, double inlier_px, double min_z, int min_views, double max_rel_sigma, double max_depth,
-                              int iters, float* depth, float* info, unsigned char* views, int* counts) {
-  ATDN_API_BEGIN
-  multiview_check_args(acc_bank, alive_bank, poses, slots, depth_init, N, B, S, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z,
-                       min_views, max_rel_sigma, max_depth, iters, depth, info, views, counts);
-  multiview_depth_host(acc_bank, alive_bank, poses, slots, depth_init, N, B, S, H, W,
-                       multiview_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, min_views, max_rel_sigma, max_depth, iters, H, W),
-                       depth, info, views, counts);
-  ATDN_API_END
-}
-
-// ------------------------------------------------------------------ pose from depth and flow (host twins of pnp.hip)
-int atdn_pnp_terms_host(const float* depth, const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W,
-                        double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, double* sums,
-                        int* counts) {
-  ATDN_API_BEGIN
-  const void* out[2] = {sums, counts};
-  const long out_bytes[2] = {(long)B * PNP_TERMS * 8, (long)B * 12};
-  pnp_check_args(depth, flow, mask, pose, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z, false, out, out_bytes, 2);
-  pnp_terms_host(depth, flow, mask, pose, B, H, W, pnp_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, H, W), sums, counts);
-  ATDN_API_END
-}
-
-int atdn_pnp_solve_host(const float* depth, const float* flow, const unsigned char* mask, const float* pose_init, int B, int H,
-                        int W, double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, int iters,
-                        float* pose_out, double* cost, int* counts) {
-  ATDN_API_BEGIN
-  const void* out[3] = {pose_out, cost, counts};
-  const long out_bytes[3] = {(long)B * 48, (long)B * 8, (long)B * 16};
-  pnp_check_args(depth, flow, mask, pose_init, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z, false, out, out_bytes, 3);
-  ATDN_CHECK(iters >= 0 && iters <= 64, "iters must be in [0, 64]");
-  pnp_solve_host(depth, flow, mask, pose_init, B, H, W, pnp_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, H, W), iters,
-                 pose_out, cost, counts);
-  ATDN_API_END
-}
-
-// ------------------------------------------------------------------ ground plane of a depth map (host twins of ground.hip)
-int atdn_ground_terms_host(const float* depth, const unsigned char* mask, const double* q, int B, int H, int W, int y0, int y1,
-                           double fx, double fy, double cx, double cy, double scale_rel, double inlier_rel, double min_z,
-                           double max_depth, double* sums, int* counts) {
-  ATDN_API_BEGIN
-  const void* out[2] = {sums, counts};
-  const long out_bytes[2] = {(long)B * GROUND_TERMS * 8, (long)B * 12};
-  ground_check_args(depth, mask, q, false, B, H, W, y0, y1, fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth, false, out,
-                    out_bytes, 2);
-  ground_terms_host(depth, mask, q, B, H, W, y1,
-                    ground_params(fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth, 0.0, 1.0, 0.0, 1, y0, W), sums, counts);
-  ATDN_API_END
-}
-
-int atdn_ground_solve_host(const float* depth, const unsigned char* mask, const double* q_init, int B, int H, int W, int y0, int y1,
-                           double fx, double fy, double cx, double cy, double nx, double ny, double nz, double scale_rel,
-                           double inlier_rel, double min_z, double max_depth, int min_votes, int iters, double* q, double* sums,
-                           int* counts) {
-  ATDN_API_BEGIN
-  const void* out[3] = {q, sums, counts};
-  const long out_bytes[3] = {(long)B * 24, (long)B * GROUND_TERMS * 8, (long)B * 24};
-  ground_check_args(depth, mask, q_init, true, B, H, W, y0, y1, fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth, false, out,
-                    out_bytes, 3);
-  ground_check_solve(nx, ny, nz, min_votes, iters);
-  ground_solve_host(depth, mask, q_init, B, H, W, y1,
-                    ground_params(fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth, nx, ny, nz, min_votes, y0, W), iters, q,
-                    sums, counts);
-  ATDN_API_END
-}
-
-int atdn_ground_classify_host(const float* depth, const unsigned char* mask, const double* q, int B, int H, int W, int y0, int y1,
-                              double fx, double fy, double cx, double cy, double inlier_rel, double min_z, double max_depth,
-                              float* residual, unsigned char* on_ground) {
-  ATDN_API_BEGIN
-  const long n = (long)H * W;
-  const void* out[2] = {residual, on_ground};
-  const long out_bytes[2] = {(long)B * n * 4, (long)B * n};
-  ground_check_args(depth, mask, q, false, B, H, W, y0, y1, fx, fy, cx, cy, 1.0, inlier_rel, min_z, max_depth, false, out, out_bytes,
-                    2);
-  ground_classify_host(depth, mask, q, B, H, W, y1,
-                       ground_params(fx, fy, cx, cy, 1.0, inlier_rel, min_z, max_depth, 0.0, 1.0, 0.0, 1, y0, W), residual,
-                       on_ground);
-  ATDN_API_END
-}
-
-// ------------------------------------------------------------------ pose from flow alone (host twins of epipolar.hip)
-int atdn_epipolar_terms_host(const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W, double fx,
-                             double fy, double cx, double cy, double scale_px, double inlier_px, double* sums, int* counts) {
-  ATDN_API_BEGIN
-  const void* out[2] = {sums, counts};
-  const long out_bytes[2] = {(long)B * PLANE_TERMS * 8, (long)B * 12};
-  epipolar_check_args(flow, mask, pose, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, false, out, out_bytes, 2);
-  epipolar_terms_host(flow, mask, pose, B, H, W, epipolar_params(fx, fy, cx, cy, scale_px, inlier_px), sums, counts);
-  ATDN_API_END
-}
-
-int atdn_epipolar_solve_host(const float* flow, const unsigned char* mask, const float* pose_init, int B, int H, int W, double fx,
-                             double fy, double cx, double cy, double scale_px, double inlier_px, int iters, float* pose_out,
-                             double* cost, int* counts) {
-  ATDN_API_BEGIN
-  const void* out[3] = {pose_out, cost, counts};
-  const long out_bytes[3] = {(long)B * 48, (long)B * 8, (long)B * 16};
-  epipolar_check_args(flow, mask, pose_init, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, false, out, out_bytes, 3);
-  ATDN_CHECK(iters >= 0 && iters <= 64, "iters must be in [0, 64]");
-  epipolar_solve_host(flow, mask, pose_init, B, H, W, epipolar_params(fx, fy, cx, cy, scale_px, inlier_px), iters, pose_out, cost,
-                      counts);
   ATDN_API_END
 }
 

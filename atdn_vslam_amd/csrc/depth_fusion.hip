@@ -100,10 +100,11 @@ __global__ __launch_bounds__(PQ_THREADS) void depth_fuse_kernel(const float* __r
   quad_count<3>(flags, bits, counts + 3 * b);
 }
 
-// Argument rules shared by the device entry point below and the host one (capi.hip).
-void depth_fuse_check_args(const float* bank, const float* poses, const int* targets, const int* sources, int N, int B, int S,
-                           int H, int W, double fx, double fy, double cx, double cy, double max_reproj, double max_rel_depth,
-                           int min_views, double min_z, const float* fused, const unsigned char* views, const int* counts) {
+// Argument rules shared by the two entry points below (sources may be null only when S == 0), and the parameters of the call.
+static DepthFuseParams depth_fuse_check_args(const float* bank, const float* poses, const int* targets, const int* sources, int N,
+                                             int B, int S, int H, int W, double fx, double fy, double cx, double cy,
+                                             double max_reproj, double max_rel_depth, int min_views, double min_z, int average,
+                                             const float* fused, const unsigned char* views, const int* counts) {
   ATDN_CHECK(bank && poses && targets && fused && views && counts && (sources || S == 0), "null argument");
   check_plane_batch(B, H, W);
   check_pinhole(fx, fy, cx, cy);
@@ -119,6 +120,7 @@ void depth_fuse_check_args(const float* bank, const float* poses, const int* tar
   const void* out[3] = {fused, views, counts};
   const long out_bytes[3] = {(long)B * n * 4, (long)B * n, (long)B * 12};
   check_disjoint(in, in_bytes, 4, out, out_bytes, 3);
+  return depth_fuse_params(fx, fy, cx, cy, max_reproj, max_rel_depth, min_views, min_z, average);
 }
 
 }  // namespace atdn
@@ -129,12 +131,21 @@ int atdn_depth_fuse(const float* bank, const float* poses, const int* targets, c
                     double fx, double fy, double cx, double cy, double max_reproj, double max_rel_depth, int min_views, double min_z,
                     int average, float* fused, unsigned char* views, int* counts, void* stream) {
   ATDN_API_BEGIN
-  depth_fuse_check_args(bank, poses, targets, sources, N, B, S, H, W, fx, fy, cx, cy, max_reproj, max_rel_depth, min_views, min_z,
-                        fused, views, counts);
+  const DepthFuseParams c = depth_fuse_check_args(bank, poses, targets, sources, N, B, S, H, W, fx, fy, cx, cy, max_reproj,
+                                                  max_rel_depth, min_views, min_z, average, fused, views, counts);
   ATDN_HIP(hipMemsetAsync(counts, 0, (size_t)B * 12, (hipStream_t)stream));
   hipLaunchKernelGGL(depth_fuse_kernel, dim3(quad_blocks((long)H * W, true), (unsigned)B), dim3(PQ_THREADS), 0, (hipStream_t)stream,
-                     bank, poses, targets, sources, N, S, H, W,
-                     depth_fuse_params(fx, fy, cx, cy, max_reproj, max_rel_depth, min_views, min_z, average), fused, views, counts);
+                     bank, poses, targets, sources, N, S, H, W, c, fused, views, counts);
   ATDN_HIP(hipGetLastError());
+  ATDN_API_END
+}
+
+int atdn_depth_fuse_host(const float* bank, const float* poses, const int* targets, const int* sources, int N, int B, int S, int H,
+                         int W, double fx, double fy, double cx, double cy, double max_reproj, double max_rel_depth, int min_views,
+                         double min_z, int average, float* fused, unsigned char* views, int* counts) {
+  ATDN_API_BEGIN
+  const DepthFuseParams c = depth_fuse_check_args(bank, poses, targets, sources, N, B, S, H, W, fx, fy, cx, cy, max_reproj,
+                                                  max_rel_depth, min_views, min_z, average, fused, views, counts);
+  depth_fuse_host(bank, poses, targets, sources, N, B, S, H, W, c, fused, views, counts);
   ATDN_API_END
 }

@@ -1,7 +1,7 @@
 // Multi-view consistency filter of the keyframe depths (the geometric-consistency fusion of multi-view stereo: COLMAP, MVSNet),
 // the rule in plain C++ float64 (no HIP needed): depth_fuse_relative composes the pose of a (target, source) pair,
 // depth_fuse_source is the rule for one pixel and one source, depth_fuse_result the pixel's outcome, depth_fuse_host the host form
-// behind atdn_depth_fuse_host (capi.hip), which serves CPU tensors. The kernel of depth_fusion.hip calls the same functions, so the
+// behind atdn_depth_fuse_host (depth_fusion.hip), which serves CPU tensors. The kernel of depth_fusion.hip calls the same functions, so the
 // two cannot drift apart; the independent statement the tests compare both with is tests/depth_fusion_ref.py (NumPy).
 //
 // bank [N, H, W] float32 (0 = no depth), poses [N, 12] float32 (rows of [R|t], world <- camera). For target i and source j, in

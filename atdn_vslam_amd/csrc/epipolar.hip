@@ -9,7 +9,7 @@
 //   epipolar_terms_kernel     (chunks, B) workgroups of pixel_quads.h with off = 0. A thread streams 9 bytes per pixel (two planes
 //                             of flow, mask), keeps the 28 sums of its four pixels in 56 VGPRs and hands them to the fixed tree
 //                             of plane_sum.h, which stores the workgroup's sums in ITS slot of the workspace.
-//   epipolar_finalise_kernel  one wave per problem: the ordered sum of plane_sum.h; thread 0 then either writes the sums out
+//   plane_finalise_kernel<EpipolarSolver> (plane_sum.h)  one wave per problem: the ordered sum of plane_sum.h; thread 0 then either writes the sums out
 //                             (atdn_epipolar_terms) or takes the Levenberg-Marquardt decision and the next step (gauge term,
 //                             6 x 6 LDL^T, two Cayley matrices, in registers) on the problem's state in the workspace.
 // The pose of evaluation 0 is read from the caller's float32 pose by both kernels; later ones from the state.
@@ -81,36 +81,6 @@ __global__ __launch_bounds__(PQ_THREADS) void epipolar_terms_kernel(const float*
   plane_chunk_reduce(acc, cnt, b, csums, ccounts);
 }
 
-// k < 0: atdn_epipolar_terms (the plane sums go to sums_out / counts_out). k >= 0: evaluation k of a solve of `iters` steps.
-__global__ __launch_bounds__(PLANE_FIN_THREADS) void epipolar_finalise_kernel(const double* __restrict__ csums,
-                                                                               const int* __restrict__ ccounts, int chunks, int k,
-                                                                               int iters, PlaneLmState* __restrict__ state,
-                                                                               const float* __restrict__ pose_init,
-                                                                               double* __restrict__ sums_out,
-                                                                               int* __restrict__ counts_out,
-                                                                               float* __restrict__ pose_out,
-                                                                               double* __restrict__ cost_out) {
-#pragma clang fp contract(off)
-  __shared__ double S[PLANE_TERMS];
-  __shared__ int Cn[3];
-  const int b = blockIdx.x;
-  const int t = threadIdx.x;
-  plane_ordered_sum(csums, ccounts, chunks, b, S, Cn);
-  if (k < 0) {
-    if (t < PLANE_TERMS) sums_out[(long)b * PLANE_TERMS + t] = S[t];
-    if (t < 3) counts_out[3 * b + t] = Cn[t];
-    return;
-  }
-  if (t != 0) return;
-  PlaneLmState& s = state[b];
-  if (k == 0) epipolar_load_pose(pose_init + 12 * b, s.trial);
-  plane_lm_update(s, S, Cn, k);
-  if (k < iters)
-    epipolar_lm_step(s);
-  else
-    epipolar_output(s, pose_init + 12 * b, pose_out + 12 * b, cost_out + b, counts_out + 4 * b);
-}
-
 static void epipolar_launch_terms(const float* flow, const unsigned char* mask, const float* pose32, const PlaneWorkspace& ws, int B,
                                   int H, int W, const EpipolarParams& cam, hipStream_t stream) {
   const dim3 grid((unsigned)plane_chunks(H, W), (unsigned)B);
@@ -123,17 +93,50 @@ static void epipolar_launch_terms(const float* flow, const unsigned char* mask, 
   ATDN_HIP(hipGetLastError());
 }
 
-// Argument rules shared by the device entry points below and the host ones (capi.hip). out[i] of out_bytes[i]: the outputs
-// (a workspace among them), none of which may overlap an input or another output.
-void epipolar_check_args(const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W, double fx, double fy,
-                         double cx, double cy, double scale_px, double inlier_px, bool grid_limit, const void* const* out,
-                         const long* out_bytes, int n_out) {
-  ATDN_CHECK(flow && pose, "null argument");
-  check_plane_solver(B, H, W, grid_limit, fx, fy, cx, cy, scale_px, inlier_px, out, n_out);
-  const long n = (long)H * W;
-  const void* in[3] = {flow, mask, pose};
-  const long in_bytes[3] = {(long)B * 2 * n * 4, (long)B * n, (long)B * 48};
+struct EpipolarCall {
+  const float* flow;
+  const unsigned char* mask;
+  const float* pose;
+  int B, H, W;
+  double fx, fy, cx, cy, scale_px, inlier_px;
+};
+
+// Argument rules of an entry pair. out[i] of out_bytes[i]: the outputs, none of which may be null or overlap an input or another
+// output. The device form (`device`) limits B to gridDim.y before anything else, and its workspace is one more output.
+static void epipolar_check_args(const EpipolarCall& c, bool device, const void* const* out, const long* out_bytes, int n_out) {
+  if (device) check_plane_batch(c.B, c.H, c.W);
+  ATDN_CHECK(c.flow && c.pose, "null argument");
+  check_plane_solver(c.B, c.H, c.W, device, c.fx, c.fy, c.cx, c.cy, c.scale_px, c.inlier_px, out, n_out);
+  const long n = (long)c.H * c.W;
+  const void* in[3] = {c.flow, c.mask, c.pose};
+  const long in_bytes[3] = {(long)c.B * 2 * n * 4, (long)c.B * n, (long)c.B * 48};
   check_disjoint(in, in_bytes, 3, out, out_bytes, n_out);
+}
+
+// Both forms of atdn_epipolar_terms: the checks and the camera
+static EpipolarParams epipolar_terms_args(const EpipolarCall& c, double* sums, int* counts, bool device, void* workspace) {
+  const void* out[3] = {sums, counts, workspace};
+  const long out_bytes[3] = {(long)c.B * PLANE_TERMS * 8, (long)c.B * 12, (long)plane_workspace_size(c.B, c.H, c.W)};
+  epipolar_check_args(c, device, out, out_bytes, device ? 3 : 2);
+  return epipolar_params(c.fx, c.fy, c.cx, c.cy, c.scale_px, c.inlier_px);
+}
+
+// Both forms of atdn_epipolar_solve
+static EpipolarParams epipolar_solve_args(const EpipolarCall& c, int iters, float* pose_out, double* cost, int* counts, bool device,
+                                          void* workspace) {
+  const void* out[4] = {pose_out, cost, counts, workspace};
+  const long out_bytes[4] = {(long)c.B * 48, (long)c.B * 8, (long)c.B * 16, (long)plane_workspace_size(c.B, c.H, c.W)};
+  epipolar_check_args(c, device, out, out_bytes, device ? 4 : 3);
+  ATDN_CHECK(iters >= 0 && iters <= 64, "iters must be in [0, 64]");
+  return epipolar_params(c.fx, c.fy, c.cx, c.cy, c.scale_px, c.inlier_px);
+}
+
+// the launches of a call: plane_run (plane_sum.h) over epipolar_launch_terms
+static void epipolar_run(const EpipolarCall& c, const EpipolarParams& cam, int iters, double* sums, int* counts, float* pose_out,
+                         double* cost, void* workspace, void* stream) {
+  plane_run<EpipolarSolver>([&](const float* pose32, const PlaneWorkspace& ws) {
+    epipolar_launch_terms(c.flow, c.mask, pose32, ws, c.B, c.H, c.W, cam, (hipStream_t)stream);
+  }, workspace, c.B, c.H, c.W, iters, c.pose, sums, counts, pose_out, cost, (hipStream_t)stream);
 }
 
 }  // namespace atdn
@@ -149,17 +152,19 @@ int atdn_epipolar_terms(const float* flow, const unsigned char* mask, const floa
                         double cx, double cy, double scale_px, double inlier_px, double* sums, int* counts, void* workspace,
                         void* stream) {
   ATDN_API_BEGIN
-  check_plane_batch(B, H, W);
-  const void* out[3] = {sums, counts, workspace};
-  const long out_bytes[3] = {(long)B * PLANE_TERMS * 8, (long)B * 12, (long)plane_workspace_size(B, H, W)};
-  epipolar_check_args(flow, mask, pose, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, true, out, out_bytes, 3);
+  const EpipolarCall c{flow, mask, pose, B, H, W, fx, fy, cx, cy, scale_px, inlier_px};
+  const EpipolarParams cam = epipolar_terms_args(c, sums, counts, true, workspace);
   ATDN_CHECK(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)sums & 7) == 0, "workspace and sums must be 8-byte aligned");
-  const EpipolarParams cam = epipolar_params(fx, fy, cx, cy, scale_px, inlier_px);
-  const PlaneWorkspace ws = plane_carve(workspace, B, H, W);
-  epipolar_launch_terms(flow, mask, pose, ws, B, H, W, cam, (hipStream_t)stream);
-  hipLaunchKernelGGL(epipolar_finalise_kernel, dim3((unsigned)B), dim3(PLANE_FIN_THREADS), 0, (hipStream_t)stream, ws.sums,
-                     ws.counts, (int)plane_chunks(H, W), -1, 0, ws.state, pose, sums, counts, (float*)nullptr, (double*)nullptr);
-  ATDN_HIP(hipGetLastError());
+  epipolar_run(c, cam, -1, sums, counts, nullptr, nullptr, workspace, stream);
+  ATDN_API_END
+}
+
+int atdn_epipolar_terms_host(const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W, double fx,
+                             double fy, double cx, double cy, double scale_px, double inlier_px, double* sums, int* counts) {
+  ATDN_API_BEGIN
+  const EpipolarCall c{flow, mask, pose, B, H, W, fx, fy, cx, cy, scale_px, inlier_px};
+  const EpipolarParams cam = epipolar_terms_args(c, sums, counts, false, nullptr);
+  epipolar_terms_host(flow, mask, pose, B, H, W, cam, sums, counts);
   ATDN_API_END
 }
 
@@ -167,19 +172,19 @@ int atdn_epipolar_solve(const float* flow, const unsigned char* mask, const floa
                         double fy, double cx, double cy, double scale_px, double inlier_px, int iters, float* pose_out, double* cost,
                         int* counts, void* workspace, void* stream) {
   ATDN_API_BEGIN
-  check_plane_batch(B, H, W);
-  const void* out[4] = {pose_out, cost, counts, workspace};
-  const long out_bytes[4] = {(long)B * 48, (long)B * 8, (long)B * 16, (long)plane_workspace_size(B, H, W)};
-  epipolar_check_args(flow, mask, pose_init, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, true, out, out_bytes, 4);
-  ATDN_CHECK(iters >= 0 && iters <= 64, "iters must be in [0, 64]");
+  const EpipolarCall c{flow, mask, pose_init, B, H, W, fx, fy, cx, cy, scale_px, inlier_px};
+  const EpipolarParams cam = epipolar_solve_args(c, iters, pose_out, cost, counts, true, workspace);
   ATDN_CHECK(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)cost & 7) == 0, "workspace and cost must be 8-byte aligned");
-  const EpipolarParams cam = epipolar_params(fx, fy, cx, cy, scale_px, inlier_px);
-  const PlaneWorkspace ws = plane_carve(workspace, B, H, W);
-  for (int k = 0; k <= iters; ++k) {
-    epipolar_launch_terms(flow, mask, k == 0 ? pose_init : nullptr, ws, B, H, W, cam, (hipStream_t)stream);
-    hipLaunchKernelGGL(epipolar_finalise_kernel, dim3((unsigned)B), dim3(PLANE_FIN_THREADS), 0, (hipStream_t)stream, ws.sums,
-                       ws.counts, (int)plane_chunks(H, W), k, iters, ws.state, pose_init, (double*)nullptr, counts, pose_out, cost);
-    ATDN_HIP(hipGetLastError());
-  }
+  epipolar_run(c, cam, iters, nullptr, counts, pose_out, cost, workspace, stream);
+  ATDN_API_END
+}
+
+int atdn_epipolar_solve_host(const float* flow, const unsigned char* mask, const float* pose_init, int B, int H, int W, double fx,
+                             double fy, double cx, double cy, double scale_px, double inlier_px, int iters, float* pose_out,
+                             double* cost, int* counts) {
+  ATDN_API_BEGIN
+  const EpipolarCall c{flow, mask, pose_init, B, H, W, fx, fy, cx, cy, scale_px, inlier_px};
+  const EpipolarParams cam = epipolar_solve_args(c, iters, pose_out, cost, counts, false, nullptr);
+  epipolar_solve_host(flow, mask, pose_init, B, H, W, cam, iters, pose_out, cost, counts);
   ATDN_API_END
 }

@@ -6,7 +6,7 @@
 // that gives the unobservable direction dth || t the mean curvature of its block; the 28 terms, the plane sum, the state and
 // the decision are those of plane_lm.h (shared with PnP), the per-pixel prefix up to epi2 is two_view_epipolar of
 // two_view_host.h (shared with two_view_pixel). epipolar_terms_host / epipolar_solve_host are the host forms behind
-// atdn_epipolar_terms_host / atdn_epipolar_solve_host (capi.hip); the kernels of epipolar.hip call the same functions. The
+// atdn_epipolar_terms_host / atdn_epipolar_solve_host (epipolar.hip); the kernels of epipolar.hip call the same functions. The
 // independent statement the tests compare both with is tests/epipolar_ref.py (NumPy). The rule is stated in full in
 // include/atdn_hip.h, atdn_epipolar_terms and atdn_epipolar_solve; only + - * / and comparisons, every operation rounded on
 // its own (fp contraction off).
@@ -200,22 +200,22 @@ inline void epipolar_terms_host(const float* flow, const unsigned char* mask, co
   }
 }
 
+// what plane_finalise_kernel (plane_sum.h) and plane_solve_host (plane_lm.h) run for this solver
+struct EpipolarSolver {
+  ATDN_HD static void load_pose(const float* pose12, double p[12]) { epipolar_load_pose(pose12, p); }
+  ATDN_HD static void lm_step(PlaneLmState& s) { epipolar_lm_step(s); }
+  ATDN_HD static void output(const PlaneLmState& s, const float* pose_in, float* pose_out, double* cost, int* counts4) {
+    epipolar_output(s, pose_in, pose_out, cost, counts4);
+  }
+};
+
 // iters Levenberg-Marquardt steps (iters + 1 evaluations) from pose_init -> pose_out [B,12], cost [B], counts [B,4]
 inline void epipolar_solve_host(const float* flow, const unsigned char* mask, const float* pose_init, int B, int H, int W,
                                 const EpipolarParams& c, int iters, float* pose_out, double* cost, int* counts) {
   const long n = (long)H * W;
-  for (int b = 0; b < B; ++b) {
-    PlaneLmState s;
-    epipolar_load_pose(pose_init + 12L * b, s.trial);
-    for (int k = 0; k <= iters; ++k) {
-      double sums[PLANE_TERMS];
-      int cnt[3];
-      epipolar_plane_host(flow + 2 * b * n, flow + (2 * b + 1) * n, mask ? mask + b * n : nullptr, s.trial, c, H, W, sums, cnt);
-      plane_lm_update(s, sums, cnt, k);
-      if (k < iters) epipolar_lm_step(s);
-    }
-    epipolar_output(s, pose_init + 12L * b, pose_out + 12L * b, cost + b, counts + 4L * b);
-  }
+  plane_solve_host<EpipolarSolver>(B, iters, [&](int b, const double* p, double* sums, int* cnt) {
+    epipolar_plane_host(flow + 2 * b * n, flow + (2 * b + 1) * n, mask ? mask + b * n : nullptr, p, c, H, W, sums, cnt);
+  }, pose_init, pose_out, cost, counts);
 }
 
 }  // namespace atdn

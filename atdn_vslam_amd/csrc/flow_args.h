@@ -1,5 +1,6 @@
-// Argument rules of the flow-geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip, epipolar.hip, depth_fusion.hip, multiview_depth.hip, bundle.hip, ground.hip, voxel_map.hip), shared by each device
-// entry point and its host twin in capi.hip, and the overlap rule that the pose solvers (pnp.hip, pose_graph.hip) share.
+// The argument rules that the geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip, epipolar.hip,
+// depth_fusion.hip, multiview_depth.hip, bundle.hip, ground.hip, voxel_map.hip, pose_graph.hip) share. Each module's own rules are
+// file-static in its .hip, beside the device entry point and the host twin that both go through them.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -49,51 +50,5 @@ inline void check_two_view_camera(const TwoViewCamera& cam) {
   ATDN_CHECK(std::isfinite(cam.min_sin2) && cam.min_sin2 >= 0.0, "min_sin2 must be finite and >= 0");
   ATDN_CHECK(std::isfinite(cam.max_depth) && cam.max_depth > 0.0, "max_depth must be finite and > 0");
 }
-
-void flow_consistency_check_args(const float* flow_fw, const float* flow_bw, int B, int H, int W, double alpha1, double alpha2,
-                                 const unsigned char* mask, const int* count);
-void two_view_check_args(const float* flow, const float* pose, const unsigned char* mask, int B, int H, int W,
-                         const TwoViewCamera& cam, const float* depth, const int* counts);
-void flow_track_check_args(const float* flow, const unsigned char* mask, const float* acc_in, const unsigned char* alive_in, int B,
-                           int H, int W, const float* acc_out, const unsigned char* alive_out, const float* pose,
-                           const TwoViewCamera& cam, const float* depth, const int* counts);
-// out[i] of out_bytes[i], i < n_out: the outputs (a workspace among them); none may be null or overlap an input or another output
-void pnp_check_args(const float* depth, const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W,
-                    double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, bool grid_limit,
-                    const void* const* out, const long* out_bytes, int n_out);
-void epipolar_check_args(const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W, double fx, double fy,
-                         double cx, double cy, double scale_px, double inlier_px, bool grid_limit, const void* const* out,
-                         const long* out_bytes, int n_out);
-// the ground plane (ground.hip): mask may be null, q only where q_optional; out as for pnp_check_args
-void ground_check_args(const float* depth, const unsigned char* mask, const double* q, bool q_optional, int B, int H, int W, int y0,
-                       int y1, double fx, double fy, double cx, double cy, double scale_rel, double inlier_rel, double min_z,
-                       double max_depth, bool grid_limit, const void* const* out, const long* out_bytes, int n_out);
-void ground_check_solve(double nx, double ny, double nz, int min_votes, int iters);
-// sources may be null only when S == 0
-void depth_fuse_check_args(const float* bank, const float* poses, const int* targets, const int* sources, int N, int B, int S,
-                           int H, int W, double fx, double fy, double cx, double cy, double max_reproj, double max_rel_depth,
-                           int min_views, double min_z, const float* fused, const unsigned char* views, const int* counts);
-// depth_init may be null
-void multiview_check_args(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
-                          const float* depth_init, int N, int B, int S, int H, int W, double fx, double fy, double cx, double cy,
-                          double scale_px, double inlier_px, double min_z, int min_views, double max_rel_sigma, double max_depth,
-                          int iters, const float* depth, const float* info, const unsigned char* views, const int* counts);
-
-// mask may be null; out[i] of out_bytes[i], i < n_out: the outputs (a workspace among them)
-void bundle_check_args(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
-                       const float* depth_init, const unsigned char* mask, int N, int B, int S, int H, int W, double fx, double fy,
-                       double cx, double cy, int stride, int iters, double scale_px, double inlier_px, double min_z, int min_views,
-                       bool grid_limit, const void* const* out, const long* out_bytes, int n_out);
-
-// the voxel map (voxel_map.hip): images, mask, indices and pending may be null
-void voxel_check_table(const void* table, long capacity);
-void voxel_check_integrate(const float* depth, const float* poses, const unsigned char* images, const unsigned char* mask,
-                           const int* indices, int N, int K, int H, int W, double fx, double fy, double cx, double cy, int stride,
-                           double voxel, double ox, double oy, double oz, double min_z, double max_z, const void* table,
-                           long capacity, const unsigned char* pending);
-void voxel_check_rehash(const void* src, long src_capacity, const void* dst, long dst_capacity);
-void voxel_check_extract(const void* table, long capacity, int min_count, double voxel, double ox, double oy, double oz, long max_out,
-                         const float* points, const unsigned char* colors, const int* counts, const int64_t* keys,
-                         const int64_t* found);
 
 }  // namespace atdn

@@ -52,8 +52,8 @@ __global__ __launch_bounds__(PQ_THREADS) void flow_consistency_kernel(const floa
   quad_count<1>(ok, one, count + b);
 }
 
-// Argument rules shared by the device entry point below and the host one (capi.hip).
-void flow_consistency_check_args(const float* flow_fw, const float* flow_bw, int B, int H, int W, double alpha1, double alpha2,
+// Argument rules shared by the two entry points below.
+static void flow_consistency_check_args(const float* flow_fw, const float* flow_bw, int B, int H, int W, double alpha1, double alpha2,
                                  const unsigned char* mask, const int* count) {
   ATDN_CHECK(flow_fw && flow_bw && mask && count, "null argument");
   check_plane_batch(B, H, W, false);
@@ -80,5 +80,13 @@ int atdn_flow_consistency(const float* flow_fw, const float* flow_bw, int B, int
   hipLaunchKernelGGL(flow_consistency_kernel, dim3(quad_blocks((long)H * W, true), (unsigned)B), dim3(PQ_THREADS), 0,
                      (hipStream_t)stream, flow_fw, flow_bw, H, W, alpha1, alpha2, mask, count);
   ATDN_HIP(hipGetLastError());
+  ATDN_API_END
+}
+
+int atdn_flow_consistency_host(const float* flow_fw, const float* flow_bw, int B, int H, int W, double alpha1, double alpha2,
+                               unsigned char* mask, int* count) {
+  ATDN_API_BEGIN
+  flow_consistency_check_args(flow_fw, flow_bw, B, H, W, alpha1, alpha2, mask, count);
+  flow_consistency_host(flow_fw, flow_bw, B, H, W, alpha1, alpha2, mask, count);
   ATDN_API_END
 }

@@ -1,5 +1,5 @@
 // Forward-backward consistency of a pair of flows, the rule in plain C++ float64 (no HIP needed): flow_consistent_pixel is the
-// rule for one pixel, flow_consistency_host the host form behind atdn_flow_consistency_host (capi.hip), which serves CPU
+// rule for one pixel, flow_consistency_host the host form behind atdn_flow_consistency_host (flow_consistency.hip), which serves CPU
 // tensors. The kernel of flow_consistency.hip evaluates the same function, so the two cannot drift apart; the independent
 // statement the tests compare both with is tests/flow_consistency_ref.py (NumPy).
 //

@@ -79,8 +79,8 @@ __global__ __launch_bounds__(PQ_THREADS) void flow_track_kernel(const float* __r
   quad_count<DEPTH ? 4 : 1>(flags, bits, counts + 4 * b);      // without a pose no TV_* bit is ever set: those counts stay zero
 }
 
-// Argument rules shared by the device entry point below and the host one (capi.hip).
-void flow_track_check_args(const float* flow, const unsigned char* mask, const float* acc_in, const unsigned char* alive_in, int B,
+// Argument rules shared by the two entry points below.
+static void flow_track_check_args(const float* flow, const unsigned char* mask, const float* acc_in, const unsigned char* alive_in, int B,
                            int H, int W, const float* acc_out, const unsigned char* alive_out, const float* pose,
                            const TwoViewCamera& cam, const float* depth, const int* counts) {
   ATDN_CHECK(flow && acc_in && alive_in && acc_out && alive_out && counts, "null argument");
@@ -128,5 +128,16 @@ int atdn_flow_track_step(const float* flow, const unsigned char* mask, const flo
     hipLaunchKernelGGL(flow_track_kernel<false>, grid, dim3(PQ_THREADS), 0, (hipStream_t)stream, flow, mask, acc_in, alive_in, H, W,
                        acc_out, alive_out, pose, cam, depth, counts);
   ATDN_HIP(hipGetLastError());
+  ATDN_API_END
+}
+
+int atdn_flow_track_step_host(const float* flow, const unsigned char* mask, const float* acc_in, const unsigned char* alive_in,
+                              int B, int H, int W, float* acc_out, unsigned char* alive_out, const float* pose, double fx,
+                              double fy, double cx, double cy, double max_epipolar, double min_sin2, double max_depth, float* depth,
+                              int* counts) {
+  ATDN_API_BEGIN
+  const TwoViewCamera cam{fx, fy, cx, cy, max_epipolar, min_sin2, max_depth};
+  flow_track_check_args(flow, mask, acc_in, alive_in, B, H, W, acc_out, alive_out, pose, cam, depth, counts);
+  flow_track_step_host(flow, mask, acc_in, alive_in, B, H, W, acc_out, alive_out, pose, cam, depth, counts);
   ATDN_API_END
 }

@@ -1,5 +1,5 @@
 // One step of a flow track, the rule in plain C++ float64 (no HIP needed): flow_track_pixel is the rule for one pixel,
-// flow_track_step_host the host form behind atdn_flow_track_step_host (capi.hip), which serves CPU tensors. The kernel of
+// flow_track_step_host the host form behind atdn_flow_track_step_host (flow_track.hip), which serves CPU tensors. The kernel of
 // flow_track.hip evaluates the same function, so the two cannot drift apart; the independent statement the tests compare both with
 // is tests/flow_track_ref.py (NumPy).
 //

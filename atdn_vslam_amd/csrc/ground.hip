@@ -226,32 +226,65 @@ __global__ __launch_bounds__(PQ_THREADS) void ground_classify_kernel(const float
   quad_store(qd, on_ground + base, in, 1);
 }
 
-// Argument rules shared by the device entry points below and the host ones (capi.hip). q may be null only where `q_optional`.
-// out[i] of out_bytes[i]: the outputs (a workspace among them), none of which may be null or overlap an input or another output.
-void ground_check_args(const float* depth, const unsigned char* mask, const double* q, bool q_optional, int B, int H, int W, int y0,
-                       int y1, double fx, double fy, double cx, double cy, double scale_rel, double inlier_rel, double min_z,
-                       double max_depth, bool grid_limit, const void* const* out, const long* out_bytes, int n_out) {
-  ATDN_CHECK(depth && (q || q_optional), "null argument");
+struct GroundCall {
+  const float* depth;
+  const unsigned char* mask;
+  const double* q;
+  int B, H, W, y0, y1;
+  double fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth;
+};
+
+// Argument rules of an entry pair. q may be null only where `q_optional`. out[i] of out_bytes[i]: the outputs, none of which may
+// be null or overlap an input or another output. The device form (`device`) limits B to gridDim.y before anything else, and its
+// workspace, where it has one, is one more output.
+static void ground_check_args(const GroundCall& c, bool q_optional, bool device, const void* const* out, const long* out_bytes,
+                              int n_out) {
+  if (device) check_plane_batch(c.B, c.H, c.W);
+  ATDN_CHECK(c.depth && (c.q || q_optional), "null argument");
   for (int i = 0; i < n_out; ++i) ATDN_CHECK(out[i], "null argument");
-  check_plane_batch(B, H, W, grid_limit);
-  ATDN_CHECK(y0 >= 0 && y0 < y1 && y1 <= H, "the rows must satisfy 0 <= y0 < y1 <= H");
-  check_pinhole(fx, fy, cx, cy);
-  ATDN_CHECK(std::isfinite(scale_rel) && scale_rel > 0.0, "scale_rel must be finite and > 0");
-  ATDN_CHECK(std::isfinite(inlier_rel) && inlier_rel > 0.0, "inlier_rel must be finite and > 0");
-  ATDN_CHECK(std::isfinite(min_z) && min_z > 0.0, "min_z must be finite and > 0");
-  ATDN_CHECK(std::isfinite(max_depth) && max_depth > 0.0, "max_depth must be finite and > 0");
-  ATDN_CHECK(!q || ((uintptr_t)q & 7) == 0, "q must be 8-byte aligned");
-  const long n = (long)H * W;
-  const void* in[3] = {depth, mask, q};
-  const long in_bytes[3] = {(long)B * n * 4, (long)B * n, (long)B * 24};
+  check_plane_batch(c.B, c.H, c.W, device);
+  ATDN_CHECK(c.y0 >= 0 && c.y0 < c.y1 && c.y1 <= c.H, "the rows must satisfy 0 <= y0 < y1 <= H");
+  check_pinhole(c.fx, c.fy, c.cx, c.cy);
+  ATDN_CHECK(std::isfinite(c.scale_rel) && c.scale_rel > 0.0, "scale_rel must be finite and > 0");
+  ATDN_CHECK(std::isfinite(c.inlier_rel) && c.inlier_rel > 0.0, "inlier_rel must be finite and > 0");
+  ATDN_CHECK(std::isfinite(c.min_z) && c.min_z > 0.0, "min_z must be finite and > 0");
+  ATDN_CHECK(std::isfinite(c.max_depth) && c.max_depth > 0.0, "max_depth must be finite and > 0");
+  ATDN_CHECK(!c.q || ((uintptr_t)c.q & 7) == 0, "q must be 8-byte aligned");
+  const long n = (long)c.H * c.W;
+  const void* in[3] = {c.depth, c.mask, c.q};
+  const long in_bytes[3] = {(long)c.B * n * 4, (long)c.B * n, (long)c.B * 24};
   check_disjoint(in, in_bytes, 3, out, out_bytes, n_out);
 }
 
-void ground_check_solve(double nx, double ny, double nz, int min_votes, int iters) {
+// Both forms of atdn_ground_terms: the checks and the parameters
+static GroundParams ground_terms_args(const GroundCall& c, double* sums, int* counts, bool device, void* workspace) {
+  const void* out[3] = {sums, counts, workspace};
+  const long out_bytes[3] = {(long)c.B * GROUND_TERMS * 8, (long)c.B * 12, (long)ground_workspace_size(c.B, c.H, c.W)};
+  ground_check_args(c, false, device, out, out_bytes, device ? 3 : 2);
+  return ground_params(c.fx, c.fy, c.cx, c.cy, c.scale_rel, c.inlier_rel, c.min_z, c.max_depth, 0.0, 1.0, 0.0, 1, c.y0, c.W);
+}
+
+// Both forms of atdn_ground_solve
+static GroundParams ground_solve_args(const GroundCall& c, double nx, double ny, double nz, int min_votes, int iters, double* q,
+                                      double* sums, int* counts, bool device, void* workspace) {
+  const void* out[4] = {q, sums, counts, workspace};
+  const long out_bytes[4] = {(long)c.B * 24, (long)c.B * GROUND_TERMS * 8, (long)c.B * 24,
+                             (long)ground_workspace_size(c.B, c.H, c.W)};
+  ground_check_args(c, true, device, out, out_bytes, device ? 4 : 3);
   ATDN_CHECK(std::isfinite(nx) && std::isfinite(ny) && std::isfinite(nz) && (nx != 0.0 || ny != 0.0 || nz != 0.0),
              "the prior normal must be finite and not zero");
   ATDN_CHECK(min_votes >= 1, "min_votes must be >= 1");
   ATDN_CHECK(iters >= 0 && iters <= 64, "iters must be in [0, 64]");
+  return ground_params(c.fx, c.fy, c.cx, c.cy, c.scale_rel, c.inlier_rel, c.min_z, c.max_depth, nx, ny, nz, min_votes, c.y0, c.W);
+}
+
+// Both forms of atdn_ground_classify (which build the call with scale_rel = 1.0)
+static GroundParams ground_classify_args(const GroundCall& c, float* residual, unsigned char* on_ground, bool device) {
+  const long n = (long)c.H * c.W;
+  const void* out[2] = {residual, on_ground};
+  const long out_bytes[2] = {(long)c.B * n * 4, (long)c.B * n};
+  ground_check_args(c, false, device, out, out_bytes, 2);
+  return ground_params(c.fx, c.fy, c.cx, c.cy, c.scale_rel, c.inlier_rel, c.min_z, c.max_depth, 0.0, 1.0, 0.0, 1, c.y0, c.W);
 }
 
 static void ground_launch_terms(const float* depth, const unsigned char* mask, const double* q, const GroundWorkspace& ws, int B,
@@ -288,17 +321,22 @@ int atdn_ground_terms(const float* depth, const unsigned char* mask, const doubl
                       double fy, double cx, double cy, double scale_rel, double inlier_rel, double min_z, double max_depth,
                       double* sums, int* counts, void* workspace, void* stream) {
   ATDN_API_BEGIN
-  check_plane_batch(B, H, W);
-  const void* out[3] = {sums, counts, workspace};
-  const long out_bytes[3] = {(long)B * GROUND_TERMS * 8, (long)B * 12, (long)ground_workspace_size(B, H, W)};
-  ground_check_args(depth, mask, q, false, B, H, W, y0, y1, fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth, true, out,
-                    out_bytes, 3);
+  const GroundCall a{depth, mask, q, B, H, W, y0, y1, fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth};
+  const GroundParams c = ground_terms_args(a, sums, counts, true, workspace);
   ATDN_CHECK(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)sums & 7) == 0, "workspace and sums must be 8-byte aligned");
-  const GroundParams c = ground_params(fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth, 0.0, 1.0, 0.0, 1, y0, W);
   const GroundWorkspace ws = ground_carve(workspace, B, H, W);
   ground_launch_terms(depth, mask, q, ws, B, H, W, y1, c, (hipStream_t)stream);
   ground_launch_finalise(ws, B, (int)cdivl((long)(y1 - y0) * W, PLANE_CHUNK), 0, GROUND_FIN_TERMS, 0, c, nullptr, nullptr, sums,
                          counts, (hipStream_t)stream);
+  ATDN_API_END
+}
+
+int atdn_ground_terms_host(const float* depth, const unsigned char* mask, const double* q, int B, int H, int W, int y0, int y1,
+                           double fx, double fy, double cx, double cy, double scale_rel, double inlier_rel, double min_z,
+                           double max_depth, double* sums, int* counts) {
+  ATDN_API_BEGIN
+  const GroundCall a{depth, mask, q, B, H, W, y0, y1, fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth};
+  ground_terms_host(depth, mask, q, B, H, W, y1, ground_terms_args(a, sums, counts, false, nullptr), sums, counts);
   ATDN_API_END
 }
 
@@ -307,15 +345,10 @@ int atdn_ground_solve(const float* depth, const unsigned char* mask, const doubl
                       double inlier_rel, double min_z, double max_depth, int min_votes, int iters, double* q, double* sums,
                       int* counts, void* workspace, void* stream) {
   ATDN_API_BEGIN
-  check_plane_batch(B, H, W);
-  const void* out[4] = {q, sums, counts, workspace};
-  const long out_bytes[4] = {(long)B * 24, (long)B * GROUND_TERMS * 8, (long)B * 24, (long)ground_workspace_size(B, H, W)};
-  ground_check_args(depth, mask, q_init, true, B, H, W, y0, y1, fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth, true, out,
-                    out_bytes, 4);
-  ground_check_solve(nx, ny, nz, min_votes, iters);
+  const GroundCall a{depth, mask, q_init, B, H, W, y0, y1, fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth};
+  const GroundParams c = ground_solve_args(a, nx, ny, nz, min_votes, iters, q, sums, counts, true, workspace);
   ATDN_CHECK(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)sums & 7) == 0 && ((uintptr_t)q & 7) == 0,
              "workspace, q and sums must be 8-byte aligned");
-  const GroundParams c = ground_params(fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth, nx, ny, nz, min_votes, y0, W);
   const GroundWorkspace ws = ground_carve(workspace, B, H, W);
   const hipStream_t st = (hipStream_t)stream;
   const int nb = (y1 - y0) * W;
@@ -337,17 +370,24 @@ int atdn_ground_solve(const float* depth, const unsigned char* mask, const doubl
   ATDN_API_END
 }
 
+int atdn_ground_solve_host(const float* depth, const unsigned char* mask, const double* q_init, int B, int H, int W, int y0, int y1,
+                           double fx, double fy, double cx, double cy, double nx, double ny, double nz, double scale_rel,
+                           double inlier_rel, double min_z, double max_depth, int min_votes, int iters, double* q, double* sums,
+                           int* counts) {
+  ATDN_API_BEGIN
+  const GroundCall a{depth, mask, q_init, B, H, W, y0, y1, fx, fy, cx, cy, scale_rel, inlier_rel, min_z, max_depth};
+  const GroundParams c = ground_solve_args(a, nx, ny, nz, min_votes, iters, q, sums, counts, false, nullptr);
+  ground_solve_host(depth, mask, q_init, B, H, W, y1, c, iters, q, sums, counts);
+  ATDN_API_END
+}
+
 int atdn_ground_classify(const float* depth, const unsigned char* mask, const double* q, int B, int H, int W, int y0, int y1,
                          double fx, double fy, double cx, double cy, double inlier_rel, double min_z, double max_depth,
                          float* residual, unsigned char* on_ground, void* stream) {
   ATDN_API_BEGIN
-  check_plane_batch(B, H, W);
+  const GroundCall a{depth, mask, q, B, H, W, y0, y1, fx, fy, cx, cy, 1.0, inlier_rel, min_z, max_depth};
+  const GroundParams c = ground_classify_args(a, residual, on_ground, true);
   const long n = (long)H * W;
-  const void* out[2] = {residual, on_ground};
-  const long out_bytes[2] = {(long)B * n * 4, (long)B * n};
-  ground_check_args(depth, mask, q, false, B, H, W, y0, y1, fx, fy, cx, cy, 1.0, inlier_rel, min_z, max_depth, true, out, out_bytes,
-                    2);
-  const GroundParams c = ground_params(fx, fy, cx, cy, 1.0, inlier_rel, min_z, max_depth, 0.0, 1.0, 0.0, 1, y0, W);
   const dim3 grid(quad_blocks(n, false), (unsigned)B);
   if (mask)
     hipLaunchKernelGGL(ground_classify_kernel<true>, grid, dim3(PQ_THREADS), 0, (hipStream_t)stream, depth, mask, q, (int)n, y1, c,
@@ -356,5 +396,14 @@ int atdn_ground_classify(const float* depth, const unsigned char* mask, const do
     hipLaunchKernelGGL(ground_classify_kernel<false>, grid, dim3(PQ_THREADS), 0, (hipStream_t)stream, depth, mask, q, (int)n, y1, c,
                        residual, on_ground);
   ATDN_HIP(hipGetLastError());
+  ATDN_API_END
+}
+
+int atdn_ground_classify_host(const float* depth, const unsigned char* mask, const double* q, int B, int H, int W, int y0, int y1,
+                              double fx, double fy, double cx, double cy, double inlier_rel, double min_z, double max_depth,
+                              float* residual, unsigned char* on_ground) {
+  ATDN_API_BEGIN
+  const GroundCall a{depth, mask, q, B, H, W, y0, y1, fx, fy, cx, cy, 1.0, inlier_rel, min_z, max_depth};
+  ground_classify_host(depth, mask, q, B, H, W, y1, ground_classify_args(a, residual, on_ground, false), residual, on_ground);
   ATDN_API_END
 }

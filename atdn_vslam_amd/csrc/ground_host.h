@@ -12,7 +12,7 @@
 //                    (ldl3_factor / ldl3_solve of lm6.h)
 //   ground_classify_pixel   e as float32 and the inlier flag of one pixel
 // The plane sum is plane_sum_host<10> of plane_lm.h: the chunks, the 4-sum, the tree and the chunk order of the pose solvers over
-// 10 terms. ground_terms_host / ground_solve_host / ground_classify_host are the host forms behind atdn_ground_*_host (capi.hip),
+// 10 terms. ground_terms_host / ground_solve_host / ground_classify_host are the host forms behind atdn_ground_*_host (ground.hip),
 // which serve CPU tensors. The kernels of ground.hip call the same functions, so the two cannot drift apart; the independent
 // statement the tests compare both with is tests/ground_ref.py (NumPy). The rule is stated in full in include/atdn_hip.h,
 // atdn_ground_terms and atdn_ground_solve; only + - * /, comparisons and integer operations, every operation rounded on its own

@@ -53,11 +53,12 @@ __global__ __launch_bounds__(PQ_THREADS) void multiview_depth_kernel(const float
   quad_count<3>(flags, bits, counts + 3 * b);
 }
 
-// Argument rules shared by the device entry point below and the host one (capi.hip).
-void multiview_check_args(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
-                          const float* depth_init, int N, int B, int S, int H, int W, double fx, double fy, double cx, double cy,
-                          double scale_px, double inlier_px, double min_z, int min_views, double max_rel_sigma, double max_depth,
-                          int iters, const float* depth, const float* info, const unsigned char* views, const int* counts) {
+// Argument rules shared by the two entry points below (depth_init may be null), and the parameters of the call.
+static MultiviewParams multiview_check_args(const float* acc_bank, const unsigned char* alive_bank, const float* poses,
+                                            const int* slots, const float* depth_init, int N, int B, int S, int H, int W, double fx,
+                                            double fy, double cx, double cy, double scale_px, double inlier_px, double min_z,
+                                            int min_views, double max_rel_sigma, double max_depth, int iters, const float* depth,
+                                            const float* info, const unsigned char* views, const int* counts) {
   ATDN_CHECK(acc_bank && alive_bank && poses && slots, "null argument");
   const void* out[4] = {depth, info, views, counts};
   check_plane_solver(B, H, W, true, fx, fy, cx, cy, scale_px, inlier_px, out, 4);
@@ -73,6 +74,7 @@ void multiview_check_args(const float* acc_bank, const unsigned char* alive_bank
   const long in_bytes[5] = {(long)N * 2 * n * 4, (long)N * n, (long)N * 48, (long)B * S * 4, (long)B * n * 4};
   const long out_bytes[4] = {(long)B * n * 4, (long)B * n * 4, (long)B * n, (long)B * 12};
   check_disjoint(in, in_bytes, 5, out, out_bytes, 4);
+  return multiview_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, min_views, max_rel_sigma, max_depth, iters, H, W);
 }
 
 }  // namespace atdn
@@ -84,13 +86,24 @@ int atdn_multiview_depth(const float* acc_bank, const unsigned char* alive_bank,
                          double scale_px, double inlier_px, double min_z, int min_views, double max_rel_sigma, double max_depth,
                          int iters, float* depth, float* info, unsigned char* views, int* counts, void* stream) {
   ATDN_API_BEGIN
-  multiview_check_args(acc_bank, alive_bank, poses, slots, depth_init, N, B, S, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z,
-                       min_views, max_rel_sigma, max_depth, iters, depth, info, views, counts);
+  const MultiviewParams c = multiview_check_args(acc_bank, alive_bank, poses, slots, depth_init, N, B, S, H, W, fx, fy, cx, cy,
+                                                 scale_px, inlier_px, min_z, min_views, max_rel_sigma, max_depth, iters, depth, info,
+                                                 views, counts);
   ATDN_HIP(hipMemsetAsync(counts, 0, (size_t)B * 12, (hipStream_t)stream));
   hipLaunchKernelGGL(multiview_depth_kernel, dim3((unsigned)cdivl((long)H * W, PQ_THREADS), (unsigned)B), dim3(PQ_THREADS), 0,
-                     (hipStream_t)stream, acc_bank, alive_bank, poses, slots, depth_init, N, S, H, W,
-                     multiview_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, min_views, max_rel_sigma, max_depth, iters, H, W),
-                     depth, info, views, counts);
+                     (hipStream_t)stream, acc_bank, alive_bank, poses, slots, depth_init, N, S, H, W, c, depth, info, views, counts);
   ATDN_HIP(hipGetLastError());
+  ATDN_API_END
+}
+
+int atdn_multiview_depth_host(const float* acc_bank, const unsigned char* alive_bank, const float* poses, const int* slots,
+                              const float* depth_init, int N, int B, int S, int H, int W, double fx, double fy, double cx, double cy,
+                              double scale_px, double inlier_px, double min_z, int min_views, double max_rel_sigma, double max_depth,
+                              int iters, float* depth, float* info, unsigned char* views, int* counts) {
+  ATDN_API_BEGIN
+  const MultiviewParams c = multiview_check_args(acc_bank, alive_bank, poses, slots, depth_init, N, B, S, H, W, fx, fy, cx, cy,
+                                                 scale_px, inlier_px, min_z, min_views, max_rel_sigma, max_depth, iters, depth, info,
+                                                 views, counts);
+  multiview_depth_host(acc_bank, alive_bank, poses, slots, depth_init, N, B, S, H, W, c, depth, info, views, counts);
   ATDN_API_END
 }

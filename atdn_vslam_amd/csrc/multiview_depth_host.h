@@ -2,7 +2,7 @@
 // MV_MAX_VIEWS later frames with known poses (the depth half of bundle adjustment, the batch form of a depth filter), by
 // Levenberg-Marquardt on the reprojection error under the Geman-McClure loss, with the information of the result. The rule in
 // plain C++ float64 (no HIP needed): multiview_pixel is the whole rule for one pixel, multiview_depth_host the host form behind
-// atdn_multiview_depth_host (capi.hip), which serves CPU tensors. The kernel of multiview_depth.hip calls the same function, so
+// atdn_multiview_depth_host (multiview_depth.hip), which serves CPU tensors. The kernel of multiview_depth.hip calls the same function, so
 // the two cannot drift apart; the independent statement the tests compare both with is tests/multiview_ref.py (NumPy). The rule
 // is stated in full in include/atdn_hip.h, atdn_multiview_depth; only + - * / and comparisons, every operation rounded on its
 // own (fp contraction off). The robust loss, the cost of a point behind a camera, the internal pose and the damping constants

@@ -1,8 +1,9 @@
 // What the two dense pose solvers (pnp_host.h: pose from depth and flow; epipolar_host.h: pose from flow alone) share, in plain
 // C++ float64 (no HIP needed): 28 terms per pixel — the 21 upper-triangle entries of a 6 x 6 Gauss-Newton Hessian, row by row, the
 // 6 gradient entries and the cost —, their order-fixed sum over a plane, the solver's state of one problem and the
-// Levenberg-Marquardt decision on it. What a pixel contributes, and how a step is taken from the accepted terms, is each solver's
-// own. Every operation rounded on its own (fp contraction off).
+// Levenberg-Marquardt decision on it, and the loop of a solve (plane_solve_host). What a pixel contributes, and how a step is
+// taken from the accepted terms, is each solver's own: a stateless struct `Solver` (PnpSolver, EpipolarSolver) names its
+// load_pose, lm_step and output. Every operation rounded on its own (fp contraction off).
 //   plane sum    a plane is cut into chunks of 1024 consecutive flat indices; inside a chunk, thread j = 0 .. 255 owns the indices
 //                4j .. 4j + 3 and forms ((t0 + t1) + t2) + t3 (an index past the plane contributes +0.0), the 256 values go through
 //                the binary tree of strides 1 .. 128 (v[i] += v[i + stride] for i a multiple of 2 * stride); the chunk sums are
@@ -83,6 +84,24 @@ inline void plane_sum_host(long n, Pixel pixel, double* sums, int counts[3]) {
         for (int e = 0; e < TERMS; ++e)
           v[(size_t)i * TERMS + e] = v[(size_t)i * TERMS + e] + v[(size_t)(i + stride) * TERMS + e];
     for (int e = 0; e < TERMS; ++e) sums[e] = ch == 0 ? v[e] : sums[e] + v[e];
+  }
+}
+
+// The solve of B problems: iters Levenberg-Marquardt steps (iters + 1 evaluations) from pose_init -> pose_out [B,12], cost [B],
+// counts [B,4]. plane(b, pose, sums, counts) writes the sums of plane b at the solver's pose.
+template <class Solver, class Plane>
+inline void plane_solve_host(int B, int iters, Plane plane, const float* pose_init, float* pose_out, double* cost, int* counts) {
+  for (int b = 0; b < B; ++b) {
+    PlaneLmState s;
+    Solver::load_pose(pose_init + 12L * b, s.trial);
+    for (int k = 0; k <= iters; ++k) {
+      double sums[PLANE_TERMS];
+      int cnt[3];
+      plane(b, s.trial, sums, cnt);
+      plane_lm_update(s, sums, cnt, k);
+      if (k < iters) Solver::lm_step(s);
+    }
+    Solver::output(s, pose_init + 12L * b, pose_out + 12L * b, cost + b, counts + 4L * b);
   }
 }
 

@@ -1,7 +1,8 @@
 // The device side of plane_lm.h, shared by the two dense pose solvers (pnp.hip, epipolar.hip): the workspace of a solve, the
 // fixed binary tree that takes the 28 sums of a workgroup's threads to its slot of the workspace, and the order-fixed sum of the
 // slots of a plane. The terms kernels run (chunks, B) workgroups of pixel_quads.h with off = 0 — workgroup c of plane b owns the
-// flat indices 1024 c .. 1024 c + 1023, a thread four consecutive ones —; the finalise kernels one wave per problem. No memset
+// flat indices 1024 c .. 1024 c + 1023, a thread four consecutive ones —; the finalise kernel (plane_finalise_kernel<Solver>, one
+// for both) one wave per problem; plane_run is the launch sequence of their entry points. No memset
 // and no atomics: every workgroup writes its own slot (store-and-sum: cdna_hip_programming.md, Guideline 12).
 // The tree and the ordered sum take the number of terms as a template parameter (28 unless given): ground.hip walks the same
 // tree over its 10 terms, with a workspace of its own.
@@ -100,6 +101,53 @@ __device__ __forceinline__ void plane_ordered_sum(const double* __restrict__ csu
     Cn[t - 32] = s;
   }
   __syncthreads();
+}
+
+// One wave per problem; Solver is PnpSolver or EpipolarSolver. k < 0: one evaluation (the plane sums go to sums_out /
+// counts_out). k >= 0: evaluation k of a solve of `iters` steps: thread 0 takes the Levenberg-Marquardt decision and then either
+// the next step or, after the last evaluation, writes the outputs.
+template <class Solver>
+__global__ __launch_bounds__(PLANE_FIN_THREADS) void plane_finalise_kernel(const double* __restrict__ csums,
+                                                                          const int* __restrict__ ccounts, int chunks, int k,
+                                                                          int iters, PlaneLmState* __restrict__ state,
+                                                                          const float* __restrict__ pose_init,
+                                                                          double* __restrict__ sums_out, int* __restrict__ counts_out,
+                                                                          float* __restrict__ pose_out, double* __restrict__ cost_out) {
+#pragma clang fp contract(off)
+  __shared__ double S[PLANE_TERMS];
+  __shared__ int Cn[3];
+  const int b = blockIdx.x;
+  const int t = threadIdx.x;
+  plane_ordered_sum(csums, ccounts, chunks, b, S, Cn);
+  if (k < 0) {
+    if (t < PLANE_TERMS) sums_out[(long)b * PLANE_TERMS + t] = S[t];
+    if (t < 3) counts_out[3 * b + t] = Cn[t];
+    return;
+  }
+  if (t != 0) return;
+  PlaneLmState& s = state[b];
+  if (k == 0) Solver::load_pose(pose_init + 12 * b, s.trial);
+  plane_lm_update(s, S, Cn, k);
+  if (k < iters)
+    Solver::lm_step(s);
+  else
+    Solver::output(s, pose_init + 12 * b, pose_out + 12 * b, cost_out + b, counts_out + 4 * b);
+}
+
+// The launches of an entry point: launch_terms(pose32, ws) is the solver's terms kernel at the float32 poses `pose32`, or at the
+// trial poses of the state where pose32 is null. iters < 0: one evaluation, sums [B,28] and counts [B,3] (2 launches). Otherwise a
+// solve of `iters` steps from `pose`: pose_out [B,12], cost [B], counts [B,4] (2 (iters + 1) launches).
+template <class Solver, class LaunchTerms>
+inline void plane_run(LaunchTerms launch_terms, void* workspace, int B, int H, int W, int iters, const float* pose, double* sums,
+                      int* counts, float* pose_out, double* cost, hipStream_t stream) {
+  const PlaneWorkspace ws = plane_carve(workspace, B, H, W);
+  const bool solve = iters >= 0;
+  for (int k = 0; k <= (solve ? iters : 0); ++k) {
+    launch_terms(k == 0 ? pose : nullptr, ws);
+    hipLaunchKernelGGL(plane_finalise_kernel<Solver>, dim3((unsigned)B), dim3(PLANE_FIN_THREADS), 0, stream, ws.sums, ws.counts,
+                       (int)plane_chunks(H, W), solve ? k : -1, solve ? iters : 0, ws.state, pose, sums, counts, pose_out, cost);
+    ATDN_HIP(hipGetLastError());
+  }
 }
 
 }  // namespace atdn

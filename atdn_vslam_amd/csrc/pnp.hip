@@ -10,12 +10,13 @@
 //                        of flow, mask), keeps the 28 sums of its pixels in 56 VGPRs, reduces them by the fixed binary tree — wave
 //                        shuffles for the strides 1 .. 32, LDS for (w0 + w1) + (w2 + w3) — and stores them in ITS slot of the
 //                        workspace (store-and-sum: cdna_hip_programming.md, Guideline 12).
-//   pnp_finalise_kernel  one wave per problem: thread e < 28 adds the chunk sums of term e in chunk order (coalesced: the 28
+//   plane_finalise_kernel<PnpSolver> (plane_sum.h)  one wave per problem: thread e < 28 adds the chunk sums of term e in chunk order (coalesced: the 28
 //                        terms of a chunk are contiguous), threads 32 .. 34 the integer counts; thread 0 then either writes the
 //                        sums out (atdn_pnp_terms) or takes the Levenberg-Marquardt decision and the next step (the 6 x 6 LDL^T
-//                        of lm6.h, fully unrolled, in registers) on the problem's PnpState in the workspace.
+//                        of lm6.h, fully unrolled, in registers) on the problem's PlaneLmState in the workspace.
 // The pose of evaluation 0 is read from the caller's float32 pose by both kernels; later ones from the state.
-// The tree, the ordered sum and the workspace are written once, in plane_sum.h, for this file and epipolar.hip.
+// The tree, the ordered sum, the workspace, the finalise kernel and the launches of a call (plane_run) are written once, in
+// plane_sum.h, for this file and epipolar.hip. The host twins of the two entry points stand below them.
 #include "../../include/atdn_hip.h"
 
 #include <cmath>
@@ -32,7 +33,7 @@ template <bool MASKED>
 __global__ __launch_bounds__(PQ_THREADS) void pnp_terms_kernel(const float* __restrict__ depth, const float* __restrict__ flow,
                                                                const unsigned char* __restrict__ mask,
                                                                const float* __restrict__ pose32,
-                                                               const PnpState* __restrict__ state, int H, int W, PnpParams cam,
+                                                               const PlaneLmState* __restrict__ state, int H, int W, PnpParams cam,
                                                                double* __restrict__ csums, int* __restrict__ ccounts) {
 #pragma clang fp contract(off)
   const int n = H * W;
@@ -47,9 +48,9 @@ __global__ __launch_bounds__(PQ_THREADS) void pnp_terms_kernel(const float* __re
 #pragma unroll
     for (int i = 0; i < 12; ++i) P[i] = state[b].trial[i];
   }
-  double acc[PNP_TERMS];
+  double acc[PLANE_TERMS];
 #pragma unroll
-  for (int e = 0; e < PNP_TERMS; ++e) acc[e] = 0.0;
+  for (int e = 0; e < PLANE_TERMS; ++e) acc[e] = 0.0;
   float z[4] = {0.0f, 0.0f, 0.0f, 0.0f}, u[4] = {0.0f, 0.0f, 0.0f, 0.0f}, v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   bool keep[4] = {true, true, true, true};
   if (q.lo < q.hi) {
@@ -68,49 +69,21 @@ __global__ __launch_bounds__(PQ_THREADS) void pnp_terms_kernel(const float* __re
     const float uk = k == 0 ? u[0] : k == 1 ? u[1] : k == 2 ? u[2] : u[3];
     const float vk = k == 0 ? v[0] : k == 1 ? v[1] : k == 2 ? v[2] : v[3];
     const bool kk = k == 0 ? keep[0] : k == 1 ? keep[1] : k == 2 ? keep[2] : keep[3];
-    double t[PNP_TERMS];
+    double t[PLANE_TERMS];
     int flags = 0;
     if (q.has(k)) {
       flags = pnp_pixel(zk, uk, vk, kk, P, cam, H, W, x, y, t);
       if (++x == W) { x = 0; ++y; }
     } else {
 #pragma unroll
-      for (int e = 0; e < PNP_TERMS; ++e) t[e] = 0.0;
+      for (int e = 0; e < PLANE_TERMS; ++e) t[e] = 0.0;
     }
 #pragma unroll
-    for (int e = 0; e < PNP_TERMS; ++e) acc[e] = k == 0 ? t[e] : acc[e] + t[e];   // ((t0 + t1) + t2) + t3
+    for (int e = 0; e < PLANE_TERMS; ++e) acc[e] = k == 0 ? t[e] : acc[e] + t[e];   // ((t0 + t1) + t2) + t3
 #pragma unroll
     for (int j = 0; j < 3; ++j) cnt[j] += __popcll(__ballot(flags & (1 << j)));   // the wave's count, in every lane
   }
   plane_chunk_reduce(acc, cnt, b, csums, ccounts);
-}
-
-// k < 0: atdn_pnp_terms (the plane sums go to sums_out / counts_out). k >= 0: evaluation k of a solve of `iters` steps.
-__global__ __launch_bounds__(PLANE_FIN_THREADS) void pnp_finalise_kernel(const double* __restrict__ csums,
-                                                                        const int* __restrict__ ccounts, int chunks, int k, int iters,
-                                                                        PnpState* __restrict__ state,
-                                                                        const float* __restrict__ pose_init,
-                                                                        double* __restrict__ sums_out, int* __restrict__ counts_out,
-                                                                        float* __restrict__ pose_out, double* __restrict__ cost_out) {
-#pragma clang fp contract(off)
-  __shared__ double S[PNP_TERMS];
-  __shared__ int Cn[3];
-  const int b = blockIdx.x;
-  const int t = threadIdx.x;
-  plane_ordered_sum(csums, ccounts, chunks, b, S, Cn);
-  if (k < 0) {
-    if (t < PNP_TERMS) sums_out[(long)b * PNP_TERMS + t] = S[t];
-    if (t < 3) counts_out[3 * b + t] = Cn[t];
-    return;
-  }
-  if (t != 0) return;
-  PnpState& s = state[b];
-  if (k == 0) pnp_internal_pose(pose_init + 12 * b, s.trial);
-  plane_lm_update(s, S, Cn, k);
-  if (k < iters)
-    pnp_lm_step(s);
-  else
-    pnp_output(s, pose_init + 12 * b, pose_out + 12 * b, cost_out + b, counts_out + 4 * b);
 }
 
 static void pnp_launch_terms(const float* depth, const float* flow, const unsigned char* mask, const float* pose32,
@@ -125,18 +98,52 @@ static void pnp_launch_terms(const float* depth, const float* flow, const unsign
   ATDN_HIP(hipGetLastError());
 }
 
-// Argument rules shared by the device entry points below and the host ones (capi.hip). out[i] of out_bytes[i]: the outputs
-// (a workspace among them), none of which may overlap an input or another output.
-void pnp_check_args(const float* depth, const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W,
-                    double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, bool grid_limit,
-                    const void* const* out, const long* out_bytes, int n_out) {
-  ATDN_CHECK(depth && flow && pose, "null argument");
-  check_plane_solver(B, H, W, grid_limit, fx, fy, cx, cy, scale_px, inlier_px, out, n_out);
-  ATDN_CHECK(std::isfinite(min_z) && min_z > 0.0, "min_z must be finite and > 0");
-  const long n = (long)H * W;
-  const void* in[4] = {depth, flow, mask, pose};
-  const long in_bytes[4] = {(long)B * n * 4, (long)B * 2 * n * 4, (long)B * n, (long)B * 48};
+struct PnpCall {
+  const float* depth;
+  const float* flow;
+  const unsigned char* mask;
+  const float* pose;
+  int B, H, W;
+  double fx, fy, cx, cy, scale_px, inlier_px, min_z;
+};
+
+// Argument rules of an entry pair. out[i] of out_bytes[i]: the outputs, none of which may be null or overlap an input or another
+// output. The device form (`device`) limits B to gridDim.y before anything else, and its workspace is one more output.
+static void pnp_check_args(const PnpCall& c, bool device, const void* const* out, const long* out_bytes, int n_out) {
+  if (device) check_plane_batch(c.B, c.H, c.W);
+  ATDN_CHECK(c.depth && c.flow && c.pose, "null argument");
+  check_plane_solver(c.B, c.H, c.W, device, c.fx, c.fy, c.cx, c.cy, c.scale_px, c.inlier_px, out, n_out);
+  ATDN_CHECK(std::isfinite(c.min_z) && c.min_z > 0.0, "min_z must be finite and > 0");
+  const long n = (long)c.H * c.W;
+  const void* in[4] = {c.depth, c.flow, c.mask, c.pose};
+  const long in_bytes[4] = {(long)c.B * n * 4, (long)c.B * 2 * n * 4, (long)c.B * n, (long)c.B * 48};
   check_disjoint(in, in_bytes, 4, out, out_bytes, n_out);
+}
+
+// Both forms of atdn_pnp_terms: the checks and the camera
+static PnpParams pnp_terms_args(const PnpCall& c, double* sums, int* counts, bool device, void* workspace) {
+  const void* out[3] = {sums, counts, workspace};
+  const long out_bytes[3] = {(long)c.B * PLANE_TERMS * 8, (long)c.B * 12, (long)plane_workspace_size(c.B, c.H, c.W)};
+  pnp_check_args(c, device, out, out_bytes, device ? 3 : 2);
+  return pnp_params(c.fx, c.fy, c.cx, c.cy, c.scale_px, c.inlier_px, c.min_z, c.H, c.W);
+}
+
+// Both forms of atdn_pnp_solve
+static PnpParams pnp_solve_args(const PnpCall& c, int iters, float* pose_out, double* cost, int* counts, bool device,
+                                void* workspace) {
+  const void* out[4] = {pose_out, cost, counts, workspace};
+  const long out_bytes[4] = {(long)c.B * 48, (long)c.B * 8, (long)c.B * 16, (long)plane_workspace_size(c.B, c.H, c.W)};
+  pnp_check_args(c, device, out, out_bytes, device ? 4 : 3);
+  ATDN_CHECK(iters >= 0 && iters <= 64, "iters must be in [0, 64]");
+  return pnp_params(c.fx, c.fy, c.cx, c.cy, c.scale_px, c.inlier_px, c.min_z, c.H, c.W);
+}
+
+// the launches of a call: plane_run (plane_sum.h) over pnp_launch_terms
+static void pnp_run(const PnpCall& c, const PnpParams& cam, int iters, double* sums, int* counts, float* pose_out, double* cost,
+                    void* workspace, void* stream) {
+  plane_run<PnpSolver>([&](const float* pose32, const PlaneWorkspace& ws) {
+    pnp_launch_terms(c.depth, c.flow, c.mask, pose32, ws, c.B, c.H, c.W, cam, (hipStream_t)stream);
+  }, workspace, c.B, c.H, c.W, iters, c.pose, sums, counts, pose_out, cost, (hipStream_t)stream);
 }
 
 }  // namespace atdn
@@ -152,17 +159,20 @@ int atdn_pnp_terms(const float* depth, const float* flow, const unsigned char* m
                    double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, double* sums,
                    int* counts, void* workspace, void* stream) {
   ATDN_API_BEGIN
-  check_plane_batch(B, H, W);
-  const void* out[3] = {sums, counts, workspace};
-  const long out_bytes[3] = {(long)B * PNP_TERMS * 8, (long)B * 12, (long)plane_workspace_size(B, H, W)};
-  pnp_check_args(depth, flow, mask, pose, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z, true, out, out_bytes, 3);
+  const PnpCall c{depth, flow, mask, pose, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z};
+  const PnpParams cam = pnp_terms_args(c, sums, counts, true, workspace);
   ATDN_CHECK(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)sums & 7) == 0, "workspace and sums must be 8-byte aligned");
-  const PnpParams cam = pnp_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, H, W);
-  const PlaneWorkspace ws = plane_carve(workspace, B, H, W);
-  pnp_launch_terms(depth, flow, mask, pose, ws, B, H, W, cam, (hipStream_t)stream);
-  hipLaunchKernelGGL(pnp_finalise_kernel, dim3((unsigned)B), dim3(PLANE_FIN_THREADS), 0, (hipStream_t)stream, ws.sums, ws.counts,
-                     (int)plane_chunks(H, W), -1, 0, ws.state, pose, sums, counts, (float*)nullptr, (double*)nullptr);
-  ATDN_HIP(hipGetLastError());
+  pnp_run(c, cam, -1, sums, counts, nullptr, nullptr, workspace, stream);
+  ATDN_API_END
+}
+
+int atdn_pnp_terms_host(const float* depth, const float* flow, const unsigned char* mask, const float* pose, int B, int H, int W,
+                        double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, double* sums,
+                        int* counts) {
+  ATDN_API_BEGIN
+  const PnpCall c{depth, flow, mask, pose, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z};
+  const PnpParams cam = pnp_terms_args(c, sums, counts, false, nullptr);
+  pnp_terms_host(depth, flow, mask, pose, B, H, W, cam, sums, counts);
   ATDN_API_END
 }
 
@@ -170,19 +180,19 @@ int atdn_pnp_solve(const float* depth, const float* flow, const unsigned char* m
                    double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, int iters,
                    float* pose_out, double* cost, int* counts, void* workspace, void* stream) {
   ATDN_API_BEGIN
-  check_plane_batch(B, H, W);
-  const void* out[4] = {pose_out, cost, counts, workspace};
-  const long out_bytes[4] = {(long)B * 48, (long)B * 8, (long)B * 16, (long)plane_workspace_size(B, H, W)};
-  pnp_check_args(depth, flow, mask, pose_init, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z, true, out, out_bytes, 4);
-  ATDN_CHECK(iters >= 0 && iters <= 64, "iters must be in [0, 64]");
+  const PnpCall c{depth, flow, mask, pose_init, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z};
+  const PnpParams cam = pnp_solve_args(c, iters, pose_out, cost, counts, true, workspace);
   ATDN_CHECK(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)cost & 7) == 0, "workspace and cost must be 8-byte aligned");
-  const PnpParams cam = pnp_params(fx, fy, cx, cy, scale_px, inlier_px, min_z, H, W);
-  const PlaneWorkspace ws = plane_carve(workspace, B, H, W);
-  for (int k = 0; k <= iters; ++k) {
-    pnp_launch_terms(depth, flow, mask, k == 0 ? pose_init : nullptr, ws, B, H, W, cam, (hipStream_t)stream);
-    hipLaunchKernelGGL(pnp_finalise_kernel, dim3((unsigned)B), dim3(PLANE_FIN_THREADS), 0, (hipStream_t)stream, ws.sums, ws.counts,
-                       (int)plane_chunks(H, W), k, iters, ws.state, pose_init, (double*)nullptr, counts, pose_out, cost);
-    ATDN_HIP(hipGetLastError());
-  }
+  pnp_run(c, cam, iters, nullptr, counts, pose_out, cost, workspace, stream);
+  ATDN_API_END
+}
+
+int atdn_pnp_solve_host(const float* depth, const float* flow, const unsigned char* mask, const float* pose_init, int B, int H,
+                        int W, double fx, double fy, double cx, double cy, double scale_px, double inlier_px, double min_z, int iters,
+                        float* pose_out, double* cost, int* counts) {
+  ATDN_API_BEGIN
+  const PnpCall c{depth, flow, mask, pose_init, B, H, W, fx, fy, cx, cy, scale_px, inlier_px, min_z};
+  const PnpParams cam = pnp_solve_args(c, iters, pose_out, cost, counts, false, nullptr);
+  pnp_solve_host(depth, flow, mask, pose_init, B, H, W, cam, iters, pose_out, cost, counts);
   ATDN_API_END
 }

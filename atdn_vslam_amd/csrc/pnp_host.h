@@ -3,7 +3,7 @@
 // Gauss-Newton normal equations of the reprojection error under the Geman-McClure loss, pnp_plane_host the fixed-order sum of
 // a plane, pnp_lm_step one Levenberg-Marquardt step (the 28 terms, the chunks, the state and the decision are those of
 // plane_lm.h, shared with epipolar_host.h; the 6 x 6 algebra, the Cayley matrix and the damping constants are those of lm6.h, shared with the pose graph; the composition from the left is
-// PnP's own), pnp_terms_host / pnp_solve_host the host forms behind atdn_pnp_terms_host / atdn_pnp_solve_host (capi.hip), which
+// PnP's own), pnp_terms_host / pnp_solve_host the host forms behind atdn_pnp_terms_host / atdn_pnp_solve_host (pnp.hip), which
 // serve CPU tensors. The kernels of pnp.hip call the same functions, so the two cannot drift apart; the independent statement
 // the tests compare both with is tests/pnp_ref.py (NumPy). The rule is stated in full in include/atdn_hip.h, atdn_pnp_terms and
 // atdn_pnp_solve; only + - * / and comparisons, every operation rounded on its own (fp contraction off).
@@ -15,10 +15,6 @@
 
 namespace atdn {
 
-// the 28 terms, the chunks of the plane sum, the state and the decision are those of plane_lm.h, shared with epipolar_host.h
-constexpr int PNP_TERMS = PLANE_TERMS;
-constexpr int PNP_CHUNK = PLANE_CHUNK;
-constexpr int PNP_CHUNK_THREADS = PLANE_CHUNK_THREADS;
 enum { PNP_CAND = 1, PNP_USED = 2, PNP_INLIER = 4 };
 
 struct PnpParams {
@@ -42,9 +38,7 @@ inline PnpParams pnp_params(double fx, double fy, double cx, double cy, double s
   return p;
 }
 
-// The solver's state of one problem. Poses are INTERNAL: p[0..8] = Rc (row-major), p[9..11] = tc, X2 = Rc X1 + tc.
-using PnpState = PlaneLmState;
-
+// The poses of the solver's state (PlaneLmState) are INTERNAL: p[0..8] = Rc (row-major), p[9..11] = tc, X2 = Rc X1 + tc.
 // public pose (12 float32, rows of [R|t], X1 = R X2 + t) -> internal pose
 ATDN_HD inline void pnp_internal_pose(const float* pose12, double p[12]) {
 #pragma clang fp contract(off)
@@ -71,10 +65,10 @@ ATDN_HD inline void pnp_public_pose(const double p[12], float* pose12) {
 // The 28 terms of pixel (x, y): z its depth, (u, v) its flow, keep its mask. Returns the PNP_* bits; t is always written
 // (+0.0 where the pixel contributes nothing).
 ATDN_HD inline int pnp_pixel(float zf, float u, float v, bool keep, const double* P, const PnpParams& c, int H, int W, int x,
-                             int y, double t[PNP_TERMS]) {
+                             int y, double t[PLANE_TERMS]) {
 #pragma clang fp contract(off)
 #pragma unroll
-  for (int i = 0; i < PNP_TERMS; ++i) t[i] = 0.0;
+  for (int i = 0; i < PLANE_TERMS; ++i) t[i] = 0.0;
   const double xd = (double)x, yd = (double)y, z = (double)zf;
   const double x2 = xd + (double)u, y2 = yd + (double)v;
   const bool inside = x2 >= 0.0 && x2 <= (double)(W - 1) && y2 >= 0.0 && y2 <= (double)(H - 1);
@@ -127,7 +121,7 @@ ATDN_HD inline int pnp_pixel(float zf, float u, float v, bool keep, const double
 }
 
 // The damped step from the accepted point: s.trial = retract(s.acc, delta), or s.acc again where the factorisation fails.
-ATDN_HD inline void pnp_lm_step(PnpState& s) {
+ATDN_HD inline void pnp_lm_step(PlaneLmState& s) {
 #pragma clang fp contract(off)
   double A[36], F[21], b[6], dl[6], E[9];
   int n = 0;
@@ -152,7 +146,7 @@ ATDN_HD inline void pnp_lm_step(PnpState& s) {
 }
 
 // The outputs of a finished solve.
-ATDN_HD inline void pnp_output(const PnpState& s, const float* pose_in, float* pose_out, double* cost, int* counts4) {
+ATDN_HD inline void pnp_output(const PlaneLmState& s, const float* pose_in, float* pose_out, double* cost, int* counts4) {
   if (s.accepted == 0) {
     for (int i = 0; i < 12; ++i) pose_out[i] = pose_in[i];
   } else {
@@ -165,7 +159,7 @@ ATDN_HD inline void pnp_output(const PnpState& s, const float* pose_in, float* p
 
 // The sums of one plane at the internal pose P, in the order of plane_sum_host (plane_lm.h).
 inline void pnp_plane_host(const float* depth, const float* fu, const float* fv, const unsigned char* mask, const double* P,
-                           const PnpParams& c, int H, int W, double sums[PNP_TERMS], int counts[3]) {
+                           const PnpParams& c, int H, int W, double sums[PLANE_TERMS], int counts[3]) {
   plane_sum_host((long)H * W, [&](long i, double* t) {
     const int y = (int)(i / W), x = (int)(i - (long)y * W);
     return pnp_pixel(depth[i], fu[i], fv[i], mask ? mask[i] != 0 : true, P, c, H, W, x, y, t);
@@ -180,27 +174,26 @@ inline void pnp_terms_host(const float* depth, const float* flow, const unsigned
     double P[12];
     pnp_internal_pose(pose + 12L * b, P);
     pnp_plane_host(depth + b * n, flow + 2 * b * n, flow + (2 * b + 1) * n, mask ? mask + b * n : nullptr, P, c, H, W,
-                   sums + (long)PNP_TERMS * b, counts + 3L * b);
+                   sums + (long)PLANE_TERMS * b, counts + 3L * b);
   }
 }
+
+// what plane_finalise_kernel (plane_sum.h) and plane_solve_host (plane_lm.h) run for this solver
+struct PnpSolver {
+  ATDN_HD static void load_pose(const float* pose12, double p[12]) { pnp_internal_pose(pose12, p); }
+  ATDN_HD static void lm_step(PlaneLmState& s) { pnp_lm_step(s); }
+  ATDN_HD static void output(const PlaneLmState& s, const float* pose_in, float* pose_out, double* cost, int* counts4) {
+    pnp_output(s, pose_in, pose_out, cost, counts4);
+  }
+};
 
 // iters Levenberg-Marquardt steps (iters + 1 evaluations) from pose_init -> pose_out [B,12], cost [B], counts [B,4]
 inline void pnp_solve_host(const float* depth, const float* flow, const unsigned char* mask, const float* pose_init, int B, int H,
                            int W, const PnpParams& c, int iters, float* pose_out, double* cost, int* counts) {
   const long n = (long)H * W;
-  for (int b = 0; b < B; ++b) {
-    PnpState s;
-    pnp_internal_pose(pose_init + 12L * b, s.trial);
-    for (int k = 0; k <= iters; ++k) {
-      double sums[PNP_TERMS];
-      int cnt[3];
-      pnp_plane_host(depth + b * n, flow + 2 * b * n, flow + (2 * b + 1) * n, mask ? mask + b * n : nullptr, s.trial, c, H, W,
-                     sums, cnt);
-      plane_lm_update(s, sums, cnt, k);
-      if (k < iters) pnp_lm_step(s);
-    }
-    pnp_output(s, pose_init + 12L * b, pose_out + 12L * b, cost + b, counts + 4L * b);
-  }
+  plane_solve_host<PnpSolver>(B, iters, [&](int b, const double* P, double* sums, int* cnt) {
+    pnp_plane_host(depth + b * n, flow + 2 * b * n, flow + (2 * b + 1) * n, mask ? mask + b * n : nullptr, P, c, H, W, sums, cnt);
+  }, pose_init, pose_out, cost, counts);
 }
 
 }  // namespace atdn

@@ -75,8 +75,8 @@ __global__ __launch_bounds__(PQ_THREADS) void depth_backproject_kernel(const flo
   p[2 * (long)n] = (float)z;
 }
 
-// Argument rules shared by the device entry point below and the host one (capi.hip).
-void two_view_check_args(const float* flow, const float* pose, const unsigned char* mask, int B, int H, int W,
+// Argument rules shared by the two entry points of atdn_flow_two_view_depth below.
+static void two_view_check_args(const float* flow, const float* pose, const unsigned char* mask, int B, int H, int W,
                          const TwoViewCamera& cam, const float* depth, const int* counts) {
   ATDN_CHECK(flow && pose && depth && counts, "null argument");
   check_plane_batch(B, H, W, false);
@@ -113,6 +113,16 @@ int atdn_flow_two_view_depth(const float* flow, const float* pose, const unsigne
     hipLaunchKernelGGL(two_view_kernel<false>, grid, dim3(PQ_THREADS), 0, (hipStream_t)stream, flow, pose, mask, H, W, cam, depth,
                        counts);
   ATDN_HIP(hipGetLastError());
+  ATDN_API_END
+}
+
+int atdn_flow_two_view_depth_host(const float* flow, const float* pose, const unsigned char* mask, int B, int H, int W, double fx,
+                                  double fy, double cx, double cy, double max_epipolar, double min_sin2, double max_depth,
+                                  float* depth, int* counts) {
+  ATDN_API_BEGIN
+  const TwoViewCamera cam{fx, fy, cx, cy, max_epipolar, min_sin2, max_depth};
+  two_view_check_args(flow, pose, mask, B, H, W, cam, depth, counts);
+  two_view_depth_host(flow, pose, mask, B, H, W, cam, depth, counts);
   ATDN_API_END
 }
 

@@ -1,5 +1,5 @@
 // Two-view geometry of a flow and a relative pose, the rule in plain C++ float64 (no HIP needed): two_view_pixel is the rule for
-// one pixel, two_view_depth_host the host form behind atdn_flow_two_view_depth_host (capi.hip), which serves CPU tensors. The
+// one pixel, two_view_depth_host the host form behind atdn_flow_two_view_depth_host (two_view.hip), which serves CPU tensors. The
 // kernel of two_view.hip evaluates the same function, so the two cannot drift apart; the independent statement the tests compare
 // both with is tests/two_view_ref.py (NumPy). The epipolar part of the pixel rule (x2 .. epi2) is two_view_epipolar, which
 // epipolar_host.h (pose from flow alone) calls too.

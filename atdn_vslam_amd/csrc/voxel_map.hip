@@ -263,21 +263,21 @@ __global__ __launch_bounds__(VOX_THREADS) void voxel_extract_kernel(uint64_t* __
   }
 }
 
-// ---- argument rules shared by the device entry points below and the host ones (capi.hip)
+// ---- argument rules, shared by the two entry points of each pair below (images, mask, indices, pending and colors may be null)
 
-void voxel_check_table(const void* table, long capacity) {
+static void voxel_check_table(const void* table, long capacity) {
   ATDN_CHECK(table, "null argument");
   ATDN_CHECK(capacity >= 2 && capacity <= VOX_MAX_CAPACITY && (capacity & (capacity - 1)) == 0,
              "capacity must be a power of two in [2, 2^31]");
   ATDN_CHECK(((uintptr_t)table & 7) == 0, "the table must be 8-byte aligned");
 }
 
-void voxel_check_grid(double voxel, double ox, double oy, double oz) {
+static void voxel_check_grid(double voxel, double ox, double oy, double oz) {
   ATDN_CHECK(std::isfinite(voxel) && voxel > 0.0, "voxel must be finite and > 0");
   ATDN_CHECK(std::isfinite(ox) && std::isfinite(oy) && std::isfinite(oz), "the origin must be finite");
 }
 
-void voxel_check_integrate(const float* depth, const float* poses, const unsigned char* images, const unsigned char* mask,
+static void voxel_check_integrate(const float* depth, const float* poses, const unsigned char* images, const unsigned char* mask,
                            const int* indices, int N, int K, int H, int W, double fx, double fy, double cx, double cy, int stride,
                            double voxel, double ox, double oy, double oz, double min_z, double max_z, const void* table,
                            long capacity, const unsigned char* pending) {
@@ -299,14 +299,14 @@ void voxel_check_integrate(const float* depth, const float* poses, const unsigne
   check_disjoint(in, in_bytes, 5, out, out_bytes, pending ? 2 : 1);
 }
 
-void voxel_check_rehash(const void* src, long src_capacity, const void* dst, long dst_capacity) {
+static void voxel_check_rehash(const void* src, long src_capacity, const void* dst, long dst_capacity) {
   voxel_check_table(src, src_capacity);
   voxel_check_table(dst, dst_capacity);
   ATDN_CHECK(dst_capacity >= src_capacity, "the destination must not be smaller than the source");
   ATDN_CHECK(disjoint(src, voxel_table_words(src_capacity) * 8, dst, voxel_table_words(dst_capacity) * 8), "the tables overlap");
 }
 
-void voxel_check_extract(const void* table, long capacity, int min_count, double voxel, double ox, double oy, double oz, long max_out,
+static void voxel_check_extract(const void* table, long capacity, int min_count, double voxel, double ox, double oy, double oz, long max_out,
                          const float* points, const unsigned char* colors, const int* counts, const int64_t* keys,
                          const int64_t* found) {
   voxel_check_table(table, capacity);
@@ -342,6 +342,13 @@ int atdn_voxel_clear(void* table, long capacity, void* stream) {
   ATDN_API_END
 }
 
+int atdn_voxel_clear_host(void* table, long capacity) {
+  ATDN_API_BEGIN
+  voxel_check_table(table, capacity);
+  voxel_clear_host((uint64_t*)table, capacity);
+  ATDN_API_END
+}
+
 int atdn_voxel_integrate(const float* depth, const float* poses, const uint8_t* images, const uint8_t* mask, const int* indices, int N,
                          int K, int H, int W, double fx, double fy, double cx, double cy, int stride, double voxel, double ox,
                          double oy, double oz, double min_z, double max_z, int retry, void* table, long capacity, uint8_t* pending,
@@ -361,6 +368,19 @@ int atdn_voxel_integrate(const float* depth, const float* poses, const uint8_t* 
   ATDN_API_END
 }
 
+int atdn_voxel_integrate_host(const float* depth, const float* poses, const uint8_t* images, const uint8_t* mask, const int* indices,
+                              int N, int K, int H, int W, double fx, double fy, double cx, double cy, int stride, double voxel,
+                              double ox, double oy, double oz, double min_z, double max_z, int retry, void* table, long capacity,
+                              uint8_t* pending) {
+  ATDN_API_BEGIN
+  voxel_check_integrate(depth, poses, images, mask, indices, N, K, H, W, fx, fy, cx, cy, stride, voxel, ox, oy, oz, min_z, max_z,
+                        table, capacity, pending);
+  voxel_integrate_host(depth, poses, images, mask, indices, N, K, H, W,
+                       voxel_params(fx, fy, cx, cy, stride, voxel, ox, oy, oz, min_z, max_z), retry != 0, (uint64_t*)table, capacity,
+                       pending);
+  ATDN_API_END
+}
+
 int atdn_voxel_rehash(const void* src, long src_capacity, void* dst, long dst_capacity, void* stream) {
   ATDN_API_BEGIN
   voxel_check_rehash(src, src_capacity, dst, dst_capacity);
@@ -368,6 +388,13 @@ int atdn_voxel_rehash(const void* src, long src_capacity, void* dst, long dst_ca
                      (hipStream_t)stream, (const uint64_t*)src, src_capacity, (uint64_t*)dst, (uint32_t)(dst_capacity - 1),
                      (int)voxel_probe_limit(dst_capacity));
   ATDN_HIP(hipGetLastError());
+  ATDN_API_END
+}
+
+int atdn_voxel_rehash_host(const void* src, long src_capacity, void* dst, long dst_capacity) {
+  ATDN_API_BEGIN
+  voxel_check_rehash(src, src_capacity, dst, dst_capacity);
+  voxel_rehash_host((const uint64_t*)src, src_capacity, (uint64_t*)dst, dst_capacity);
   ATDN_API_END
 }
 
@@ -379,5 +406,14 @@ int atdn_voxel_extract(void* table, long capacity, int min_count, double voxel, 
                      (uint64_t*)table, capacity, min_count, voxel_params(1.0, 1.0, 0.0, 0.0, 1, voxel, ox, oy, oz, 0.0, 0.0),
                      max_out, points, colors, counts, keys, found);
   ATDN_HIP(hipGetLastError());
+  ATDN_API_END
+}
+
+int atdn_voxel_extract_host(void* table, long capacity, int min_count, double voxel, double ox, double oy, double oz,
+                            long max_out, float* points, uint8_t* colors, int* counts, int64_t* keys, int64_t* found) {
+  ATDN_API_BEGIN
+  voxel_check_extract(table, capacity, min_count, voxel, ox, oy, oz, max_out, points, colors, counts, keys, found);
+  voxel_extract_host((const uint64_t*)table, capacity, min_count, voxel_params(1.0, 1.0, 0.0, 0.0, 1, voxel, ox, oy, oz, 0.0, 0.0),
+                     max_out, points, colors, counts, keys, found);
   ATDN_API_END
 }

@@ -1,6 +1,6 @@
 // Voxel map: every keyframe's depth accumulated into one voxel-hashed point cloud — the rule in plain C++ (no HIP needed).
 // voxel_point is the rule for one pixel (float64, every operation rounded on its own, fp contraction off), voxel_home the home
-// slot of a key, voxel_emit the extraction of one voxel; voxel_*_host are the host forms behind atdn_voxel_*_host (capi.hip),
+// slot of a key, voxel_emit the extraction of one voxel; voxel_*_host are the host forms behind atdn_voxel_*_host (voxel_map.hip),
 // which serve CPU tensors. The kernels of voxel_map.hip call the same functions, so the two cannot drift apart; the independent
 // statement the tests compare both with is tests/voxel_map_ref.py (NumPy). The rule is stated in full in include/atdn_hip.h.
 //

@@ -21,6 +21,7 @@
 #include <climits>
 
 #include "common.h"
+#include "warm_start_host.h"
 
 namespace atdn {
 
@@ -94,5 +95,16 @@ int atdn_flow_forward_interpolate(const float* flow_low, int B, int h, int w, fl
   hipLaunchKernelGGL(forward_interpolate_kernel, dim3((unsigned)cdivl(n, WS_QPB), (unsigned)B), dim3(WS_QPB * WS_SPLIT), 0,
                      (hipStream_t)stream, flow_low, h, w, out);
   ATDN_HIP(hipGetLastError());
+  ATDN_API_END
+}
+
+// (the host form has always worded its size rules as one)
+int atdn_flow_forward_interpolate_host(const float* flow_low, int B, int h, int w, float* out) {
+  ATDN_API_BEGIN
+  ATDN_CHECK(flow_low && out, "null argument");
+  ATDN_CHECK(B >= 1 && h >= 1 && w >= 1 && (long)h * w <= (1L << 24), "bad batch or grid size");
+  const long bytes = (long)B * 2 * h * w * 4;
+  ATDN_CHECK(disjoint(flow_low, bytes, out, bytes), "input and output overlap");
+  forward_interpolate_host(flow_low, B, h, w, out);
   ATDN_API_END
 }

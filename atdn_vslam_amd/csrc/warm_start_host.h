@@ -1,5 +1,5 @@
 // Forward interpolation of a flow field along itself, host form (plain C++, no HIP): the rules of warm_start.hip in float64.
-// atdn_flow_forward_interpolate_host (capi.hip) is this function behind argument checks; it serves CPU tensors and is what the
+// atdn_flow_forward_interpolate_host (warm_start.hip) is this function behind argument checks; it serves CPU tensors and is what the
 // CPU tests compare with the recorded outputs of the GMA wheel's forward_interpolate (whl:GMA/core/utils/utils.py:28-56).
 //
 // For one flow [2, h, w] (channel 0 = dx, 1 = dy) and the row-major source index i = y * w + x:

@@ -1,8 +1,6 @@
 """Calibration and depth helpers (atdn_vslam/utils/depth.py): `read_calib` and `project_depth` with the reference's call contracts,
 plus what the odometry path needs to use a calibration on its own grid: `intrinsics` and `resize_calib`. Depth itself comes from
 `transforms.two_view_depth` (a flow, a relative pose and a calibration); the reference has no producer of it."""
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -66,9 +64,7 @@ def project_depth(depth, calib, device=None):
     if d.is_cuda:
         points = torch.empty((3, H, W), dtype=torch.float32, device=d.device)
         with torch.cuda.device(d.device):
-            _lib.check(_lib.lib().atdn_depth_backproject(C.c_void_p(d.data_ptr()), 1, H, W, fx, fy, cx, cy,
-                                                         C.c_void_p(points.data_ptr()),
-                                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            _lib.check(_lib.lib().atdn_depth_backproject(_lib.ptr(d), 1, H, W, fx, fy, cx, cy, _lib.ptr(points), _lib.stream()))
         return points
     z = d.reshape(H, W).double()
     x = torch.arange(W, dtype=torch.float64).view(1, W)

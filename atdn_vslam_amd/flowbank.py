@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr, stream as _stream
 from .evaluation import relative_motions
 from .transforms import InputPadder
 
@@ -35,14 +36,6 @@ BANK_HW = (376, 1232)       # what the pose head reads (neural_slam.py:198; Line
 CROP_SIZE = (376, 1241)     # FlowKittiDataset2/3's source width before the centre crop (datasets.py:120-122,184-186)
 TRAIN_SEED = 4265664478     # train_odometry.py:64
 GEOMETRIES = ("slam", "crop")
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def crop_slice(width, target=BANK_HW[1]):

@@ -28,16 +28,9 @@ import numpy as np
 import torch
 
 from . import _lib, transforms
+from ._lib import ptr as _ptr, stream as _stream
 
 MAX_TOP_K = 16
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def embedding_hw(hw):

@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._lib import ptr as _ptr, stream as _stream
 from .weights_spec import F32, clvo_state_spec, gma_state_spec, vae_state_spec
 
 _BUFFER_LEAVES = ("running_mean", "running_var", "num_batches_tracked", "rel_ind")
@@ -42,14 +43,6 @@ def _build_tree(root, spec):
             mod.register_buffer(leaf, t)
         else:
             mod.register_parameter(leaf, nn.Parameter(t, requires_grad=False))
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class SplitF16RangeError(RuntimeError):

@@ -1,12 +1,12 @@
 """Pose algebra of the odometry path (atdn_vslam/utils/transforms.py) and the frame padder
 (whl:GMA/core/utils/utils.py:8-25), host side of libatdn_hip."""
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr
 
 
 def _np32(x):
@@ -14,11 +14,6 @@ def _np32(x):
         x = x.detach().to("cpu")
         x = x.numpy()
     return np.ascontiguousarray(np.asarray(x, dtype=np.float32))
-
-
-def _stream():
-    """The current stream of the current device, as the library's `void* stream` argument."""
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _byte_plane(t, what, B, H, W):
@@ -91,12 +86,7 @@ def forward_interpolate(flow):
     B = src.shape[0] if src.dim() == 4 else 1
     h, w = src.shape[-2:]
     out = torch.empty_like(src)
-    if src.is_cuda:
-        with torch.cuda.device(src.device):
-            _lib.check(_lib.lib().atdn_flow_forward_interpolate(C.c_void_p(src.data_ptr()), B, h, w, C.c_void_p(out.data_ptr()),
-                                                                _stream()))
-    else:
-        _lib.check(_lib.lib().atdn_flow_forward_interpolate_host(C.c_void_p(src.data_ptr()), B, h, w, C.c_void_p(out.data_ptr())))
+    _lib.call("atdn_flow_forward_interpolate", src.device, _ptr(src), B, h, w, _ptr(out))
     return out
 
 
@@ -113,14 +103,7 @@ def _flow_consistency_counts(flow_fw, flow_bw, alpha1, alpha2):
     B, _, H, W = fw.shape
     mask = torch.empty((B, 1, H, W), dtype=torch.uint8, device=fw.device)
     count = torch.empty((B,), dtype=torch.int32, device=fw.device)
-    L = _lib.lib()
-    if fw.is_cuda:
-        with torch.cuda.device(fw.device):
-            _lib.check(L.atdn_flow_consistency(C.c_void_p(fw.data_ptr()), C.c_void_p(bw.data_ptr()), B, H, W, float(alpha1),
-                                               float(alpha2), C.c_void_p(mask.data_ptr()), C.c_void_p(count.data_ptr()), _stream()))
-    else:
-        _lib.check(L.atdn_flow_consistency_host(C.c_void_p(fw.data_ptr()), C.c_void_p(bw.data_ptr()), B, H, W, float(alpha1),
-                                                float(alpha2), C.c_void_p(mask.data_ptr()), C.c_void_p(count.data_ptr())))
+    _lib.call("atdn_flow_consistency", fw.device, _ptr(fw), _ptr(bw), B, H, W, float(alpha1), float(alpha2), _ptr(mask), _ptr(count))
     return mask, count
 
 
@@ -155,6 +138,39 @@ def _pose_rows(pose, B, device):
     return p.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
+def _pose_matrices(rows):
+    """Rows of [R|t], float32 [B,12] -> [B,4,4] with the last row 0 0 0 1."""
+    pose = torch.zeros((rows.shape[0], 4, 4), dtype=torch.float32, device=rows.device)
+    pose[:, 3, 3] = 1.0
+    pose[:, :3, :] = rows.view(-1, 3, 4)
+    return pose
+
+
+def _flow_inputs(flow, pose, mask, depth=None):
+    """The checked, contiguous inputs of the functions of a flow, a pose and a mask (and a depth), with the batch axis added to a
+    3-d flow: (single, flow [B,2,H,W], depth or None, pose rows [B,12], mask uint8 or None, B, H, W), all on the flow's device."""
+    if flow.dim() not in (3, 4) or flow.shape[-3] != 2:
+        raise RuntimeError("expected a flow [2,H,W] or [B,2,H,W], got %s" % (tuple(flow.shape),))
+    single = flow.dim() == 3
+    f = (flow[None] if single else flow).detach().float().contiguous()
+    B, _, H, W = f.shape
+    d = None
+    if depth is not None:
+        d = torch.as_tensor(depth)
+        if d.numel() != B * H * W or tuple(d.shape[-2:]) != (H, W):
+            raise RuntimeError("expected a depth of %d x %d x %d values, got %s" % (B, H, W, tuple(d.shape)))
+        if d.device != f.device:
+            raise RuntimeError("flow on %s but depth on %s" % (f.device, d.device))
+        d = d.detach().float().contiguous()
+    p = _pose_rows(pose, B, f.device)
+    m = None
+    if mask is not None:
+        m = _byte_plane(torch.as_tensor(mask), "a mask", B, H, W)
+        if m.device != f.device:
+            raise RuntimeError("flow on %s but mask on %s" % (f.device, m.device))
+    return single, f, d, p, m, B, H, W
+
+
 def two_view_depth(flow, pose, calib, mask=None, max_epipolar=1.0, min_parallax_deg=0.05, max_depth=80.0):
     """Depth and epipolar agreement of a flow and a relative pose under a calibration. `flow` [B,2,H,W] (or [2,H,W]) is the flow
     from image 1 to image 2, channel 0 = x; `pose` [B,4,4], [B,3,4] or [B,12] the relative pose with X1 = R X2 + t — what
@@ -169,30 +185,11 @@ def two_view_depth(flow, pose, calib, mask=None, max_epipolar=1.0, min_parallax_
     library's host form. The rule is float64 and stated in full in include/atdn_hip.h, atdn_flow_two_view_depth; the same inputs
     give the same bits on every call and on both paths."""
     from .depth import intrinsics
-    if flow.dim() not in (3, 4) or flow.shape[-3] != 2:
-        raise RuntimeError("expected a flow [2,H,W] or [B,2,H,W], got %s" % (tuple(flow.shape),))
-    single = flow.dim() == 3
-    f = (flow[None] if single else flow).detach().float().contiguous()
-    B, _, H, W = f.shape
-    p = _pose_rows(pose, B, f.device)
-    fx, fy, cx, cy = intrinsics(calib)
-    m = None
-    if mask is not None:
-        m = _byte_plane(torch.as_tensor(mask), "a mask", B, H, W)
-        if m.device != f.device:
-            raise RuntimeError("flow on %s but mask on %s" % (f.device, m.device))
-    min_sin2 = _min_sin2(min_parallax_deg)
+    single, f, _, p, m, B, H, W = _flow_inputs(flow, pose, mask)
     depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=f.device)
     counts = torch.empty((B, 3), dtype=torch.int32, device=f.device)
-    L = _lib.lib()
-    args = (C.c_void_p(f.data_ptr()), C.c_void_p(p.data_ptr()), C.c_void_p(m.data_ptr()) if m is not None else None, B, H, W,
-            fx, fy, cx, cy, float(max_epipolar), min_sin2, float(max_depth), C.c_void_p(depth.data_ptr()),
-            C.c_void_p(counts.data_ptr()))
-    if f.is_cuda:
-        with torch.cuda.device(f.device):
-            _lib.check(L.atdn_flow_two_view_depth(*args, _stream()))
-    else:
-        _lib.check(L.atdn_flow_two_view_depth_host(*args))
+    _lib.call("atdn_flow_two_view_depth", f.device, _ptr(f), _ptr(p), _ptr(m), B, H, W, *intrinsics(calib), float(max_epipolar),
+              _min_sin2(min_parallax_deg), float(max_depth), _ptr(depth), _ptr(counts))
     return (depth[0], counts[0]) if single else (depth, counts)
 
 
@@ -247,16 +244,33 @@ def fuse_depths(bank, poses, targets, sources, calib, max_reproj=1.0, max_rel_de
     fused = torch.empty((B, 1, H, W), dtype=torch.float32, device=bank.device)
     views = torch.empty((B, H, W), dtype=torch.uint8, device=bank.device)
     counts = torch.empty((B, 3), dtype=torch.int32, device=bank.device)
-    L = _lib.lib()
-    args = (C.c_void_p(bank.data_ptr()), C.c_void_p(p.data_ptr()), C.c_void_p(t.data_ptr()), C.c_void_p(s.data_ptr()) if S else None,
-            N, B, S, H, W, fx, fy, cx, cy, float(max_reproj), float(max_rel_depth), int(min_views), float(min_z),
-            1 if average else 0, C.c_void_p(fused.data_ptr()), C.c_void_p(views.data_ptr()), C.c_void_p(counts.data_ptr()))
-    if bank.is_cuda:
-        with torch.cuda.device(bank.device):
-            _lib.check(L.atdn_depth_fuse(*args, _stream()))
-    else:
-        _lib.check(L.atdn_depth_fuse_host(*args))
+    _lib.call("atdn_depth_fuse", bank.device, _ptr(bank), _ptr(p), _ptr(t), _ptr(s) if S else None, N, B, S, H, W, fx, fy, cx, cy,
+              float(max_reproj), float(max_rel_depth), int(min_views), float(min_z), 1 if average else 0, _ptr(fused), _ptr(views),
+              _ptr(counts))
     return fused, views, counts
+
+
+def _flow_bank_inputs(acc_bank, alive_bank, poses, slots):
+    """The checked, contiguous flow bank of `multiview_depth` and the bundle adjustment: (acc_bank float32 [N,2,H,W], alive uint8,
+    pose rows [N,12], slots int32 [B,S], N, B, S, H, W), all on the bank's device."""
+    if not isinstance(acc_bank, torch.Tensor) or acc_bank.dim() != 4 or acc_bank.shape[1] != 2:
+        raise RuntimeError("expected a flow bank [N,2,H,W], got %s" % (tuple(getattr(acc_bank, "shape", ())),))
+    if acc_bank.dtype != torch.float32 or not acc_bank.is_contiguous():
+        acc_bank = acc_bank.detach().float().contiguous()
+    N, _, H, W = (int(v) for v in acc_bank.shape)
+    device = acc_bank.device
+    if not isinstance(alive_bank, torch.Tensor) or alive_bank.device != device:
+        raise RuntimeError("flow bank on %s but the liveness bank on %s" % (device, getattr(alive_bank, "device", "the host")))
+    alive = _byte_plane(alive_bank, "a liveness bank", N, H, W)
+    if isinstance(poses, torch.Tensor) and poses.device != device:
+        raise RuntimeError("bank on %s but poses on %s" % (device, poses.device))
+    p = _pose_rows(torch.as_tensor(poses), N, device)
+    s = _index_tensor(slots, "slots", device)
+    s = s[None] if s.dim() == 1 else s
+    if s.dim() != 2 or s.shape[0] < 1 or s.shape[1] < 1:
+        raise RuntimeError("expected slots [B,S], got %s" % (tuple(s.shape),))
+    B, S = int(s.shape[0]), int(s.shape[1])
+    return acc_bank, alive, p, s, N, B, S, H, W
 
 
 def multiview_depth(acc_bank, alive_bank, poses, slots, calib, depth_init=None, iters=4, scale_px=4.0, inlier_px=2.0, min_z=0.1,
@@ -277,23 +291,8 @@ def multiview_depth(acc_bank, alive_bank, poses, slots, calib, depth_init=None, 
     synchronisation); CPU tensors go through the library's host form. The rule is float64 and stated in full in
     include/atdn_hip.h, atdn_multiview_depth; the same inputs give the same bits on every call and on both paths."""
     from .depth import intrinsics
-    if not isinstance(acc_bank, torch.Tensor) or acc_bank.dim() != 4 or acc_bank.shape[1] != 2:
-        raise RuntimeError("expected a flow bank [N,2,H,W], got %s" % (tuple(getattr(acc_bank, "shape", ())),))
-    if acc_bank.dtype != torch.float32 or not acc_bank.is_contiguous():
-        acc_bank = acc_bank.detach().float().contiguous()
-    N, _, H, W = (int(v) for v in acc_bank.shape)
+    acc_bank, alive, p, s, N, B, S, H, W = _flow_bank_inputs(acc_bank, alive_bank, poses, slots)
     device = acc_bank.device
-    if not isinstance(alive_bank, torch.Tensor) or alive_bank.device != device:
-        raise RuntimeError("flow bank on %s but the liveness bank on %s" % (device, getattr(alive_bank, "device", "the host")))
-    alive = _byte_plane(alive_bank, "a liveness bank", N, H, W)
-    if isinstance(poses, torch.Tensor) and poses.device != device:
-        raise RuntimeError("bank on %s but poses on %s" % (device, poses.device))
-    p = _pose_rows(torch.as_tensor(poses), N, device)
-    s = _index_tensor(slots, "slots", device)
-    s = s[None] if s.dim() == 1 else s
-    if s.dim() != 2 or s.shape[0] < 1 or s.shape[1] < 1:
-        raise RuntimeError("expected slots [B,S], got %s" % (tuple(s.shape),))
-    B, S = int(s.shape[0]), int(s.shape[1])
     z0 = None
     if depth_init is not None:
         if not isinstance(depth_init, torch.Tensor) or depth_init.device != device:
@@ -306,16 +305,9 @@ def multiview_depth(acc_bank, alive_bank, poses, slots, calib, depth_init=None, 
     info = torch.empty((B, 1, H, W), dtype=torch.float32, device=device)
     views = torch.empty((B, H, W), dtype=torch.uint8, device=device)
     counts = torch.empty((B, 3), dtype=torch.int32, device=device)
-    L = _lib.lib()
-    args = (C.c_void_p(acc_bank.data_ptr()), C.c_void_p(alive.data_ptr()), C.c_void_p(p.data_ptr()), C.c_void_p(s.data_ptr()),
-            C.c_void_p(z0.data_ptr()) if z0 is not None else None, N, B, S, H, W, fx, fy, cx, cy, float(scale_px), float(inlier_px),
-            float(min_z), int(min_views), float(max_rel_sigma), float(max_depth), int(iters), C.c_void_p(depth.data_ptr()),
-            C.c_void_p(info.data_ptr()), C.c_void_p(views.data_ptr()), C.c_void_p(counts.data_ptr()))
-    if acc_bank.is_cuda:
-        with torch.cuda.device(device):
-            _lib.check(L.atdn_multiview_depth(*args, _stream()))
-    else:
-        _lib.check(L.atdn_multiview_depth_host(*args))
+    _lib.call("atdn_multiview_depth", device, _ptr(acc_bank), _ptr(alive), _ptr(p), _ptr(s), _ptr(z0), N, B, S, H, W, fx, fy, cx, cy,
+              float(scale_px), float(inlier_px), float(min_z), int(min_views), float(max_rel_sigma), float(max_depth), int(iters),
+              _ptr(depth), _ptr(info), _ptr(views), _ptr(counts))
     return depth, info, views, counts
 
 
@@ -328,23 +320,8 @@ def bundle_sums(S):
 
 def _bundle_inputs(acc_bank, alive_bank, poses, slots, calib, depth_init, mask, stride, min_views):
     from .depth import intrinsics
-    if not isinstance(acc_bank, torch.Tensor) or acc_bank.dim() != 4 or acc_bank.shape[1] != 2:
-        raise RuntimeError("expected a flow bank [N,2,H,W], got %s" % (tuple(getattr(acc_bank, "shape", ())),))
-    if acc_bank.dtype != torch.float32 or not acc_bank.is_contiguous():
-        acc_bank = acc_bank.detach().float().contiguous()
-    N, _, H, W = (int(v) for v in acc_bank.shape)
+    acc_bank, alive, p, s, N, B, S, H, W = _flow_bank_inputs(acc_bank, alive_bank, poses, slots)
     device = acc_bank.device
-    if not isinstance(alive_bank, torch.Tensor) or alive_bank.device != device:
-        raise RuntimeError("flow bank on %s but the liveness bank on %s" % (device, getattr(alive_bank, "device", "the host")))
-    alive = _byte_plane(alive_bank, "a liveness bank", N, H, W)
-    if isinstance(poses, torch.Tensor) and poses.device != device:
-        raise RuntimeError("bank on %s but poses on %s" % (device, poses.device))
-    p = _pose_rows(torch.as_tensor(poses), N, device)
-    s = _index_tensor(slots, "slots", device)
-    s = s[None] if s.dim() == 1 else s
-    if s.dim() != 2 or s.shape[0] < 1 or s.shape[1] < 1:
-        raise RuntimeError("expected slots [B,S], got %s" % (tuple(s.shape),))
-    B, S = int(s.shape[0]), int(s.shape[1])
     if not isinstance(depth_init, torch.Tensor):
         raise RuntimeError("bundle adjustment needs an initial depth [B,1,H,W] (a tensor on the bank's device)")
     if depth_init.device != device:
@@ -360,16 +337,14 @@ def _bundle_inputs(acc_bank, alive_bank, poses, slots, calib, depth_init, mask, 
     if int(stride) < 1:
         raise RuntimeError("stride must be >= 1, got %r" % (stride,))
     fx, fy, cx, cy = intrinsics(calib)
-    ptrs = (C.c_void_p(acc_bank.data_ptr()), C.c_void_p(alive.data_ptr()), C.c_void_p(p.data_ptr()), C.c_void_p(s.data_ptr()),
-            C.c_void_p(z0.data_ptr()), C.c_void_p(m.data_ptr()) if m is not None else None, N, B, S, H, W, fx, fy, cx, cy, int(stride))
+    ptrs = (_ptr(acc_bank), _ptr(alive), _ptr(p), _ptr(s), _ptr(z0), _ptr(m), N, B, S, H, W, fx, fy, cx, cy, int(stride))
     return ptrs, (acc_bank, alive, p, s, z0, m), device, B, S, H, W
 
 
-def _bundle_workspace(L, device, B, S, H, W, stride):
-    nbytes = int(L.atdn_bundle_workspace_bytes(B, S, H, W, int(stride)))
-    if nbytes <= 0:
-        raise RuntimeError("bundle adjustment: batch, view count or image size out of range")
-    return torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=device)
+def _bundle_call(name, device, B, S, H, W, stride, *args):
+    ws = _lib.workspace("atdn_bundle_workspace_bytes", device, B, S, H, W, int(stride),
+                        message="bundle adjustment: batch, view count or image size out of range")
+    _lib.call(name, device, *args, workspace=ws)
 
 
 def bundle_terms(acc_bank, alive_bank, poses, slots, calib, depth, mask=None, stride=2, scale_px=4.0, inlier_px=2.0, min_z=0.1,
@@ -381,15 +356,8 @@ def bundle_terms(acc_bank, alive_bank, poses, slots, calib, depth, mask=None, st
     ptrs, keep, device, B, S, H, W = _bundle_inputs(acc_bank, alive_bank, poses, slots, calib, depth, mask, stride, min_views)
     sums = torch.empty((B, bundle_sums(S)), dtype=torch.float64, device=device)
     counts = torch.empty((B, 3), dtype=torch.int32, device=device)
-    L = _lib.lib()
-    args = ptrs + (float(scale_px), float(inlier_px), float(min_z), int(min_views), C.c_void_p(sums.data_ptr()),
-                   C.c_void_p(counts.data_ptr()))
-    if device.type == "cuda":
-        with torch.cuda.device(device):
-            ws = _bundle_workspace(L, device, B, S, H, W, stride)
-            _lib.check(L.atdn_bundle_terms(*args, C.c_void_p(ws.data_ptr()), _stream()))
-    else:
-        _lib.check(L.atdn_bundle_terms_host(*args))
+    _bundle_call("atdn_bundle_terms", device, B, S, H, W, stride, *ptrs, float(scale_px), float(inlier_px), float(min_z),
+                 int(min_views), _ptr(sums), _ptr(counts))
     return sums, counts
 
 
@@ -414,15 +382,8 @@ def bundle_adjust(acc_bank, alive_bank, poses, slots, calib, depth_init, mask=No
     depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=device)
     cost = torch.empty((B, 2), dtype=torch.float64, device=device)
     counts = torch.empty((B, 4), dtype=torch.int32, device=device)
-    L = _lib.lib()
-    args = ptrs + (int(iters), float(scale_px), float(inlier_px), float(min_z), int(min_views), C.c_void_p(poses_out.data_ptr()),
-                   C.c_void_p(depth.data_ptr()), C.c_void_p(cost.data_ptr()), C.c_void_p(counts.data_ptr()))
-    if device.type == "cuda":
-        with torch.cuda.device(device):
-            ws = _bundle_workspace(L, device, B, S, H, W, stride)
-            _lib.check(L.atdn_bundle_adjust(*args, C.c_void_p(ws.data_ptr()), _stream()))
-    else:
-        _lib.check(L.atdn_bundle_adjust_host(*args))
+    _bundle_call("atdn_bundle_adjust", device, B, S, H, W, stride, *ptrs, int(iters), float(scale_px), float(inlier_px), float(min_z),
+                 int(min_views), _ptr(poses_out), _ptr(depth), _ptr(cost), _ptr(counts))
     return poses_out, depth, cost, counts
 
 
@@ -438,31 +399,9 @@ def epipolar_score(counts):
 def _pnp_inputs(depth, flow, pose, calib, mask, scale_px, inlier_px, min_z):
     """The checked, contiguous inputs of `reprojection_terms` and `pose_from_depth`, with the batch axis added to 3-d forms."""
     from .depth import intrinsics
-    if flow.dim() not in (3, 4) or flow.shape[-3] != 2:
-        raise RuntimeError("expected a flow [2,H,W] or [B,2,H,W], got %s" % (tuple(flow.shape),))
-    single = flow.dim() == 3
-    f = (flow[None] if single else flow).detach().float().contiguous()
-    B, _, H, W = f.shape
-    d = torch.as_tensor(depth)
-    if d.numel() != B * H * W or tuple(d.shape[-2:]) != (H, W):
-        raise RuntimeError("expected a depth of %d x %d x %d values, got %s" % (B, H, W, tuple(d.shape)))
-    if d.device != f.device:
-        raise RuntimeError("flow on %s but depth on %s" % (f.device, d.device))
-    d = d.detach().float().contiguous()
-    p = _pose_rows(pose, B, f.device)
-    m = None
-    if mask is not None:
-        m = _byte_plane(torch.as_tensor(mask), "a mask", B, H, W)
-        if m.device != f.device:
-            raise RuntimeError("flow on %s but mask on %s" % (f.device, m.device))
-    ptr = (C.c_void_p(d.data_ptr()), C.c_void_p(f.data_ptr()), C.c_void_p(m.data_ptr()) if m is not None else None,
-           C.c_void_p(p.data_ptr()), B, H, W) + tuple(intrinsics(calib)) + (float(scale_px), float(inlier_px), float(min_z))
+    single, f, d, p, m, B, H, W = _flow_inputs(flow, pose, mask, depth=torch.as_tensor(depth))
+    ptr = (_ptr(d), _ptr(f), _ptr(m), _ptr(p), B, H, W) + tuple(intrinsics(calib)) + (float(scale_px), float(inlier_px), float(min_z))
     return single, (d, f, m, p), ptr, B, H, W
-
-
-def _pnp_workspace(B, H, W, device):
-    n = int(_lib.lib().atdn_pnp_workspace_bytes(B, H, W))
-    return torch.empty((max(n, 8) + 7) // 8, dtype=torch.float64, device=device)
 
 
 def reprojection_terms(depth, flow, pose, calib, mask=None, scale_px=4.0, inlier_px=2.0, min_z=0.1):
@@ -481,14 +420,8 @@ def reprojection_terms(depth, flow, pose, calib, mask=None, scale_px=4.0, inlier
     dev = keep[1].device
     sums = torch.empty((B, 28), dtype=torch.float64, device=dev)
     counts = torch.empty((B, 3), dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    out = (C.c_void_p(sums.data_ptr()), C.c_void_p(counts.data_ptr()))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            ws = _pnp_workspace(B, H, W, dev)
-            _lib.check(L.atdn_pnp_terms(*ptr, *out, C.c_void_p(ws.data_ptr()), _stream()))
-    else:
-        _lib.check(L.atdn_pnp_terms_host(*ptr, *out))
+    _lib.call("atdn_pnp_terms", dev, *ptr, _ptr(sums), _ptr(counts),
+              workspace=_lib.workspace("atdn_pnp_workspace_bytes", dev, B, H, W))
     return (sums[0], counts[0]) if single else (sums, counts)
 
 
@@ -511,45 +444,21 @@ def pose_from_depth(depth, flow, pose_init, calib, mask=None, iters=16, scale_px
     include/atdn_hip.h, atdn_pnp_solve; the same inputs give the same bits on every call and on both paths."""
     single, keep, ptr, B, H, W = _pnp_inputs(depth, flow, pose_init, calib, mask, scale_px, inlier_px, min_z)
     dev = keep[1].device
-    pose = torch.zeros((B, 4, 4), dtype=torch.float32, device=dev)
-    pose[:, 3, 3] = 1.0
     rows = torch.empty((B, 12), dtype=torch.float32, device=dev)
     cost = torch.empty((B,), dtype=torch.float64, device=dev)
     counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    out = (int(iters), C.c_void_p(rows.data_ptr()), C.c_void_p(cost.data_ptr()), C.c_void_p(counts.data_ptr()))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            ws = _pnp_workspace(B, H, W, dev)
-            _lib.check(L.atdn_pnp_solve(*ptr, *out, C.c_void_p(ws.data_ptr()), _stream()))
-    else:
-        _lib.check(L.atdn_pnp_solve_host(*ptr, *out))
-    pose[:, :3, :] = rows.view(B, 3, 4)
+    _lib.call("atdn_pnp_solve", dev, *ptr, int(iters), _ptr(rows), _ptr(cost), _ptr(counts),
+              workspace=_lib.workspace("atdn_pnp_workspace_bytes", dev, B, H, W))
+    pose = _pose_matrices(rows)
     return (pose[0], cost[0], counts[0]) if single else (pose, cost, counts)
 
 
 def _epipolar_inputs(flow, pose, calib, mask, scale_px, inlier_px):
     """The checked, contiguous inputs of `epipolar_terms` and `pose_from_flow`, with the batch axis added to 3-d forms."""
     from .depth import intrinsics
-    if flow.dim() not in (3, 4) or flow.shape[-3] != 2:
-        raise RuntimeError("expected a flow [2,H,W] or [B,2,H,W], got %s" % (tuple(flow.shape),))
-    single = flow.dim() == 3
-    f = (flow[None] if single else flow).detach().float().contiguous()
-    B, _, H, W = f.shape
-    p = _pose_rows(pose, B, f.device)
-    m = None
-    if mask is not None:
-        m = _byte_plane(torch.as_tensor(mask), "a mask", B, H, W)
-        if m.device != f.device:
-            raise RuntimeError("flow on %s but mask on %s" % (f.device, m.device))
-    ptr = (C.c_void_p(f.data_ptr()), C.c_void_p(m.data_ptr()) if m is not None else None, C.c_void_p(p.data_ptr()), B, H, W) + \
-        tuple(intrinsics(calib)) + (float(scale_px), float(inlier_px))
+    single, f, _, p, m, B, H, W = _flow_inputs(flow, pose, mask)
+    ptr = (_ptr(f), _ptr(m), _ptr(p), B, H, W) + tuple(intrinsics(calib)) + (float(scale_px), float(inlier_px))
     return single, (f, m, p), ptr, B, H, W
-
-
-def _epipolar_workspace(B, H, W, device):
-    n = int(_lib.lib().atdn_epipolar_workspace_bytes(B, H, W))
-    return torch.empty((max(n, 8) + 7) // 8, dtype=torch.float64, device=device)
 
 
 def epipolar_terms(flow, pose, calib, mask=None, scale_px=2.0, inlier_px=1.0):
@@ -568,14 +477,8 @@ def epipolar_terms(flow, pose, calib, mask=None, scale_px=2.0, inlier_px=1.0):
     dev = keep[0].device
     sums = torch.empty((B, 28), dtype=torch.float64, device=dev)
     counts = torch.empty((B, 3), dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    out = (C.c_void_p(sums.data_ptr()), C.c_void_p(counts.data_ptr()))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            ws = _epipolar_workspace(B, H, W, dev)
-            _lib.check(L.atdn_epipolar_terms(*ptr, *out, C.c_void_p(ws.data_ptr()), _stream()))
-    else:
-        _lib.check(L.atdn_epipolar_terms_host(*ptr, *out))
+    _lib.call("atdn_epipolar_terms", dev, *ptr, _ptr(sums), _ptr(counts),
+              workspace=_lib.workspace("atdn_epipolar_workspace_bytes", dev, B, H, W))
     return (sums[0], counts[0]) if single else (sums, counts)
 
 
@@ -593,20 +496,12 @@ def pose_from_flow(flow, pose_init, calib, mask=None, iters=16, scale_px=2.0, in
     bits on every call and on both paths."""
     single, keep, ptr, B, H, W = _epipolar_inputs(flow, pose_init, calib, mask, scale_px, inlier_px)
     dev = keep[0].device
-    pose = torch.zeros((B, 4, 4), dtype=torch.float32, device=dev)
-    pose[:, 3, 3] = 1.0
     rows = torch.empty((B, 12), dtype=torch.float32, device=dev)
     cost = torch.empty((B,), dtype=torch.float64, device=dev)
     counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    out = (int(iters), C.c_void_p(rows.data_ptr()), C.c_void_p(cost.data_ptr()), C.c_void_p(counts.data_ptr()))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            ws = _epipolar_workspace(B, H, W, dev)
-            _lib.check(L.atdn_epipolar_solve(*ptr, *out, C.c_void_p(ws.data_ptr()), _stream()))
-    else:
-        _lib.check(L.atdn_epipolar_solve_host(*ptr, *out))
-    pose[:, :3, :] = rows.view(B, 3, 4)
+    _lib.call("atdn_epipolar_solve", dev, *ptr, int(iters), _ptr(rows), _ptr(cost), _ptr(counts),
+              workspace=_lib.workspace("atdn_epipolar_workspace_bytes", dev, B, H, W))
+    pose = _pose_matrices(rows)
     return (pose[0], cost[0], counts[0]) if single else (pose, cost, counts)
 
 
@@ -647,14 +542,8 @@ def _ground_inputs(depth, calib, mask, rows, q=None):
             raise RuntimeError("depth on %s but q on %s" % (d.device, qq.device))
         qq = qq.detach().to(torch.float64).contiguous()
     y0, y1 = ground_rows(calib, H) if rows is None else (int(rows[0]), int(rows[1]))
-    ptr = (C.c_void_p(d.data_ptr()), C.c_void_p(m.data_ptr()) if m is not None else None,
-           C.c_void_p(qq.data_ptr()) if qq is not None else None, B, H, W, y0, y1) + tuple(intrinsics(calib))
+    ptr = (_ptr(d), _ptr(m), _ptr(qq), B, H, W, y0, y1) + tuple(intrinsics(calib))
     return single, (d, m, qq), ptr, B, H, W, (y0, y1)
-
-
-def _ground_workspace(B, H, W, device):
-    n = int(_lib.lib().atdn_ground_workspace_bytes(B, H, W))
-    return torch.empty((max(n, 8) + 7) // 8, dtype=torch.float64, device=device)
 
 
 def ground_terms(depth, q, calib, mask=None, rows=None, scale_rel=GROUND_DEFAULTS["scale_rel"],
@@ -675,15 +564,8 @@ def ground_terms(depth, q, calib, mask=None, rows=None, scale_rel=GROUND_DEFAULT
     dev = keep[0].device
     sums = torch.empty((B, 10), dtype=torch.float64, device=dev)
     counts = torch.empty((B, 3), dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    args = ptr + (float(scale_rel), float(inlier_rel), float(min_z), float(max_depth), C.c_void_p(sums.data_ptr()),
-                  C.c_void_p(counts.data_ptr()))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            ws = _ground_workspace(B, H, W, dev)
-            _lib.check(L.atdn_ground_terms(*args, C.c_void_p(ws.data_ptr()), _stream()))
-    else:
-        _lib.check(L.atdn_ground_terms_host(*args))
+    _lib.call("atdn_ground_terms", dev, *ptr, float(scale_rel), float(inlier_rel), float(min_z), float(max_depth), _ptr(sums),
+              _ptr(counts), workspace=_lib.workspace("atdn_ground_workspace_bytes", dev, B, H, W))
     return (sums[0], counts[0]) if single else (sums, counts)
 
 
@@ -709,15 +591,9 @@ def ground_plane(depth, calib, normal_prior=(0.0, 1.0, 0.0), q_init=None, mask=N
     q = torch.empty((B, 3), dtype=torch.float64, device=dev)
     sums = torch.empty((B, 10), dtype=torch.float64, device=dev)
     counts = torch.empty((B, 6), dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    args = ptr + tuple(n0) + (float(scale_rel), float(inlier_rel), float(min_z), float(max_depth), int(min_votes), int(iters),
-                              C.c_void_p(q.data_ptr()), C.c_void_p(sums.data_ptr()), C.c_void_p(counts.data_ptr()))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            ws = _ground_workspace(B, H, W, dev)
-            _lib.check(L.atdn_ground_solve(*args, C.c_void_p(ws.data_ptr()), _stream()))
-    else:
-        _lib.check(L.atdn_ground_solve_host(*args))
+    _lib.call("atdn_ground_solve", dev, *ptr, *n0, float(scale_rel), float(inlier_rel), float(min_z), float(max_depth),
+              int(min_votes), int(iters), _ptr(q), _ptr(sums), _ptr(counts),
+              workspace=_lib.workspace("atdn_ground_workspace_bytes", dev, B, H, W))
     return (q[0], sums[0], counts[0]) if single else (q, sums, counts)
 
 
@@ -733,14 +609,7 @@ def ground_classify(depth, q, calib, mask=None, rows=None, inlier_rel=GROUND_DEF
     dev = keep[0].device
     residual = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
     on_ground = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
-    L = _lib.lib()
-    args = ptr + (float(inlier_rel), float(min_z), float(max_depth), C.c_void_p(residual.data_ptr()),
-                  C.c_void_p(on_ground.data_ptr()))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            _lib.check(L.atdn_ground_classify(*args, _stream()))
-    else:
-        _lib.check(L.atdn_ground_classify_host(*args))
+    _lib.call("atdn_ground_classify", dev, *ptr, float(inlier_rel), float(min_z), float(max_depth), _ptr(residual), _ptr(on_ground))
     return (residual[0], on_ground[0]) if single else (residual, on_ground)
 
 
@@ -859,15 +728,8 @@ def flow_track_step(flow, acc, alive, pose=None, calib=None, mask=None, depth=No
             same_device(t, what)
             if t.dtype != dt or not t.is_contiguous() or t.numel() != count:
                 raise RuntimeError("%s must be contiguous %s of %d values, got %s %s" % (what, dt, count, t.dtype, tuple(t.shape)))
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
-    L = _lib.lib()
-    args = (ptr(f), ptr(m), ptr(a), ptr(live), B, H, W, ptr(a_out), ptr(l_out), ptr(p), fx, fy, cx, cy, float(max_epipolar),
-            min_sin2, float(max_depth), ptr(d), ptr(counts))
-    if f.is_cuda:
-        with torch.cuda.device(dev):
-            _lib.check(L.atdn_flow_track_step(*args, _stream()))
-    else:
-        _lib.check(L.atdn_flow_track_step_host(*args))
+    _lib.call("atdn_flow_track_step", dev, _ptr(f), _ptr(m), _ptr(a), _ptr(live), B, H, W, _ptr(a_out), _ptr(l_out), _ptr(p), fx, fy,
+              cx, cy, float(max_epipolar), min_sin2, float(max_depth), _ptr(d), _ptr(counts))
     d_ret = depth if depth is not None else (None if d is None else (d[0] if single else d))
     if out is not None:
         return a_out, l_out, d_ret, counts
@@ -917,8 +779,7 @@ def _pose_graph_inputs(poses, edge_index, edge_pose, edge_weight, edge_robust, f
         raise RuntimeError("edge_index and edge_weight are required")
     rob = arg(edge_robust, (B, E), torch.uint8, "edge_robust")
     fix = arg(fixed, (B, N), torch.uint8, "fixed")
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-    return batched, dev, (B, N, E), (p, idx, z, w, rob, fix), ptr
+    return batched, dev, (B, N, E), (p, idx, z, w, rob, fix)
 
 
 def pose_graph_terms(poses, edge_index, edge_pose, edge_weight, edge_robust=None, robust_scale=None):
@@ -933,25 +794,13 @@ def pose_graph_terms(poses, edge_index, edge_pose, edge_weight, edge_robust=None
     i == j or a weight that is not >= 0). Device tensors go through libatdn_hip's kernel on the current stream (one launch, no
     synchronisation), CPU tensors through the library's host form. The rule is float64, fixes the order of every sum and is
     stated in full in include/atdn_hip.h, atdn_pose_graph_terms; the same bits on every call and on both paths."""
-    batched, dev, (B, N, E), t, ptr = _pose_graph_inputs(poses, edge_index, edge_pose, edge_weight, edge_robust, None, robust_scale)
+    batched, dev, (B, N, E), t = _pose_graph_inputs(poses, edge_index, edge_pose, edge_weight, edge_robust, None, robust_scale)
     cost = torch.empty((B,), dtype=torch.float64, device=dev)
     chi2 = torch.empty((B, E), dtype=torch.float64, device=dev)
     counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    args = tuple(ptr(x) for x in t[:5]) + (B, N, E, 1.0 if robust_scale is None else float(robust_scale), ptr(cost), ptr(chi2),
-                                           ptr(counts))
-    if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            ws = _pose_graph_workspace(B, N, E, dev)
-            _lib.check(L.atdn_pose_graph_terms(*args, ptr(ws), _stream()))
-    else:
-        _lib.check(L.atdn_pose_graph_terms_host(*args))
+    _lib.call("atdn_pose_graph_terms", dev, *(_ptr(x) for x in t[:5]), B, N, E, 1.0 if robust_scale is None else float(robust_scale),
+              _ptr(cost), _ptr(chi2), _ptr(counts), workspace=_lib.workspace("atdn_pose_graph_workspace_bytes", dev, B, N, E))
     return (cost, chi2, counts) if batched else (cost[0], chi2[0], counts[0])
-
-
-def _pose_graph_workspace(B, N, E, device):
-    n = int(_lib.lib().atdn_pose_graph_workspace_bytes(B, N, E))
-    return torch.empty((max(n, 8) + 7) // 8, dtype=torch.float64, device=device)
 
 
 def pose_graph_optimize(poses, edge_index, edge_pose, edge_weight, edge_robust=None, robust_scale=None, fixed=None, iters=10,
@@ -969,7 +818,7 @@ def pose_graph_optimize(poses, edge_index, edge_pose, edge_weight, edge_robust=N
     comes back with its input bits; so does every node when no step is accepted. An edge of weight (0, 0) gives the same bits as
     the list without it. CPU tensors go through the library's host form. The rule is stated in full in include/atdn_hip.h,
     atdn_pose_graph_solve; the same inputs give the same bits on every call and on both paths."""
-    batched, dev, (B, N, E), t, ptr = _pose_graph_inputs(poses, edge_index, edge_pose, edge_weight, edge_robust, fixed, robust_scale)
+    batched, dev, (B, N, E), t = _pose_graph_inputs(poses, edge_index, edge_pose, edge_weight, edge_robust, fixed, robust_scale)
     p, idx, z, w, rob, fix = t
     if fix is None:
         fix = torch.zeros((B, N), dtype=torch.uint8, device=dev)
@@ -978,21 +827,15 @@ def pose_graph_optimize(poses, edge_index, edge_pose, edge_weight, edge_robust=N
                                                                     else [robust_scale])]
     if not scales:
         raise RuntimeError("robust_scale is an empty sequence")
-    L = _lib.lib()
     total = None
     for scale in scales:
         rows = torch.empty((B, N, 12), dtype=torch.float32, device=dev)
         cost = torch.empty((B, 2), dtype=torch.float64, device=dev)
         chi2 = torch.empty((B, E), dtype=torch.float64, device=dev)
         counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
-        args = (ptr(p), ptr(idx), ptr(z), ptr(w), ptr(rob), ptr(fix), B, N, E, scale, int(iters), int(cg_iters), float(cg_tol),
-                ptr(rows), ptr(cost), ptr(chi2), ptr(counts))
-        if dev.type == "cuda":
-            with torch.cuda.device(dev):
-                ws = _pose_graph_workspace(B, N, E, dev)
-                _lib.check(L.atdn_pose_graph_solve(*args, ptr(ws), _stream()))
-        else:
-            _lib.check(L.atdn_pose_graph_solve_host(*args))
+        _lib.call("atdn_pose_graph_solve", dev, _ptr(p), _ptr(idx), _ptr(z), _ptr(w), _ptr(rob), _ptr(fix), B, N, E, scale, int(iters),
+                  int(cg_iters), float(cg_tol), _ptr(rows), _ptr(cost), _ptr(chi2), _ptr(counts),
+                  workspace=_lib.workspace("atdn_pose_graph_workspace_bytes", dev, B, N, E))
         if total is not None:
             counts[:, 2:] += total[:, 2:]
         total = counts
@@ -1043,16 +886,13 @@ class InputPadder:
         tensors (the reference pads on whatever device the frame is on) use torch."""
         if not x.is_cuda:
             return torch.nn.functional.pad(x, self._pad, mode="replicate")
-        import ctypes as C
-        from . import _lib
         l, r, t, b = self._pad
         src = x.float().contiguous()
         H, W = src.shape[-2:]
         out = torch.empty(tuple(src.shape[:-2]) + (H + t + b, W + l + r), dtype=torch.float32, device=src.device)
         planes = int(src.numel() // (H * W))
         with torch.cuda.device(src.device):
-            _lib.check(_lib.lib().atdn_pad_frames(C.c_void_p(src.data_ptr()), planes, H, W, l, r, t, b,
-                                                  C.c_void_p(out.data_ptr()), _stream()))
+            _lib.check(_lib.lib().atdn_pad_frames(_ptr(src), planes, H, W, l, r, t, b, _ptr(out), _lib.stream()))
         return out
 
     def unpad(self, x):

@@ -6,22 +6,17 @@ positions and colour bytes. Integer sums commute, so the cloud does not depend o
 over calls or on the table's size: the same bits on the device, in the library's host form (CPU tensors) and in the NumPy
 restatement of the tests.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
-from .transforms import _byte_plane, _index_tensor, _pose_rows, _stream
+from ._lib import ptr as _ptr
+from .transforms import _byte_plane, _index_tensor, _pose_rows
 
 COUNTERS = ("candidates", "inserted", "outside", "dropped", "voxels")
 MAX_POINTS = 2 ** 31 - 1
 _HEADER_WORDS = 8
 _GROW_ROUNDS = 8            # doublings tried for the pixels an integrate dropped before the call gives up
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class VoxelMap:
@@ -52,12 +47,7 @@ class VoxelMap:
 
     # ------------------------------------------------------------------ the table
     def _call(self, name, *args):
-        L = _lib.lib()
-        if self.device.type == "cuda":
-            with torch.cuda.device(self.device):
-                _lib.check(getattr(L, name)(*args, _stream()))
-        else:
-            _lib.check(getattr(L, name + "_host")(*args))
+        _lib.call(name, self.device, *args)
 
     def _new_table(self, capacity):
         words = int(_lib.lib().atdn_voxel_table_bytes(capacity)) // 8

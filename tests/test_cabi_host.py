@@ -83,6 +83,22 @@ def test_ctypes_argument_lists_match_the_header_prototypes():
         assert got == want or {got, want} <= {"long", "int64_t"}, "%s: returns `%s` in the header, %s in the table" % (name, ret, res)
 
 
+def test_host_twins_take_the_device_arguments_without_workspace_and_stream():
+    """The convention `_lib.call` rests on: every `atdn_X_host` has a device form `atdn_X` of the same result type whose
+    arguments are the host form's followed by exactly one or two `void*` (the stream, or a workspace and the stream)."""
+    twins = [name for name in _lib.SIGNATURES if name.endswith("_host")]
+    assert twins
+    for name in twins:
+        device = name[:-len("_host")]
+        assert device in _lib.SIGNATURES, name
+        host_res, host_args = _lib.SIGNATURES[name]
+        dev_res, dev_args = _lib.SIGNATURES[device]
+        assert dev_res == host_res, name
+        assert dev_args[:len(host_args)] == host_args, name
+        extra = dev_args[len(host_args):]
+        assert len(extra) in (1, 2) and all(t is C.c_void_p for t in extra), name
+
+
 def test_pose_algebra_matches_reference(golden_dir):
     g = np.load(os.path.join(golden_dir, "pose.npz"))
     for i in range(16):

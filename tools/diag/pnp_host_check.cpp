@@ -26,7 +26,7 @@ static int run(int B, int H, int W) {
   float* out = new float[B * 12];
   double* cost = new double[B];
   int* counts = new int[B * 4];
-  double* sums = new double[B * atdn::PNP_TERMS];
+  double* sums = new double[B * atdn::PLANE_TERMS];
   int* counts3 = new int[B * 3];
   const double fx = 0.58 * W, fy = 0.58 * W, cx = (W - 1) / 2.0 + 0.3, cy = (H - 1) / 2.0 - 0.2;
   const atdn::PnpParams cam = atdn::pnp_params(fx, fy, cx, cy, 4.0, 2.0, 0.1, H, W);
@@ -71,7 +71,7 @@ static int run(int B, int H, int W) {
   atdn::pnp_solve_host(depth, flow, mask, start, B, H, W, cam, 0, out, cost, counts);
   atdn::pnp_terms_host(depth, flow, mask, start, B, H, W, cam, sums, counts3);
   for (int b = 0; b < B; ++b) {
-    if (memcmp(out + 12 * b, start + 12 * b, 48) != 0 || memcmp(&cost[b], &sums[atdn::PNP_TERMS * b + 27], 8) != 0) ++bad;
+    if (memcmp(out + 12 * b, start + 12 * b, 48) != 0 || memcmp(&cost[b], &sums[atdn::PLANE_TERMS * b + 27], 8) != 0) ++bad;
     if (memcmp(counts + 4 * b, counts3 + 3 * b, 12) != 0 || counts[4 * b + 3] != 0) ++bad;
   }
   delete[] depth; delete[] flow; delete[] mask; delete[] truth; delete[] start; delete[] out; delete[] cost; delete[] counts;
