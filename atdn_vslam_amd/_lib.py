@@ -146,7 +146,12 @@ SIGNATURES = {
     "atdn_voxel_rehash_host": (C.c_int, [_vp, C.c_long, _vp, C.c_long]),
     "atdn_voxel_extract": (C.c_int, [_vp, C.c_long, C.c_int] + [C.c_double] * 4 + [C.c_long] + [_vp] * 6),
     "atdn_voxel_extract_host": (C.c_int, [_vp, C.c_long, C.c_int] + [C.c_double] * 4 + [C.c_long] + [_vp] * 5),
-    "atdn_map_search": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "atdn_view_workspace_bytes": (C.c_long, [C.c_int, C.c_int, C.c_int]),
+    "atdn_view_render": (C.c_int, [_vp] * 3 + [C.c_int, _vp] + [C.c_int] * 3 + [C.c_double] * 6 + [C.c_int] + [C.c_double] * 2 +
+                         [C.c_int] + [_vp] * 6),
+    "atdn_view_render_host": (C.c_int, [_vp] * 3 + [C.c_int, _vp] + [C.c_int] * 3 + [C.c_double] * 6 + [C.c_int] + [C.c_double] * 2 +
+                              [C.c_int] + [_vp] * 4),
+    "atdn_map_search":(C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "atdn_map_gather_images_u8": (C.c_int, [_vp, C.c_int, C.c_long, _vp, C.c_int, _vp, _vp]),
     "atdn_corr_lookup": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
     "atdn_corr_pyramid": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),

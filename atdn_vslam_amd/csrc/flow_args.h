@@ -1,5 +1,5 @@
 // The argument rules that the geometry entry points (flow_consistency.hip, two_view.hip, flow_track.hip, pnp.hip, epipolar.hip,
-// depth_fusion.hip, multiview_depth.hip, bundle.hip, ground.hip, voxel_map.hip, pose_graph.hip) share. Each module's own rules are
+// depth_fusion.hip, multiview_depth.hip, bundle.hip, ground.hip, voxel_map.hip, map_view.hip, pose_graph.hip) share. Each module's own rules are
 // file-static in its .hip, beside the device entry point and the host twin that both go through them.
 #pragma once
 #include <cmath>

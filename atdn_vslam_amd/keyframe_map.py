@@ -250,6 +250,50 @@ class KeyframeMap:
                 vm.integrate(depth, poses, calib, images=self.image_bank[:n], indices=np.arange(a, min(a + batch, n)), stride=stride)
         return vm
 
+    @torch.no_grad()
+    def render_depths(self, cloud, calib, indices=None, fill=False, batch=8, **options):
+        """The map's cloud seen from the keyframes' own poses: the depth every keyframe would have measured had it seen what all
+        of them saw. `cloud` is a `voxel_map.VoxelMap` on the map's device (`options`: the keyword arguments of its `render` —
+        min_count, splat, max_splat, near, far) or a tuple `(points, colors, counts)` of device tensors, e.g. a cloud read with
+        `VoxelMap.load_ply` (`options`: those of `transforms.render_points`, `size` among them). `indices` (a host sequence; all
+        keyframes by default) names the keyframes, `batch` of them are rendered per call, `calib` is the calibration of the
+        map's grid. Returns the rendered depths, float32 [len(indices),H,W] on the device, 0 = nothing rendered. `fill=True`
+        also writes the rendered depth into the depth bank at exactly the pixels that hold 0 (a keyframe's own measurements
+        stay); with False nothing in the map changes."""
+        from .transforms import render_points
+        n = self.n
+        ix = list(range(n)) if indices is None else [int(i) for i in indices]
+        if any(not 0 <= i < n for i in ix):
+            raise IndexError("keyframe index outside [0, %d)" % n)
+        if isinstance(cloud, (tuple, list)):
+            points, colors, counts = cloud[:3]
+            if "size" not in options:
+                raise ValueError("render_depths of a bare cloud needs size=, the edge of its voxels")
+            size = options.pop("size")
+
+            def render(poses):
+                return render_points(points, colors, counts, poses, calib, self.hw, size, **options)[0]
+        else:
+            if cloud.device != self.device:
+                raise ValueError("the voxel map is on %s but the keyframe map on %s" % (cloud.device, self.device))
+
+            def render(poses):
+                return cloud.render(poses, calib, self.hw, **options)[0]
+        poses = self._poses[:n, :3, :].reshape(n, 12).to(self.device)
+        batch = max(1, int(batch))
+        out = torch.zeros((len(ix),) + self.hw, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            for a in range(0, len(ix), batch):
+                sel = torch.tensor(ix[a:a + batch], dtype=torch.int64).to(self.device, non_blocking=True)
+                out[a:a + len(sel)] = render(poses.index_select(0, sel))
+            if fill and ix:
+                if self.depth_bank is None:
+                    self.depth_bank = torch.zeros((self.capacity,) + self.hw, dtype=torch.float32, device=self.device)
+                sel = torch.tensor(ix, dtype=torch.int64).to(self.device, non_blocking=True)
+                own = self.depth_bank.index_select(0, sel)
+                self.depth_bank.index_copy_(0, sel, torch.where(own == 0, out, own))
+        return out
+
     @classmethod
     def from_directory(cls, keyframes_path, device, mapping_net=None):
         """The map of a keyframe directory as the reference and slam.NeuralSLAM write it: `rgb/*.pth` (sorted; uint8

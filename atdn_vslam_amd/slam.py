@@ -126,6 +126,12 @@ class NeuralSLAM:
     accumulated into one voxel-hashed point cloud (`build_voxel_map`, `voxel_options` its keyword arguments): `map.ply` and the
     `voxel_map` attribute. A cold start with the option removes a `map.ply` of an earlier session. With False (the default)
     nothing anywhere changes.
+    `map_depth=True` or `"fill"` (needs `voxel_map=True`): after `build_voxel_map()` the cloud is rendered back into every
+    keyframe's own pose (`write_map_depth`; `voxel_map.VoxelMap.render` with its defaults): `map_depth/%06d.pth`, float32
+    [1,376,1232], 0 = nothing rendered — the depth a keyframe would have had, had it seen what all of them saw. With `"fill"` the
+    rendered depth also goes into the depth bank at exactly the pixels that hold 0, so the geometric leg of relocalisation reads
+    it. A cold start with the option removes a `map_depth/` of an earlier session. With False (the default) no file, no code path
+    and no bit changes anywhere.
     """
 
     FLOW_CHECKPOINT = "atdn_vslam/checkpoints/gma-kitti.pth"  # utils/gma_parameters.py
@@ -134,11 +140,16 @@ class NeuralSLAM:
                  precision=None, map_options=None, resident_map=False, warm_start=False, calib=None, keyframe_depth="pair",
                  loop_closure=False, loop_options=None, refine_pose=False, fuse_depth=False, fuse_options=None,
                  multiview_options=None, bundle_options=None, bundle_pose=False, ground=False, ground_options=None,
-                 camera_height=None, voxel_map=False, voxel_options=None):
+                 camera_height=None, voxel_map=False, voxel_options=None, map_depth=False):
         from .depth import intrinsics
         if voxel_map and (calib is None or not resident_map):
             raise ValueError("voxel_map=True needs the calibration and the keyframe map in device memory: pass calib= and "
                              "resident_map=True")
+        if map_depth not in (False, True, "fill"):
+            raise ValueError('map_depth is False, True or "fill", got %r' % (map_depth,))
+        if map_depth and not voxel_map:
+            raise ValueError("map_depth needs the voxel map: pass voxel_map=True")
+        self._map_depth = map_depth
         self._voxel_map = bool(voxel_map)
         self._voxel_options = dict(voxel_options or {})
         self.voxel_map = None        # voxel_map.VoxelMap of the last build_voxel_map()
@@ -234,6 +245,10 @@ class NeuralSLAM:
                         os.remove(f)
             if self._voxel_map and os.path.exists(os.path.join(self._base, "map.ply")):
                 os.remove(os.path.join(self._base, "map.ply"))
+            if self._map_depth:
+                for f in glob.glob(os.path.join(self._base, "map_depth", "*")):
+                    os.remove(f)
+                os.makedirs(os.path.join(self._base, "map_depth"), exist_ok=True)
             if self._multiview:
                 for sub in ("depth_info", "depth_mv_views") + (("bundle",) if self._bundle else ()):
                     os.makedirs(os.path.join(self._base, sub), exist_ok=True)
@@ -293,6 +308,8 @@ class NeuralSLAM:
                 self.fuse_depths(**self._fuse_options)               # after the loop closure: it sees the optimised poses
             if self._voxel_map:
                 self.build_voxel_map(**self._voxel_options)          # after both: the optimised poses, the fused depths
+                if self._map_depth:
+                    self.write_map_depth(fill=self._map_depth == "fill")
         elif len(self._keyframes) == 0:
             print("There is no explored enviromnent yet!")
         elif self._mode == "mapping" and mapping_weights is not None:
@@ -370,6 +387,31 @@ class NeuralSLAM:
         self.voxel_map = self._map.voxel_map(self._calib, fused=fused, **options)
         self.voxel_map.save_ply(os.path.join(self._base, "map.ply"), min_count=min_count)
         return self.voxel_map
+
+    @torch.no_grad()
+    def render_map(self, poses, **options):
+        """`self.voxel_map` seen from arbitrary `poses` ([B,12], [B,3,4] or [B,4,4]; world <- camera; any device) under this
+        object's calibration at the map's frame size: `VoxelMap.render` (`options`: min_count, splat, max_splat, near, far).
+        Returns `(depth [B,H,W] float32, colors [B,3,H,W] uint8 or None, support [B,H,W] uint8, counts [B,3] int64)` on the
+        device."""
+        if self.voxel_map is None:
+            raise RuntimeError("render_map needs the voxel map: construct NeuralSLAM(..., voxel_map=True) and end the odometry, "
+                               "or call build_voxel_map()")
+        return self.voxel_map.render(torch.as_tensor(poses).to(self.voxel_map.device), self._calib, SLAM_SIZE, **options)
+
+    @torch.no_grad()
+    def write_map_depth(self, fill=False, **options):
+        """Render `self.voxel_map` into every keyframe's own pose (`KeyframeMap.render_depths`; `options`: its keyword
+        arguments) and write `map_depth/<the frame's name>`, float32 [1,H,W], 0 = nothing rendered. `fill=True` also fills the
+        depth bank's zero pixels. Returns the rendered depths [K,H,W] on the device; None (and no file) without a voxel map."""
+        if self.voxel_map is None:
+            return None
+        depths = self._map.render_depths(self.voxel_map, self._calib, fill=fill, **options)
+        os.makedirs(os.path.join(self._base, "map_depth"), exist_ok=True)
+        host = depths.cpu()
+        for i, kf in enumerate(self._keyframes):
+            torch.save(host[i:i + 1].clone(), os.path.join(self._base, "map_depth", os.path.basename(kf.rgb_file_name)))
+        return depths
 
     @torch.no_grad()
     def __call__(self, im):

@@ -864,6 +864,49 @@ def voxel_map(depth, poses, calib, images=None, mask=None, indices=None, stride=
     return m.extract(min_count)
 
 
+def render_points(points, colors, counts, poses, calib, hw, size, splat=1.0, max_splat=64, near=0.5, far=40.0, min_count=1):
+    """A point cloud seen from B cameras, with a z-buffer: the inverse of `voxel_map`. `points` [M,3] float32, `colors` [M,3]
+    uint8 or None and `counts` [M] int32 are what `VoxelMap.extract` returns or `VoxelMap.load_ply` reads (M = 0 is fine);
+    `poses` ([B,12], [B,3,4] or [B,4,4]; rows of [R|t], world <- camera) the cameras, `calib` (fx, fy, cx, cy) or a calibration
+    matrix without skew, `hw` = (H, W) the image size. A point with at least `min_count` support and near <= z <= far is a flat
+    square splat of `splat` voxel edges of `size` (at least one pixel, at most `max_splat` pixels a side); a pixel shows the
+    nearest splat that covers it, among equal depths the better supported one. Returns `(depth [B,H,W] float32, colors
+    [B,3,H,W] uint8 or None, support [B,H,W] uint8 = min(count, 255) of the winner, counts [B,3] int64 = candidates, visible
+    points, covered pixels)` on the points' device, zeros at empty pixels. Device tensors go through libatdn_hip's kernels on the
+    current stream (no synchronisation), CPU tensors through the library's host form. The rule is float64 and an integer
+    minimum, stated in full in include/atdn_hip.h, atdn_view_render: the same bits on every call and on both paths."""
+    from .depth import intrinsics
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError("expected points [M,3], got %s" % (tuple(getattr(points, "shape", ())),))
+    dev = points.device
+    M = int(points.shape[0])
+    pts = points.detach().to(torch.float32).contiguous()
+    if not isinstance(counts, torch.Tensor) or tuple(counts.shape) != (M,) or counts.device != dev:
+        raise RuntimeError("expected counts [%d] on %s" % (M, dev))
+    cnt = counts.detach().to(torch.int32).contiguous()
+    col = None
+    if colors is not None:
+        if not isinstance(colors, torch.Tensor) or colors.dtype != torch.uint8 or tuple(colors.shape) != (M, 3) or colors.device != dev:
+            raise RuntimeError("expected colors [%d,3] uint8 on %s" % (M, dev))
+        col = colors.detach().contiguous()
+    p = torch.as_tensor(poses)
+    if p.device != dev and isinstance(poses, torch.Tensor):
+        raise RuntimeError("points on %s but poses on %s" % (dev, p.device))
+    B = 1 if tuple(p.shape) in ((4, 4), (3, 4), (12,)) else int(p.shape[0])
+    p = _pose_rows(p, B, dev)
+    H, W = int(hw[0]), int(hw[1])
+    work = _lib.workspace("atdn_view_workspace_bytes", dev, B, H, W,
+                          message="render_points: B, H, W must be >= 1, B <= 65535 and B * H * W < 2^31")
+    depth = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    out_colors = None if col is None else torch.empty((B, 3, H, W), dtype=torch.uint8, device=dev)
+    support = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    out_counts = torch.empty((B, 3), dtype=torch.int64, device=dev)
+    _lib.call("atdn_view_render", dev, _ptr(pts) if M else None, _ptr(col) if M else None, _ptr(cnt) if M else None, M, _ptr(p), B,
+              H, W, *intrinsics(calib), float(size), float(splat), int(max_splat), float(near), float(far), int(min_count),
+              _ptr(depth), _ptr(out_colors), _ptr(support), _ptr(out_counts), workspace=work)
+    return depth, out_colors, support, out_counts
+
+
 class InputPadder:
     """Replicate-pads frames to multiples of 8 ('sintel' mode splits the padding on both sides)."""
 

@@ -43,6 +43,7 @@ class VoxelMap:
         self.has_colors = None              # set by the first integrate: every call gives images, or none does
         self._points_bound = 0              # host-side upper bound of the points in the table
         self._counts = dict.fromkeys(COUNTERS, 0)
+        self._extraction = None             # extract(1) as render() last saw it; dropped by integrate and _grow
         self.table = self._new_table(capacity)
 
     # ------------------------------------------------------------------ the table
@@ -59,6 +60,7 @@ class VoxelMap:
 
     def _grow(self, capacity):
         """Rehash into a cleared table of `capacity` slots."""
+        self._extraction = None
         table = self._new_table(capacity)
         self._call("atdn_voxel_rehash", _ptr(self.table), self.capacity, _ptr(table), capacity)
         self.table, self.capacity = table, capacity
@@ -128,6 +130,7 @@ class VoxelMap:
         if capacity != self.capacity:
             self._grow(capacity)
         self.has_colors = images is not None
+        self._extraction = None
         self._points_bound += pixels
         pending = torch.empty((K, H, W), dtype=torch.uint8, device=self.device)
 
@@ -175,6 +178,20 @@ class VoxelMap:
             points, counts = points[order], counts[order]
             colors = None if colors is None else colors[order]
         return points, colors, counts, keys
+
+    def render(self, poses, calib, hw, min_count=1, splat=1.0, max_splat=64, near=None, far=None):
+        """The cloud seen from the cameras `poses` ([B,12], [B,3,4] or [B,4,4]; rows of [R|t], world <- camera) under `calib` at
+        `hw` = (H, W): `transforms.render_points` of the extraction, with this map's `voxel` as the splat's unit and, by default,
+        its `min_z` and `max_z` as `near` and `far`. Returns `(depth [B,H,W] float32, colors [B,3,H,W] uint8 or None, support
+        [B,H,W] uint8, counts [B,3] int64)` on the map's device. The extraction (every voxel; `min_count` is applied by the
+        render) is kept until the next `integrate`, so repeated renders do not extract again."""
+        from .transforms import render_points
+        if self._extraction is None:
+            self._extraction = self.extract(1)[:3]
+        points, colors, counts = self._extraction
+        return render_points(points, colors, counts, poses, calib, hw, self.voxel, splat=splat, max_splat=max_splat,
+                             near=self.min_z if near is None else near, far=self.max_z if far is None else far,
+                             min_count=min_count)
 
     def save_ply(self, path, min_count=1):
         """Write the cloud as a binary little-endian PLY: x y z float, red green blue uchar (a coloured map only), count int.

@@ -1117,6 +1117,58 @@ int atdn_voxel_extract_host(void* table, long capacity, int min_count, double vo
                             long max_out, float* points, uint8_t* colors, int* counts, int64_t* keys, int64_t* found);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Map view  —  a point cloud (what atdn_voxel_extract writes, or a cloud read back from map.ply) rendered into B cameras with a
+ * z-buffer: the inverse of atdn_voxel_integrate and the library's second scatter primitive. Every point is a flat square splat
+ * that carries one 64-bit word; a pixel keeps the MINIMUM word of the splats that cover it. min commutes: every bit of the
+ * result is a function of the SET of points alone, independent of thread order and launch geometry. The reference has nothing
+ * like it.
+ *
+ * The rule. Float64 with every operation rounded on its own (no fused multiply-add); only + - * /, comparisons and the
+ * conversions named below.
+ *   points [M,3] fp32; colors [M,3] uint8 or NULL (red, green, blue); counts [M] int32; poses [B,12] fp32, rows of [R|t],
+ *   world <- camera; (fx, fy, cx, cy) float64; H, W; size > 0 the edge of a voxel; splat > 0 the footprint in voxel edges;
+ *   max_splat >= 1 the cap of a footprint's side in pixels; 0 < near <= far, far finite and representable in fp32; min_count >= 1.
+ * Per camera b and point i with counts[i] >= min_count (a CANDIDATE; n = counts[i]):
+ *   d_a = (double)p_a - (double)t_a;  c_a = dot3(r_0a, d_0, r_1a, d_1, r_2a, d_2), dot3 = (x0*y0 + x1*y1) + x2*y2 (column a
+ *   of R: c = R^T d);  z = c_2
+ *   in range iff near <= z && z <= far (a NaN fails)
+ *   u = (c_0/z)*fx + cx,  v = (c_1/z)*fy + cy
+ *   hx = (((0.5*splat)*size)*fx)/z, then 0.5 where hx < 0.5 and 0.5*max_splat where hx > 0.5*max_splat; hy with fy
+ *   the footprint is the half-open square [u-hx, u+hx) x [v-hy, v+hy): with a = u-hx and e = u+hx it covers the columns
+ *     x0 = 0 where a < 0, else ceil(a), which needs a <= W-1;   x1 = W-1 where e > W-1, else ceil(e)-1, which needs e > 0
+ *   ceil(a) = a truncated to an integer, plus 1 if the integer converted back is below a. Both needs are compared in double
+ *   before any conversion, so a NaN or an infinity that fails one converts nothing. Rows y0, y1 likewise from v, hy and H.
+ *   the point is VISIBLE iff it is in range, both needs hold on both axes, and x0 <= x1 && y0 <= y1
+ *   word = (bits((float)z) << 32) | ((255 - min(n,255)) << 24) | (red << 16) | (green << 8) | blue   (colour bytes 0 without
+ *   colours), the same on every pixel (y0..y1) x (x0..x1)
+ * Per pixel: the minimum word over the visible points that cover it; all ones = empty. Positive fp32 bit patterns order like the
+ * numbers, so the minimum is the nearest point; among equal fp32 depths the larger min(n,255), then the smaller packed colour.
+ * Outputs, 0 everywhere at an empty pixel:
+ *   depth [B,H,W] fp32 = the word's high half reinterpreted;  colors_out [B,3,H,W] uint8 or NULL;  support [B,H,W] uint8 =
+ *   min(n,255) of the winner;  counts_out [B,3] int64 = candidates, visible points, covered pixels of camera b.
+ * A NaN or an infinity in a pose or a point writes nothing: that (camera, point) is simply not visible.
+ * ------------------------------------------------------------------------------------------------- */
+
+/* Bytes of the device form's workspace, 8*B*H*W: one word per pixel. 0 for sizes the entry point refuses (a dimension < 1,
+ * B > 65535 or B*H*W >= 2^31). */
+long atdn_view_workspace_bytes(int B, int H, int W);
+
+/* Renders M >= 0 points into B cameras (M == 0: points, colors and counts may be NULL; empty images). All pointers DEVICE;
+ * points, counts, poses and depth 4-byte aligned, counts_out and workspace 8-byte aligned; no output may overlap an input or
+ * another output (the workspace counts as an output). Three launches on `stream` (asynchronous, capturable, no host
+ * synchronisation, no memset): a clear of the workspace and counts_out, the splat — plain 64-bit read, then an unsigned 64-bit
+ * atomic min whose result nobody reads, only where the new word is smaller — and the resolve. No thread waits for another, there
+ * is no lock and no retry, every loop bound is an argument or a constant. The _host twin takes host memory, runs on the calling
+ * thread and gives the same bits. */
+int atdn_view_render(const float* points, const uint8_t* colors, const int* counts, int M, const float* poses, int B, int H, int W,
+                     double fx, double fy, double cx, double cy, double size, double splat, int max_splat, double near, double far,
+                     int min_count, float* depth, uint8_t* colors_out, uint8_t* support, int64_t* counts_out, void* workspace,
+                     void* stream);
+int atdn_view_render_host(const float* points, const uint8_t* colors, const int* counts, int M, const float* poses, int B, int H,
+                          int W, double fx, double fy, double cx, double cy, double size, double splat, int max_splat, double near,
+                          double far, int min_count, float* depth, uint8_t* colors_out, uint8_t* support, int64_t* counts_out);
+
+/* ---------------------------------------------------------------------------------------------------
  * Keyframe map  —  replaces the keyframe list of NeuralSLAM's relocalisation (keyframe_map.py)
  *   embeddings: Frame.embedding, one MappingVAE call per keyframe (slam_framework/neural_slam.py:88-103,158-164)
  *   search:     the per-keyframe torch.norm loop, torch.stack and argmin (neural_slam.py:374-383)
