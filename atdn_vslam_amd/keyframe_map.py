@@ -21,13 +21,13 @@ embedding, and answers a relocalisation query with a loop of `torch.norm(kf.embe
 Poses live on the host ([K,4,4] float32), as in the reference.
 """
 import ctypes as C
-import glob
-import os
 
 import numpy as np
 import torch
 
 from . import _lib, transforms
+from . import keyframe_dir as kd
+from .keyframe_dir import KeyframeDir
 from ._lib import ptr as _ptr, stream as _stream
 
 MAX_TOP_K = 16
@@ -300,13 +300,13 @@ class KeyframeMap:
         [3,H,W]), `poses.pth` ([K,12]) and, where a keyframe has one, `depth/<the frame's name>` (float32 [1,H,W]). Every file is read once; the directory is validated (poses.pth present, as many
         poses as frames, all frames of the first one's size) before anything touches the device.
         With `mapping_net` the keyframes are embedded too."""
-        poses_file = os.path.join(keyframes_path, "poses.pth")
-        if not os.path.exists(poses_file):
-            raise FileNotFoundError("%s is missing: not a keyframe directory (end_odometry() writes it)" % poses_file)
-        files = sorted(glob.glob(os.path.join(keyframes_path, "rgb", "*.pth")))
+        directory = KeyframeDir(keyframes_path)
+        if not directory.exists(kd.POSES):
+            raise FileNotFoundError("%s is missing: not a keyframe directory (end_odometry() writes it)" % directory.path(kd.POSES))
+        files = directory.frames()
         if not files:
             raise ValueError("%s holds no keyframe (rgb/*.pth)" % keyframes_path)
-        poses = _homogeneous(torch.load(poses_file, map_location="cpu"))
+        poses = _homogeneous(directory.load(kd.POSES, map_location="cpu"))
         if len(poses) != len(files):
             raise ValueError("%s: %d poses in poses.pth but %d frames under rgb/" % (keyframes_path, len(poses), len(files)))
         frames, hw = [], None
@@ -325,9 +325,8 @@ class KeyframeMap:
         for im, pose in zip(frames, poses):
             m.append(im, pose)
         for k, f in enumerate(files):
-            depth_file = os.path.join(keyframes_path, "depth", os.path.basename(f))
-            if os.path.exists(depth_file):
-                m.set_depth(k, torch.load(depth_file, map_location="cpu"))
+            if directory.exists(kd.DEPTH, f):
+                m.set_depth(k, directory.load(kd.DEPTH, f, map_location="cpu"))
         if mapping_net is not None:
             m.embed(mapping_net)
         return m

@@ -27,6 +27,9 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from . import keyframe_dir as kd
+from .keyframe_dir import KeyframeDir
+
 RGB_MEAN = (0.485, 0.456, 0.406)
 RGB_STD = (0.229, 0.224, 0.225)
 
@@ -192,14 +195,14 @@ class KeyframeImages(torch.utils.data.Dataset):
     """`<keyframes_path>/rgb/%06d.pth` as float images (ColorDataset(pth=True), localization/datasets.py:8-62)."""
 
     def __init__(self, keyframes_path):
-        self.dir = os.path.join(keyframes_path, "rgb")
-        self.n = len([f for f in os.listdir(self.dir) if f.endswith(".pth")])
+        self.dir = KeyframeDir(keyframes_path)
+        self.n = len([f for f in os.listdir(self.dir.path(kd.RGB)) if f.endswith(".pth")])
 
     def __len__(self):
         return self.n
 
     def __getitem__(self, i):
-        return torch.load(os.path.join(self.dir, "%06d.pth" % i)).float()
+        return self.dir.load(kd.RGB, i).float()
 
 
 def map_loss(im_pred, im):
@@ -231,7 +234,7 @@ def create_map(keyframes_path, device="cuda", num_epochs=50, batch_size=16, augm
     opt = torch.optim.AdamW(net.parameters(), lr=1e-3, weight_decay=1e-3)
     sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, num_epochs * len(loader), eta_min=1e-5)
     losses = []
-    out = os.path.join(keyframes_path, "MappingVAE_weights.pth")
+    out = KeyframeDir(keyframes_path).path(kd.WEIGHTS)
     for epoch in range(num_epochs):
         running = 0.0
         for im in loader:

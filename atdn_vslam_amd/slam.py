@@ -15,13 +15,15 @@ the keyframes (`mapping.create_map`, the reference's `__create_map`: 50 epochs o
 mapping run) — then every keyframe is embedded on the HIP path and the state machine enters relocalization.
 """
 import copy
-import glob
 import math
 import os
 
 import torch
 
+from . import keyframe_dir as kd
 from . import transforms
+from .keyframe_depth import KeyframeDepthRecorder
+from .keyframe_dir import KeyframeDir
 from .modules import ATDNVO, MappingVAE, RAFTGMA
 from .pipeline import SLAM_SIZE, resize_frames
 
@@ -62,6 +64,33 @@ def _homogeneous(poses12):
     p = torch.as_tensor(poses12, dtype=torch.float32).view(-1, 3, 4)
     last = torch.tensor([0.0, 0.0, 0.0, 1.0]).view(1, 1, 4).repeat(len(p), 1, 1)
     return torch.cat([p, last], dim=1)
+
+
+def _check_options(calib, resident_map, keyframe_depth, loop_closure, refine_pose, fuse_depth, ground, camera_height, voxel_map,
+                   map_depth):
+    """The rules between NeuralSLAM's options; the first one that is broken raises ValueError."""
+    if voxel_map and (calib is None or not resident_map):
+        raise ValueError("voxel_map=True needs the calibration and the keyframe map in device memory: pass calib= and "
+                         "resident_map=True")
+    if map_depth not in (False, True, "fill"):
+        raise ValueError('map_depth is False, True or "fill", got %r' % (map_depth,))
+    if map_depth and not voxel_map:
+        raise ValueError("map_depth needs the voxel map: pass voxel_map=True")
+    if ground and calib is None:
+        raise ValueError("ground=True needs the calibration: pass calib=")
+    if ground and camera_height is not None and not (math.isfinite(float(camera_height)) and float(camera_height) > 0.0):
+        raise ValueError("camera_height must be finite and > 0, got %r" % (camera_height,))
+    if fuse_depth and (calib is None or not resident_map):
+        raise ValueError("fuse_depth=True needs the calibration and the keyframe map in device memory: pass calib= and "
+                         "resident_map=True")
+    if refine_pose and calib is None:
+        raise ValueError("refine_pose=True needs the calibration: pass calib=")
+    if loop_closure and not resident_map:
+        raise ValueError("loop_closure=True needs the keyframe map in device memory: pass resident_map=True")
+    if keyframe_depth not in ("pair", "track", "multiview", "bundle"):
+        raise ValueError('keyframe_depth is "pair", "track" or "multiview", or "bundle", got %r' % (keyframe_depth,))
+    if keyframe_depth != "pair" and calib is None:
+        raise ValueError('keyframe_depth="%s" needs the calibration: pass calib=' % keyframe_depth)
 
 
 class NeuralSLAM:
@@ -142,65 +171,44 @@ class NeuralSLAM:
                  multiview_options=None, bundle_options=None, bundle_pose=False, ground=False, ground_options=None,
                  camera_height=None, voxel_map=False, voxel_options=None, map_depth=False):
         from .depth import intrinsics
-        if voxel_map and (calib is None or not resident_map):
-            raise ValueError("voxel_map=True needs the calibration and the keyframe map in device memory: pass calib= and "
-                             "resident_map=True")
-        if map_depth not in (False, True, "fill"):
-            raise ValueError('map_depth is False, True or "fill", got %r' % (map_depth,))
-        if map_depth and not voxel_map:
-            raise ValueError("map_depth needs the voxel map: pass voxel_map=True")
-        self._map_depth = map_depth
-        self._voxel_map = bool(voxel_map)
-        self._voxel_options = dict(voxel_options or {})
-        self.voxel_map = None        # voxel_map.VoxelMap of the last build_voxel_map()
-        self._fused_device = None    # the fused depths of the last fuse_depths() (device), kept for the voxel map only
+        _check_options(calib, resident_map, keyframe_depth, loop_closure, refine_pose, fuse_depth, ground, camera_height, voxel_map,
+                       map_depth)
+        self._args = args
+        self._base = args.keyframes_path
+        self._dir = KeyframeDir(self._base)
+        self._device = torch.device(args.device if getattr(args, "device", None) not in (None, "cpu") else "cuda:0")
+        self._calib = None if calib is None else intrinsics(calib)
+        self._precision = precision
+        self._warm_start = bool(warm_start)   # odometry mode only; relocalisation pairs are not consecutive frames
+        self._refine_pose = bool(refine_pose)
+        self.last_refine_counts = None
+        # keyframe depth: the recorder decides which pairs give which keyframe its depth, _record_depth writes what it returns
+        self._depth = KeyframeDepthRecorder(keyframe_depth, SLAM_SIZE, self._calib, self._device, multiview_options, bundle_options)
+        self._bundle_pose = bool(bundle_pose) and keyframe_depth == "bundle"
+        self.multiview_counts = None   # [1,3] int32 (device) of the last multi-view keyframe depth: candidates, solved, valid
+        self.bundle_cost = self.bundle_counts = None   # [1,2] float64, [1,4] int32 (device) of the last keyframe's adjustment
+        self._ground = bool(ground)
         if ground:
-            if calib is None:
-                raise ValueError("ground=True needs the calibration: pass calib=")
-            if camera_height is not None and not (math.isfinite(float(camera_height)) and float(camera_height) > 0.0):
-                raise ValueError("camera_height must be finite and > 0, got %r" % (camera_height,))
             self._ground_options = dict(ground_options or {})
             self._ground_accept = {k: self._ground_options.pop(k) for k in ("min_inlier_share", "max_tilt_deg")
                                    if k in self._ground_options}
             self._camera_height = None if camera_height is None else float(camera_height)
             self._ground_scales = {}     # keyframe index -> scale of its interval
-        self._ground = bool(ground)
-        if fuse_depth and (calib is None or not resident_map):
-            raise ValueError("fuse_depth=True needs the calibration and the keyframe map in device memory: pass calib= and "
-                             "resident_map=True")
-        self._fuse_depth = bool(fuse_depth)
-        self._fuse_options = dict(fuse_options or {})
-        self.fusion_counts = None    # [K,3] int32 (host) of the last fuse_depths(): pixels with a depth, seen, kept
-        if refine_pose and calib is None:
-            raise ValueError("refine_pose=True needs the calibration: pass calib=")
-        self._refine_pose = bool(refine_pose)
-        self.last_refine_counts = None
-        if loop_closure and not resident_map:
-            raise ValueError("loop_closure=True needs the keyframe map in device memory: pass resident_map=True")
+        # (with "pair" the depth carries the scale of the keyframe's first pair only, not of the interval: no scaled poses)
+        self._scale_poses = bool(ground) and camera_height is not None and keyframe_depth != "pair"
+        # what end_odometry() does after the map is embedded
+        self._map_options = dict(map_options or {})   # keyword arguments of mapping.create_map (e.g. num_epochs)
         self._loop_closure = bool(loop_closure)
         self._loop_options = dict(loop_options or {})
         self.loop_report = None      # the report of the last close_loops()
-        if keyframe_depth not in ("pair", "track", "multiview", "bundle"):
-            raise ValueError('keyframe_depth is "pair", "track" or "multiview", or "bundle", got %r' % (keyframe_depth,))
-        if keyframe_depth != "pair" and calib is None:
-            raise ValueError('keyframe_depth="%s" needs the calibration: pass calib=' % keyframe_depth)
-        self._args = args
-        self._calib = None if calib is None else intrinsics(calib)
-        self._track_depth = keyframe_depth in ("track", "multiview", "bundle")
-        self._multiview = keyframe_depth in ("multiview", "bundle")
-        self._bundle = keyframe_depth == "bundle"
-        self._bundle_options = dict(bundle_options or {})
-        self._bundle_pose = bool(bundle_pose) and self._bundle
-        self.bundle_cost = self.bundle_counts = None   # [1,2] float64, [1,4] int32 (device) of the last keyframe's adjustment
-        self._multiview_options = dict(multiview_options or {})
-        self.multiview_counts = None   # [1,3] int32 (device) of the last multi-view keyframe depth: candidates, solved, valid
-        self._track = None           # depth.FlowTrack of the latest keyframe (keyframe_depth="track"), created with the first frame
-        self._track_index = None     # index of the keyframe the track is anchored at
-        self._depth_pending = None   # index of the keyframe that is the first frame of the next pair
-        self._warm_start = bool(warm_start)   # odometry mode only; relocalisation pairs are not consecutive frames
-        self._map_options = dict(map_options or {})   # keyword arguments of mapping.create_map (e.g. num_epochs)
-        self._base = args.keyframes_path
-        self._device = torch.device(args.device if getattr(args, "device", None) not in (None, "cpu") else "cuda:0")
+        self._fuse_depth = bool(fuse_depth)
+        self._fuse_options = dict(fuse_options or {})
+        self.fusion_counts = None    # [K,3] int32 (host) of the last fuse_depths(): pixels with a depth, seen, kept
+        self._fused_device = None    # the fused depths of the last fuse_depths() (device), kept for the voxel map only
+        self._voxel_map = bool(voxel_map)
+        self._voxel_options = dict(voxel_options or {})
+        self.voxel_map = None        # voxel_map.VoxelMap of the last build_voxel_map()
+        self._map_depth = map_depth
         # frame-by-frame caller that returns a host pose per call (one device synchronisation each): the split-f16 range guard
         # is read after EVERY forward, so no pose computed from clamped activations is ever returned
         self._flow_net = RAFTGMA(max_batch=1, precision=precision, saturation_check_every=1, low_latency=True)
@@ -215,7 +223,6 @@ class NeuralSLAM:
         self._keyframes = []
         self._policy = KeyframePolicy()
         self._current_pose = torch.eye(4, dtype=torch.float32)
-        self._precision = precision
         self._resident = bool(resident_map)
         self._map = None            # keyframe_map.KeyframeMap when resident_map=True
         self._batch_flow_net = None  # relocalize_batch's flow handle (batch > 1), created on first use
@@ -225,44 +232,13 @@ class NeuralSLAM:
             self._mode = "odometry"
             self.end_odometry(mapping_weights)
         elif start_mode == "relocalization":
-            w = mapping_weights if mapping_weights is not None else os.path.join(self._base, "MappingVAE_weights.pth")
-            self._set_mapping_net(w)
+            self._set_mapping_net(mapping_weights if mapping_weights is not None else self._dir.path(kd.WEIGHTS))
             self._load_keyframes(embed=True)
             self._mode = "relocalization"
         else:
-            os.makedirs(os.path.join(self._base, "rgb"), exist_ok=True)
-            for f in glob.glob(os.path.join(self._base, "rgb", "*")):
-                os.remove(f)
-            # keyframe depths of an earlier session go like its frames; the directory itself appears only with a calibration
-            if self._calib is not None:
-                os.makedirs(os.path.join(self._base, "depth"), exist_ok=True)
-            for f in glob.glob(os.path.join(self._base, "depth", "*")):
-                os.remove(f)
-            if self._fuse_depth:
-                for sub in ("depth_fused", "depth_views"):
-                    os.makedirs(os.path.join(self._base, sub), exist_ok=True)
-                    for f in glob.glob(os.path.join(self._base, sub, "*")):
-                        os.remove(f)
-            if self._voxel_map and os.path.exists(os.path.join(self._base, "map.ply")):
-                os.remove(os.path.join(self._base, "map.ply"))
-            if self._map_depth:
-                for f in glob.glob(os.path.join(self._base, "map_depth", "*")):
-                    os.remove(f)
-                os.makedirs(os.path.join(self._base, "map_depth"), exist_ok=True)
-            if self._multiview:
-                for sub in ("depth_info", "depth_mv_views") + (("bundle",) if self._bundle else ()):
-                    os.makedirs(os.path.join(self._base, sub), exist_ok=True)
-                    for f in glob.glob(os.path.join(self._base, sub, "*")):
-                        os.remove(f)
-            if self._ground:
-                os.makedirs(os.path.join(self._base, "ground"), exist_ok=True)
-                for f in glob.glob(os.path.join(self._base, "ground", "*")) + glob.glob(os.path.join(self._base, "poses_scaled.pth")):
-                    os.remove(f)
-            # a cold start owns the directory: poses and map weights of an earlier session go too
-            for stale in ("poses.pth", "poses_closed.pth", "MappingVAE_weights.pth"):
-                stale_path = os.path.join(self._base, stale)
-                if os.path.exists(stale_path):
-                    os.remove(stale_path)
+            options = dict(calib=calib is not None, fuse_depth=fuse_depth, multiview=keyframe_depth in ("multiview", "bundle"),
+                           bundle=keyframe_depth == "bundle", ground=ground, map_depth=map_depth, voxel_map=voxel_map)
+            self._dir.prepare_cold_start([name for name, on in options.items() if on])
             self._mode = "idle"
             if self._resident:
                 from .keyframe_map import KeyframeMap
@@ -280,16 +256,15 @@ class NeuralSLAM:
         neural_slam.py:160 does; skipped only when `mapping_weights` is given explicitly), embed every keyframe and
         enter relocalization."""
         if self._mode == "odometry" and len(self._keyframes) > 0:
-            self._flush_track()
+            self._record_depth(self._depth.close(False))
             poses = torch.stack([kf.pose.flatten()[:12] for kf in self._keyframes], dim=0)
-            torch.save(poses, os.path.join(self._base, "poses.pth"))
-            if self._ground and self._camera_height is not None and self._track_depth:
+            self._dir.save(poses, kd.POSES)
+            if self._scale_poses:
                 from .evaluation import rescale_intervals
                 scales = [self._ground_scales.get(i, 1.0) for i in range(len(self._keyframes) - 1)]
                 scaled = torch.from_numpy(rescale_intervals(poses.numpy(), scales)[:, :3, :].reshape(-1, 12)).float()
-                torch.save(scaled, os.path.join(self._base, "poses_scaled.pth"))
+                self._dir.save(scaled, kd.POSES_SCALED)
             self._mode = "mapping"
-            default = os.path.join(self._base, "MappingVAE_weights.pth")
             if mapping_weights is None:
                 # map creation (neural_slam.py:160,305-352): the reference ALWAYS trains the auto-encoder on the current
                 # keyframes here and overwrites MappingVAE_weights.pth — a file left in the directory by an earlier
@@ -298,7 +273,7 @@ class NeuralSLAM:
                 # argument skips the training.
                 from .mapping import create_map
                 create_map(self._base, device=self._device, **self._map_options)
-                mapping_weights = default
+                mapping_weights = self._dir.path(kd.WEIGHTS)
             self._set_mapping_net(mapping_weights)
             self._embed_keyframes()
             self._mode = "relocalization"
@@ -335,7 +310,7 @@ class NeuralSLAM:
         if report["counts"] is not None:
             for i, kf in enumerate(self._keyframes):
                 kf.pose = self._map.poses[i].clone()
-            torch.save(self._map.poses[:, :3, :].reshape(-1, 12).clone(), os.path.join(self._base, "poses_closed.pth"))
+            self._dir.save(self._map.poses[:, :3, :].reshape(-1, 12).clone(), kd.POSES_CLOSED)
         return report
 
     @torch.no_grad()
@@ -355,12 +330,10 @@ class NeuralSLAM:
         if self._voxel_map:
             self._fused_device = fused
         fused, views = fused.cpu(), views.cpu()
-        for sub in ("depth_fused", "depth_views"):
-            os.makedirs(os.path.join(self._base, sub), exist_ok=True)
+        self._dir.create(kd.DEPTH_FUSED, kd.DEPTH_VIEWS)
         for i, kf in enumerate(self._keyframes):
-            name = os.path.basename(kf.rgb_file_name)
-            torch.save(fused[i:i + 1].clone(), os.path.join(self._base, "depth_fused", name))
-            torch.save(views[i].clone(), os.path.join(self._base, "depth_views", name))
+            self._dir.save(fused[i:i + 1].clone(), kd.DEPTH_FUSED, kf.rgb_file_name)
+            self._dir.save(views[i].clone(), kd.DEPTH_VIEWS, kf.rgb_file_name)
         self.fusion_counts = counts.cpu()
         return self.fusion_counts
 
@@ -385,7 +358,7 @@ class NeuralSLAM:
         if fused is not None and int(fused.shape[0]) != len(self._map):
             fused = None
         self.voxel_map = self._map.voxel_map(self._calib, fused=fused, **options)
-        self.voxel_map.save_ply(os.path.join(self._base, "map.ply"), min_count=min_count)
+        self.voxel_map.save_ply(self._dir.path(kd.MAP_PLY), min_count=min_count)
         return self.voxel_map
 
     @torch.no_grad()
@@ -407,10 +380,10 @@ class NeuralSLAM:
         if self.voxel_map is None:
             return None
         depths = self._map.render_depths(self.voxel_map, self._calib, fill=fill, **options)
-        os.makedirs(os.path.join(self._base, "map_depth"), exist_ok=True)
+        self._dir.create(kd.MAP_DEPTH)
         host = depths.cpu()
         for i, kf in enumerate(self._keyframes):
-            torch.save(host[i:i + 1].clone(), os.path.join(self._base, "map_depth", os.path.basename(kf.rgb_file_name)))
+            self._dir.save(host[i:i + 1].clone(), kd.MAP_DEPTH, kf.rgb_file_name)
         return depths
 
     @torch.no_grad()
@@ -433,36 +406,16 @@ class NeuralSLAM:
                     self._current_pose = self._current_pose @ pred_mat
                 else:
                     self._current_pose = transforms.accumulate(self._current_pose, rot, tr)  # float32 pose @ pred_mat
-                if self._track_index is not None:
-                    self._track.extend(flow, pred_mat)
-                if self._depth_pending is not None:
-                    # the previous frame is a keyframe: this pair's flow starts at its pixels, so the depth is the keyframe's
-                    depth, _ = transforms.two_view_depth(flow, pred_mat[None].to(self._device), self._calib)
-                    torch.save(depth[0].to("cpu"), os.path.join(self._base, "depth", "%06d.pth" % self._depth_pending))
-                    if self._ground:
-                        self._fit_ground(self._depth_pending, depth)
-                    if self._map is not None:
-                        self._map.set_depth(self._depth_pending, depth[0])
-                    self._depth_pending = None
+                self._record_depth(self._depth.pair(flow, pred_mat))
                 if self._policy(pred_mat):
-                    name = os.path.join(self._base, "rgb", "%06d.pth" % len(self._keyframes))
-                    self._store_keyframe(im2, name)
-                    self._keyframes.append(Frame(name, self._current_pose))
-                    if self._track_depth:
-                        self._flush_track(new_keyframe=True)
-                        self._start_track(len(self._keyframes) - 1)
-                    elif self._calib is not None:
-                        self._depth_pending = len(self._keyframes) - 1
+                    self._add_keyframe(im2)
+                    self._record_depth(self._depth.close(True))    # (may move the new keyframe's pose: bundle_pose)
+                    self._depth.anchor(len(self._keyframes) - 1)
                 self._image_buffer = im2
             else:
                 self._image_buffer = self._padder.pad(im)[0]
-                name = os.path.join(self._base, "rgb", "000000.pth")
-                self._store_keyframe(im, name)
-                self._keyframes.append(Frame(name, self._current_pose))
-                if self._track_depth:
-                    self._start_track(0)
-                elif self._calib is not None:
-                    self._depth_pending = 0
+                self._add_keyframe(im)
+                self._depth.anchor(0)
             return self._current_pose
         if self._mode == "relocalization":
             q = im.to(self._device).float()
@@ -482,8 +435,7 @@ class NeuralSLAM:
         if self._mapping_net is not None:
             self._mapping_net = self._mapping_net.to(device)
         self._batch_flow_net = None   # (a resident keyframe map stays where it was built: its search names both devices)
-        if self._track is not None:
-            self._track.to(self._device)   # keyframe_depth="track": a running track goes along with the networks
+        self._depth.to(self._device)   # keyframe_depth="track": a running track goes along with the networks
 
     def get_keyframe(self, index):
         return self._keyframes[index]
@@ -504,8 +456,7 @@ class NeuralSLAM:
         if self._calib is None:
             raise RuntimeError("keyframe_points needs the calibration: construct NeuralSLAM(..., calib=...)")
         kf = self._keyframes[index]
-        number = os.path.splitext(os.path.basename(kf.rgb_file_name))[0]
-        depth = torch.load(os.path.join(self._base, "depth_fused" if fused else "depth", number + ".pth")).to(self._device)
+        depth = self._dir.load(kd.DEPTH_FUSED if fused else kd.DEPTH, kf.rgb_file_name).to(self._device)
         points = project_depth(depth, self._calib)
         points = points[:, depth[0] > 0]
         pose = torch.as_tensor(kf.pose, dtype=torch.float32).to(self._device)
@@ -513,58 +464,43 @@ class NeuralSLAM:
         return (pose[:3, 0:1] * points[0:1] + pose[:3, 1:2] * points[1:2]) + (pose[:3, 2:3] * points[2:3] + pose[:3, 3:4])
 
     # ------------------------------------------------------------------ internals
-    def _start_track(self, index):
-        """keyframe_depth="track": the flow track of keyframe `index` begins with the next pair."""
-        if self._track is None:
-            from .depth import FlowTrack
-            self._track = FlowTrack(SLAM_SIZE, self._calib, self._device, history=16 if self._multiview else 0)
-        self._track.start()
-        self._track_index = index
+    def _add_keyframe(self, im):
+        """The frame `im` becomes the next keyframe, at the running pose."""
+        name = self._dir.path(kd.RGB, len(self._keyframes))
+        self._store_keyframe(im, name)
+        self._keyframes.append(Frame(name, self._current_pose))
 
-    def _flush_track(self, new_keyframe=False):
-        """Write the depth of the keyframe the track is anchored at, if any pair has extended it. `new_keyframe`: the last
-        step of the track is the frame of the keyframe just registered (the last of the list)."""
-        if self._track_index is not None and self._track.steps > 0:
-            depth = self._track.depth
-            name = "%06d.pth" % self._track_index
-            if self._bundle:
-                poses, depth, info, views, self.multiview_counts, self.bundle_cost, self.bundle_counts = self._track.bundle(
-                    multiview_options=self._multiview_options, **self._bundle_options)
-                poses = poses[0].to("cpu")
-                torch.save(dict(poses=poses, cost=self.bundle_cost[0].to("cpu"), counts=self.bundle_counts[0].to("cpu")),
-                           os.path.join(self._base, "bundle", name))
-                if self._bundle_pose and new_keyframe and self._track.steps <= self._track.history:
-                    last = torch.eye(4, dtype=torch.float64)
-                    last[:3, :] = poses[-1].reshape(3, 4).double()
-                    anchor = torch.as_tensor(self._keyframes[self._track_index].pose).double()
-                    pose = (anchor @ last).float()
-                    self._keyframes[-1].pose = pose
-                    self._current_pose = pose
-                    if self._map is not None:
-                        self._map.poses[len(self._keyframes) - 1] = pose
-            elif self._multiview:
-                depth, info, views, self.multiview_counts = self._track.multiview(**self._multiview_options)
-            if self._multiview:
-                torch.save(info[0].to("cpu"), os.path.join(self._base, "depth_info", name))
-                torch.save(views[0].to("cpu"), os.path.join(self._base, "depth_mv_views", name))
-            torch.save(depth[0].to("cpu"), os.path.join(self._base, "depth", name))
-            if self._ground:
-                self._fit_ground(self._track_index, depth)
+    def _record_depth(self, result):
+        """Everything a keyframe_depth.KeyframeDepth leads to (None: nothing): the keyframe's files, the bundle_pose feedback,
+        the ground fit, the depth bank."""
+        if result is None:
+            return
+        index, save = result.index, self._dir.save
+        if result.poses is not None:
+            poses = result.poses[0].to("cpu")
+            self.bundle_cost, self.bundle_counts = result.cost, result.counts
+            save(dict(poses=poses, cost=result.cost[0].to("cpu"), counts=result.counts[0].to("cpu")), kd.BUNDLE, index)
+        if result.info is not None:
+            self.multiview_counts = result.multiview_counts
+            save(result.info[0].to("cpu"), kd.DEPTH_INFO, index)
+            save(result.views[0].to("cpu"), kd.DEPTH_MV_VIEWS, index)
+        save(result.depth[0].to("cpu"), kd.DEPTH, index)
+        if self._bundle_pose and result.new_keyframe and result.complete:
+            # the window's last step is the frame of the keyframe just registered (the last of the list)
+            last = torch.eye(4, dtype=torch.float64)
+            last[:3, :] = poses[-1].reshape(3, 4).double()
+            anchor = torch.as_tensor(self._keyframes[index].pose).double()
+            pose = (anchor @ last).float()
+            self._keyframes[-1].pose = pose
+            self._current_pose = pose
             if self._map is not None:
-                self._map.set_depth(self._track_index, depth[0])
-        self._track_index = None
-
-    def _fit_ground(self, index, depth):
-        """ground=True: the road's plane of keyframe `index` from its depth [1,1,H,W] on the device -> ground/%06d.pth."""
-        opts = self._ground_options
-        q, sums, counts = transforms.ground_plane(depth, self._calib, **opts)
-        q, sums, counts = q[0].to("cpu"), sums[0].to("cpu"), counts[0].to("cpu")
-        normal, height = transforms.ground_height(q)
-        accepted = bool(transforms.ground_accept(q, counts, opts.get("normal_prior", (0.0, 1.0, 0.0)), **self._ground_accept))
-        scale = self._camera_height / float(height) if accepted and self._camera_height is not None else 1.0
-        self._ground_scales[index] = scale
-        torch.save(dict(q=q, normal=normal, height=height, sums=sums, counts=counts, accepted=accepted, scale=scale),
-                   os.path.join(self._base, "ground", "%06d.pth" % index))
+                self._map.poses[len(self._keyframes) - 1] = pose
+        if self._ground:
+            ground = transforms.ground_record(result.depth, self._calib, self._ground_options, self._ground_accept, self._camera_height)
+            self._ground_scales[index] = ground["scale"]
+            save(ground, kd.GROUND, index)
+        if self._map is not None:
+            self._map.set_depth(index, result.depth[0])
 
     def _set_mapping_net(self, weights):
         self._mapping_net = MappingVAE()
@@ -597,21 +533,18 @@ class NeuralSLAM:
             kf.embedding = self._map.embedding(i)
 
     def _load_keyframes(self, embed):
+        closed = embed and self._dir.exists(kd.POSES_CLOSED)
         if self._resident:
             from .keyframe_map import KeyframeMap
             self._map = KeyframeMap.from_directory(self._base, self._device)
-            closed = os.path.join(self._base, "poses_closed.pth")
-            if embed and os.path.exists(closed):                  # a relocalisation start after a loop closure
-                self._map.update_poses(torch.load(closed))
-            files = sorted(glob.glob(os.path.join(self._base, "rgb", "*.pth")))
-            self._keyframes = [Frame(f, self._map.poses[i].clone()) for i, f in enumerate(files)]
+            if closed:                                            # a relocalisation start after a loop closure
+                self._map.update_poses(self._dir.load(kd.POSES_CLOSED))
+            self._keyframes = [Frame(f, self._map.poses[i].clone()) for i, f in enumerate(self._dir.frames())]
             if embed:
                 self._embed_keyframes()
             return
-        closed = os.path.join(self._base, "poses_closed.pth")
-        poses = _homogeneous(torch.load(closed if embed and os.path.exists(closed) else os.path.join(self._base, "poses.pth")))
-        files = sorted(glob.glob(os.path.join(self._base, "rgb", "*")))
-        for i, f in enumerate(files):
+        poses = _homogeneous(self._dir.load(kd.POSES_CLOSED if closed else kd.POSES))
+        for i, f in enumerate(self._dir.frames("*")):
             code = self._embed(torch.load(f)) if embed else None
             self._keyframes.append(Frame(f, poses[i], code))
 

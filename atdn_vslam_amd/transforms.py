@@ -654,6 +654,20 @@ def ground_accept(q, counts, normal_prior=(0.0, 1.0, 0.0), min_inlier_share=0.2,
     return (used > 0) & (share >= float(min_inlier_share)) & (cos >= math.cos(math.radians(float(max_tilt_deg))))
 
 
+def ground_record(depth, calib, options=None, accept=None, camera_height=None):
+    """The ground of one depth image [1,1,H,W], as a keyframe's `ground/%06d.pth` holds it: `ground_plane` (`options` its keyword
+    arguments) on the depth's device, then on the host `q`, `sums`, `counts` of the one image, `normal` and `height`
+    (`ground_height`), `accepted` (bool: `ground_accept`, `accept` its thresholds) and `scale` (float: `camera_height` / height
+    when accepted and a `camera_height` is given, 1.0 otherwise)."""
+    options = dict(options or {})
+    q, sums, counts = ground_plane(depth, calib, **options)
+    q, sums, counts = q[0].to("cpu"), sums[0].to("cpu"), counts[0].to("cpu")
+    normal, height = ground_height(q)
+    accepted = bool(ground_accept(q, counts, options.get("normal_prior", (0.0, 1.0, 0.0)), **(accept or {})))
+    scale = float(camera_height) / float(height) if accepted and camera_height is not None else 1.0
+    return dict(q=q, normal=normal, height=height, sums=sums, counts=counts, accepted=accepted, scale=scale)
+
+
 def flow_track_step(flow, acc, alive, pose=None, calib=None, mask=None, depth=None, max_epipolar=1.0, min_parallax_deg=0.05,
                     max_depth=80.0, out=None):
     """One step of a flow track: the correspondences of an anchor frame's pixels carried one frame further and, given a pose,

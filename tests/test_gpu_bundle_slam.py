@@ -2,6 +2,7 @@
 and poses, that the trajectory is that of "multiview" bit for bit unless bundle_pose=True, and what bundle_pose=True stores. The
 synthetic weights give arbitrary flows: this pins the plumbing, not accuracy."""
 import os
+import sys
 
 import pytest
 import torch
@@ -9,40 +10,20 @@ import torch
 from atdn_vslam_amd import depth as depth_mod
 from atdn_vslam_amd import synthetic as syn
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from slam_cases import _Args, _bits, EverySecond, SLAM_CALIB, _tree  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SLAM_CALIB = depth_mod.resize_calib((718.856, 718.856, 607.1928, 185.2157), (376, 1241), (376, 1232))
-
-
-class _Args:
-    def __init__(self, path):
-        self.device = DEV
-        self.keyframes_path = path
-
-
-def _tree(root):
-    return sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs) + \
-        sorted(os.path.relpath(os.path.join(d, s), root) + "/" for d, ss, _ in os.walk(root) for s in ss)
-
-
-def _bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
 
 
 def test_neuralslam_bundle_keyframe_depth(tmp_path):
     """Five synthetic frames, every second pair ends in a keyframe: keyframes are frames 0, 2, 4; keyframes 0 and 1 get a window
     of two steps each. The thresholds are opened wide so that the arbitrary flows leave some candidates."""
-    from atdn_vslam_amd.slam import KeyframePolicy, NeuralSLAM
+    from atdn_vslam_amd.slam import NeuralSLAM
     gsd, hsd = syn.to_torch(syn.make_gma_state(seed=1)), syn.to_torch(syn.make_clvo_state(seed=1))
     vsd = syn.to_torch(syn.make_vae_state(seed=2))
     frames = torch.from_numpy(syn.make_frames(5, 376, 1241, seed=8))
-
-    class EverySecond(KeyframePolicy):
-        calls = 0
-
-        def __call__(self, pred_mat):
-            self.calls += 1
-            return self.calls % 2 == 0
 
     with pytest.raises(ValueError, match="calib"):
         NeuralSLAM(_Args(str(tmp_path)), odometry_weights=hsd, flow_weights=gsd, keyframe_depth="bundle")
@@ -60,7 +41,7 @@ def test_neuralslam_bundle_keyframe_depth(tmp_path):
         for k, f in enumerate(frames):
             poses.append(slam(f).clone())
             if k == 0 and mode == "bundle":                            # the track exists now: record what it is fed
-                track = slam._track
+                track = slam._depth.track
                 assert track.history == 16
                 start, extend = track.start, track.extend
 

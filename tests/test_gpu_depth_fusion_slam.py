@@ -7,17 +7,16 @@ import numpy as np
 import pytest
 import torch
 
-from atdn_vslam_amd import depth as depth_mod
 from atdn_vslam_amd import synthetic as syn
 from atdn_vslam_amd import transforms
 from atdn_vslam_amd.keyframe_map import KeyframeMap
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from depth_fusion_ref import check_reference, scene  # noqa: E402
+from slam_cases import _Args, EverySecond, SLAM_CALIB, _tree  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SLAM_CALIB = depth_mod.resize_calib((718.856, 718.856, 607.1928, 185.2157), (376, 1241), (376, 1232))
 
 
 def _map_of(bank, poses, capacity=2):
@@ -71,32 +70,14 @@ def test_keyframe_map_fuse_depths():
     assert (second[2][:, 0] == first[2][:, 2]).all()                   # what was kept is what now has a depth
 
 
-class _Args:
-    def __init__(self, path):
-        self.device = DEV
-        self.keyframes_path = path
-
-
-def _tree(root):
-    return sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs) + \
-        sorted(os.path.relpath(os.path.join(d, s), root) + "/" for d, ss, _ in os.walk(root) for s in ss)
-
-
 def test_neuralslam_fuse_depth(tmp_path):
     """Five synthetic frames, every second pair ends in a keyframe: keyframes are frames 0, 2, 4; keyframes 0 and 1 get a depth.
     The synthetic weights give arbitrary flows, so the depths hardly agree: this test pins the plumbing — which files appear,
     that they hold what the map's own fuse_depths returns, that nothing else changes — not accuracy."""
-    from atdn_vslam_amd.slam import KeyframePolicy, NeuralSLAM
+    from atdn_vslam_amd.slam import NeuralSLAM
     gsd, hsd = syn.to_torch(syn.make_gma_state(seed=1)), syn.to_torch(syn.make_clvo_state(seed=1))
     vsd = syn.to_torch(syn.make_vae_state(seed=2))
     frames = torch.from_numpy(syn.make_frames(5, 376, 1241, seed=8))
-
-    class EverySecond(KeyframePolicy):
-        calls = 0
-
-        def __call__(self, pred_mat):
-            self.calls += 1
-            return self.calls % 2 == 0
 
     for kw in (dict(fuse_depth=True), dict(fuse_depth=True, calib=SLAM_CALIB), dict(fuse_depth=True, resident_map=True)):
         with pytest.raises(ValueError, match="fuse_depth"):

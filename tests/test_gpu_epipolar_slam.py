@@ -2,6 +2,7 @@
 transforms.two_view_depth called by hand on the same flow and the same predicted pose, and with refine_pose=False nothing moves.
 Synthetic weights: the flows are noise and the refined poses mean nothing, but every relation below is exact."""
 import os
+import sys
 
 import pytest
 import torch
@@ -10,16 +11,13 @@ from atdn_vslam_amd import depth as depth_mod
 from atdn_vslam_amd import synthetic as syn
 from atdn_vslam_amd import transforms
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from slam_cases import _Args  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 HW = (376, 1232)
 CALIB = depth_mod.resize_calib((718.856, 718.856, 607.1928, 185.2157), (376, 1241), (376, 1232))
-
-
-class _Args:
-    def __init__(self, path):
-        self.device = DEV
-        self.keyframes_path = path
 
 
 @pytest.fixture(scope="module")
@@ -133,7 +131,7 @@ def test_neural_slam_refines_every_pair(gsd, hsd, frames, tmp_path, monkeypatch,
         slam._policy = EverySecond()
         slam.start_odometry()
         poses = [slam(f).clone() for f in frames]
-        slam._flush_track()
+        slam._record_depth(slam._depth.close())
         files = sorted(os.listdir(os.path.join(path, "depth")))
         return slam, poses, [torch.load(os.path.join(path, "depth", f)) for f in files]
 

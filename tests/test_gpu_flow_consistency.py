@@ -16,6 +16,7 @@ from atdn_vslam_amd.modules import RAFTGMA
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from flow_consistency_ref import MIN_MARGIN, RANDOM_CASES, flow_consistency_ref, reference_batch, smooth_pair  # noqa: E402
+from slam_cases import _Args  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -305,12 +306,6 @@ def test_forward_backward_leaves_a_consecutive_chain_alone(gsd, low_latency):
 
 
 # ----------------------------------------------------------------------------- relocalisation
-class _Args:
-    def __init__(self, path):
-        self.device = DEV
-        self.keyframes_path = path
-
-
 def _reloc_directory(golden_dir, vsd, root):
     """The three-keyframe directory of tests/test_gpu_keyframe_map.py (tests/golden/make_golden_slam.py), rebuilt from its seeds."""
     g = np.load(os.path.join(golden_dir, "reloc.npz"))

@@ -15,10 +15,10 @@ from atdn_vslam_amd import _lib, depth as depth_mod, synthetic as syn, transform
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import flow_track_ref as R  # noqa: E402
 from flow_track_ref import CASES, FULL_CASE, MIN_MARGIN, same_bits, same_steps  # noqa: E402
+from slam_cases import _Args, SLAM_CALIB  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SLAM_CALIB = depth_mod.resize_calib((718.856, 718.856, 607.1928, 185.2157), (376, 1241), (376, 1232))
 
 
 def _dev(a):
@@ -269,12 +269,6 @@ class _Recorder:
 
     def __getattr__(self, name):
         return getattr(self._owner, name)
-
-
-class _Args:
-    def __init__(self, path):
-        self.device = DEV
-        self.keyframes_path = path
 
 
 def _listing(root, sub):

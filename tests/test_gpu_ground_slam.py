@@ -3,52 +3,32 @@ ground/%06d.pth holds what transforms.ground_plane and the host helpers give for
 poses_scaled.pth is evaluation.rescale_intervals of poses.pth and the stored scales. The synthetic weights give arbitrary flows and
 depths: this pins the plumbing, not accuracy."""
 import os
+import sys
 
 import pytest
 import torch
 
-from atdn_vslam_amd import depth as depth_mod
 from atdn_vslam_amd import evaluation, transforms
 from atdn_vslam_amd import synthetic as syn
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from slam_cases import _Args, _bits_flat as _bits, EverySecond, _files, SLAM_CALIB  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SLAM_CALIB = depth_mod.resize_calib((718.856, 718.856, 607.1928, 185.2157), (376, 1241), (376, 1232))
 # wide open: the arbitrary depths of synthetic weights should leave a plane to fit and to accept
 PLANE = dict(iters=4, scale_rel=0.5, inlier_rel=0.5, min_z=1e-3, max_depth=1e6, min_votes=1, rows=(0, 376))
 ACCEPT = dict(min_inlier_share=0.0, max_tilt_deg=180.0)
 CAMERA_HEIGHT = 1.65
 
 
-class _Args:
-    def __init__(self, path):
-        self.device = DEV
-        self.keyframes_path = path
-
-
-def _files(root):
-    return sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs)
-
-
-def _bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.reshape(-1).contiguous().view(torch.uint8),
-                                                                      b.reshape(-1).contiguous().view(torch.uint8))
-
-
 def test_neuralslam_ground(tmp_path):
     """Five synthetic frames, every second pair ends in a keyframe (frames 0, 2, 4). keyframe_depth="track" without and with the
     ground fit, and "pair" with it."""
-    from atdn_vslam_amd.slam import KeyframePolicy, NeuralSLAM
+    from atdn_vslam_amd.slam import NeuralSLAM
     gsd, hsd = syn.to_torch(syn.make_gma_state(seed=1)), syn.to_torch(syn.make_clvo_state(seed=1))
     vsd = syn.to_torch(syn.make_vae_state(seed=2))
     frames = torch.from_numpy(syn.make_frames(5, 376, 1241, seed=8))
-
-    class EverySecond(KeyframePolicy):
-        calls = 0
-
-        def __call__(self, pred_mat):
-            self.calls += 1
-            return self.calls % 2 == 0
 
     with pytest.raises(ValueError, match="calib"):
         NeuralSLAM(_Args(str(tmp_path)), odometry_weights=hsd, flow_weights=gsd, ground=True)

@@ -12,6 +12,7 @@ root: 2.3e-6 .. 2.5e-6. REL_TOL = 5e-6 is twice that bound. It holds for D <= 16
 """
 import functools
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -21,6 +22,9 @@ from atdn_vslam_amd import synthetic as syn
 from atdn_vslam_amd.keyframe_map import KeyframeMap, gather_images, search_bank
 from atdn_vslam_amd.modules import MappingVAE
 from atdn_vslam_amd.pipeline import SLAM_SIZE
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from slam_cases import _Args  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -253,12 +257,6 @@ def test_embed_writes_bank_rows_in_place(n, vsd):
     other.load_state_dict(syn.to_torch(syn.make_vae_state(seed=3)))
     m.embed(other.to(DEV).eval(), batch=16)
     assert m.n_embedded == 2 * n + 2 and not torch.equal(m.embedding_bank[:n], before)
-
-
-class _Args:
-    def __init__(self, path):
-        self.device = DEV
-        self.keyframes_path = path
 
 
 def _reloc_directory(golden_dir, vsd, root):

@@ -4,6 +4,7 @@ Synthetic weights make the flows, and so the measured loop edges, meaningless: t
 solver's accuracy is the subject of tests/test_pose_graph_host.py and tests/test_gpu_pose_graph.py)."""
 import math
 import os
+import sys
 
 import pytest
 import torch
@@ -11,16 +12,13 @@ import torch
 from atdn_vslam_amd import loop_closure, transforms
 from atdn_vslam_amd import synthetic as syn
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from slam_cases import _Args  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 K = 5
 OPTIONS = dict(min_gap=2, min_score=0.0)
-
-
-class _Args:
-    def __init__(self, path):
-        self.device = DEV
-        self.keyframes_path = path
 
 
 @pytest.fixture(scope="module")

@@ -10,7 +10,6 @@ import pytest
 import torch
 
 from atdn_vslam_amd import _lib, transforms
-from atdn_vslam_amd import depth as depth_mod
 from atdn_vslam_amd import synthetic as syn
 from atdn_vslam_amd.keyframe_map import KeyframeMap
 from atdn_vslam_amd.voxel_map import VoxelMap
@@ -18,10 +17,10 @@ from atdn_vslam_amd.voxel_map import VoxelMap
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import map_view_ref as R  # noqa: E402
 import voxel_map_ref as V  # noqa: E402
+from slam_cases import _Args, EverySecond, SLAM_CALIB, _tree  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SLAM_CALIB = depth_mod.resize_calib((718.856, 718.856, 607.1928, 185.2157), (376, 1241), (376, 1232))
 # the small hand camera: 5 x 7, fx = fy = 4, principal point on pixel (3, 2); with size 0.25 a point at z = 2 has
 # hx = 0.5 * splat * 0.25 * 4 / 2 = splat / 4 pixels (0.5 after the clamp for splat <= 2), all exact in binary
 HW, CAL, SIZE = (5, 7), (4.0, 4.0, 3.0, 2.0), 0.25
@@ -408,32 +407,14 @@ def test_keyframe_map_render_depths_fills_exactly_the_zero_pixels():
         assert (want[k][hole] != 0).any()
 
 
-class _Args:
-    def __init__(self, path):
-        self.device = DEV
-        self.keyframes_path = path
-
-
-def _tree(root):
-    return sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs) + \
-        sorted(os.path.relpath(os.path.join(d, s), root) + "/" for d, ss, _ in os.walk(root) for s in ss)
-
-
 def test_neuralslam_map_depth(tmp_path):
     """Five synthetic frames, keyframes 0, 2, 4 (as the voxel map's SLAM test). The synthetic weights give arbitrary flows and
     depths: this pins the plumbing — map_depth/ appears only with the option and holds voxel_map.render at the keyframe poses,
     every other file is what it was — not accuracy."""
-    from atdn_vslam_amd.slam import KeyframePolicy, NeuralSLAM
+    from atdn_vslam_amd.slam import NeuralSLAM
     gsd, hsd = syn.to_torch(syn.make_gma_state(seed=1)), syn.to_torch(syn.make_clvo_state(seed=1))
     vsd = syn.to_torch(syn.make_vae_state(seed=2))
     frames = torch.from_numpy(syn.make_frames(5, 376, 1241, seed=8))
-
-    class EverySecond(KeyframePolicy):
-        calls = 0
-
-        def __call__(self, pred_mat):
-            self.calls += 1
-            return self.calls % 2 == 0
 
     with pytest.raises(ValueError, match="map_depth"):
         NeuralSLAM(_Args(str(tmp_path)), odometry_weights=hsd, flow_weights=gsd, calib=SLAM_CALIB, resident_map=True, map_depth=True)

@@ -2,6 +2,7 @@
 flows and poses, and that nothing "track" writes changes. The synthetic weights give arbitrary flows: this pins the plumbing,
 not accuracy."""
 import os
+import sys
 
 import pytest
 import torch
@@ -9,36 +10,20 @@ import torch
 from atdn_vslam_amd import depth as depth_mod
 from atdn_vslam_amd import synthetic as syn
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from slam_cases import _Args, EverySecond, SLAM_CALIB, _tree  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SLAM_CALIB = depth_mod.resize_calib((718.856, 718.856, 607.1928, 185.2157), (376, 1241), (376, 1232))
-
-
-class _Args:
-    def __init__(self, path):
-        self.device = DEV
-        self.keyframes_path = path
-
-
-def _tree(root):
-    return sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs) + \
-        sorted(os.path.relpath(os.path.join(d, s), root) + "/" for d, ss, _ in os.walk(root) for s in ss)
 
 
 def test_neuralslam_multiview_keyframe_depth(tmp_path):
     """Five synthetic frames, every second pair ends in a keyframe: keyframes are frames 0, 2, 4; keyframes 0 and 1 get a depth
     over two steps each. The thresholds are opened wide so that the arbitrary flows leave some valid pixels."""
-    from atdn_vslam_amd.slam import KeyframePolicy, NeuralSLAM
+    from atdn_vslam_amd.slam import NeuralSLAM
     gsd, hsd = syn.to_torch(syn.make_gma_state(seed=1)), syn.to_torch(syn.make_clvo_state(seed=1))
     vsd = syn.to_torch(syn.make_vae_state(seed=2))
     frames = torch.from_numpy(syn.make_frames(5, 376, 1241, seed=8))
-
-    class EverySecond(KeyframePolicy):
-        calls = 0
-
-        def __call__(self, pred_mat):
-            self.calls += 1
-            return self.calls % 2 == 0
 
     with pytest.raises(ValueError, match='"pair", "track" or "multiview"'):
         NeuralSLAM(_Args(str(tmp_path)), odometry_weights=hsd, flow_weights=gsd, calib=SLAM_CALIB, keyframe_depth="stereo")
@@ -56,7 +41,7 @@ def test_neuralslam_multiview_keyframe_depth(tmp_path):
         for k, f in enumerate(frames):
             poses.append(slam(f).clone())
             if k == 0 and mode == "multiview":                         # the track exists now: record what it is fed
-                track = slam._track
+                track = slam._depth.track
                 assert track.history == 16
                 start, extend = track.start, track.extend
 
@@ -73,7 +58,7 @@ def test_neuralslam_multiview_keyframe_depth(tmp_path):
         run[mode] = (slam, path, poses)
     (ref, ref_path, ref_poses), (slam, path, poses) = run["track"], run["multiview"]
     assert all(torch.equal(a, b) for a, b in zip(poses, ref_poses)) and len(slam) == len(ref) == 3
-    assert ref._track.history == 0 and ref.multiview_counts is None
+    assert ref._depth.track.history == 0 and ref.multiview_counts is None
     names = ["%06d.pth" % i for i in range(3)]
     depth = ["depth/" + n for n in names[:2]]
     after = ["poses.pth"] + ["rgb/" + n for n in names]

@@ -7,21 +7,16 @@ import numpy as np
 import pytest
 import torch
 
-from atdn_vslam_amd import depth as depth_mod
 from atdn_vslam_amd import synthetic as syn
 from atdn_vslam_amd import transforms
 from atdn_vslam_amd.keyframe_map import KeyframeMap
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from slam_cases import _Args, EverySecond, SLAM_CALIB  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 HW = (376, 1232)
-SLAM_CALIB = depth_mod.resize_calib((718.856, 718.856, 607.1928, 185.2157), (376, 1241), (376, 1232))
-
-
-class _Args:
-    def __init__(self, path):
-        self.device = DEV
-        self.keyframes_path = path
 
 
 @pytest.fixture(scope="module")
@@ -162,14 +157,7 @@ def test_geometric_relocalization(golden_dir, gsd, hsd, vsd, tmp_path):
 def test_cold_start_session_fills_the_depth_bank(gsd, hsd, vsd, tmp_path, mode):
     """Four frames, every second pair ends in a keyframe: the session's own map holds the depths it wrote, and from_directory
     loads the same ones."""
-    from atdn_vslam_amd.slam import KeyframePolicy, NeuralSLAM
-
-    class EverySecond(KeyframePolicy):
-        calls = 0
-
-        def __call__(self, pred_mat):
-            self.calls += 1
-            return self.calls % 2 == 0
+    from atdn_vslam_amd.slam import NeuralSLAM
 
     path = os.path.join(str(tmp_path), mode)
     os.makedirs(path)

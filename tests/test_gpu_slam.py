@@ -2,6 +2,7 @@
 the C ABI, against the committed reference outputs (tests/golden/vae.npz, reloc.npz, slam.npz, keyframes.npz) and the
 CPU oracle."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -9,6 +10,9 @@ import torch
 
 from atdn_vslam_amd import synthetic as syn
 from atdn_vslam_amd.modules import MappingVAE
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from slam_cases import _Args  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -47,12 +51,6 @@ def test_vae_checkpoint_with_decoder_keys_loads(vsd):
     net.load_state_dict(full)
     with pytest.raises(RuntimeError):
         net(torch.zeros(1, 3, 376, 1232))  # CPU tensor: no fallback
-
-
-class _Args:
-    def __init__(self, path):
-        self.device = DEV
-        self.keyframes_path = path
 
 
 @pytest.fixture(scope="module")

@@ -17,12 +17,12 @@ from atdn_vslam_amd import transforms
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from two_view_ref import CASES, FULL_CASE, DEFAULTS, check_case, min_sin2_of, reference_batch  # noqa: E402
+from slam_cases import _Args, EverySecond, SLAM_CALIB  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 # 4 x the reference's own float32-against-float64 gap on each fixture case (tests/test_two_view_host.py)
 PROJECT_TOL = {"5x7": 4 * 3.353e-06, "47x154": 4 * 6.757e-06}
-SLAM_CALIB = depth_mod.resize_calib((718.856, 718.856, 607.1928, 185.2157), (376, 1241), (376, 1232))
 
 
 def _dev(a):
@@ -303,12 +303,6 @@ def test_visual_odometry_with_a_calibration(gsd, hsd, kitti_frames):
     assert vo.last_depth is None and vo.last_counts is None
 
 
-class _Args:
-    def __init__(self, path):
-        self.device = DEV
-        self.keyframes_path = path
-
-
 def _listing(root):
     return sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs) + \
         sorted(os.path.relpath(os.path.join(d, s), root) + "/" for d, ss, _ in os.walk(root) for s in ss)
@@ -317,14 +311,7 @@ def _listing(root):
 def test_neuralslam_keyframe_depth(gsd, hsd, kitti_frames, tmp_path):
     """Five frames, every second pair ends in a keyframe: keyframes are frames 0, 2, 4; the pairs (0,1) and (2,3) give keyframes 0
     and 1 their depth, keyframe 2 has no successor and no file."""
-    from atdn_vslam_amd.slam import KeyframePolicy, NeuralSLAM
-
-    class EverySecond(KeyframePolicy):
-        calls = 0
-
-        def __call__(self, pred_mat):
-            self.calls += 1
-            return self.calls % 2 == 0
+    from atdn_vslam_amd.slam import NeuralSLAM
 
     run = {}
     for name, calib in (("plain", None), ("calib", SLAM_CALIB)):

@@ -7,17 +7,16 @@ import numpy as np
 import pytest
 import torch
 
-from atdn_vslam_amd import depth as depth_mod
 from atdn_vslam_amd import synthetic as syn
 from atdn_vslam_amd.keyframe_map import KeyframeMap
 from atdn_vslam_amd.voxel_map import VoxelMap
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import voxel_map_ref as V  # noqa: E402
+from slam_cases import _Args, EverySecond, SLAM_CALIB, _tree  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SLAM_CALIB = depth_mod.resize_calib((718.856, 718.856, 607.1928, 185.2157), (376, 1241), (376, 1232))
 
 
 def _np(cloud):
@@ -60,32 +59,14 @@ def test_keyframe_map_voxel_map():
         m.voxel_map(s["calib"], fused=torch.from_numpy(fused[:2]).to(DEV))
 
 
-class _Args:
-    def __init__(self, path):
-        self.device = DEV
-        self.keyframes_path = path
-
-
-def _tree(root):
-    return sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs) + \
-        sorted(os.path.relpath(os.path.join(d, s), root) + "/" for d, ss, _ in os.walk(root) for s in ss)
-
-
 def test_neuralslam_voxel_map(tmp_path):
     """Five synthetic frames, every second pair ends in a keyframe: keyframes are frames 0, 2, 4; keyframes 0 and 1 get a depth.
     The synthetic weights give arbitrary flows and depths: this test pins the plumbing — which files appear, that map.ply holds
     what the map's own voxel_map returns from the fused depths, that nothing else changes — not accuracy."""
-    from atdn_vslam_amd.slam import KeyframePolicy, NeuralSLAM
+    from atdn_vslam_amd.slam import NeuralSLAM
     gsd, hsd = syn.to_torch(syn.make_gma_state(seed=1)), syn.to_torch(syn.make_clvo_state(seed=1))
     vsd = syn.to_torch(syn.make_vae_state(seed=2))
     frames = torch.from_numpy(syn.make_frames(5, 376, 1241, seed=8))
-
-    class EverySecond(KeyframePolicy):
-        calls = 0
-
-        def __call__(self, pred_mat):
-            self.calls += 1
-            return self.calls % 2 == 0
 
     for kw in (dict(voxel_map=True), dict(voxel_map=True, calib=SLAM_CALIB), dict(voxel_map=True, resident_map=True)):
         with pytest.raises(ValueError, match="voxel_map"):
