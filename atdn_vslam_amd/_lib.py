@@ -151,6 +151,10 @@ SIGNATURES = {
                          [C.c_int] + [_vp] * 6),
     "atdn_view_render_host": (C.c_int, [_vp] * 3 + [C.c_int, _vp] + [C.c_int] * 3 + [C.c_double] * 6 + [C.c_int] + [C.c_double] * 2 +
                               [C.c_int] + [_vp] * 4),
+    "atdn_voxel_votes": (C.c_int, [_vp, C.c_int] + [_vp] * 3 + [C.c_int] * 4 + [C.c_double] * 8 + [C.c_int] * 2 + [_vp, _vp]),
+    "atdn_voxel_votes_host": (C.c_int, [_vp, C.c_int] + [_vp] * 3 + [C.c_int] * 4 + [C.c_double] * 8 + [C.c_int] * 2 + [_vp]),
+    "atdn_voxel_remove": (C.c_int, [_vp, C.c_long, _vp, _vp, C.c_long, _vp, _vp]),
+    "atdn_voxel_remove_host": (C.c_int, [_vp, C.c_long, _vp, _vp, C.c_long, _vp]),
     "atdn_map_search":(C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "atdn_map_gather_images_u8": (C.c_int, [_vp, C.c_int, C.c_long, _vp, C.c_int, _vp, _vp]),
     "atdn_corr_lookup": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),

@@ -251,6 +251,30 @@ class KeyframeMap:
         return vm
 
     @torch.no_grad()
+    def carve(self, voxel_map, calib, fused=None, batch=8, **options):
+        """Free-space carving of `voxel_map` (a `voxel_map.VoxelMap` on the map's device) against every keyframe of this map:
+        `VoxelMap.carve` (`options`: its keyword arguments — min_free, ratio, min_support, near, far, rel, abs_tol, radius)
+        straight from the depth bank and the poses, `batch` keyframes per launch through an index list (no gather copy).
+        `fused` ([n,H,W] float32 on the map's device, what `fuse_depths` returns) replaces the depth bank — pass what the
+        voxel map was integrated from. `calib` is the calibration of the map's grid. Returns `VoxelMap.carve`'s report; a map
+        without a depth bank raises."""
+        n = self.n
+        if voxel_map.device != self.device:
+            raise ValueError("the voxel map is on %s but the keyframe map on %s" % (voxel_map.device, self.device))
+        if fused is None:
+            if self.depth_bank is None or n == 0:
+                raise RuntimeError("carve: the map holds no depth (set_depth gives a keyframe its depth map)")
+            depth = self.depth_bank[:n]
+        else:
+            depth = torch.as_tensor(fused)
+            if tuple(depth.shape) != (n,) + self.hw or depth.device != self.device:
+                raise ValueError("fused must be [%d,%d,%d] on %s, got %s on %s" %
+                                 ((n,) + self.hw + (self.device, tuple(depth.shape), depth.device)))
+        poses = self._poses[:n, :3, :].reshape(n, 12).to(self.device)
+        with torch.cuda.device(self.device):
+            return voxel_map.carve(depth, poses, calib, batch=batch, **options)
+
+    @torch.no_grad()
     def render_depths(self, cloud, calib, indices=None, fill=False, batch=8, **options):
         """The map's cloud seen from the keyframes' own poses: the depth every keyframe would have measured had it seen what all
         of them saw. `cloud` is a `voxel_map.VoxelMap` on the map's device (`options`: the keyword arguments of its `render` —

@@ -67,7 +67,7 @@ def _homogeneous(poses12):
 
 
 def _check_options(calib, resident_map, keyframe_depth, loop_closure, refine_pose, fuse_depth, ground, camera_height, voxel_map,
-                   map_depth):
+                   map_depth, carve=False):
     """The rules between NeuralSLAM's options; the first one that is broken raises ValueError."""
     if voxel_map and (calib is None or not resident_map):
         raise ValueError("voxel_map=True needs the calibration and the keyframe map in device memory: pass calib= and "
@@ -76,6 +76,8 @@ def _check_options(calib, resident_map, keyframe_depth, loop_closure, refine_pos
         raise ValueError('map_depth is False, True or "fill", got %r' % (map_depth,))
     if map_depth and not voxel_map:
         raise ValueError("map_depth needs the voxel map: pass voxel_map=True")
+    if carve and not voxel_map:
+        raise ValueError("carve=True needs the voxel map: pass voxel_map=True")
     if ground and calib is None:
         raise ValueError("ground=True needs the calibration: pass calib=")
     if ground and camera_height is not None and not (math.isfinite(float(camera_height)) and float(camera_height) > 0.0):
@@ -161,6 +163,12 @@ class NeuralSLAM:
     rendered depth also goes into the depth bank at exactly the pixels that hold 0, so the geometric leg of relocalisation reads
     it. A cold start with the option removes a `map_depth/` of an earlier session. With False (the default) no file, no code path
     and no bit changes anywhere.
+    `carve=True` (needs `voxel_map=True`): `build_voxel_map()` carves free space after the last integrate and before `map.ply`
+    is written (`KeyframeMap.carve`, `carve_options` its keyword arguments — min_free, ratio, min_support, near, far, rel,
+    abs_tol, radius, batch) against the depths it integrated — the fused ones with `fuse_depth`, the depth bank otherwise: a
+    voxel that enough keyframes see straight through, and more than confirm it, leaves the cloud. `carve_report` keeps
+    `VoxelMap.carve`'s report, `map.ply` holds the carved cloud and `map_depth` renders it. No new file or directory. With
+    False (the default) no code path and no bit changes anywhere.
     """
 
     FLOW_CHECKPOINT = "atdn_vslam/checkpoints/gma-kitti.pth"  # utils/gma_parameters.py
@@ -169,10 +177,10 @@ class NeuralSLAM:
                  precision=None, map_options=None, resident_map=False, warm_start=False, calib=None, keyframe_depth="pair",
                  loop_closure=False, loop_options=None, refine_pose=False, fuse_depth=False, fuse_options=None,
                  multiview_options=None, bundle_options=None, bundle_pose=False, ground=False, ground_options=None,
-                 camera_height=None, voxel_map=False, voxel_options=None, map_depth=False):
+                 camera_height=None, voxel_map=False, voxel_options=None, map_depth=False, carve=False, carve_options=None):
         from .depth import intrinsics
         _check_options(calib, resident_map, keyframe_depth, loop_closure, refine_pose, fuse_depth, ground, camera_height, voxel_map,
-                       map_depth)
+                       map_depth, carve)
         self._args = args
         self._base = args.keyframes_path
         self._dir = KeyframeDir(self._base)
@@ -209,6 +217,9 @@ class NeuralSLAM:
         self._voxel_options = dict(voxel_options or {})
         self.voxel_map = None        # voxel_map.VoxelMap of the last build_voxel_map()
         self._map_depth = map_depth
+        self._carve = bool(carve)
+        self._carve_options = dict(carve_options or {})
+        self.carve_report = None     # VoxelMap.carve's report of the last build_voxel_map() with carve=True
         # frame-by-frame caller that returns a host pose per call (one device synchronisation each): the split-f16 range guard
         # is read after EVERY forward, so no pose computed from clamped activations is ever returned
         self._flow_net = RAFTGMA(max_batch=1, precision=precision, saturation_check_every=1, low_latency=True)
@@ -344,7 +355,8 @@ class NeuralSLAM:
         the keyframes' poses as they are now (the optimised ones after a loop closure) and their depths — the fused depths of
         the last `fuse_depths()` of this object when `fuse_depth=True`, the depth bank otherwise. Writes
         `<keyframes_path>/map.ply` (binary little-endian: x y z float, red green blue uchar, count int; the voxels with at least
-        `min_count` points in ascending key order), keeps the VoxelMap as `self.voxel_map` and returns it. A map in which no
+        `min_count` points in ascending key order; with `carve=True` after free-space carving against the same depths, whose
+        report is kept as `self.carve_report`), keeps the VoxelMap as `self.voxel_map` and returns it. A map in which no
         keyframe has a depth writes nothing and returns None."""
         if getattr(self, "_map", None) is None or self._calib is None:
             raise RuntimeError("build_voxel_map needs the keyframe map in device memory and the calibration: construct "
@@ -358,6 +370,8 @@ class NeuralSLAM:
         if fused is not None and int(fused.shape[0]) != len(self._map):
             fused = None
         self.voxel_map = self._map.voxel_map(self._calib, fused=fused, **options)
+        if self._carve:
+            self.carve_report = self._map.carve(self.voxel_map, self._calib, fused=fused, **self._carve_options)
         self.voxel_map.save_ply(self._dir.path(kd.MAP_PLY), min_count=min_count)
         return self.voxel_map
 

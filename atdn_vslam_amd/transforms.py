@@ -921,6 +921,51 @@ def render_points(points, colors, counts, poses, calib, hw, size, splat=1.0, max
     return depth, out_colors, support, out_counts
 
 
+def visibility_votes(points, depth, poses, calib, indices=None, near=0.5, far=40.0, rel=0.05, abs_tol=0.25, radius=1, out=None):
+    """Per point of a cloud, how many keyframes have it in view, confirm it and see straight through it. `points` [M,3] float32 is
+    what `VoxelMap.extract` returns or `VoxelMap.load_ply` reads (M = 0 is fine); `depth` [N,H,W] float32 and `poses` ([N,12],
+    [N,3,4] or [N,4,4]; rows of [R|t], world <- camera) are banks of N keyframes, `calib` (fx, fy, cx, cy) or a calibration
+    matrix without skew. `indices` (integers, host or on the device) lists the keyframes that vote — the whole bank by default;
+    an index outside the bank casts no vote, a repeat votes again. A point with near <= z <= far in a keyframe whose pixel lies
+    at least `radius` pixels inside the image is IN VIEW; with band = rel * z + abs_tol it has SUPPORT where the pixel's depth
+    lies within z -+ band, and is FREE where every depth of the (2 radius + 1)^2 window is measured (within [near, far]) and
+    beyond z + band; anything else is occluded or unknown. Returns `votes` [M,3] int32 = (in view, support, free) on the
+    points' device; `out=` (an earlier result) is added to and returned. Device tensors go through libatdn_hip's kernel on the
+    current stream (no synchronisation), CPU tensors through the library's host form. The rule is float64 and integer sums,
+    stated in full in include/atdn_hip.h, atdn_voxel_votes: the same bits on every call, on both paths and however the
+    keyframes are split over calls."""
+    from .depth import intrinsics
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError("expected points [M,3], got %s" % (tuple(getattr(points, "shape", ())),))
+    dev = points.device
+    M = int(points.shape[0])
+    pts = points.detach().to(torch.float32).contiguous()
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
+        raise RuntimeError("expected a depth bank [N,H,W], got %s" % (tuple(getattr(depth, "shape", ())),))
+    if depth.device != dev:
+        raise RuntimeError("points on %s but depth on %s" % (dev, depth.device))
+    if depth.dtype != torch.float32 or not depth.is_contiguous():
+        depth = depth.detach().float().contiguous()
+    N, H, W = (int(v) for v in depth.shape)
+    if isinstance(poses, torch.Tensor) and poses.device != dev:
+        raise RuntimeError("points on %s but poses on %s" % (dev, poses.device))
+    p = _pose_rows(poses, N, dev)
+    ix = None if indices is None else _index_tensor(indices, "indices", dev).reshape(-1)
+    K = N if ix is None else int(ix.shape[0])
+    if out is None:
+        votes, accumulate = torch.empty((M, 3), dtype=torch.int32, device=dev), 0
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != (M, 3) or out.device != dev or \
+                not out.is_contiguous():
+            raise RuntimeError("expected out [%d,3] int32, contiguous, on %s" % (M, dev))
+        votes, accumulate = out, 1
+    if K < 1:
+        return votes if accumulate else votes.zero_()
+    _lib.call("atdn_voxel_votes", dev, _ptr(pts) if M else None, M, _ptr(depth), _ptr(p), _ptr(ix), N, K, H, W, *intrinsics(calib),
+              float(near), float(far), float(rel), float(abs_tol), int(radius), accumulate, _ptr(votes) if M else None)
+    return votes
+
+
 class InputPadder:
     """Replicate-pads frames to multiples of 8 ('sintel' mode splits the padding on both sides)."""
 

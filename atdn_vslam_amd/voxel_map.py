@@ -43,7 +43,8 @@ class VoxelMap:
         self.has_colors = None              # set by the first integrate: every call gives images, or none does
         self._points_bound = 0              # host-side upper bound of the points in the table
         self._counts = dict.fromkeys(COUNTERS, 0)
-        self._extraction = None             # extract(1) as render() last saw it; dropped by integrate and _grow
+        self._extraction = None             # extract(1) as render() last saw it; dropped by integrate, _grow and remove
+        self.removed = dict(voxels=0, points=0)   # what remove() took out so far (host side; the table's counters do not change)
         self.table = self._new_table(capacity)
 
     # ------------------------------------------------------------------ the table
@@ -192,6 +193,71 @@ class VoxelMap:
         return render_points(points, colors, counts, poses, calib, hw, self.voxel, splat=splat, max_splat=max_splat,
                              near=self.min_z if near is None else near, far=self.max_z if far is None else far,
                              min_count=min_count)
+
+    # ------------------------------------------------------------------ carving
+    def votes(self, depth, poses, calib, indices=None, batch=8, **thresholds):
+        """Visibility votes of every voxel of the map (`extract(1)`) against the keyframes `indices` (a host sequence or a tensor;
+        the whole bank by default) of the banks `depth` [N,H,W] and `poses`: `transforms.visibility_votes`, where the rule and the
+        `thresholds` near, far, rel, abs_tol, radius are described; `near` and `far` default to this map's `min_z` and `max_z`,
+        `abs_tol` to its `voxel`. The keyframes go `batch` at a time through the index list, accumulated on the device. Returns
+        `(keys [M] int64, votes [M,3] int32 = in view, support, free)` on the map's device, in ascending key order."""
+        from .transforms import visibility_votes
+        points, _, _, keys = self.extract(1)
+        if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
+            raise RuntimeError("expected a depth bank [N,H,W], got %s" % (tuple(getattr(depth, "shape", ())),))
+        if depth.device != self.device:
+            raise RuntimeError("the voxel map is on %s but the depth on %s" % (self.device, depth.device))
+        if depth.dtype != torch.float32 or not depth.is_contiguous():
+            depth = depth.detach().float().contiguous()
+        N = int(depth.shape[0])
+        if isinstance(poses, torch.Tensor) and poses.device != self.device:
+            raise RuntimeError("the voxel map is on %s but the poses on %s" % (self.device, poses.device))
+        p = _pose_rows(poses, N, self.device)
+        ix = _index_tensor(np.arange(N) if indices is None else indices, "indices", self.device).reshape(-1)
+        options = dict(near=self.min_z, far=self.max_z, abs_tol=self.voxel)
+        options.update(thresholds)
+        batch = max(1, int(batch))
+        votes = torch.zeros((int(points.shape[0]), 3), dtype=torch.int32, device=self.device)
+        for a in range(0, int(ix.shape[0]), batch):
+            visibility_votes(points, depth, p, calib, indices=ix[a:a + batch], out=votes, **options)
+        return keys, votes
+
+    def remove(self, keys):
+        """Empty the voxels `keys` (int64, a tensor on the map's device or a host sequence): their counts and sums become 0, their
+        slots stay (atdn_voxel_remove in include/atdn_hip.h), so `extract` no longer returns them and a later `integrate` refills
+        them like any voxel. `counts` is unchanged: `inserted` keeps meaning points ever inserted and `voxels` occupied slots.
+        What was removed is added to the host-side `removed` dict (voxels, points). Returns (voxels emptied, points they held,
+        keys not found or already empty) as host ints."""
+        if isinstance(keys, torch.Tensor):
+            if keys.device != self.device:
+                raise RuntimeError("the voxel map is on %s but the keys on %s" % (self.device, keys.device))
+            k = keys.detach().reshape(-1)
+            if k.dtype != torch.int64:
+                raise RuntimeError("keys must be int64, got %s" % k.dtype)
+            k = k.contiguous()
+        else:
+            k = torch.from_numpy(np.asarray(keys, dtype=np.int64).reshape(-1)).to(self.device)
+        R = int(k.shape[0])
+        removed = torch.empty((3,), dtype=torch.int64, device=self.device)
+        self._extraction = None
+        self._call("atdn_voxel_remove", _ptr(self.table), self.capacity, _ptr(k) if R else None, None, R, _ptr(removed))
+        voxels, points, missing = (int(v) for v in removed.cpu().tolist())
+        self.removed["voxels"] += voxels
+        self.removed["points"] += points
+        return voxels, points, missing
+
+    def carve(self, depth, poses, calib, indices=None, min_free=2, ratio=1.0, min_support=0, batch=8, **thresholds):
+        """Free-space carving: vote (`votes`, with its `thresholds`), decide, remove. A voxel goes iff
+        `(free >= min_free) & (free > ratio * support) | (support < min_support)`: at least `min_free` keyframes see straight
+        through it and more than `ratio` times as many as confirm it, or fewer than `min_support` confirm it (0: never). Returns a
+        report (dict): `voxels` before, `removed_voxels`, `removed_points`, and `free_hist` / `support_hist`, the numbers of
+        voxels with 0, 1, .. 7 and 8 or more free / support votes."""
+        keys, votes = self.votes(depth, poses, calib, indices=indices, batch=batch, **thresholds)
+        support, free = votes[:, 1], votes[:, 2]
+        go = ((free >= int(min_free)) & (free.double() > float(ratio) * support.double())) | (support < int(min_support))
+        voxels, points, _ = self.remove(keys[go])
+        hist = [torch.bincount(v.clamp(max=8).long(), minlength=9).cpu().tolist() for v in (free, support)]
+        return dict(voxels=int(keys.shape[0]), removed_voxels=voxels, removed_points=points, free_hist=hist[0], support_hist=hist[1])
 
     def save_ply(self, path, min_count=1):
         """Write the cloud as a binary little-endian PLY: x y z float, red green blue uchar (a coloured map only), count int.

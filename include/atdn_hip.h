@@ -1169,6 +1169,65 @@ int atdn_view_render_host(const float* points, const uint8_t* colors, const int*
                           double far, int min_count, float* depth, uint8_t* colors_out, uint8_t* support, int64_t* counts_out);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Visibility votes and carving  —  per point of the map's cloud: how many keyframes have it in view, how many measured a depth
+ * that confirms it, how many see straight through it; and the removal of voxels from the table. The only way a voxel leaves
+ * the voxel map. A gather (point x keyframe: one projection, a window of depth reads, three integer votes), no render and no
+ * scatter. Integer sums commute: every bit of the votes is independent of thread order, launch geometry and of how the
+ * keyframes are split over calls. The reference has nothing like it.
+ *
+ * The rule. Float64 with every operation rounded on its own (no fused multiply-add); only + - * /, comparisons and the
+ * conversions named below.
+ *   points [M,3] fp32 (what atdn_voxel_extract writes, or a cloud read from map.ply); depth [N,H,W] fp32; poses [N,12] fp32, rows
+ *   of [R|t], world <- camera; indices [K] int32 or NULL as in atdn_voxel_integrate (an index outside [0, N) contributes
+ *   nothing, a repeat votes again, NULL means keyframe j at list position j and K <= N); (fx, fy, cx, cy) float64;
+ *   0 < near <= far, far finite; rel >= 0 and abs >= 0, finite; radius in 0..8; accumulate in {0, 1}.
+ * Per point i and list position j (keyframe k):
+ *   d_a = (double)p_a - (double)t_a;  c_a = dot3(r_0a, d_0, r_1a, d_1, r_2a, d_2), dot3 = (x0*y0 + x1*y1) + x2*y2 (column a
+ *   of R: c = R^T d, as in the map view);  z = c_2
+ *   IN RANGE iff near <= z && z <= far (a NaN fails)
+ *   u = (c_0/z)*fx + cx,  v = (c_1/z)*fy + cy,  a = u + 0.5,  b = v + 0.5
+ *   IN VIEW iff in range and a >= radius && a < W - radius && b >= radius && b < H - radius, every comparison made in double
+ *   before any conversion (a NaN or an infinity converts nothing); then x and y are a and b truncated (both non-negative), and
+ *   the whole (2 radius + 1)^2 window around (x, y) lies inside the image
+ *   band = rel*z + abs,  lo = z - band,  hi = z + band
+ *   a depth m is MEASURED iff near <= m && m <= far, evaluated on (double)depth: 0, NaN, +-inf and negative values fail
+ *   SUPPORT iff the centre depth is measured and lo <= m && m <= hi
+ *   FREE iff every pixel of the window is measured and has m > hi (the centre belongs to the window: FREE and SUPPORT exclude
+ *   each other; requiring the whole window keeps slanted surfaces and silhouettes from carving themselves)
+ *   everything else is occluded or unknown and casts no vote
+ * votes [M,3] int32 = per point the number of list positions IN VIEW, with SUPPORT, FREE: written with accumulate == 0, added
+ * to what is there with accumulate == 1.
+ *
+ * Removal. keys [R] int64, flags [R] uint8 or NULL (NULL: every key; else the keys with a non-zero flag). Each flagged key is
+ * looked up by a read-only probe: the home slot and the min(capacity, 1024) limit of insertion, ended by an empty slot. Where
+ * the key is found with n > 0, n, S and C become 0 and the key word stays: the emptied voxel keeps its slot, so no probe chain
+ * breaks; atdn_voxel_extract skips it (n >= min_count >= 1 fails before any division), atdn_voxel_rehash carries it along
+ * unchanged, a later atdn_voxel_integrate refills it like any voxel. The header's five counters are not touched: `inserted`
+ * keeps meaning points ever inserted, `voxels` occupied slots. removed [3] int64 = voxels emptied, points they held, flagged
+ * keys not found or already empty (a repeated key counts once as emptied, then as already empty).
+ * ------------------------------------------------------------------------------------------------- */
+
+/* Votes of M >= 0 points (M == 0: nothing is launched, points and votes may be NULL). All pointers DEVICE and 4-byte aligned;
+ * votes may not overlap an input. One launch with accumulate == 1, two with 0 (a clear of votes first), on `stream`
+ * (asynchronous, capturable, no host synchronisation, no memset): int32 atomic adds whose results nobody reads, only where a
+ * vote is non-zero. No thread waits for another, there is no lock and no retry, every loop bound is an argument or a constant.
+ * The _host twin takes host memory, runs on the calling thread and gives the same bits. */
+int atdn_voxel_votes(const float* points, int M, const float* depth, const float* poses, const int* indices, int N, int K, int H,
+                     int W, double fx, double fy, double cx, double cy, double near, double far, double rel, double abs, int radius,
+                     int accumulate, int* votes, void* stream);
+int atdn_voxel_votes_host(const float* points, int M, const float* depth, const float* poses, const int* indices, int N, int K,
+                          int H, int W, double fx, double fy, double cx, double cy, double near, double far, double rel, double abs,
+                          int radius, int accumulate, int* votes);
+
+/* Empties the voxels of the flagged keys (R >= 0; R == 0: removed = 0 and nothing else). table, keys and removed 8-byte aligned;
+ * neither the table nor removed may overlap keys, flags or each other. Two launches on `stream` (a clear of removed, then a
+ * thread per key: a 64-bit exchange on n, plain zero stores on S and C), no memset, no host synchronisation. Must not run
+ * concurrently with another call on the same table. */
+int atdn_voxel_remove(void* table, long capacity, const int64_t* keys, const uint8_t* flags, long R, int64_t* removed,
+                      void* stream);
+int atdn_voxel_remove_host(void* table, long capacity, const int64_t* keys, const uint8_t* flags, long R, int64_t* removed);
+
+/* ---------------------------------------------------------------------------------------------------
  * Keyframe map  —  replaces the keyframe list of NeuralSLAM's relocalisation (keyframe_map.py)
  *   embeddings: Frame.embedding, one MappingVAE call per keyframe (slam_framework/neural_slam.py:88-103,158-164)
  *   search:     the per-keyframe torch.norm loop, torch.stack and argmin (neural_slam.py:374-383)
