@@ -21,7 +21,8 @@ struct EncoderWeights {
 
 class GmaNet {
  public:
-  // precision: 0 = exact-fp32 MFMA everywhere; 1 = split-f16 (3 x f16 MFMA, fp32-grade) for every TAP-mode GEMM
+  // precision: 0 = exact-fp32 MFMA everywhere; 1 = split-f16 (3 x f16 MFMA, fp32-grade) for every TAP-mode GEMM; 2 = plain f16
+  // (hi x hi only); 3 = split-f16 arithmetic on mode 2's op sequence (two-pass stem, separate normalisation passes): verification
   GmaNet(int H, int W, int max_batch, int precision);
   // Order matters: the body synchronises the device and destroys graphs, streams and events; the buffers and the weight
   // arena are members, so they are freed after it.
@@ -52,7 +53,8 @@ class GmaNet {
   int H, W, H8, W8, N, ldN, maxB, precision;
   int dev_ = 0;   // device the handle lives on
   // feature network, split-f16 pipeline (precision 1): conv2 of every residual block normalises conv1's raw output in its own
-  // patch loader (conv_sf6.h NORM); the f16 fast mode keeps the separate normalisation pass
+  // patch loader (conv_sf6.h NORM); the f16 fast mode (and precision 3, its op sequence at split precision) keeps the separate
+  // normalisation pass
   bool norm_on_load_ = false;
   // precision 0 (exact-fp32 MFMA everywhere) keeps the classical data flow: row-major correlation pyramid pooled from the
   // level-0 volume, separate lookup and convc1, fp32 logits + softmax pass + attention x V on the GEMM engine. The split-f16

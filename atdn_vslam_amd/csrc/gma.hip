@@ -132,7 +132,8 @@ void GmaNet::profile(int B, int iters, int reps, float* ms, hipStream_t st, int 
 }
 
 GmaNet::GmaNet(int H_, int W_, int max_batch, int precision_) : H(H_), W(W_), maxB(max_batch), precision(precision_) {
-  ATDN_CHECK(precision >= 0 && precision <= 2, "precision must be 0 (fp32 MFMA), 1 (split-f16 MFMA) or 2 (plain f16 MFMA)");
+  ATDN_CHECK(precision >= 0 && precision <= 3,
+             "precision must be 0 (fp32 MFMA), 1 (split-f16 MFMA), 2 (plain f16 MFMA) or 3 (split-f16 MFMA on the f16 mode's op sequence)");
   ATDN_CHECK(H % 8 == 0 && W % 8 == 0 && H > 0 && W > 0, "frame size must be a multiple of 8 (use the padder)");
   // below 128 the reference itself has no result: bilinear_sampler normalises by (H_l - 1), utils.py:63-64, and level 3 is
   // H/64 x W/64 cells — NaN in its 81 level-3 lookup channels and in everything computed from them
@@ -141,7 +142,9 @@ GmaNet::GmaNet(int H_, int W_, int max_batch, int precision_) : H(H_), W(W_), ma
              "divides by H/64 - 1 and W/64 - 1 when it samples that level, and returns NaN below)");
   ATDN_CHECK(max_batch >= 1 && max_batch <= 64, "max_batch out of range");
   H8 = H / 8; W8 = W / 8; N = H8 * W8; ldN = round_up(N, 32);
-  norm_on_load_ = precision == 1;   // (the f16 fast mode keeps the separate normalisation pass: its conv kernels are FAST builds)
+  // (the f16 fast mode keeps the separate normalisation pass: its conv kernels are FAST builds; precision 3 runs that op sequence —
+  // two-pass stem, separate in_apply_sf passes — in split-f16 arithmetic, so that it can be held to the fp64 yardstick)
+  norm_on_load_ = precision == 1;
   classic_ = precision == 0;        // exact-fp32 mode: row-major pyramid + separate lookup, logits + softmax pass + GEMM
   const char* ng = getenv("ATDN_NO_GRAPH");
   use_graph_ = !(ng && ng[0] == '1');

@@ -19,7 +19,7 @@
 //     tensor MODE_NORM wrote) and the same partial sums; nobody materialises relu(IN(.)) any more — layer1.0's first
 //     conv normalises in its patch loader (conv_sf6.h, as every second conv of a block already does) and the block's
 //     residual pass normalises the shortcut on the fly (in_apply_sf_kernel). The split-f16 feature network runs this;
-//     the f16 fast mode keeps the two-pass form.
+//     the f16 fast mode keeps the two-pass form (and precision 3 runs it in split-f16 arithmetic for the parity tests).
 //   * the sf output of a row tile (32 pixels x 256 B, contiguous in memory) is assembled in a wave-private LDS slab and
 //     stored as whole lines, 1 KiB per wave instruction.
 #include "conv_mfma.h"
@@ -153,18 +153,21 @@ __global__ __launch_bounds__(256, MODE == 1 ? 4 : 3) void stem_sf_kernel(const S
       for (int j = 0; j < 2; ++j) {
         const int n = 32 * j + r;
         const float bias = a.bias[n];
+        // (the group's sum in fp64, rounded once, as in MODE_RAW_STATS below and for its reason: a running fp32 sum of a flat
+        // frame's one DC level rounds the same way in every group of the image)
         float v[16];
-        float sum = 0.f;
+        double dsum = 0.0;
         int cnt = 0;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int ox = tx0 + (e & 3) + 8 * (e >> 2) + 4 * h;
           v[e] = acc[i][j][e] * a.wscale + bias;
-          if (oy < a.Ho && ox < a.Wo) { sum += v[e]; ++cnt; }
+          if (oy < a.Ho && ox < a.Wo) { dsum += (double)v[e]; ++cnt; }
         }
-        sum += __shfl_xor(sum, 32);
+        dsum += __shfl_xor(dsum, 32);
         cnt += __shfl_xor(cnt, 32);
-        const float mean = sum / (float)(cnt > 0 ? cnt : 1);
+        const float sum = (float)dsum;
+        const float mean = (float)(dsum / (double)(cnt > 0 ? cnt : 1));
         float m2 = 0.f;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {

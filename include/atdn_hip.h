@@ -41,10 +41,15 @@ const char* atdn_last_error(void);
  *            (x = hi + lo, fp32 accumulate): fp32-grade results at 5.3x the matrix rate (the default);
  *            ATDN_PRECISION_F16 = the fast mode: the same kernels and tensors, but only the hi x hi MFMA of every
  *            product (plain f16 operands, fp32 accumulate) — what the reference itself runs on a GPU under
- *            `mixed_precision` autocast (utils/gma_parameters.py:11); flow within ~1e-2 px of the fp32 CPU path. */
+ *            `mixed_precision` autocast (utils/gma_parameters.py:11); flow within ~1e-2 px of the fp32 CPU path;
+ *            ATDN_PRECISION_SPLIT_F16_TWO_PASS = split-f16 arithmetic on the f16 mode's op sequence: the two-pass stem
+ *            (statistics, then recompute + normalise) and separate normalisation passes in the feature network instead of
+ *            normalise-on-load. Kept for verification: it is the only way to hold that precision-independent plumbing, which
+ *            otherwise only the f16 mode runs, to the fp32-grade yardstick; slower than ATDN_PRECISION_SPLIT_F16. */
 #define ATDN_PRECISION_F32 0
 #define ATDN_PRECISION_SPLIT_F16 1
 #define ATDN_PRECISION_F16 2
+#define ATDN_PRECISION_SPLIT_F16_TWO_PASS 3
 int atdn_gma_create(atdn_gma** out, int H, int W, int max_batch, int precision);
 
 /* Low-latency form for the reference's per-frame call pattern — NeuralSLAM.__call__ runs the flow network on ONE pair per

@@ -125,7 +125,11 @@ def make_pair(content, hw):
     return f
 
 
-MODES = (("split_f16", False), ("f32", False), ("split_f16", True))   # (precision, low_latency) of test_gpu_flow_geometry._net
+# (precision, low_latency) of test_gpu_flow_geometry._net. TWO_PASS = the f16 mode's op sequence in split-f16 arithmetic: the stem as a
+# statistics pass (stem_sf_kernel<1>) and a recompute + normalise pass (<2>), and in_apply_sf_kernel between the convolutions of every
+# residual block instead of normalise-on-load — code that otherwise only precision="f16" runs, under tolerances that hide it.
+TWO_PASS = ("split_f16_two_pass", False)
+MODES = (("split_f16", False), ("f32", False), ("split_f16", True), TWO_PASS)
 HARD = ("black", "grey", "lowcontrast", "sky_road")
 
 # (geometry, content, precision, low_latency), all B = 1
@@ -133,6 +137,7 @@ CASES = ([(SMALL, c, "split_f16", False) for c in CONTENTS] +
          [(SMALL, c, p, ll) for c in HARD for p, ll in MODES[1:]] +
          [(RAGGED, c, "split_f16", False) for c in ("black", "white", "grey", "lowcontrast", "sky_road")] +
          [(RAGGED, "sky_road", "f32", False)] +
+         [(RAGGED, c) + TWO_PASS for c in ("grey", "lowcontrast", "sky_road")] +
          [(KITTI, "sky_road", "split_f16", False)])
 
 
@@ -149,6 +154,7 @@ MIXED = [
     ("small-flat", SMALL, ("grey", "sky_road", "lowcontrast"), (0, 1, 2), MODES, True),
     ("ragged", RAGGED, ("white", "sky_road", "black"), (0, 1, 2), MODES, False),
     # (the low-latency form is for one to four pairs per call: at B = 16 the default path and the exact-fp32 mode)
+    # (nor the two-pass encoder plumbing: its per-image indexing is held at B = 3 above, ragged geometry included)
     ("kitti16", KITTI, tuple(_K16), (0, 7), MODES[:2], False),
 ]
 MIXED_CASES = [(m, p, ll) for m in MIXED for p, ll in m[4]]

@@ -22,7 +22,12 @@ SEQ = {ODD: (4, (0, 1, 2)), DEAD1: (2, (0,)), FULL: (3, (0, 1)), FULL_T: (2, (0,
 # (geometry, B, precision, low_latency)
 CASES = [(ODD, 1, "split_f16", False), (ODD, 3, "split_f16", False), (ODD, 1, "split_f16", True), (ODD, 1, "f32", False),
          (DEAD1, 1, "split_f16", False), (DEAD1, 1, "split_f16", True), (DEAD1, 1, "f32", False),
-         (FULL, 1, "split_f16", False), (FULL, 2, "split_f16", False), (FULL_T, 1, "split_f16", False)]
+         (FULL, 1, "split_f16", False), (FULL, 2, "split_f16", False), (FULL_T, 1, "split_f16", False),
+         # the two-pass encoder plumbing at split precision (flow_content_cases.TWO_PASS). The stem's 8 x 32-pixel tiles on the
+         # half-resolution map: 76x108 = 4 of 8 rows and 12 of 32 columns live in the last tiles (the statistics pass's pixel
+         # counts matter), 124x132 = 4 rows and 4 columns, 64x512 = whole tiles only
+         (ODD, 1, "split_f16_two_pass", False), (ODD, 3, "split_f16_two_pass", False),
+         (DEAD1, 1, "split_f16_two_pass", False), (FULL, 1, "split_f16_two_pass", False)]
 INIT_CASES = [(hw, prec) for hw in (ODD, DEAD1) for prec in ("split_f16", "f32")]
 REJECTED = [(64, 64), (120, 136), (136, 120)]
 SEED_INIT = 7

@@ -141,3 +141,26 @@ def test_argument_errors_are_reported():
     assert b"16x4x13" in L.atdn_last_error()
     with pytest.raises(RuntimeError):
         _lib.check(L.atdn_pose_rel2abs(None, None, 3, None))
+
+
+def test_precision_values_agree_between_the_header_and_the_module():
+    """The four arithmetic modes of the flow network: include/atdn_hip.h's ATDN_PRECISION_* constants are RAFTGMA.PRECISIONS'
+    values, atdn_gma_create takes each of them (no device needed) and refuses the next one with the reason."""
+    from atdn_vslam_amd.modules import RAFTGMA
+    text = open(os.path.join(ROOT, "include", "atdn_hip.h")).read()
+    header = {name.lower(): int(v) for name, v in re.findall(r"^#define ATDN_PRECISION_(\w+) (\d+)\s*$", text, re.M)}
+    assert header == {"f32": 0, "split_f16": 1, "f16": 2, "split_f16_two_pass": 3}
+    assert RAFTGMA.PRECISIONS == header
+    assert set(RAFTGMA._SF_PRECISIONS) == set(header) - {"f32"}
+    L = _lib.lib()
+    for value in sorted(header.values()):
+        h = C.c_void_p()
+        _lib.check(L.atdn_gma_create(C.byref(h), 128, 128, 1, value))
+        L.atdn_gma_destroy(h)
+    for value in (4, -1):
+        h = C.c_void_p()
+        assert L.atdn_gma_create(C.byref(h), 128, 128, 1, value) != 0
+        msg = L.atdn_last_error()
+        assert b"precision must be 0 (fp32 MFMA), 1 (split-f16 MFMA), 2 (plain f16 MFMA) or 3" in msg, msg
+    with pytest.raises(ValueError, match="precision must be one of"):
+        RAFTGMA(precision="split_f16_one_pass")

@@ -40,6 +40,19 @@ and rstd = 315 multiplies it. The reference accumulates its statistics in double
 After it, 184x328 grey split-f16: fmap 2.4e-5 (fp32 oracle 2.5e-5), pyr0..3 1.03e-4 / 6.4e-5 / 4.0e-5 / 2.1e-5, lookup0 9.5e-5
 (need_m at most 1.17); 128x128 grey: pyr0 3.9e-5 split-f16 and 4.3e-5 f32 where they were 1.47e-4 and 1.11e-4 (fp32 oracle 5.4e-5).
 
+The two-pass encoder plumbing (cc.TWO_PASS, precision "split_f16_two_pass": the f16 mode's op sequence in split-f16 arithmetic —
+stem_sf_kernel<1> / <2> and the separate in_apply_sf_kernel passes, which no flat frame had ever reached). Cases: black, grey,
+lowcontrast, sky_road at 128x128; grey, lowcontrast, sky_road at 184x328; the three B = 3 launches (both orders at 128x128); the clip
+and the continued clip of the sequence test. 10 more parametrisations, 396 comparisons, every neighbour / reversal / sequence
+comparison bit-equal. stem_sf_kernel<1> still had the running fp32 group sum described above. With it every case passed, but grey stood
+at twice the one-pass path's error and against the cap: 184x328 fmap 5.0e-5, pyr0..3 1.62e-4 / 9.90e-5 (cap 1e-4) / 4.6e-5 / 2.4e-5,
+lookup0 1.63e-4 (need_m 2.24); 128x128 fmap 4.0e-5, pyr0 9.4e-5. With the group summed in fp64 and rounded once (the same fix): 184x328
+fmap 2.4e-5, pyr0..3 1.15e-4 / 6.6e-5 / 4.2e-5 / 2.1e-5, lookup0 1.07e-4 (need_m 1.27); 128x128 fmap 2.5e-5, pyr0 3.9e-5 — the one-pass
+path's figures. Worst need_m after the fix: 128x128 black 1.42 (net1), grey 2.23 (attn), lowcontrast 2.10 (attn), sky_road 0.94 (net1);
+184x328 grey 1.81 (attn), lowcontrast 2.44 (attn), sky_road 2.24 (net1); [black, textured, white] 1.55 (attn, textured), [grey, sky_road,
+lowcontrast] 2.23 (attn, grey), both orders alike; [white, sky_road, black] 2.24 (net1, sky_road). Closest to a cap: 184x328 grey pyr1,
+6.6e-5 of 1e-4.
+
 Worst need_m = (max|x_hip - x64| - FLOOR * max|x64|) / max|x32 - x64| per case (PARITY-WORST lines):
     128x128 split-f16   black 1.53 (mfg0)   white 1.26 (net1)   grey 2.23 (attn)   lowcontrast 2.10 (attn)   faint 1.59 (attn)
                         identical 1.55 (attn)   half_saturated 1.48 (net1)   top_black 1.49 (net1)   checker 1.34 (net1)
@@ -201,19 +214,21 @@ def test_sequence_modes_through_a_flat_frame(sd):
     """tests/test_gpu_round3.py::test_clip_modes_are_bit_identical_to_pair_mode, for a clip that passes through a black and a
     low-contrast frame: each shared frame's feature maps and statistics slot serve the pair before and the pair after it. A clip
     on the default handle, and the same frames one per call through forward_consecutive on the low-latency handle, give the bits
-    of pair mode on the same handle."""
+    of pair mode on the same handle. The clip and the continued clip also on the two-pass encoder plumbing (cc.TWO_PASS): there
+    run_encoder_sf takes first_img and the clip's private buffers through the stem's two passes and the in_apply_sf passes."""
     hw = cc.SMALL
     fr = torch.from_numpy(cc.sequence_frames(hw)).to(DEV)
-    net = fg._net(sd, 4, "split_f16", False)
-    low_p, up_p = net(fr[0:4], fr[1:5], iters=ITERS, test_mode=True)
-    low_s, up_s = net.forward_sequence(fr, iters=ITERS)
-    assert torch.equal(low_s, low_p) and torch.equal(up_s, up_p)
-    net.forward_sequence(fr[0:2], iters=ITERS)                                  # a clip that ends on the black frame ...
-    low_c, up_c = net.forward_sequence(fr[1:5], iters=ITERS, continued=True)    # ... continued from it
-    assert torch.equal(low_c, low_p[1:4]) and torch.equal(up_c, up_p[1:4])
-    assert bool(torch.isfinite(up_p).all())
-    assert fg._sf_clamped(net, hw) == 0.0
-    del net
+    for precision in ("split_f16", cc.TWO_PASS[0]):
+        net = fg._net(sd, 4, precision, False)
+        low_p, up_p = net(fr[0:4], fr[1:5], iters=ITERS, test_mode=True)
+        low_s, up_s = net.forward_sequence(fr, iters=ITERS)
+        assert torch.equal(low_s, low_p) and torch.equal(up_s, up_p), precision
+        net.forward_sequence(fr[0:2], iters=ITERS)                                  # a clip that ends on the black frame ...
+        low_c, up_c = net.forward_sequence(fr[1:5], iters=ITERS, continued=True)    # ... continued from it
+        assert torch.equal(low_c, low_p[1:4]) and torch.equal(up_c, up_p[1:4]), precision
+        assert bool(torch.isfinite(up_p).all()), precision
+        assert fg._sf_clamped(net, hw) == 0.0, precision
+        del net
     ll = fg._net(sd, 1, "split_f16", True)
     frames = [fr[t].clone() for t in range(5)]
     chain = [ll.forward_consecutive(frames[t], frames[t + 1], iters=ITERS) for t in range(4)]

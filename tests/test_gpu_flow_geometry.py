@@ -21,6 +21,14 @@ cor1 = relu(convc1(lookup)), the 126 convolved channels of motion_features and o
 flow_low and flow_up; then flow_low / flow_up after 12 iterations. Pyramid and attention rows: the first and last, both sides of
 every 128-pixel strip boundary and 32 seeded rows (all rows where N <= 1024). Every case ends with debug_read("sf_clamped") == 0.
 
+Two-pass encoder plumbing (precision "split_f16_two_pass": the f16 mode's op sequence in split-f16 arithmetic — stem_sf_kernel<1>
+statistics pass, stem_sf_kernel<2> recompute + normalise, in_apply_sf_kernel without residual / with an sf residual / with the raw
+down-sample shortcut normalised on the fly — which otherwise only precision="f16" runs, under 0.03 / 0.15 px). 128x128 B = 1 (whole
+8 x 32 stem tiles), 184x328 B = 1 / 3 (92x164 stem map: 4 of 8 rows and 4 of 32 columns in the last tiles; at B = 3 six images x
+92 x 164 x 16 float4 = 1,448,448 against in_apply_sf's 4096 x 256 threads: the grid-stride loop runs a second, ragged, time),
+376x1232 B = 2. Measured on the MI355X: worst need_m 2.12 (mf0, 128x128), 1.44 (mfg0, 184x328, both B), 1.26 (net1, 376x1232 pair 1);
+the four cases add 126 comparisons.
+
 Kernels each case reaches (rocprofv3 --kernel-trace, one iteration; conv_sf6_kernel<TH, 16, BN, ...> = TH x 16-pixel tiles x BN
 channels, GEMM tiles from choose_tile):
   376x1232 (47x154, N = 7238)   split-f16 B = 1: the 3x3 convolutions at 1/8 resolution (motion encoder, cnet layer3) and every
@@ -236,11 +244,16 @@ def _run_case(sd, oracle, hw, B, precision="split_f16", low_latency=False):
     chk.finish()
 
 
+TWO_PASS = "split_f16_two_pass"
 CASES = ([(KITTI, B, "split_f16", False) for B in (1, 2, 4, 16)] + [(KITTI, B, "split_f16", True) for B in (1, 2, 4)] +
          [(KITTI, B, "f32", False) for B in (1, 16)] +
          [(RAGGED, 1, "split_f16", False), (RAGGED, 3, "split_f16", False), (RAGGED, 1, "split_f16", True), (RAGGED, 1, "f32", False)] +
          [(TALL, 1, "split_f16", False)] +
-         [(SMALL, 1, "split_f16", False), (SMALL, 3, "split_f16", False), (SMALL, 1, "f32", False)])
+         [(SMALL, 1, "split_f16", False), (SMALL, 3, "split_f16", False), (SMALL, 1, "f32", False)] +
+         # the f16 mode's encoder plumbing (two-pass stem, separate in_apply_sf passes) in split-f16 arithmetic: whole 8 x 32 stem
+         # tiles (128x128); a ragged stem map, and at B = 3 six images of 92x164x64 = more float4 than in_apply_sf's grid covers in
+         # one stride (184x328); many stem groups per image (376x1232, pairs 0 and 1)
+         [(SMALL, 1, TWO_PASS, False), (RAGGED, 1, TWO_PASS, False), (RAGGED, 3, TWO_PASS, False), (KITTI, 2, TWO_PASS, False)])
 
 
 def _case_id(c):

@@ -33,6 +33,12 @@ the fifth strip is at 1.0e-8 (oracle 7e-9), column 512 at 4e-9, the 31 padding c
 1.7e-5 f32 mode, oracle 1.9e-5) and level with it at 248x264 (1.4e-5 / 1.2e-5 / 1.3e-5); the two pixels 64 px outside return
 exact zeros in both modes.
 
+Two-pass encoder plumbing (precision "split_f16_two_pass", see tests/test_gpu_flow_geometry.py) at 152x216 B = 1 / 3 (stem map
+76x108: 4 of 8 rows and 12 of 32 columns live in the last 8 x 32 stem tiles, so the statistics pass's per-group pixel counts
+matter), 248x264 (124x132: 4 rows, 4 columns) and 128x1024 (64x512: whole tiles only). Measured: worst need_m 1.23 (attn, 152x216
+B = 1), 3.20 (attn, B = 3 pair 1: the element and the figure of the one-pass split-f16 case above), 1.00 (attn, 248x264), 1.13 (attn,
+128x1024); 108 comparisons.
+
 Kernels each geometry reaches (rocprofv3 --kernel-trace in a run of its own, one iteration; names as in the geometry file):
   152x216 (19x27, N = 513; 9x13, 4x6, 2x3 below)   split-f16 B = 1 / 3: corr_bricks_kernel in 5 strips per pair (the fifth: one
         live row), lookup_conv_kernel in 17 blocks of 32 pixels (the last: one live pixel), qk_softmax_kernel + attn_v3_kernel in
