@@ -20,8 +20,8 @@ extern template TileChoice conv_dispatch<MODE_ROW, EpiBias<ACT_NONE>>(const Conv
 extern template TileChoice conv_dispatch<MODE_ROW, EpiBias<ACT_RELU>>(const ConvShape&, EpiBias<ACT_RELU>, hipStream_t);
 extern template TileChoice conv_dispatch<MODE_TAP, EpiScale>(const ConvShape&, EpiScale, hipStream_t);
 
-extern template TileChoice conv_sf_dispatch<EpiBias<ACT_NONE>>(const ConvShape&, float, EpiBias<ACT_NONE>, hipStream_t);
-extern template TileChoice conv_sf_dispatch<SfBias<ACT_NONE>>(const ConvShape&, float, SfBias<ACT_NONE>, hipStream_t);
+extern template TileChoice conv_sf_dispatch<EpiBias<ACT_NONE>>(const ConvShape&, float, EpiBias<ACT_NONE>, bool, hipStream_t);
+extern template TileChoice conv_sf_dispatch<SfBias<ACT_NONE>>(const ConvShape&, float, SfBias<ACT_NONE>, bool, hipStream_t);
 
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& msg) { g_last_error = msg; }
@@ -573,8 +573,7 @@ int atdn_conv2d_nhwc_sf_epi(const float* src, int nimg, int H, int W, int Cin, c
   ATDN_CHECK(sf_store >= 0 && sf_store <= 15 && (sf_store & 6) != 6,
              "sf_store: bit 0 names the epilogue, bit 1 or bit 2 the tile form, bit 3 the plain-f16 (FAST) kernels");
   const int tile_form = (sf_store & 2) ? 1 : (sf_store & 4) ? 2 : 0;   // 1x5 / 5x1: rectangular 8 x 16 x 128 tiles / run tiles
-  // bit 3: the dispatch below runs as it does inside a precision-mode-2 forward; the flag is back at its old value on return
-  FastGuard fast_scope((sf_store & 8) != 0);
+  const bool fast = (sf_store & 8) != 0;   // bit 3: the dispatch below gets the flag a precision-mode-2 forward passes
   sf_store &= 1;
   ATDN_CHECK(!sf_store || Cout % 32 == 0, "the split-f16 store needs Cout % 32 == 0");
   StateDict sd;
@@ -604,11 +603,11 @@ int atdn_conv2d_nhwc_sf_epi(const float* src, int nimg, int H, int W, int Cin, c
   if (sf_store) {
     const long orows = (long)nimg * Ho * Wo;
     osf.alloc(orows * Cout);
-    conv_sf_dispatch(s, L.wscale, SfBias<ACT_NONE>{L.b, osf.p, (long)Ho * Wo * Cout, Cout}, st);
+    conv_sf_dispatch(s, L.wscale, SfBias<ACT_NONE>{L.b, osf.p, (long)Ho * Wo * Cout, Cout}, fast, st);
     launch_from_sf(osf.p, dst, orows, Cout, st);
     ATDN_HIP(hipStreamSynchronize(st));
   } else {
-    conv_sf_dispatch(s, L.wscale, EpiBias<ACT_NONE>{L.b, dst, (long)Ho * Wo * Cout, Cout, 1.f}, st);
+    conv_sf_dispatch(s, L.wscale, EpiBias<ACT_NONE>{L.b, dst, (long)Ho * Wo * Cout, Cout, 1.f}, fast, st);
     ATDN_HIP(hipStreamSynchronize(st));
   }
   ATDN_API_END

@@ -264,19 +264,8 @@ inline void launch_conv_sf(const ConvShape& s, float wscale, const Epi& ep, hipS
   ATDN_HIP(hipGetLastError());
 }
 
-// Plain-f16 arithmetic (precision mode 2) for the calling thread's sf convolutions: conv_sf_dispatch issues only the
-// hi x hi MFMA of every product while this is set (GmaNet sets it around its forward).
-bool& sf_fast_mode();
-
-// Sets the flag for a scope and puts the previous value back (also when the scope is left by an exception): GmaNet's forward in
-// precision mode 2, and the unit-test entry atdn_conv2d_nhwc_sf_epi when its caller asks for the FAST builds.
-struct FastGuard {
-  bool prev;
-  explicit FastGuard(bool on) : prev(sf_fast_mode()) { sf_fast_mode() = on; }
-  ~FastGuard() { sf_fast_mode() = prev; }
-  FastGuard(const FastGuard&) = delete;
-  FastGuard& operator=(const FastGuard&) = delete;
-};
+// `fast`, here and in every sf launcher: plain-f16 arithmetic (precision mode 2), only the hi x hi MFMA of every product. The
+// caller states it with each launch (GmaNet: its fast_ member); there is no default and no ambient state.
 
 // The run-time flag as the kernels' FAST template argument: f(std::true_type{}) or f(std::false_type{}), so that a launch ladder
 // is written once for both arithmetic modes.
@@ -287,10 +276,11 @@ inline auto with_fast(bool fast, F&& f) {
 
 // Definitions are explicitly instantiated in conv_sf_inst_*.hip
 template <class Epi>
-TileChoice conv_sf_dispatch(const ConvShape& s, float wscale, Epi ep, hipStream_t st);
+TileChoice conv_sf_dispatch(const ConvShape& s, float wscale, Epi ep, bool fast, hipStream_t st);
 // two independent convolutions with the same epilogue class as one launch where the halo-patch path serves both with the same
 // kernel (conv_sf6.h: conv_sf6_pair_kernel), as two launches otherwise; instantiated for SfBias<ACT_RELU>
 template <class Epi>
-void conv_sf_dispatch_pair(const ConvShape& s0, float wscale0, Epi ep0, const ConvShape& s1, float wscale1, Epi ep1, hipStream_t st);
+void conv_sf_dispatch_pair(const ConvShape& s0, float wscale0, Epi ep0, const ConvShape& s1, float wscale1, Epi ep1, bool fast,
+                           hipStream_t st);
 
 }  // namespace atdn

@@ -50,17 +50,18 @@ class GmaNet {
                ST_MASK, ST_GRU_CTX, ST_ATTN_LOGITS, ST_AGG_VT, ST_CONVC1, ST_GRU_ZR_V, ST_GRU_Q_V, ST_COUNT };
   void profile(int B, int iters, int reps, float* ms, hipStream_t st, int mode = 0);
 
-  int H, W, H8, W8, N, ldN, maxB, precision;
+  const int H, W, H8, W8, N, ldN, maxB, precision;
+  // What `precision` means, said once (the constructor is the only place that compares it):
+  // sf_: precision >= 1, the split-f16 pipeline — bricked pyramid (every level a GEMM against pooled features in brick order,
+  // 4 x 8 cells = one 128-byte line), lookup fused with convc1 (lookup_fused.hip), fused attention kernels (attention.hip), sf
+  // tensors, sequence forms. Without it (precision 0, exact-fp32 MFMA everywhere) the classical data flow: row-major correlation
+  // pyramid pooled from the level-0 volume, separate lookup and convc1, fp32 logits + softmax pass + attention x V on the GEMM engine.
+  // fast_: precision == 2, plain-f16 arithmetic — handed to every launcher of the sf pipeline (conv_sf.h). Precision 3 runs mode
+  // 2's op sequence with fast_ false.
+  // norm_on_load_: precision == 1 — conv2 of every residual block of the feature network normalises conv1's raw output in its own
+  // patch loader (conv_sf6.h NORM); precisions 2 and 3 keep the two-pass stem and the separate normalisation pass.
+  const bool sf_, fast_, norm_on_load_;
   int dev_ = 0;   // device the handle lives on
-  // feature network, split-f16 pipeline (precision 1): conv2 of every residual block normalises conv1's raw output in its own
-  // patch loader (conv_sf6.h NORM); the f16 fast mode (and precision 3, its op sequence at split precision) keeps the separate
-  // normalisation pass
-  bool norm_on_load_ = false;
-  // precision 0 (exact-fp32 MFMA everywhere) keeps the classical data flow: row-major correlation pyramid pooled from the
-  // level-0 volume, separate lookup and convc1, fp32 logits + softmax pass + attention x V on the GEMM engine. The split-f16
-  // modes use the bricked pyramid (every level a GEMM against pooled features in brick order, 4 x 8 cells = one 128-byte
-  // line), the lookup fused with convc1 (lookup_fused.hip) and the fused attention kernels (attention.hip).
-  bool classic_ = false;
   // Low-latency form for the per-frame callers (neural_slam.py:202 calls the flow network with ONE pair per frame): launches
   // that would leave most of the chip idle at small B are cut finer — today attention x V, along its key axis (attention.h).
   // Another summation order than the default path, so it is opt-in (set before finalize()); the default path keeps clip mode,
@@ -112,7 +113,11 @@ class GmaNet {
   void probe_begin(hipStream_t st);
   void probe_end(hipStream_t st);     // one copy of the slot table back, then the stream is synchronised
   void probe(const std::string& name, bool limited, const float* p, long rows, long cols, long ld, hipStream_t st);
-  void run_body(int B, int iters, hipStream_t st);  // everything between input prep and upsampling
+  void body(int B, int iters, hipStream_t st);      // everything between input prep and upsampling: run_body_sf or run_body
+  void init_coords(const float* flow_init, int B, hipStream_t st);   // coords1, flow4 and the flow channels of x, in the mode's format
+  // what forward and forward_predictions share: argument checks, pair mode, probe begin, image prep, init_coords, the input probe rows
+  void begin_pair(const float* im1, const float* im2, int B, int iters, const float* flow_init, hipStream_t st);
+  void run_body(int B, int iters, hipStream_t st);
   void run_encoder(const EncoderWeights& E, bool instance, int nimg, hipStream_t st, float** out_buf, int* outH,
                    int* outW);
   void iteration(int B, hipStream_t st);
@@ -162,7 +167,7 @@ class GmaNet {
   void mark(int stage, hipStream_t st);
 
   hipStream_t cap_stream_ = nullptr;
-  std::map<std::pair<int, int>, hipGraphExec_t> graphs_;  // key: (B, iters * 2 + seq)
+  std::map<std::pair<int, int>, hipGraphExec_t> graphs_;  // key: (B, iters * 4 + seq_)
 };
 
 }  // namespace atdn

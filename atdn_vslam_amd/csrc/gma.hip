@@ -26,17 +26,17 @@ extern template TileChoice conv_dispatch<MODE_TAP, EpiGruQ>(const ConvShape&, Ep
 extern template TileChoice conv_dispatch<MODE_TAP, EpiFlowDelta>(const ConvShape&, EpiFlowDelta, hipStream_t);
 
 extern template TileChoice conv_dispatch<MODE_ROW, SfBias<ACT_RELU>>(const ConvShape&, SfBias<ACT_RELU>, hipStream_t);
-#define ATDN_EXTERN_SF(EPI) extern template TileChoice conv_sf_dispatch<EPI>(const ConvShape&, float, EPI, hipStream_t);
+#define ATDN_EXTERN_SF(EPI) extern template TileChoice conv_sf_dispatch<EPI>(const ConvShape&, float, EPI, bool, hipStream_t);
 ATDN_EXTERN_SF(SfBias<ACT_NONE>) ATDN_EXTERN_SF(SfBias<ACT_RELU>) ATDN_EXTERN_SF(EpiBias<ACT_NONE>)
 ATDN_EXTERN_SF(EpiBiasStats) ATDN_EXTERN_SF(SfBiasReluAddRelu) ATDN_EXTERN_SF(SfContextSplit)
 ATDN_EXTERN_SF(SfQK) ATDN_EXTERN_SF(SfVT)
 ATDN_EXTERN_SF(SfGruZR) ATDN_EXTERN_SF(SfGruQ)
 extern template void conv_sf_dispatch_pair<SfBias<ACT_RELU>>(const ConvShape&, float, SfBias<ACT_RELU>, const ConvShape&, float,
-                                                             SfBias<ACT_RELU>, hipStream_t);
+                                                             SfBias<ACT_RELU>, bool, hipStream_t);
 
 namespace {
 
-// (precision mode 2: the sf convolutions of this thread issue only the hi x hi MFMA while a FastGuard lives, conv_sf.h)
+// (precision mode 2: GmaNet::fast_ goes to every sf launcher as its `fast` argument — only the hi x hi MFMA is issued, conv_sf.h)
 
 constexpr int XLD = 384;       // GRU input x = [inp | motion(126) flow(2) | motion_global]  (update.py:130)
 constexpr int CORR_LD = 352;   // 4*81 lookup channels padded to a multiple of 32
@@ -104,7 +104,7 @@ void GmaNet::mark(int stage, hipStream_t st) {
 
 void GmaNet::profile(int B, int iters, int reps, float* ms, hipStream_t st, int mode) {
   ATDN_CHECK(ready_ && B >= 1 && B <= maxB && reps >= 1, "bad profile request");
-  ATDN_CHECK(mode == 0 || precision >= 1, "sequence modes are built for the split-f16 pipeline");
+  ATDN_CHECK(mode == 0 || sf_, "sequence modes are built for the split-f16 pipeline");
   ATDN_CHECK(!probe_, "switch the range probe off before profiling: its launches would be timed with the stages");
   for (int i = 0; i < ST_COUNT; ++i) ms[i] = 0.f;
   seq_ = mode;   // 0 pair, 1 sequence, 2 continued sequence (feature slot 0 is read as it stands: timing only)
@@ -112,11 +112,10 @@ void GmaNet::profile(int B, int iters, int reps, float* ms, hipStream_t st, int 
   for (int r = 0; r < reps; ++r) {
     Timer t;
     timer_ = &t;
-    if (precision >= 1) launch_init_coords_sf(nullptr, B, H8, W8, coords1_.p, flow4_.p, x_.p, XLD, 254, st);
-    else launch_init_coords(nullptr, B, H8, W8, coords1_.p, flow4_.p, x_.p + 254, XLD, st);
+    init_coords(nullptr, B, st);
     ATDN_HIP(hipEventCreate(&t.start));
     ATDN_HIP(hipEventRecord(t.start, st));
-    try { if (precision >= 1) { FastGuard fg(precision == 2); run_body_sf(B, iters, st); } else run_body(B, iters, st); } catch (...) { timer_ = nullptr; throw; }
+    try { body(B, iters, st); } catch (...) { timer_ = nullptr; throw; }
     timer_ = nullptr;
     ATDN_HIP(hipStreamSynchronize(st));
     hipEvent_t prev = t.start;
@@ -131,7 +130,11 @@ void GmaNet::profile(int B, int iters, int reps, float* ms, hipStream_t st, int 
   }
 }
 
-GmaNet::GmaNet(int H_, int W_, int max_batch, int precision_) : H(H_), W(W_), maxB(max_batch), precision(precision_) {
+// (fast_: the f16 fast mode's conv kernels are FAST builds, so it keeps the separate normalisation pass; precision 3 runs that op
+// sequence — two-pass stem, separate in_apply_sf passes — in split-f16 arithmetic, so that it can be held to the fp64 yardstick)
+GmaNet::GmaNet(int H_, int W_, int max_batch, int precision_)
+    : H(H_), W(W_), H8(H_ / 8), W8(W_ / 8), N(H8 * W8), ldN(round_up(N, 32)), maxB(max_batch), precision(precision_),
+      sf_(precision_ >= 1), fast_(precision_ == 2), norm_on_load_(precision_ == 1) {
   ATDN_CHECK(precision >= 0 && precision <= 3,
              "precision must be 0 (fp32 MFMA), 1 (split-f16 MFMA), 2 (plain f16 MFMA) or 3 (split-f16 MFMA on the f16 mode's op sequence)");
   ATDN_CHECK(H % 8 == 0 && W % 8 == 0 && H > 0 && W > 0, "frame size must be a multiple of 8 (use the padder)");
@@ -141,11 +144,6 @@ GmaNet::GmaNet(int H_, int W_, int max_batch, int precision_) : H(H_), W(W_), ma
              "frame size must be at least 128x128: level 3 of the correlation pyramid needs at least 2x2 cells (the reference "
              "divides by H/64 - 1 and W/64 - 1 when it samples that level, and returns NaN below)");
   ATDN_CHECK(max_batch >= 1 && max_batch <= 64, "max_batch out of range");
-  H8 = H / 8; W8 = W / 8; N = H8 * W8; ldN = round_up(N, 32);
-  // (the f16 fast mode keeps the separate normalisation pass: its conv kernels are FAST builds; precision 3 runs that op sequence —
-  // two-pass stem, separate in_apply_sf passes — in split-f16 arithmetic, so that it can be held to the fp64 yardstick)
-  norm_on_load_ = precision == 1;
-  classic_ = precision == 0;        // exact-fp32 mode: row-major pyramid + separate lookup, logits + softmax pass + GEMM
   const char* ng = getenv("ATDN_NO_GRAPH");
   use_graph_ = !(ng && ng[0] == '1');
   (void)hipGetDevice(&dev_);   // (no throw: argument errors must be reportable without a device; finalize() needs one anyway)
@@ -175,7 +173,7 @@ GmaNet::~GmaNet() {
 
 // ---------------------------------------------------------------- range probe (gma.h)
 void GmaNet::set_probe(bool on) {
-  ATDN_CHECK(!on || precision == 0,
+  ATDN_CHECK(!on || !sf_,
              "the range probe needs an exact-fp32 handle (ATDN_PRECISION_F32): only that path writes every intermediate tensor "
              "as plain fp32 and never clamps; the split-f16 / f16 paths store range-limited values and fuse some tensors away");
   probe_ = on;
@@ -211,14 +209,13 @@ void GmaNet::probe_end(hipStream_t st) {
 void GmaNet::finalize() {
   ATDN_CHECK(!ready_, "finalize called twice");
   const std::string u = "update_block.";
-  const bool sf = precision >= 1;
   auto tap = [&](const std::vector<std::string>& names, bool has_bias = true) {
-    return sf ? pack_conv_sf(arena_, sd_, names, nullptr, has_bias)
+    return sf_ ? pack_conv_sf(arena_, sd_, names, nullptr, has_bias)
               : pack_conv(arena_, sd_, names, MODE_TAP, 0, nullptr, has_bias);
   };
-  fnet_ = pack_encoder(arena_, sd_, "fnet.", false, sf);
-  cnet_ = pack_encoder(arena_, sd_, "cnet.", true, sf);
-  if (sf) {
+  fnet_ = pack_encoder(arena_, sd_, "fnet.", false, sf_);
+  cnet_ = pack_encoder(arena_, sd_, "cnet.", true, sf_);
+  if (sf_) {
     // the feature head folded into the correlation (weights.h); these modes never launch fnet_.head itself —
     // debug_read("fmap") multiplies with the fp32 copy below
     fhead_fold_ = pack_fnet_head_folded(arena_, sd_, "fnet.conv2", &corr_mul_);
@@ -226,7 +223,7 @@ void GmaNet::finalize() {
     fhead_b32_off_ = pack_vector(arena_, sd_.get("fnet.conv2.bias").data);
   }
   convc1_ = tap({u + "encoder.convc1"});
-  if (sf) pack_fragment_major16(arena_, convc1_);   // the fused lookup kernel loads operand-order weights (16x16x32)
+  if (sf_) pack_fragment_major16(arena_, convc1_);   // the fused lookup kernel loads operand-order weights (16x16x32)
   convc2_ = tap({u + "encoder.convc2"});
   convf1_ = pack_conv(arena_, sd_, {u + "encoder.convf1"}, MODE_ROW, 4);
   {  // the same weights in split-f16 fragment order for flow_conv7_sf_kernel (small_convs.hip): K = 8 rows x (8 taps x 2
@@ -262,7 +259,7 @@ void GmaNet::finalize() {
   to_qk_ = tap({"att.to_qk"}, false);
   for (int p = 0; p < 2; ++p) {
     const std::string t = std::to_string(p + 1);
-    if (sf) {
+    if (sf_) {
       // hx = [h(0:128) | inp(128:256) | motion(256:384) | motion_global(384:512)] (update.py:50,130): the inp slice
       // does not change over the iterations, so its contribution is computed once per pair (run_body_sf)
       // The iterations convolve [h | motion | agg] with agg = A . motion as attention x V stores it: to_v, gamma and the
@@ -282,7 +279,7 @@ void GmaNet::finalize() {
   }
   fh1_ = tap({u + "flow_head.conv1"});
   fh2_ = tap({u + "flow_head.conv2"});
-  if (sf) {   // conv2 once more, as fp32 rows [tap * 2 + output][256] (the fused flow head multiplies in fp32)
+  if (sf_) {   // conv2 once more, as fp32 rows [tap * 2 + output][256] (the fused flow head multiplies in fp32)
     const HostTensor& w = sd_.get(u + "flow_head.conv2.weight");
     ATDN_CHECK(w.shape.size() == 4 && w.shape[0] == 2 && w.shape[1] == 256 && w.shape[2] == 3 && w.shape[3] == 3, "flow head conv2 shape");
     fh2_w32_off_ = arena_.alloc(18 * 256);
@@ -299,14 +296,14 @@ void GmaNet::finalize() {
   mask2_ = tap({u + "mask.2"});
   gamma_off_ = pack_vector(arena_, sd_.get(u + "aggregator.gamma").data);
   // to_v in fp32 [128][128]: debug_read("x") rebuilds motion_global from the stored aggregate with it
-  if (sf) to_v_w32_off_ = pack_vector(arena_, sd_.get(u + "aggregator.to_v.weight").data);
+  if (sf_) to_v_w32_off_ = pack_vector(arena_, sd_.get(u + "aggregator.to_v.weight").data);
   arena_.upload();
   resolve_encoder(arena_, fnet_);
   resolve_encoder(arena_, cnet_);
   for (PackedConv* L : {&convc1_, &convc2_, &convf1_, &convf2_, &convm_, &to_v_, &to_qk_, &gru_zr_[0], &gru_zr_[1],
                         &gru_q_[0], &gru_q_[1], &fh1_, &fh2_, &mask0_, &mask2_})
     resolve(arena_, *L);
-  if (sf) for (PackedConv* L : {&gru_zr_ctx_[0], &gru_zr_ctx_[1], &gru_q_ctx_[0], &gru_q_ctx_[1], &fhead_fold_}) resolve(arena_, *L);
+  if (sf_) for (PackedConv* L : {&gru_zr_ctx_[0], &gru_zr_ctx_[1], &gru_q_ctx_[0], &gru_q_ctx_[1], &fhead_fold_}) resolve(arena_, *L);
   gamma_ = arena_.dev(gamma_off_);
 
   // ---- workspace (sized for maxB pairs; everything stays resident in HBM between calls)
@@ -314,9 +311,9 @@ void GmaNet::finalize() {
   const int H2 = conv_out(H, 7, 2, 3), W2 = conv_out(W, 7, 2, 3);
   const long n8 = (long)B * N;
   img4_.alloc(2L * B * H * W * 4);
-  for (int i = 0; i < (sf ? 4 : 3); ++i) enc_[i].alloc(2L * B * H2 * W2 * 64);
+  for (int i = 0; i < (sf_ ? 4 : 3); ++i) enc_[i].alloc(2L * B * H2 * W2 * 64);
   // (split-f16 modes: no 256-channel feature tensor; pre-head features of 2B slots and the folded head's output for B sources)
-  if (sf) { fpre_.alloc(2L * B * N * 128); fsrc_.alloc((long)B * N * 160); }
+  if (sf_) { fpre_.alloc(2L * B * N * 128); fsrc_.alloc((long)B * N * 160); }
   else fmap_.alloc(2L * B * N * 256);
   const long groups = (long)cdiv(H2 * W2, 64) * 4 + 8;
   psum_.alloc(2L * B * groups * 128); pm2_.alloc(2L * B * groups * 128); pcnt_.alloc(2L * B * groups); fin_.alloc(2L * B * 32 * 128 * 4 * 2);
@@ -327,9 +324,9 @@ void GmaNet::finalize() {
   for (int l = 0; l < 4; ++l) {
     brickBW_[l] = cdiv(pyrW_[l], 8); brickBH_[l] = cdiv(pyrH_[l], 4); brickNB_[l] = brickBW_[l] * brickBH_[l] * 32;
     // (bricked: a pair's region holds whole 128-pixel strips, kernels.h: BrickPyramid)
-    pyr_[l].alloc(classic_ ? n8 * pyrH_[l] * pyrW_[l] : (long)B * brick_pixel_blocks(N) * kBrickPixelBlock * brickNB_[l]);
+    pyr_[l].alloc(!sf_ ? n8 * pyrH_[l] * pyrW_[l] : (long)B * brick_pixel_blocks(N) * kBrickPixelBlock * brickNB_[l]);
   }
-  if (sf) {
+  if (sf_) {
     for (int l = 0; l < 4; ++l) fbrick_[l].alloc((long)B * brickNB_[l] * 160);
     for (int l = 1; l < 4; ++l) fplain_[l - 1].alloc((long)B * pyrH_[l] * pyrW_[l] * 128);
     coords_used_.alloc(n8 * 2);
@@ -338,11 +335,11 @@ void GmaNet::finalize() {
   const AttnGeom ag = attn_geom(B, N, ldN);
   qk_.alloc(n8 * 256); attn_.alloc(std::max(n8 * ldN, attn_floats(ag)));
   // (V^T exists on the exact-fp32 path only: the split-f16 modes aggregate the motion features as they are stored)
-  if (classic_) vT_.alloc((long)B * 128 * ldN);
-  if (sf) { rowmax_.alloc((long)B * ag.Npad); rinv_.alloc((long)B * ag.Npad); }
+  if (!sf_) vT_.alloc((long)B * 128 * ldN);
+  if (sf_) { rowmax_.alloc((long)B * ag.Npad); rinv_.alloc((long)B * ag.Npad); }
   // (only where the split can engage: attn_v_splits() is 1 from 8 pairs per launch on at KITTI size)
-  if (sf && low_latency_ && attn_v_splits(attn_geom(1, N, ldN)) > 1) attn_part_.alloc(8L * B * ag.Npad * 128);
-  if (sf && low_latency_) {
+  if (sf_ && low_latency_ && attn_v_splits(attn_geom(1, N, ldN)) > 1) attn_part_.alloc(8L * B * ag.Npad * 128);
+  if (sf_ && low_latency_) {
     for (int i = 0; i < 4; ++i) enc2_[i].alloc((long)B * H2 * W2 * 64);
     ATDN_HIP(hipStreamCreateWithFlags(&par_stream_, hipStreamNonBlocking));
     par_events_.resize(2 * (1 + 64));
@@ -350,9 +347,9 @@ void GmaNet::finalize() {
   }
   corrfeat_.alloc(n8 * CORR_LD); cor1_.alloc(n8 * 256); corflo_.alloc(n8 * 256); flo1_.alloc(n8 * 128);
   z_.alloc(n8 * 128); rh_.alloc(n8 * 128); fh_.alloc(n8 * 256); mask_.alloc(n8 * 576);
-  if (sf) fhG_.alloc(2 * n8 * 18);   // (two copies: one per 128-channel block of the fused flow head)
+  if (sf_) fhG_.alloc(2 * n8 * 18);   // (two copies: one per 128-channel block of the fused flow head)
   coords1_.alloc(n8 * 2); flow4_.alloc(n8 * 4);
-  if (sf) for (int p = 0; p < 2; ++p) { pre_zr_[p].alloc(n8 * 256); pre_q_[p].alloc(n8 * 128); }
+  if (sf_) for (int p = 0; p < 2; ++p) { pre_zr_[p].alloc(n8 * 256); pre_q_[p].alloc(n8 * 128); }
   // pad lanes that kernels read but never write must be finite zeros
   ATDN_HIP(hipMemset(corrfeat_.p, 0, corrfeat_.n * sizeof(float)));
   if (vT_.p) ATDN_HIP(hipMemset(vT_.p, 0, vT_.n * sizeof(float)));
@@ -603,9 +600,9 @@ void GmaNet::mask_head(int B, hipStream_t st) {
   if (probe_) probe("mask", false, mask_.p, (long)B * N, 576, 576, st);   // (fp32 on the default path too: mask_head_sf)
 }
 
-// =============================================================== split-f16 pipeline (precision == 1)
+// =============================================================== split-f16 pipeline (sf_)
 // Same op sequence; every TAP-mode GEMM runs on conv_sf_kernel and every tensor that feeds one is stored in the
-// sf format (sf.h). ROW-mode layers (7x7 stems, convf1) stay on the exact-fp32 engine and write sf directly.
+// sf format (sf.h). Every launcher here receives fast_ (plain-f16 arithmetic in mode 2). ROW-mode layers (7x7 stems, convf1) stay on the exact-fp32 engine and write sf directly.
 void GmaNet::run_encoder_sf(const EncoderWeights& E, bool instance, int nimg, hipStream_t st, float** out_buf, int first_img,
                             DeviceBuf* bufs, float* final_dst) {
   const float* images = img4_.p + (long)first_img * H * W * 4;
@@ -620,7 +617,7 @@ void GmaNet::run_encoder_sf(const EncoderWeights& E, bool instance, int nimg, hi
     if (in_slot >= 0) { s.in_mean = mean_[in_slot].p; s.in_rstd = rstd_[in_slot].p; }
     const int oh = conv_out(ih, L.KH, stride, pad), ow = conv_out(iw, L.KW, stride, pad);
     EpiBiasStats ep{L.b, dst, (long)oh * ow * L.N, L.N, psum_.p, pm2_.p, 0, pcnt_.p};
-    TileChoice t = conv_sf_dispatch(s, L.wscale, ep, st);
+    TileChoice t = conv_sf_dispatch(s, L.wscale, ep, fast_, st);
     const int groups = t.groups_per_img;
     ATDN_CHECK((long)nimg * groups * L.N <= psum_.n && (long)nimg * groups <= pcnt_.n, "statistics scratch too small");
     if (t.counted)
@@ -691,13 +688,13 @@ void GmaNet::run_encoder_sf(const EncoderWeights& E, bool instance, int nimg, hi
       const float* res = X;
       if (Bk.has_ds) {
         ConvShape sd = conv_shape(Bk.ds, X, c, (long)h * w * c, nimg, h, w, 2, 0, 0);
-        conv_sf_dispatch(sd, Bk.ds.wscale, SfBias<ACT_NONE>{Bk.ds.b, R, ohw * co, co}, st);
+        conv_sf_dispatch(sd, Bk.ds.wscale, SfBias<ACT_NONE>{Bk.ds.b, R, ohw * co, co}, fast_, st);
         res = R;
       }
       ConvShape s1 = conv_shape(Bk.c1, X, c, (long)h * w * c, nimg, h, w, stride, 1, 1);
-      conv_sf_dispatch(s1, Bk.c1.wscale, SfBias<ACT_RELU>{Bk.c1.b, Y, ohw * co, co}, st);
+      conv_sf_dispatch(s1, Bk.c1.wscale, SfBias<ACT_RELU>{Bk.c1.b, Y, ohw * co, co}, fast_, st);
       ConvShape s2 = conv_shape(Bk.c2, Y, co, ohw * co, nimg, oh, ow, 1, 1, 1);
-      conv_sf_dispatch(s2, Bk.c2.wscale, SfBiasReluAddRelu{Bk.c2.b, res, ohw * co, co, O, ohw * co, co}, st);
+      conv_sf_dispatch(s2, Bk.c2.wscale, SfBiasReluAddRelu{Bk.c2.b, res, ohw * co, co, O, ohw * co, co}, fast_, st);
     }
     std::swap(X, O);
     h = oh; w = ow; c = co;
@@ -712,7 +709,7 @@ void GmaNet::iteration_sf(int B, hipStream_t st) {
   if (par_) fork(st, par_stream_);   // the flow branch starts where the previous iteration (or the set-up) ended
   // cor1 = relu(convc1(lookup(coords1))) in one kernel: the 324 samples of a pixel never leave the CU
   launch_lookup_conv(brick_pyramid(), coords1_.p, n8, coords_used_.p, convc1_.wf16, convc1_.wscale, convc1_.b, cor1_.p,
-                     sf_fast_mode(), st);
+                     fast_, st);
   mark(ST_LOOKUP, st);
   // (Round 3 captured the flow branch — convf1, convf2: independent of the correlation branch — as a parallel branch of the
   // graph on a second stream: +0.3 % on bench.py's two-stream loop, but -3 % in the sequence driver, whose lane streams then
@@ -727,25 +724,25 @@ void GmaNet::iteration_sf(int B, hipStream_t st) {
   if (par_) {
     // low-latency capture: the flow branch (convf1 -> convf2) runs beside the correlation branch (lookup + convc1 -> convc2);
     // it was forked at the top of the iteration (the lookup above is already on `st`)
-    launch_flow_conv7_sf(flow4_.p, B, H8, W8, arena_.dev(convf1_sf_off_), convf1_wscale_, convf1_.b, flo1_.p, sf_fast_mode(), par_stream_);
-    conv_sf_dispatch(sf2, convf2_.wscale, SfBias<ACT_RELU>{convf2_.b, corflo_.p + 192, (long)N * 256, 256}, par_stream_);
-    conv_sf_dispatch(s, convc2_.wscale, SfBias<ACT_RELU>{convc2_.b, corflo_.p, (long)N * 256, 256}, st);
+    launch_flow_conv7_sf(flow4_.p, B, H8, W8, arena_.dev(convf1_sf_off_), convf1_wscale_, convf1_.b, flo1_.p, fast_, par_stream_);
+    conv_sf_dispatch(sf2, convf2_.wscale, SfBias<ACT_RELU>{convf2_.b, corflo_.p + 192, (long)N * 256, 256}, fast_, par_stream_);
+    conv_sf_dispatch(s, convc2_.wscale, SfBias<ACT_RELU>{convc2_.b, corflo_.p, (long)N * 256, 256}, fast_, st);
     fork(par_stream_, st);   // join
   } else {
-    launch_flow_conv7_sf(flow4_.p, B, H8, W8, arena_.dev(convf1_sf_off_), convf1_wscale_, convf1_.b, flo1_.p, sf_fast_mode(), st);
+    launch_flow_conv7_sf(flow4_.p, B, H8, W8, arena_.dev(convf1_sf_off_), convf1_wscale_, convf1_.b, flo1_.p, fast_, st);
     conv_sf_dispatch_pair(s, convc2_.wscale, SfBias<ACT_RELU>{convc2_.b, corflo_.p, (long)N * 256, 256},
-                          sf2, convf2_.wscale, SfBias<ACT_RELU>{convf2_.b, corflo_.p + 192, (long)N * 256, 256}, st);
+                          sf2, convf2_.wscale, SfBias<ACT_RELU>{convf2_.b, corflo_.p + 192, (long)N * 256, 256}, fast_, st);
   }
   s = conv_shape(convm_, corflo_.p, 256, (long)N * 256, B, H8, W8, 1, 1, 1);
   float* mf = x_.p + 128;
-  conv_sf_dispatch(s, convm_.wscale, SfBias<ACT_RELU>{convm_.b, mf, (long)N * XLD, XLD}, st);
+  conv_sf_dispatch(s, convm_.wscale, SfBias<ACT_RELU>{convm_.b, mf, (long)N * XLD, XLD}, fast_, st);
   mark(ST_MOTION, st);
 
   // agg = A . motion into x[:, 256:384]: attention x V reads the motion features as the motion encoder has just stored them
   // (its LDS reads transpose them), so there is no V^T pass; to_v, gamma and the residual of gma.py:111-115 are in the gate
   // weights (finalize). The agg_vt stage has no mark and reports 0, as convc1 does since it was fused.
   launch_attn_v(attn_.p, rinv_.p, attn_geom(B, N, ldN), nullptr, nullptr, mf, x_.p + 256, (long)N * XLD, XLD,
-                sf_fast_mode(), st, attn_part_.p);   // (attn_part_ is null unless the handle was built low-latency)
+                fast_, st, attn_part_.p);   // (attn_part_ is null unless the handle was built low-latency)
   mark(ST_AGG, st);
 
   for (int p = 0; p < 2; ++p) {
@@ -755,10 +752,10 @@ void GmaNet::iteration_sf(int B, hipStream_t st) {
     ConvShape g = conv_shape(gru_zr_[p], hin, 128, (long)N * 128, B, H8, W8, 1, ph, pw);
     g.C0 = 128; g.src1 = x_.p + 128; g.ld1 = XLD; g.sb1 = (long)N * XLD; g.C1 = 256;  // [h | motion | agg]
     conv_sf_dispatch(g, gru_zr_[p].wscale,
-                     SfGruZR{gru_zr_[p].b, hin, z_.p, rh_.p, (long)N * 128, pre_zr_[p].p, (long)N * 256}, st);
+                     SfGruZR{gru_zr_[p].b, hin, z_.p, rh_.p, (long)N * 128, pre_zr_[p].p, (long)N * 256}, fast_, st);
     mark(p ? ST_GRU_ZR_V : ST_GRU_ZR, st);
     g.src0 = rh_.p; g.w = gru_q_[p].w; g.wfrag16 = gru_q_[p].wf16; g.ldw = gru_q_[p].ldw; g.N = gru_q_[p].N;
-    conv_sf_dispatch(g, gru_q_[p].wscale, SfGruQ{gru_q_[p].b, hin, z_.p, hout, (long)N * 128, pre_q_[p].p}, st);
+    conv_sf_dispatch(g, gru_q_[p].wscale, SfGruQ{gru_q_[p].b, hin, z_.p, hout, (long)N * 128, pre_q_[p].p}, fast_, st);
     mark(p ? ST_GRU_Q_V : ST_GRU_Q, st);
   }
 
@@ -766,7 +763,7 @@ void GmaNet::iteration_sf(int B, hipStream_t st) {
   const SfFlowDelta fd{fh2_.b, coords1_.p, flow4_.p, x_.p, XLD, (long)N * XLD, 254, W8, (long)N};
   // conv1 with conv2's partial sums in its epilogue, then the 3 x 3 gather (small_convs.h)
   const long fh_gs = (long)maxB * N * 18;   // second copy of the partial sums: channels 128..255 (conv_sf_inst_e.hip)
-  launch_flow_head_fused(s, fh1_.wscale, SfFlowHeadPartial{fh1_.b, arena_.dev(fh2_w32_off_), fhG_.p, (long)N, fh2_mul_, 1.0f / fh2_mul_, fh_gs}, st);
+  launch_flow_head_fused(s, fh1_.wscale, SfFlowHeadPartial{fh1_.b, arena_.dev(fh2_w32_off_), fhG_.p, (long)N, fh2_mul_, 1.0f / fh2_mul_, fh_gs}, fast_, st);
   launch_flow_gather(fhG_.p, fh_gs, B, H8, W8, fd, st);
   mark(ST_FLOWHEAD, st);
 }
@@ -790,7 +787,7 @@ void GmaNet::run_body_sf(int B, int iters, hipStream_t st) {
   // head sees the same bits the same frame's head would see as a source of any other call).
   run_encoder_sf(fnet_, true, nfeat, st, &f, seq_ == 2 ? 1 : 0, nullptr, fpre_.p + (seq_ == 2 ? (long)N * 128 : 0));
   ConvShape s = conv_shape(fhead_fold_, fpre_.p, 128, (long)N * 128, B, H8, W8, 1, 0, 0);
-  conv_sf_dispatch(s, fhead_fold_.wscale, SfBias<ACT_NONE>{fhead_fold_.b, fsrc_.p, (long)N * 160, 160}, st);
+  conv_sf_dispatch(s, fhead_fold_.wscale, SfBias<ACT_NONE>{fhead_fold_.b, fsrc_.p, (long)N * 160, 160}, fast_, st);
   mark(ST_FNET, st);
 
   // all-pairs correlation (corr.py:55-63) and its pyramid (corr.py:16-30): every level = folded source features x (target
@@ -812,7 +809,7 @@ void GmaNet::run_body_sf(int B, int iters, hipStream_t st) {
     }
     launch_brick_rows(plain, plain_sb, B, pyrH_[l], pyrW_[l], 128, 160, fbrick_[l].p, (long)brickNB_[l] * 160, st);
     launch_corr_bricks(fsrc_.p, (long)N * 160, fbrick_[l].p, (long)brickNB_[l] * 160, B, N, brickNB_[l], 160,
-                       corr_mul_ / sqrtf(256.0f), pyr_[l].p, sf_fast_mode(), st);
+                       corr_mul_ / sqrtf(256.0f), pyr_[l].p, fast_, st);
     if (l == 0) mark(ST_CORR, st);
   }
   mark(ST_POOL, st);
@@ -820,18 +817,18 @@ void GmaNet::run_body_sf(int B, int iters, hipStream_t st) {
   run_encoder_sf(cnet_, false, B, sB, &f, 0, par_ ? enc2_ : nullptr);
   s = conv_shape(cnet_.head, f, 128, (long)N * 128, B, H8, W8, 1, 0, 0);
   conv_sf_dispatch(s, cnet_.head.wscale,
-                   SfContextSplit{cnet_.head.b, h_[0].p, (long)N * 128, x_.p, (long)N * XLD, XLD}, sB);
+                   SfContextSplit{cnet_.head.b, h_[0].p, (long)N * 128, x_.p, (long)N * XLD, XLD}, fast_, sB);
   mark(ST_CNET, st);
 
   s = conv_shape(to_qk_, x_.p, XLD, (long)N * XLD, B, H8, W8, 1, 0, 0);
-  conv_sf_dispatch(s, to_qk_.wscale, SfQK{1.0f / sqrtf(128.0f), 128, qk_.p, (long)N * 256, 256}, sB);
+  conv_sf_dispatch(s, to_qk_.wscale, SfQK{1.0f / sqrtf(128.0f), 128, qk_.p, (long)N * 256, 256}, fast_, sB);
   {
     // Q K^T with the row softmax fused in (attention.hip): a cheap first sweep (f16 x f16 logits) for the row maxima,
     // then the full-precision sweep that writes exp(s - max) in MFMA-operand order and the row sums
     const AttnGeom ag = attn_geom(B, N, ldN);
     launch_qk_rowmax(qk_.p, ag, rowmax_.p, sB);
     mark(ST_ATTN_LOGITS, st);
-    launch_qk_softmax(qk_.p, ag, rowmax_.p, attn_.p, rinv_.p, sf_fast_mode(), sB);
+    launch_qk_softmax(qk_.p, ag, rowmax_.p, attn_.p, rinv_.p, fast_, sB);
   }
   mark(ST_ATTN, st);
 
@@ -839,9 +836,9 @@ void GmaNet::run_body_sf(int B, int iters, hipStream_t st) {
   for (int p = 0; p < 2; ++p) {
     const int ph = p ? 2 : 0, pw = p ? 0 : 2;
     ConvShape g = conv_shape(gru_zr_ctx_[p], x_.p, XLD, (long)N * XLD, B, H8, W8, 1, ph, pw);
-    conv_sf_dispatch(g, gru_zr_ctx_[p].wscale, EpiBias<ACT_NONE>{nullptr, pre_zr_[p].p, (long)N * 256, 256, 1.f}, sB);
+    conv_sf_dispatch(g, gru_zr_ctx_[p].wscale, EpiBias<ACT_NONE>{nullptr, pre_zr_[p].p, (long)N * 256, 256, 1.f}, fast_, sB);
     g = conv_shape(gru_q_ctx_[p], x_.p, XLD, (long)N * XLD, B, H8, W8, 1, ph, pw);
-    conv_sf_dispatch(g, gru_q_ctx_[p].wscale, EpiBias<ACT_NONE>{nullptr, pre_q_[p].p, (long)N * 128, 128, 1.f}, sB);
+    conv_sf_dispatch(g, gru_q_ctx_[p].wscale, EpiBias<ACT_NONE>{nullptr, pre_q_[p].p, (long)N * 128, 128, 1.f}, fast_, sB);
   }
   mark(ST_GRU_CTX, st);
   if (par_) fork(sB, st);   // join: the iterations need both chains
@@ -859,15 +856,15 @@ void GmaNet::run_body_sf(int B, int iters, hipStream_t st) {
 
 void GmaNet::mask_head_sf(int B, hipStream_t st) {
   ConvShape s = conv_shape(mask0_, h_[0].p, 128, (long)N * 128, B, H8, W8, 1, 1, 1);
-  conv_sf_dispatch(s, mask0_.wscale, SfBias<ACT_RELU>{mask0_.b, fh_.p, (long)N * 256, 256}, st);
+  conv_sf_dispatch(s, mask0_.wscale, SfBias<ACT_RELU>{mask0_.b, fh_.p, (long)N * 256, 256}, fast_, st);
   s = conv_shape(mask2_, fh_.p, 256, (long)N * 256, B, H8, W8, 1, 0, 0);
-  conv_sf_dispatch(s, mask2_.wscale, EpiBias<ACT_NONE>{mask2_.b, mask_.p, (long)N * 576, 576, 0.25f}, st);
+  conv_sf_dispatch(s, mask2_.wscale, EpiBias<ACT_NONE>{mask2_.b, mask_.p, (long)N * 576, 576, 0.25f}, fast_, st);
 }
 
 void GmaNet::capture(int B, int iters) {
   // parallel branches: low-latency handles, one or two pairs per launch (gma.h). If a capture with branches cannot be built (a
   // runtime that refuses the cross-stream dependency), the same body is captured again as one chain: same kernels either way.
-  const bool want_par = low_latency_ && precision >= 1 && B <= 2 && par_stream_ != nullptr && !preds_out_ && par_ok_;
+  const bool want_par = low_latency_ && sf_ && B <= 2 && par_stream_ != nullptr && !preds_out_ && par_ok_;
   for (int attempt = want_par ? 0 : 1; attempt < 2; ++attempt) {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
@@ -875,7 +872,7 @@ void GmaNet::capture(int B, int iters) {
     par_ = attempt == 0;
     par_next_ = 0;
     try {
-      if (precision >= 1) { FastGuard fg(precision == 2); run_body_sf(B, iters, cap_stream_); } else run_body(B, iters, cap_stream_);
+      body(B, iters, cap_stream_);
       par_ = false;
       ATDN_HIP(hipStreamEndCapture(cap_stream_, &graph));
       ATDN_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
@@ -903,7 +900,7 @@ void GmaNet::capture(int B, int iters) {
 void GmaNet::forward_sequence(const float* frames, int B, int iters, const float* flow_init, float* flow_low,
                                float* flow_up, hipStream_t st, bool continued) {
   ATDN_CHECK(ready_, "weights not finalized");
-  ATDN_CHECK(precision >= 1, "sequence mode is built for the split-f16 pipeline");
+  ATDN_CHECK(sf_, "sequence mode is built for the split-f16 pipeline");
   ATDN_CHECK(B >= 1 && B <= maxB, "batch exceeds max_batch of this handle");
   ATDN_CHECK(iters >= 1 && iters <= 64, "iters out of range");
   ATDN_CHECK(frames && flow_low && flow_up, "null tensor");
@@ -922,7 +919,7 @@ void GmaNet::forward_sequence(const float* frames, int B, int iters, const float
   // frames 0..B-1 are the first images, frame B the last second image: img4 = [frame 0 .. frame B]
   last_frame_ = 0;   // stays 0 if anything below throws: the next call cannot continue from a half-launched clip
   launch_prep_images(frames, frames + (long)B * frame, B, H, W, img4_.p, st, 1);
-  launch_init_coords_sf(flow_init, B, H8, W8, coords1_.p, flow4_.p, x_.p, XLD, 254, st);
+  init_coords(flow_init, B, st);
   launch_body(B, iters, st);
   launch_upsample(mask_.p, flow4_.p, B, H8, W8, flow_low, flow_up, st);
   last_frame_ = B;
@@ -935,26 +932,41 @@ void GmaNet::launch_body(int B, int iters, hipStream_t st) {
     if (!graphs_.count(key)) capture(B, iters);
     ATDN_HIP(hipGraphLaunch(graphs_[key], st));
   } else {
-    if (precision >= 1) { FastGuard fg(precision == 2); run_body_sf(B, iters, st); } else run_body(B, iters, st);
+    body(B, iters, st);
+  }
+}
+
+void GmaNet::body(int B, int iters, hipStream_t st) {
+  if (sf_) run_body_sf(B, iters, st);
+  else run_body(B, iters, st);
+}
+
+void GmaNet::init_coords(const float* flow_init, int B, hipStream_t st) {
+  if (sf_) launch_init_coords_sf(flow_init, B, H8, W8, coords1_.p, flow4_.p, x_.p, XLD, 254, st);
+  else launch_init_coords(flow_init, B, H8, W8, coords1_.p, flow4_.p, x_.p + 254, XLD, st);
+}
+
+void GmaNet::begin_pair(const float* im1, const float* im2, int B, int iters, const float* flow_init, hipStream_t st) {
+  ATDN_CHECK(ready_, "weights not finalized");
+  ATDN_CHECK(B >= 1 && B <= maxB, "batch exceeds max_batch of this handle");
+  ATDN_CHECK(iters >= 1 && iters <= 64, "iters out of range");
+  ATDN_CHECK(im1 && im2, "null tensor");
+  seq_ = 0;
+  last_frame_ = 0;   // pair mode overwrites the feature slots: a later continued sequence call fails loudly instead of reading it
+  last_B_ = B;
+  if (probe_) probe_begin(st);
+  launch_prep_images(im1, im2, B, H, W, img4_.p, st, B);
+  init_coords(flow_init, B, st);
+  if (probe_) {   // (probe_ implies the exact-fp32 path)
+    probe("image", true, img4_.p, 2L * B * H * W, 3, 4, st);    // 2 (x / 255) - 1; the stems split it on load (stem_sf.hip)
+    probe("flow_init", true, flow4_.p, (long)B * N, 2, 4, st);
   }
 }
 
 void GmaNet::forward(const float* im1, const float* im2, int B, int iters, const float* flow_init, float* flow_low,
                      float* flow_up, hipStream_t st) {
-  ATDN_CHECK(ready_, "weights not finalized");
-  ATDN_CHECK(B >= 1 && B <= maxB, "batch exceeds max_batch of this handle");
-  ATDN_CHECK(iters >= 1 && iters <= 64, "iters out of range");
-  ATDN_CHECK(im1 && im2 && flow_low && flow_up, "null tensor");
-  seq_ = 0;
-  last_frame_ = 0;   // pair mode overwrites the feature slots: a later continued sequence call fails loudly instead of reading it
-  if (probe_) probe_begin(st);
-  launch_prep_images(im1, im2, B, H, W, img4_.p, st, B);
-  if (precision >= 1) launch_init_coords_sf(flow_init, B, H8, W8, coords1_.p, flow4_.p, x_.p, XLD, 254, st);
-  else launch_init_coords(flow_init, B, H8, W8, coords1_.p, flow4_.p, x_.p + 254, XLD, st);
-  if (probe_) {   // (probe_ implies the exact-fp32 path)
-    probe("image", true, img4_.p, 2L * B * H * W, 3, 4, st);    // 2 (x / 255) - 1; the stems split it on load (stem_sf.hip)
-    probe("flow_init", true, flow4_.p, (long)B * N, 2, 4, st);
-  }
+  ATDN_CHECK(flow_low && flow_up, "null tensor");
+  begin_pair(im1, im2, B, iters, flow_init, st);
   launch_body(B, iters, st);
   launch_upsample(mask_.p, flow4_.p, B, H8, W8, flow_low, flow_up, st);
   if (probe_) {
@@ -966,27 +978,14 @@ void GmaNet::forward(const float* im1, const float* im2, int B, int iters, const
 
 void GmaNet::forward_predictions(const float* im1, const float* im2, int B, int iters, const float* flow_init, float* preds,
                                  hipStream_t st) {
-  ATDN_CHECK(ready_, "weights not finalized");
-  ATDN_CHECK(B >= 1 && B <= maxB, "batch exceeds max_batch of this handle");
-  ATDN_CHECK(iters >= 1 && iters <= 64, "iters out of range");
-  ATDN_CHECK(im1 && im2 && preds, "null tensor");
-  seq_ = 0;
-  last_frame_ = 0;
-  last_B_ = B;
-  if (probe_) probe_begin(st);
-  launch_prep_images(im1, im2, B, H, W, img4_.p, st, B);
-  if (precision >= 1) launch_init_coords_sf(flow_init, B, H8, W8, coords1_.p, flow4_.p, x_.p, XLD, 254, st);
-  else launch_init_coords(flow_init, B, H8, W8, coords1_.p, flow4_.p, x_.p + 254, XLD, st);
-  if (probe_) {
-    probe("image", true, img4_.p, 2L * B * H * W, 3, 4, st);
-    probe("flow_init", true, flow4_.p, (long)B * N, 2, 4, st);
-  }
+  ATDN_CHECK(preds, "null tensor");
+  begin_pair(im1, im2, B, iters, flow_init, st);
   struct Guard {   // the body reads the destination from the handle: never leave it set behind an exception
     GmaNet* n; ~Guard() { n->preds_out_ = nullptr; n->preds_stride_ = 0; }
   } guard{this};
   preds_out_ = preds;
   preds_stride_ = (long)B * 2 * H * W;
-  if (precision >= 1) { FastGuard fg(precision == 2); run_body_sf(B, iters, st); } else run_body(B, iters, st);
+  body(B, iters, st);
   if (probe_) probe_end(st);
 }
 
@@ -1002,7 +1001,7 @@ BrickPyramid GmaNet::brick_pyramid() const {
 
 long GmaNet::debug_read(const char* name, float* host, long capacity, hipStream_t st) {
   const std::string k(name);
-  if (!classic_ && k.size() == 4 && k.compare(0, 3, "pyr") == 0 && k[3] >= '0' && k[3] <= '3') {
+  if (sf_ && k.size() == 4 && k.compare(0, 3, "pyr") == 0 && k[3] >= '0' && k[3] <= '3') {
     // bricked level -> the reference's row-major [pixel][H_l * W_l]
     const int l = k[3] - '0';
     const long rows = (long)maxB * N, total = rows * pyrH_[l] * pyrW_[l];
@@ -1013,7 +1012,7 @@ long GmaNet::debug_read(const char* name, float* host, long capacity, hipStream_
     ATDN_HIP(hipMemcpy(host, scratch_.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return n;
   }
-  if (!classic_ && k == "corrfeat") {
+  if (sf_ && k == "corrfeat") {
     // the fused kernel keeps the samples on chip: recompute them at the coordinates the last lookup used — for the pairs of the
     // last forward only: the pyramid and the coordinates of the handle's other pairs are whatever an earlier call (or the
     // allocator) left there, and sampling that raised the format's saturation alarm behind a parity test (round 5)
@@ -1031,7 +1030,7 @@ long GmaNet::debug_read(const char* name, float* host, long capacity, hipStream_
   else if (k == "mask") b = &mask_; else if (k == "coords1") b = &coords1_; else if (k == "flow4") b = &flow4_;
   else if (k == "qk") b = &qk_; else if (k == "img4") b = &img4_;
   else if (k == "cor1") b = &cor1_;   // relu(convc1(lookup)) of the last iteration: the fused kernel's product phase
-  if (k == "fmap" && !classic_) {
+  if (k == "fmap" && sf_) {
     // the split-f16 modes never form W f + b (the head is folded into the correlation): the tap keeps its meaning, rebuilt in
     // fp32 from the decoded pre-head features, [2 * maxB slots][N][256] in fpre_'s slot order
     const long rows = 2L * maxB * N;
@@ -1046,7 +1045,7 @@ long GmaNet::debug_read(const char* name, float* host, long capacity, hipStream_
   if (k == "agg") {
     // the stored aggregate A . motion itself, [maxB * N][128]: channels 256..383 of the split-f16 GRU input (the exact-fp32
     // path stores motion_global there and has no such tensor)
-    if (classic_) return -1;
+    if (!sf_) return -1;
     scratch_.reserve(x_.n);
     launch_from_sf(x_.p, scratch_.p, x_.n / 32, 32, st);
     ATDN_HIP(hipStreamSynchronize(st));
@@ -1058,7 +1057,7 @@ long GmaNet::debug_read(const char* name, float* host, long capacity, hipStream_
   }
   if (!b) return -1;
   long n = std::min(capacity, b->n);
-  if (k == "attn" && !classic_) {   // fragment-major exp(s - max) + row sums -> normalised fp32 rows [maxB][N][ldN]
+  if (k == "attn" && sf_) {   // fragment-major exp(s - max) + row sums -> normalised fp32 rows [maxB][N][ldN]
     const long rows = (long)maxB * N * ldN;
     scratch_.reserve(rows);
     ATDN_HIP(hipMemsetAsync(scratch_.p, 0, (size_t)rows * sizeof(float), st));
@@ -1068,7 +1067,7 @@ long GmaNet::debug_read(const char* name, float* host, long capacity, hipStream_
     ATDN_HIP(hipMemcpy(host, scratch_.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return n;
   }
-  const bool is_sf = precision >= 1 && (k == "fmap" || k == "net" || k == "x" || k == "attn" || k == "corrfeat" || k == "qk" || k == "cor1");
+  const bool is_sf = sf_ && (k == "fmap" || k == "net" || k == "x" || k == "attn" || k == "corrfeat" || k == "qk" || k == "cor1");
   const float* src = b->p;
   if (is_sf) {  // decode the split-f16 tensor into a scratch fp32 copy first
     scratch_.reserve(b->n);

@@ -4,8 +4,6 @@
 
 namespace atdn {
 
-bool& sf_fast_mode();  // see conv_sf.h
-
 struct PyramidLevels {  // correlation pyramid of ONE batch: level l is [B*N][H_l*W_l] fp32
   const float* base[4];
   int H[4], W[4];

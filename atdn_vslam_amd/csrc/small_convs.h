@@ -14,7 +14,7 @@ void launch_flow_conv7_sf(const float* flow4, int nimg, int H, int W, const floa
 // conv1 writes G[img][pix][tap * 2 + output] = conv2's weights x relu(conv1) of THAT pixel; the gather sums each
 // pixel's 3 x 3 neighbourhood (zero padding outside the map) and applies SfFlowDelta (conv2's bias, coordinate update).
 struct ConvShape;
-void launch_flow_head_fused(const ConvShape& s, float wscale, const SfFlowHeadPartial& ep, hipStream_t st);
+void launch_flow_head_fused(const ConvShape& s, float wscale, const SfFlowHeadPartial& ep, bool fast, hipStream_t st);
 void launch_flow_gather(const float* G, long gstride, int nimg, int H, int W, const SfFlowDelta& ep, hipStream_t st);
 
 }  // namespace atdn

@@ -1311,8 +1311,8 @@ int atdn_conv2d_nhwc_sf(const float* src, int nimg, int H, int W, int Cin, const
  * tiles where the shape allows them (run length >= 43), both whatever the grid size; without them the product's dispatch rules
  * choose, which take small grids to smaller tiles. Other kernel shapes ignore the bits.
  * Bit 3 (value 8, combined with any of the above: 8..13) runs the dispatch as a precision-"f16" forward does: the FAST builds of
- * the same kernels, which issue the hi x hi MFMA alone, i.e. wscale * sum f16(x) * f16(w / wscale) + bias in fp32. The setting
- * lasts for this call only. Valid values: 0..15 with (sf_store & 6) != 6. */
+ * the same kernels, which issue the hi x hi MFMA alone, i.e. wscale * sum f16(x) * f16(w / wscale) + bias in fp32. The bit is
+ * an argument of this call's dispatch: no state outlives the call. Valid values: 0..15 with (sf_store & 6) != 6. */
 int atdn_conv2d_nhwc_sf_epi(const float* src, int nimg, int H, int W, int Cin, const float* weight_host,
                             const float* bias_host, int Cout, int KH, int KW, int stride, int padH, int padW, int sf_store,
                             float* dst, void* stream);
